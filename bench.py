@@ -6,6 +6,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N ...        # started plainly with N > 1: launches the line above itself (N fresh children, before
                                         # this process touches the GPU) and relays rank 0's JSON line
+    python bench.py ... --dump-outputs DIR                   # also write what the last timed step returned as DIR/<name>.npy
 
 A step is ONE full ELBO evaluation (reference elbo(sva, lfx, y), SVA:340-360) over one batch of synthetic
 data already resident in HBM: Kuu assembly, cholesky(Kuu), diagonal-block inverses / T panels, KL, then the
@@ -298,6 +299,18 @@ def profile_traffic(config, kernel_prefix):
             return rec
         best = best or rec
     return best
+
+
+def dump_outputs(out_dir, elbo, terms):
+    """--dump-outputs: what the last timed step returned to its caller - the ELBO and every field of its svgp_terms record - as
+    DIR/<name>.npy (float64 scalars).  The inputs are seeded (approxgp/synthetic.py), so two builds run with the same arguments can
+    be compared output for output.  Returns the names written."""
+    arrays = {"elbo": elbo}
+    arrays.update({f"terms_{k}": getattr(terms, k) for k, _ in getattr(terms, "_fields_", ()) if k != "reserved"})
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(v, dtype=np.float64))
+    return sorted(arrays)
 
 
 def launcher_command(n_gpus, argv, port):
@@ -605,7 +618,7 @@ def bench_config(args, name, ctx, torch, dist, dev, world, rank, use_dist, steps
     ach = flops_strip / (strip_avg_ms * 1e-3) / 1e12 if strip_avg_ms > 0 else None
     res = {
         "elapsed": elapsed, "t_region": t_region, "ms_per_step": 1e3 * elapsed / steps, "evals_per_s": world * steps / elapsed,
-        "points_per_s": n * world * steps / elapsed, "elbo": val, "n_points_global": int(terms.n_points),
+        "points_per_s": n * world * steps / elapsed, "elbo": val, "terms": terms, "n_points_global": int(terms.n_points),
         "roofline": {"kernel": kernel_name, "bound": "mfma", "achieved": ach,
                      "peak": PEAK_TFLOPS[dtype], "unit": "TFLOP/s", "frac": (ach / PEAK_TFLOPS[dtype]) if ach else None, "traffic": None,
                      "flops_per_launch": flops_strip, "ms_per_launch": strip_avg_ms, "overlapped_with_prep": bool(overlapped),
@@ -649,7 +662,11 @@ def main():
     ap.add_argument("--sustained-out", default=None, help="also write the `sustained` object to this JSON file")
     ap.add_argument("--c5-resident", type=int, default=int(os.environ.get("BENCH_C5_RESIDENT", "12500000")),
                     help="points resident per GPU for the C5 minibatch leg (SURVEY 8e: 1.25e7); the window moves every step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (the ELBO and its terms) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # `python bench.py --gpus N` with N > 1, started plainly: become the launcher of N fresh ranks (before torch / HIP are
     # even imported here), so that an N-GPU line is an N-rank RCCL run however the script was started
@@ -704,6 +721,8 @@ def main():
     host_comm = use_dist and lib_comm_error is not None
     res, model, data, p = bench_config(args, name, ctx, torch, dist, dev, world, rank, use_dist, args.steps, args.warmup,
                                        host_comm=host_comm)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["elbo"], res["terms"])
     num_data = res["num_data"]
     out = {
         "metric": "SVGP ELBO evals/sec at N=1e6, M=1024" if name in ("H", "H32") else f"SVGP ELBO evals/sec ({name})",

@@ -96,3 +96,29 @@ def test_multi_rank_line_carries_baseline_parity_and_kuf():
     # main() attaches all three on rank 0 whatever the world size
     assert 'if rank == 0 and not args.no_kuf:' in main_src and 'if rank == 0 and not args.no_cpu_baseline:' in main_src
     assert "world == 1 and not args.no_kuf" not in main_src and "world == 1 and not args.no_cpu_baseline" not in main_src
+
+
+def test_dump_outputs_writes_what_the_last_step_returned(tmp_path):
+    """--dump-outputs: the ELBO and every field of the svgp_terms record the timed path returned, one float64 .npy each; the
+    host-side fallback's step returns no record, and then the ELBO alone is written."""
+    import numpy as np
+    from approxgp import _ffi
+
+    b = _bench()
+    terms = _ffi.Terms(elbo=-12.5, expectation=-10.0, kl=2.5, scale=1.0, logdet_kuu=-3.25, n_points=3000, n_neg_var=0,
+                       chol_info=0, reserved=7)
+    names = b.dump_outputs(str(tmp_path / "out"), -12.5, terms)
+    assert names == sorted(["elbo", "terms_elbo", "terms_expectation", "terms_kl", "terms_scale", "terms_logdet_kuu",
+                            "terms_n_points", "terms_n_neg_var", "terms_chol_info"])
+    for name in names:
+        a = np.load(tmp_path / "out" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == ()
+    assert float(np.load(tmp_path / "out" / "elbo.npy")) == -12.5
+    assert float(np.load(tmp_path / "out" / "terms_n_points.npy")) == 3000.0
+    assert b.dump_outputs(str(tmp_path / "fallback"), -1.0, type("_T", (), {"n_points": 6000})) == ["elbo"]
+
+
+def test_steps_must_be_positive():
+    """`--steps` is the number of timed steps: zero would time nothing and divide by it, so it is refused before any GPU work."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
