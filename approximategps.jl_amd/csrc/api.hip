@@ -205,7 +205,7 @@ KernelParams kparams(const svgp_model* m) {
 // info + the factorisation's hand-over counters and flags: 1 + 2 nP ints, rounded up to 256 bytes - a memset whose size is not a
 // multiple of 16 bytes becomes TWO fill kernels (aligned body + tail), ~5 us of every call's prologue
 inline size_t info_bytes(int64_t Mp) { return (sizeof(int) * size_t(1 + 2 * (Mp / 128)) + 255) / 256 * 256; }
-int ensure_overlap(svgp_ctx* ctx, size_t state_doubles); int ensure_overlap(svgp_ctx* ctx, size_t state_doubles);   // (below) second stream + the row events
+int ensure_overlap(svgp_ctx* ctx, size_t state_doubles);   // (below) second stream + the row events
 int enqueue_prep(svgp_ctx* ctx, svgp_model* m, bool overlap = false, const RowHook* hook = nullptr) {
   hipStream_t s = ctx->stream;
   const KernelParams kp = kparams(m);
@@ -280,17 +280,7 @@ int ensure_stream2(svgp_ctx* ctx) {
   // the factorisation): lowest priority, so that where both have workgroups to dispatch the main stream's serial chain goes first
   static const int prio_knob = exp_int("SVGP_STREAM2_LOW_PRIO", 1);   // A/B knob (experiments build)
   int least = 0, greatest = 0;
-  // A/B knob (round 4): keep SVGP_STREAM2_RESERVE CUs out of the second stream's reach (hipExtStreamCreateWithCUMask), so that the
-  // factorisation's launches always find free CUs beside the segmented strips
-  static const int reserve = exp_int("SVGP_STREAM2_RESERVE", 0);
-  if (reserve > 0 && reserve < ctx->num_cus) {
-    std::vector<uint32_t> mask(size_t((ctx->num_cus + 31) / 32), 0xffffffffu);
-    for (int c = 0; c < reserve; ++c) {   // spread the reserved CUs: one every num_cus / reserve
-      const int cu = int((int64_t(c) * ctx->num_cus) / reserve);
-      mask[size_t(cu / 32)] &= ~(1u << (cu % 32));
-    }
-    HIPC(ctx, hipExtStreamCreateWithCUMask(&ctx->stream2, uint32_t(mask.size()), mask.data()));
-  } else if (prio_knob && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
+  if (prio_knob && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
     HIPC(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, least));
   } else {
     HIPC(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
@@ -354,18 +344,16 @@ struct StripOuts {
   void* Ct = nullptr;
   int64_t lda = 0;
   bool skip_expect = false;   // svgp_marginals: the caller wants the moments themselves
-  int64_t mom_shift = 0;      // the batch's moments start at this index of the context's moment arrays (a batch evaluated in two parts)
-  bool no_ctail = false;      // never a concurrent tail launch (the second stream is taken: segmented head)
 };
 
 // enqueue the fused strip kernel + final reduce over points [off, off+len) of (x, y)
 int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, const void* y, int64_t off, int64_t len,
                    const StripOuts& o) {
   StripPlan plan = strip_plan(m->dtype, m->Mp, len, ctx->num_cus);
-  if (plan.concurrent_tail && (o.A || o.C || o.At || o.Ct || o.no_ctail)) plan = strip_plan_single(m->dtype, m->Mp, len, ctx->num_cus);
+  if (plan.concurrent_tail && (o.A || o.C || o.At || o.Ct)) plan = strip_plan_single(m->dtype, m->Mp, len, ctx->num_cus);
   const size_t wb_main = plan.grid ? strip_work_bytes(m->dtype, m->Mp, plan.nt, plan.grid) : 0;
   const size_t wb_tail = plan.nt_tail ? strip_work_bytes(m->dtype, m->Mp, plan.nt_tail, plan.grid_tail) : 0;
-  int rc = ensure_scratch(ctx, plan.concurrent_tail ? wb_main : (wb_main > wb_tail ? wb_main : wb_tail), size_t(len + o.mom_shift));
+  int rc = ensure_scratch(ctx, plan.concurrent_tail ? wb_main : (wb_main > wb_tail ? wb_main : wb_tail), size_t(len));
   if (rc) return rc;
   if (plan.concurrent_tail) {
     rc = ensure_stream2(ctx);
@@ -386,8 +374,8 @@ int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, con
   a.x = x;
   a.work = ctx->work;
   a.counter = ctx->counter;
-  a.mom_mu = ctx->mom + o.mom_shift;
-  a.mom_var = ctx->mom + ctx->mom_cap + o.mom_shift;
+  a.mom_mu = ctx->mom;
+  a.mom_var = ctx->mom + ctx->mom_cap;
   a.A_out = o.A;
   a.C_out = o.C;
   a.At_out = o.At;
@@ -447,7 +435,6 @@ int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, con
     }
   }
   ctx->timing.strip_launches = (plan.grid ? 1 : 0) + (plan.nt_tail ? 1 : 0);
-  if (o.mom_shift) return SVGP_OK;   // the second part of a batch: the caller joins the parts and runs the expectation over both
   TREC(ctx, ctx->ev[2], ctx->stream);
   if (o.skip_expect) return SVGP_OK;
   launch_expect(m->dtype, ctx->stream, lp, a.mom_mu, a.mom_var, y, off, len, ctx->partial, ctx->negcnt, o.mu, o.var);
@@ -464,7 +451,7 @@ int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, con
 // at most one round of strips the evaluation therefore runs as SEGMENTED strips (strip.hip: SEG) on the second stream: the Kuf
 // pre-generation right away, phase-1 panel I behind ev_row[I], phase 2 with the last panel; the main stream joins before the
 // expectation.  Nothing spins and no launch waits while resident, so the factorisation's launches always find free CUs.
-struct OverlapPlan { bool on = false; int nt = 0, grid = 0; int64_t nstrips = 0, head_points = 0; };
+struct OverlapPlan { bool on = false; int nt = 0, grid = 0; int64_t nstrips = 0; };
 
 OverlapPlan overlap_plan(const svgp_ctx* ctx, const svgp_model* m, int64_t len, const StripOuts& o) {
   OverlapPlan p;
@@ -480,24 +467,11 @@ OverlapPlan overlap_plan(const svgp_ctx* ctx, const svgp_model* m, int64_t len, 
   p.nt = sp.grid ? sp.nt : sp.nt_tail;
   p.nstrips = sp.grid ? sp.nstrips : sp.nstrips_tail;
   p.grid = sp.grid ? sp.grid : sp.grid_tail;
-  // the segmented kernels exist for 32- / 64-point strips (f64) and 32 / 64 / 128 (f32) on 256 threads (launch_strip_seg); a wider plan -
-  // only an experiments build can ask for one (SVGP_STRIP_NT=128) - keeps the one-launch path
-  if (p.nt > (m->dtype == SVGP_F64 ? 64 : 128)) return p;
-  if (p.nstrips <= p.grid && nP < min_panels) return p;   // one round: pays from about five panels on (multi-round heads: below)
-  p.head_points = len;
-  if (p.nstrips > p.grid) {
-    // More than one round of strips (C5: 4, C2: 3): a SEGMENTED HEAD - the first round's worth of strips runs beside the
-    // factorisation like a one-round batch, the rest as the one-launch kernel behind the prep on the main stream (its dynamic queue
-    // intact), the two joined before the expectation.  The head's phase 1 fills the chip while the chain would have had it alone.
-    // MEASURED, default OFF (profiles/round4/overlap.md): C5 (4 rounds of fp32 strips) 5.02 -> 4.91 ms wall, C2 (3 rounds, M = 512) 1.339
-    // -> 1.340, H32 / C3 unchanged - the head's panel launches are long (a full round of full-width strips) and the factorisation
-    // waits for their CUs (C5 prep 0.48 -> 0.84 ms), which gives back most of what the head gains.  SVGP_OVERLAP_HEAD=1 enables it
-    // in the experiments build; the product build never takes this branch.
-    const int64_t rounds = (p.nstrips + p.grid - 1) / p.grid;
-    if (!ctx->kn.overlap_head || !sp.grid || nP < ctx->kn.overlap_head_min_panels || rounds > 8) return OverlapPlan{};
-    p.nstrips = p.grid;
-    p.head_points = int64_t(p.grid) * p.nt;
-  }
+  // More than one round of strips (C5: 4, C2: 3) does not overlap.  Measured and not adopted (round 4, profiles/round4/overlap.md;
+  // no longer in the tree): a SEGMENTED HEAD - the first round beside the factorisation, the rest behind the prep - C5 5.02 -> 4.91 ms,
+  // C2 / H32 / C3 unchanged: the head's long panel launches hold the CUs the factorisation waits for (C5 prep 0.48 -> 0.84 ms).
+  if (p.nstrips > p.grid) return OverlapPlan{};
+  if (nP < min_panels) return p;   // one round: pays from about five panels on
   p.on = true;
   return p;
 }
@@ -516,7 +490,6 @@ struct SegRun {
   int split = 1;   // forward: phase 2 in a closing launch of its own, `split` workgroups per strip (small batches; kernels.hpp: seg_split)
   int nP = 0, rc = SVGP_OK;
   size_t wb1 = 0;
-  int64_t head = 0;
   std::function<int()>* pre = nullptr;   // work for the second stream ahead of the pre-generation (the gradient's chain-independent prep)
 };
 
@@ -559,9 +532,7 @@ void seg_row_hook(void* user, int row) {
 // forward evaluation, stage 1 (BEFORE the prep is enqueued): every allocation and the strips' arguments
 int seg_prepare_forward(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, int64_t off, int64_t len, const OverlapPlan& op, SegRun& r) {
   const int nP = int(m->Mp / 128);
-  const int64_t head = op.head_points < len ? op.head_points : len;
-  // the segmented strips' scratch is per STRIP and lives beside the main launch's per-workgroup scratch (a segmented head runs
-  // concurrently with the rest of its batch): its own buffer
+  // the segmented strips' scratch is per STRIP (the one-launch kernel's is per workgroup): a buffer of its own
   const size_t wb1 = strip_work_bytes(m->dtype, m->Mp, op.nt, int(op.nstrips)), wb = wb1;
   // (A checkpointed phase 2 beside the factorisation - bitwise-tested, measured in round 4, profiles/round4/overlap.md: the factorisation
   // slows by what the strips' extra work beside it occupies, 16 384 / 1024 f64 1.046 -> 1.06-1.07 ms, M = 2048 1.94 -> 2.11 - left the
@@ -573,33 +544,24 @@ int seg_prepare_forward(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx
     HIPC(ctx, hipMalloc(&ctx->work_seg, wb));
     ctx->work_seg_bytes = wb;
   }
-  int rc = ensure_scratch(ctx, 0, size_t(len));
+  const int rc = ensure_scratch(ctx, 0, size_t(len));
   if (rc) return rc;
-  if (head < len) {   // the part behind the head: sized and allocated BEFORE anything is enqueued (ensure_scratch may reallocate)
-    const StripPlan rp = strip_plan_single(m->dtype, m->Mp, len - head, ctx->num_cus);
-    const size_t w1 = rp.grid ? strip_work_bytes(m->dtype, m->Mp, rp.nt, rp.grid) : 0;
-    const size_t w2 = rp.nt_tail ? strip_work_bytes(m->dtype, m->Mp, rp.nt_tail, rp.grid_tail) : 0;
-    rc = ensure_scratch(ctx, w1 > w2 ? w1 : w2, size_t(len));
-    if (rc) return rc;
-  }
-  r.ctx = ctx; r.m = m; r.op = op; r.grad = false; r.nP = nP; r.wb1 = wb1; r.head = head;
-  // A small batch (fewer strips than workgroup slots; not a segmented head): phase 2 - one panel C_J after the other inside a strip's
+  r.ctx = ctx; r.m = m; r.op = op; r.grad = false; r.nP = nP; r.wb1 = wb1;
+  // A small batch (fewer strips than workgroup slots): phase 2 - one panel C_J after the other inside a strip's
   // workgroup - is latency-bound on the few CUs it reaches, and its panels are independent: a closing launch with S workgroups per strip
-  r.split = (head < len) ? 1 : seg_split_factor(ctx, nP, op.nstrips);
+  r.split = seg_split_factor(ctx, nP, op.nstrips);
   StripArgs& a = r.a;
   a.T = m->T; a.U = m->U; a.zs = m->zs; a.mp = m->mp; a.x = x; a.work = ctx->work_seg; a.counter = ctx->counter2;
   a.mom_mu = ctx->mom; a.mom_var = ctx->mom + ctx->mom_cap;
-  a.ldx = ldx; a.off = off; a.len = head; a.Mp = m->Mp; a.M = m->M; a.kp = kparams(m); a.mean_const = m->desc.mean_const;
+  a.ldx = ldx; a.off = off; a.len = len; a.Mp = m->Mp; a.M = m->M; a.kp = kparams(m); a.mean_const = m->desc.mean_const;
   a.seg_state = ctx->seg_state;
   return SVGP_OK;
 }
 
-// forward evaluation, stage 2 (AFTER the prep, whose launch loop enqueued the segments): the rest of the batch, the join, the expectation
-int seg_finish_forward(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, const void* y, int64_t off, int64_t len,
-                       const StripOuts& o, SegRun& r) {
+// forward evaluation, stage 2 (AFTER the prep, whose launch loop enqueued the segments): the join, the expectation
+int seg_finish_forward(svgp_ctx* ctx, svgp_model* m, const void* y, int64_t off, int64_t len, const StripOuts& o, SegRun& r) {
   hipStream_t s = ctx->stream, s2 = ctx->stream2;
   if (r.rc) return r.rc;
-  const int64_t head = r.head;
   int launches = r.nP + 1;
   if (r.split > 1) {   // phase 2 + moments, r.split workgroups per strip
     StripArgs& a = r.a;
@@ -612,15 +574,6 @@ int seg_finish_forward(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx,
     ++launches;
   }
   HIPC(ctx, hipEventRecord(ctx->ev_join, s2));
-  if (head < len) {   // the rest of the batch: the one-launch kernel behind the prep, on the main stream, beside the head's tail
-    StripOuts rest = o;
-    rest.mom_shift = head;
-    rest.no_ctail = true;
-    rest.skip_expect = true;
-    const int rc = enqueue_strips(ctx, m, x, ldx, y, off + head, len - head, rest);
-    if (rc) return rc;
-    launches += int(ctx->timing.strip_launches);
-  }
   HIPC(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
   TREC(ctx, ctx->ev[2], s);
   ctx->timing.strip_launches = launches;
@@ -669,32 +622,22 @@ int elbo_enqueue(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t of
     if (rc) return rc;
   }
   ctx->overlapped = op.on;
-  // (experiments build) diagnostic: the overlap's prep - reordered, with its row events recorded - but the strips behind it as usual:
-  // what the events alone cost the chain
-  const bool dry = op.on && ctx->kn.overlap_dry == 1;
   SegRun seg;
   RowHook hook{seg_row_hook, &seg};
-  if (op.on && !dry) {
+  if (op.on) {
     rc = seg_prepare_forward(ctx, m, data->x, data->ldx, off, len, op, seg);
     if (rc) return rc;
   }
   TREC(ctx, ctx->ev[0], s);
-  rc = enqueue_prep(ctx, m, op.on, (op.on && !dry) ? &hook : nullptr);
-  if (rc == SVGP_OK && op.on && !dry) rc = seg.rc;
+  rc = enqueue_prep(ctx, m, op.on, op.on ? &hook : nullptr);
+  if (rc == SVGP_OK && op.on) rc = seg.rc;
   if (rc) {   // a failure between the fork and the join leaves work on the second stream that the main stream never waited for: drain it,
               // so that the next call on this context cannot meet it in the shared scratch
     if (op.on && ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     return rc;
   }
   TREC(ctx, ctx->ev[1], s);
-  if (dry) {
-    ctx->overlapped = false;   // ev_ov[1] is not recorded on this path
-    rc = enqueue_strips(ctx, m, data->x, data->ldx, data->y, off, len, StripOuts{});
-    if (rc) return rc;
-    TREC(ctx, ctx->ev[3], s);
-    return SVGP_OK;
-  }
-  rc = op.on ? seg_finish_forward(ctx, m, data->x, data->ldx, data->y, off, len, StripOuts{}, seg)
+  rc = op.on ? seg_finish_forward(ctx, m, data->y, off, len, StripOuts{}, seg)
              : enqueue_strips(ctx, m, data->x, data->ldx, data->y, off, len, StripOuts{});
   if (rc) {
     if (op.on && ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
@@ -940,12 +883,6 @@ int32_t svgp_ctx_destroy(svgp_ctx* c) {
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
   if (c->kuf_buf) (void)hipFree(c->kuf_buf);
   if (c->ext_g) (void)hipFree(c->ext_g);
-  for (auto& st : c->pst)
-    if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  if (c->ev_pipe_prep) (void)hipEventDestroy(c->ev_pipe_prep);
-  if (c->pwork) (void)hipFree(c->pwork);
-  if (c->pcounter) (void)hipFree(c->pcounter);
-  if (c->pmom) (void)hipFree(c->pmom);
   if (c->gws) { c->gws->release(); delete c->gws; }
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
@@ -1416,68 +1353,6 @@ int grad_workspace(svgp_ctx* ctx, svgp_model* m, int64_t len, GradWs** out) {
   return SVGP_OK;
 }
 
-// ---- chunk pipeline of a value-and-gradient evaluation (round 5) -----------------------------------------------
-// A batch of more than one chunk used to run strictly serially on one stream: strips(k) [MFMA, ragged end: the last 13 % of a launch
-// run one workgroup per CU] -> point gradients -> kernel-gradient reductions(k) [f64 VALU, no MFMA] -> SYRK(k) [MFMA] -> strips(k + 1)
-// [starts in its MFMA-free pre-generation] ...  Now the per-chunk arrays (A, P point-major, g_mu | g_v, the point-gradient partials)
-// exist in `lanes` sets; the strips + point gradients of chunk k run on a pipeline stream (chunk k on stream k mod `streams`), the
-// consumers of chunk k (reductions, sum5, SYRK) on the main stream behind ev_strips[lane], and the strips of chunk k + lanes wait for
-// ev_done[lane].  Every accumulation (slice buffer, row partials, sums) stays on the main stream in chunk order, so the result is
-// bitwise the serial one.
-struct PipeCfg { int lanes = 1, streams = 1, prio = 0; };
-PipeCfg pipe_cfg(const svgp_ctx* ctx) { return PipeCfg{ctx->kn.pipe_lanes, ctx->kn.pipe_streams, ctx->kn.pipe_prio}; }
-
-int ensure_pipe(svgp_ctx* ctx, GradWs* w, const svgp_model* m, const PipeCfg& pc, size_t work_bytes, size_t nc) {
-  const size_t es = m->es;
-  for (int q = 0; q < pc.streams; ++q) {
-    if (ctx->pst[q]) continue;
-    int least = 0, greatest = 0;
-    if (pc.prio != 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-      HIPC(ctx, hipStreamCreateWithPriority(&ctx->pst[q], hipStreamNonBlocking, pc.prio < 0 ? least : greatest));
-    else
-      HIPC(ctx, hipStreamCreateWithFlags(&ctx->pst[q], hipStreamNonBlocking));
-  }
-  if (!ctx->ev_pipe_prep) HIPC(ctx, hipEventCreateWithFlags(&ctx->ev_pipe_prep, kSyncEvent));
-  if (pc.streams > 1) {   // the second pipeline stream's strips: their own scratch strips, queue head and moments
-    if (work_bytes > ctx->pwork_bytes) {
-      if (ctx->pwork) (void)hipFree(ctx->pwork);
-      ctx->pwork = nullptr; ctx->pwork_bytes = 0;
-      HIPC(ctx, hipMalloc(&ctx->pwork, work_bytes));
-      ctx->pwork_bytes = work_bytes;
-    }
-    if (nc > ctx->pmom_cap) {
-      if (ctx->pmom) (void)hipFree(ctx->pmom);
-      ctx->pmom = nullptr; ctx->pmom_cap = 0;
-      HIPC(ctx, hipMalloc(&ctx->pmom, 2 * nc * sizeof(double)));
-      ctx->pmom_cap = nc;
-    }
-    if (!ctx->pcounter) HIPC(ctx, hipMalloc(&ctx->pcounter, 64));
-  }
-  if (w->lanes.empty()) {
-    GradWs::Lane l0;
-    l0.At = w->At; l0.Pt = w->Pt; l0.gmu = w->gmu; l0.gv = w->gv; l0.partial5 = w->partial5;
-    w->lanes.push_back(l0);
-  }
-  const size_t mn = size_t(w->Mp) * size_t(w->nc) * es;
-  while (int(w->lanes.size()) < pc.lanes) {
-    GradWs::Lane l;
-    struct { void** p; size_t b; bool zero; } req[] = {
-        {&l.At, mn, true}, {&l.Pt, mn, true}, {&l.gmu, 2 * size_t(w->nc) * es + 256, false}, {(void**)&l.partial5, size_t(w->part5_strips) * 5 * 8, false}};
-    for (auto& r : req) {
-      if (hipMalloc(r.p, r.b) != hipSuccess) return fail(ctx, SVGP_OOM, "hipMalloc failed for the gradient pipeline");
-      w->all.push_back(*r.p);
-      if (r.zero) HIPC(ctx, hipMemsetAsync(*r.p, 0, r.b, ctx->stream));   // read beyond the written points of a short last chunk (against g_v = 0)
-    }
-    l.gv = static_cast<char*>(l.gmu) + size_t(w->nc) * es;
-    w->lanes.push_back(l);
-  }
-  for (GradWs::Lane& l : w->lanes) {
-    if (!l.ev_strips) HIPC(ctx, hipEventCreateWithFlags(&l.ev_strips, kSyncEvent));
-    if (!l.ev_done) HIPC(ctx, hipEventCreateWithFlags(&l.ev_done, kSyncEvent));
-  }
-  return SVGP_OK;
-}
-
 }  // namespace
 
 namespace {
@@ -1526,9 +1401,6 @@ int grad_enqueue(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t of
   // a failure between the fork and the join of the segmented strips leaves work on the second stream that the main stream never
   // waited for: drain it, so that the next call on this context cannot meet it in the shared scratch
   if (rc != SVGP_OK && ctx->overlapped && ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
-  if (rc != SVGP_OK && ctx->pipelined)   // likewise the chunk pipeline's streams
-    for (hipStream_t st : ctx->pst)
-      if (st) (void)hipStreamSynchronize(st);
   return rc;
 }
 
@@ -1562,14 +1434,7 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   // the main stream computes meanwhile.  Same conditions as the forward path (overlap_plan), plus: the whole batch is one chunk.
   OverlapPlan gop;
   if (len <= nc && centered == false) {
-    gop = overlap_plan(ctx, m, len, StripOuts{});
-    if (gop.on) {   // the gradient's strips: the single-launch plan's geometry (no concurrent tail there)
-      const StripPlan sp = strip_plan_single(dt, Mp, len, ctx->num_cus);
-      gop.nt = sp.grid ? sp.nt : sp.nt_tail;
-      gop.grid = sp.grid ? sp.grid : sp.grid_tail;
-      gop.nstrips = sp.grid ? sp.nstrips : sp.nstrips_tail;
-      if (gop.head_points < len || gop.nstrips > gop.grid || (sp.grid && sp.nt_tail)) gop.on = false;   // one chunk, one round only
-    }
+    gop = overlap_plan(ctx, m, len, StripOuts{});   // (one round of the single-launch plan's strips: no concurrent tail there)
     if (gop.on) {
       rc = ensure_overlap(ctx, size_t(gop.nstrips) * strip_seg_state_doubles(dt, gop.nt));
       // the size the chunk loop below asks for (per workgroup >= per strip here): nothing may reallocate once segments are enqueued
@@ -1706,45 +1571,19 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   }
   rc = ensure_scratch(ctx, wb_max, size_t(nc));
   if (rc) return rc;
-  // chunk pipeline (ensure_pipe; experiments build)
-  static const int kg_overlap = exp_int("SVGP_KGRAD_OVERLAP", 0);   // experiments build
-  const PipeCfg pc = pipe_cfg(ctx);
-  const bool pipe_any = !gop.on && !kg_overlap && nchunks >= 2 && pc.lanes >= 2;
-  const bool pipe = pipe_any && ctx->kn.pipe_mode != 2;   // mode 1: strips(k + 1) on a pipeline stream beside the consumers of chunk k
-  const bool trail = pipe_any && ctx->kn.pipe_mode == 2;  // mode 2: everything on the main stream but kgrad(k), which trails on a pipeline stream beside SYRK(k) and strips(k + 1)
-  ctx->pipelined = pipe_any;
-  if (pipe_any) {
-    PipeCfg pcc = pc;
-    if (trail) pcc.streams = 1;
-    rc = ensure_pipe(ctx, w, m, pcc, wb_max, size_t(nc));
-    if (rc) return rc;
-    if (pipe) HIPC(ctx, hipEventRecord(ctx->ev_pipe_prep, s));   // R, alpha, the cleared accumulators: everything the strips read
-  }
-  for (int64_t c0 = 0, kc = 0; c0 < len; c0 += nc, ++kc) {
+  // The chunks run one after the other on the main stream.  Measured and not adopted (no longer in the tree): a chunk pipeline with
+  // the strips of chunk k + 1 on other streams beside the consumers of chunk k (round 5), and the kernel-gradient reductions on the
+  // second stream beside the SYRK (H 97.8-98.3 vs 98.2-98.4 ms: the SYRK's 504 workgroups leave them no room to run).
+  for (int64_t c0 = 0; c0 < len; c0 += nc) {
     const int64_t clen = (len - c0 < nc) ? len - c0 : nc;
     const int64_t ncp = (clen + 127) / 128 * 128;
     // forward strips + likelihood gradients + phase 3 in ONE launch: leaves A, P point-major and g_mu, g_v of the chunk
     int nt, grid; int64_t nstrips;
     chunk_plan(clen, nt, grid, nstrips);
-    // this chunk's buffer set and the stream of its strips (serial path: lane 0 = the workspace's own arrays, the main stream)
-    const int lane = pipe_any ? int(kc % pc.lanes) : 0, pq = pipe ? int(kc % pc.streams) : 0;
-    GradWs::Lane L;
-    if (pipe_any) L = w->lanes[size_t(lane)];
-    else { L.At = w->At; L.Pt = w->Pt; L.gmu = w->gmu; L.gv = w->gv; L.partial5 = w->partial5; }
-    hipStream_t ss = pipe ? ctx->pst[pq] : s;
-    if (pipe) {
-      if (kc < pc.streams) HIPC(ctx, hipStreamWaitEvent(ss, ctx->ev_pipe_prep, 0));
-      if (kc >= pc.lanes) HIPC(ctx, hipStreamWaitEvent(ss, L.ev_done, 0));   // the lane's previous chunk has been consumed
-    }
-    if (trail && kc >= pc.lanes) HIPC(ctx, hipStreamWaitEvent(s, L.ev_done, 0));   // the reductions of the lane's previous chunk have read P / g
     // (g_mu | g_v, w->nc apart: the weighted SYRK reads g_v over the chunk padded to 128 points - launch_point_grads writes that padding)
     LikParams lpc{};
     StripArgs a = gop.on ? gseg.a : strip_args(c0, clen, lpc);
     if (gop.on) lpc = lpc_seg;
-    if (!gop.on) {
-      a.At_out = L.At; a.Pt_out = L.Pt;
-      if (pipe && pq == 1) { a.work = ctx->pwork; a.counter = ctx->pcounter; a.mom_mu = ctx->pmom; a.mom_var = ctx->pmom + ctx->pmom_cap; }
-    }
     if (gop.on) {   // (single chunk) the segments are on the second stream already; the closing launch (phase 2 + 3) waits for R and alpha,
                     // and the main stream joins before the point gradients
       hipStream_t s2 = ctx->stream2;
@@ -1764,8 +1603,8 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
       }
       if (syrk_early) {   // W = w A A' behind the last phase-1 segment, beside the main stream's Lk^-1 / R / alpha
         const int64_t n16 = (clen + 15) / 16 * 16, sl_e = ((ncp + ns_syrk - 1) / ns_syrk + 15) / 16 * 16;
-        if (n16 > clen) HIPC(ctx, hipMemsetAsync(static_cast<char*>(L.At) + size_t(clen) * size_t(Mp) * es, 0, size_t(n16 - clen) * size_t(Mp) * es, s2));
-        launch_syrk_uniform(dt, s2, L.At, -0.5 / lp.sigma2, scale, n_global_dev, gc.num_data, 2.0, Mp, n16, sl_e, ns_syrk, w->G1, 1);
+        if (n16 > clen) HIPC(ctx, hipMemsetAsync(static_cast<char*>(w->At) + size_t(clen) * size_t(Mp) * es, 0, size_t(n16 - clen) * size_t(Mp) * es, s2));
+        launch_syrk_uniform(dt, s2, w->At, -0.5 / lp.sigma2, scale, n_global_dev, gc.num_data, 2.0, Mp, n16, sl_e, ns_syrk, w->G1, 1);
         KCHECK(ctx, "syrk (beside the prep of phase 3)");
       }
       HIPC(ctx, hipStreamWaitEvent(s2, ctx->ev_R, 0));
@@ -1777,41 +1616,19 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
       HIPC(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
     } else {
       // the head of the strips' queue: zeroed here for the first chunk, by the previous chunk's launch_point_grads for the others
-      if (kc == 0 || pipe_any) HIPC(ctx, hipMemsetAsync(a.counter, 0, sizeof(unsigned), ss));
-      launch_strip_grad(dt, ss, a, nt, grid, nstrips);
+      if (c0 == 0) HIPC(ctx, hipMemsetAsync(a.counter, 0, sizeof(unsigned), s));
+      launch_strip_grad(dt, s, a, nt, grid, nstrips);
       KCHECK(ctx, "strip (value and gradient)");
     }
-    launch_point_grads(dt, ss, lpc, a.mom_mu, a.mom_var, gc.ext_gmu ? nullptr : data->y, off + c0, clen, scale, n_global_dev, gc.num_data, L.gmu, L.gv, L.partial5,
-                       (!gop.on && !pipe_any) ? a.counter : nullptr, ncp);
+    launch_point_grads(dt, s, lpc, a.mom_mu, a.mom_var, gc.ext_gmu ? nullptr : data->y, off + c0, clen, scale, n_global_dev, gc.num_data, w->gmu, w->gv,
+                       w->partial5, gop.on ? nullptr : a.counter, ncp);
     KCHECK(ctx, "point gradients");
     const int n5 = point_grad_blocks(clen);   // rows of partial5: one per 256-point block
-    if (pipe) {   // the consumers of this chunk: on the main stream, behind the chunk's strips
-      HIPC(ctx, hipEventRecord(L.ev_strips, ss));
-      HIPC(ctx, hipStreamWaitEvent(s, L.ev_strips, 0));
-    }
-    if (trail) {
-      HIPC(ctx, hipEventRecord(L.ev_strips, s));
-      HIPC(ctx, hipStreamWaitEvent(ctx->pst[0], L.ev_strips, 0));
-    }
-    // Knob (off): the kernel-gradient reductions (f64 VALU, latency-bound, no MFMA) on the second stream BESIDE the SYRK
-    // (MFMA-bound); both only read this chunk's A / P / g, the join comes before the next chunk's strips overwrite them.
-    // Measured and not adopted: H 97.8-98.3 vs 98.2-98.4 ms, C5 16.5-16.6 vs 16.6-16.7 ms (same box) - the SYRK's 504
-    // workgroups leave kgrad no room to run beside them.
-    hipStream_t sk = trail ? ctx->pst[0] : s;
-    if (kg_overlap) {
-      rc = ensure_stream2(ctx);
-      if (rc) return rc;
-      sk = ctx->stream2;
-      HIPC(ctx, hipEventRecord(ctx->ev_fork, s));
-      HIPC(ctx, hipStreamWaitEvent(sk, ctx->ev_fork, 0));
-    }
     int64_t ksl = ((clen + w->ns_uf - 1) / w->ns_uf + 127) / 128 * 128;
-    launch_kgrad(dt, sk, kp, m->zs, Mp, M, data->x, data->ldx, off + c0, 0, clen, clen, L.Pt, L.gmu, L.gv, w->alpha, ksl, w->ns_uf,
+    launch_kgrad(dt, s, kp, m->zs, Mp, M, data->x, data->ldx, off + c0, 0, clen, clen, w->Pt, w->gmu, w->gv, w->alpha, ksl, w->ns_uf,
                  w->rp_uf, w->sp_uf, 1);
     KCHECK(ctx, "kgrad uf");
-    if (kg_overlap) HIPC(ctx, hipEventRecord(ctx->ev_join, sk));
-    if (trail) HIPC(ctx, hipEventRecord(L.ev_done, sk));
-    launch_sum5(s, L.partial5, n5, w->sums);
+    launch_sum5(s, w->partial5, n5, w->sums);
     int64_t sl = ((ncp + ns_syrk - 1) / ns_syrk + 15) / 16 * 16;   // as even as the 16-point k-step allows
     // W (+)= A diag(2 g_v) A' (lower tiles, split-K slices): the first chunk overwrites, so the slice buffer needs no zeroing
     if (syrk_early) {
@@ -1820,17 +1637,13 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
       // g_v is the same for every point (Gaussian: -scale / (2 sigma^2)): the unweighted loop, the weight applied to the accumulators.
       // Columns of the chunk's last strip beyond its last point hold the replicated last point: zero them up to the k-step boundary
       const int64_t n16 = (clen + 15) / 16 * 16;
-      if (n16 > clen) HIPC(ctx, hipMemsetAsync(static_cast<char*>(L.At) + size_t(clen) * size_t(Mp) * es, 0, size_t(n16 - clen) * size_t(Mp) * es, s));
-      launch_syrk_uniform(dt, s, L.At, -0.5 / lp.sigma2, scale, n_global_dev, gc.num_data, 2.0, Mp, n16, sl, ns_syrk, w->G1, c0 == 0 ? 1 : 0);
+      if (n16 > clen) HIPC(ctx, hipMemsetAsync(static_cast<char*>(w->At) + size_t(clen) * size_t(Mp) * es, 0, size_t(n16 - clen) * size_t(Mp) * es, s));
+      launch_syrk_uniform(dt, s, w->At, -0.5 / lp.sigma2, scale, n_global_dev, gc.num_data, 2.0, Mp, n16, sl, ns_syrk, w->G1, c0 == 0 ? 1 : 0);
     } else {
-      launch_gemm_pm(dt, s, L.At, L.At, L.gv, 2.0, Mp, ncp, sl, ns_syrk, w->G1, c0 == 0 ? 1 : 0);
+      launch_gemm_pm(dt, s, w->At, w->At, w->gv, 2.0, Mp, ncp, sl, ns_syrk, w->G1, c0 == 0 ? 1 : 0);
     }
     KCHECK(ctx, "syrk");
-    if (kg_overlap) HIPC(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-    if (pipe) HIPC(ctx, hipEventRecord(L.ev_done, s));
   }
-  if (trail)   // join: the trailing reductions of the last chunks
-    for (int64_t q = 0; q < std::min<int64_t>(nchunks, pc.lanes); ++q) HIPC(ctx, hipStreamWaitEvent(s, w->lanes[size_t(q)].ev_done, 0));
   if (gc.ext_gmu) launch_add_f64(s, w->sums, gc.ext_sum_e);   // sums[0] = sum E: the host's, before any collective
   TREC(ctx, ctx->ev[2], s);
   // M-sized tail.  With W = A diag(2 g_v) A' and a = A g_mu:

@@ -1000,27 +1000,6 @@ __global__ void __launch_bounds__(512, 2) kuf_cols_kernel(KernelParams kp, const
   }
 }
 
-// Kuf for 32 < d <= 64 (round 3; the standalone Kuf metric kernels keep their z fragments in registers / LDS for d <= 32):
-// one thread per inducing row and 16 points, direct differences.  Off the ELBO path (svgp_kuf only).
-template <typename T>
-__global__ void __launch_bounds__(k256) kuf_generic_kernel(KernelParams kp, const T* __restrict__ zs, int64_t M, int64_t Mp,
-                                                           const T* __restrict__ x, int64_t ldx, int64_t off, int64_t len,
-                                                           T* __restrict__ K) {
-  const int64_t i = int64_t(blockIdx.x) * k256 + threadIdx.x;
-  const int64_t j0 = int64_t(blockIdx.y) * 16;
-  if (i >= M) return;
-  const T* __restrict__ invl = static_cast<const T*>(kp.invl);
-  for (int jj = 0; jj < 16 && j0 + jj < len; ++jj) {
-    const int64_t j = j0 + jj;
-    T r2 = T(0);
-    for (int f = 0; f < kp.d; ++f) {
-      const T df = zs[int64_t(f) * Mp + i] - x[int64_t(f) * ldx + off + j] * invl[f];
-      r2 = fma(df, df, r2);
-    }
-    K[i + j * M] = kappa<T>(kp.family, r2, T(kp.variance));
-  }
-}
-
 template <typename T, int NT, int BK, int NTHR, int MINW = 2, int PAD = 16, bool GRAD = false, bool BIGD = false, bool SEG = false>
 void launch_strip_t(hipStream_t s, const StripArgs& a, int grid, int64_t nstrips) {
   using G = TileGemm<T, NT, BK, NTHR, PAD>;
@@ -1047,7 +1026,7 @@ void launch_strip_d(hipStream_t s, const StripArgs& a, int grid, int64_t nstrips
 
 // Strip geometry.  Default: 64-point strips on 256-thread workgroups, two workgroups per CU, so the two
 // waves on a SIMD belong to different workgroups and do not park at the same barrier.
-// SVGP_STRIP_NT=128 selects the 128-point / 512-thread build, SVGP_STRIP_BK=32 the 32-deep k-step (tuning knobs).
+// SVGP_STRIP_NT=64 / 128 (128: f32 only) overrides the width (tuning knob).
 // Measured and rejected for f64: 64 x 64 per wave on one workgroup per CU (1 wave/SIMD): 54.9 ms vs 42.1 ms at H.
 // (every knob below is a constant - its default - in the product build: knobs.hpp)
 static int env_int(const char* name, int dflt) { return exp_int(name, dflt); }
@@ -1056,7 +1035,7 @@ int strip_nt(int dtype, int64_t Mp, int64_t /*len*/) {
   // f64: 64-point strips; f32: 128-point strips (a wave then owns 64 x 64 = 16 MFMA tiles, the same 64 accumulator
   // VGPRs as the f64 wave, and twice the MFMA work per barrier and per byte of T/U).  SVGP_STRIP_NT overrides.
   static const int forced = env_int("SVGP_STRIP_NT", 0);
-  if (forced == 64 || forced == 128) return forced;
+  if (forced == 64 || (forced == 128 && dtype == 1)) return forced;
   // measured (same box): H32 22.4 -> 20.5 ms, C3 84.1 -> 77.8 ms, C5 5.9 -> 5.4 ms; C4 (Mp = 8192) 131.7 -> 136.0 ms
   return dtype == 0 ? 64 : env_int("SVGP_F32_NT", Mp <= 2048 ? 128 : 64);
 }
@@ -1130,7 +1109,6 @@ StripPlan strip_plan_single(int dtype, int64_t Mp, int64_t len, int num_cus) {
 }
 
 void launch_strip(int dtype, hipStream_t s, const StripArgs& a, int nt, int grid, int64_t nstrips) {
-  static const bool bk32 = env_int("SVGP_STRIP_BK", 16) == 32;
   if (nt == 32 && dtype == 0) {
     launch_strip_d<double, 32, false>(s, a, grid, nstrips);
   } else if (nt == 32) {
@@ -1138,23 +1116,11 @@ void launch_strip(int dtype, hipStream_t s, const StripArgs& a, int nt, int grid
   } else if (nt == 64) {
     if (dtype == 0) launch_strip_d<double, 64, false>(s, a, grid, nstrips);
     else launch_strip_d<float, 64, false>(s, a, grid, nstrips);   // BK = 32 measured identical
-  } else if (dtype == 1 && env_int("SVGP_F32_THREADS", 256) == 256) {
+  } else if (dtype == 1) {
     launch_strip_d<float, 128, false>(s, a, grid, nstrips);
-  }
-#ifdef SVGP_EXPERIMENTS   // the 512-thread, 128-point builds (SVGP_STRIP_NT=128 / SVGP_F32_THREADS=512): measured and rejected, round 1-3
-  else if (dtype == 0) {
-    if (bk32 && a.kp.d <= 8) launch_strip_t<double, 128, 32, 512>(s, a, grid, nstrips);
-    else launch_strip_t<double, 128, 16, 512>(s, a, grid, nstrips);
   } else {
-    if (bk32 && a.kp.d <= 8) launch_strip_t<float, 128, 32, 512>(s, a, grid, nstrips);
-    else launch_strip_t<float, 128, 16, 512>(s, a, grid, nstrips);
-  }
-#else
-  else {
-    (void)bk32;
     leave_note("internal: no strip kernel for this (dtype, width)");   // unreachable: strip_nt() only plans the widths above
   }
-#endif
 }
 
 // the segmented strips (a.seg_*): nt = 32 / 64 (f64), 32 / 64 / 128 (f32); d <= 16 (wider inputs take the one-launch path).
@@ -1314,18 +1280,6 @@ static void launch_kuf_f(hipStream_t s, const KernelParams& kp, const T* zs, int
   else if (kp.d <= 8) launch_kuf_cols<T, 8, FAMILY>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
   else if (kp.d <= 16) launch_kuf_cols<T, 16, FAMILY>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
   else if (kp.d <= 32) {
-#ifdef SVGP_EXPERIMENTS
-    // A/B: two 16-row blocks per wave (128-row chunks) - 121-ish VGPRs instead of 139-169, i.e. two workgroups per CU
-    static const int nblk2 = exp_int("SVGP_KUF_NBLK2", 0);
-    if constexpr (sizeof(T) == 8) {
-      if (nblk2) {
-        if (kp.d <= 20) launch_kuf_cols<T, 20, FAMILY, 2>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
-        else if (kp.d <= 24) launch_kuf_cols<T, 24, FAMILY, 2>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
-        else launch_kuf_cols<T, 32, FAMILY, 2>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
-        return;
-      }
-    }
-#endif
     if (kp.d <= 20) launch_kuf_cols<T, 20, FAMILY>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
     else if (kp.d <= 24) launch_kuf_cols<T, 24, FAMILY>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
     else launch_kuf_cols<T, 32, FAMILY>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
@@ -1339,14 +1293,6 @@ static void launch_kuf_f(hipStream_t s, const KernelParams& kp, const T* zs, int
 template <typename T>
 static void launch_kuf_t(hipStream_t s, const KernelParams& kp, const T* zs, int64_t M, int64_t Mp, const T* x, int64_t ldx,
                          int64_t off, int64_t len, T* Kuf) {
-#ifdef SVGP_EXPERIMENTS
-  static const bool generic_knob = exp_int("SVGP_KUF_GENERIC", 0) == 1;   // A/B: the round-3 path for d > 32
-  if (kp.d > 32 && generic_knob) {
-    hipLaunchKernelGGL(kuf_generic_kernel<T>, dim3((unsigned)((M + 255) / 256), (unsigned)((len + 15) / 16)), dim3(k256), 0, s, kp, zs, M, Mp, x, ldx,
-                       off, len, Kuf);
-    return;
-  }
-#endif
   if (kp.family == KSE) launch_kuf_f<T, KSE>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
   else if (kp.family == KM32) launch_kuf_f<T, KM32>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);
   else launch_kuf_f<T, KM52>(s, kp, zs, M, Mp, x, ldx, off, len, Kuf);

@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # The EXPERIMENTS build of the library (knobs.hpp): the same sources with -DSVGP_EXPERIMENTS - every tuning knob / A-B switch read from the
-# environment and the measured-and-rejected variants of rounds 1-5 compiled in - as approximategps.jl_amd/csrc/ablate/libsvgp_experiments.so.
+# environment; each setting runs code the product build also runs - as approximategps.jl_amd/csrc/ablate/libsvgp_experiments.so.
 # Use it through SVGP_MI355X_LIB=<that path> (approxgp/_ffi.py); it exports svgp_debug_experiments, the product library does not.
 set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"; SRC="$ROOT/approximategps.jl_amd/csrc"; OUT="$SRC/ablate"; mkdir -p "$OUT"

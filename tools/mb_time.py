@@ -1,5 +1,5 @@
 """Median wall clock of svgp_elbo and svgp_elbo_grad over minibatch shapes, one process (process-wide knobs such as
-SVGP_STREAM2_RESERVE are read once): tools/mb_time.py [f64|f32]"""
+SVGP_STREAM2_LOW_PRIO are read once): tools/mb_time.py [f64|f32]"""
 import os, sys, time
 R = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(R, "..")); sys.path.insert(0, os.path.join(R, "..", "approximategps.jl_amd"))
