@@ -42,6 +42,11 @@ class Grads(C.Structure):
                 ("inv_lengthscale", C.POINTER(C.c_double)), ("z", C.c_void_p), ("m", C.c_void_p), ("Lq", C.c_void_p)]
 
 
+class InputGrad(C.Structure):
+    """svgp_input_grad: where d elbo / d x goes (element (f, j) at x[f * ld + j]; on_device 0: host, 1: device)."""
+    _fields_ = [("x", C.c_void_p), ("ld", C.c_int64), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_prep", C.c_double), ("ms_strip", C.c_double), ("ms_expect", C.c_double),
                 ("ms_kuf", C.c_double),
@@ -75,6 +80,10 @@ SYMBOLS = {
     "svgp_marginals": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P]),
     "svgp_elbo_grad_ext": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, _P, C.POINTER(C.c_double),
                                        C.POINTER(Terms), C.POINTER(Grads)]),
+    "svgp_elbo_grad_inputs": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.POINTER(C.c_double), C.POINTER(Terms),
+                                          C.POINTER(Grads), C.POINTER(InputGrad)]),
+    "svgp_elbo_grad_ext_inputs": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, _P,
+                                              C.POINTER(C.c_double), C.POINTER(Terms), C.POINTER(Grads), C.POINTER(InputGrad)]),
     "svgp_prior_kl": (C.c_int32, [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "svgp_elbo_host": (C.c_int32, [_P, C.POINTER(ModelDesc), C.c_int32, C.c_int64, _P, _P, C.c_double,
                                    C.POINTER(C.c_double), C.POINTER(Terms)]),
@@ -277,6 +286,7 @@ class DeviceData:
             n, d = x.shape  # RowVecs: n×d column-major, feature-contiguous
             xbuf = np.asfortranarray(x)
         self._x = xbuf
+        self.layout = layout
         self._y = None if y is None else np.ascontiguousarray(np.asarray(y, dtype=dt))
         if self._y is not None and self._y.shape[0] != n:
             raise ValueError("x and y lengths differ")
@@ -289,6 +299,7 @@ class DeviceData:
     def wrap(cls, ctx: Context, dtype, d: int, n: int, ldx: int, x_ptr: int, y_ptr: int | None):
         self = cls.__new__(cls)
         self.ctx, self.n, self.d, self.dtype = ctx, n, d, dtype_code(dtype)
+        self.layout = ROWVECS   # feature-major storage
         h = C.c_void_p()
         ctx.check(ctx.lib.svgp_data_wrap_device(ctx.h, self.dtype, d, n, ldx, C.c_void_p(x_ptr),
                                                 C.c_void_p(y_ptr) if y_ptr else None, C.byref(h)))
@@ -369,13 +380,33 @@ class DeviceModel:
         self.ctx.check(self.ctx.lib.svgp_marginals(self.ctx.h, self.h, data.h, off, length, _ptr(mu), _ptr(var)))
         return mu, var
 
-    def elbo_grad(self, data: DeviceData, off=0, length=None, num_data=0.0, z_shape=None, shard=None, ext=None, out=None):
+    def elbo_grad(self, data: DeviceData, off=0, length=None, num_data=0.0, z_shape=None, shard=None, ext=None, out=None,
+                  inputs=None):
         """-> (elbo, terms, dict(variance, inv_lengthscale, z, m, Lq, lik_sigma2, mean_const)); z in the layout it was given.
         shard = (scale, kl_weight) evaluates the data-parallel shard form svgp_elbo_grad_shard instead.
         ext = (sum_e, g_mu, g_v): a likelihood the host evaluated on `marginals` (svgp_elbo_grad_ext).
         out = the gradient dict of an earlier call: its arrays are written in place instead of allocating M^2 fresh elements per step
-        (a training loop that has consumed the previous gradient; at M = 2048 the first touch of 33 MB of new pages costs ~2 ms)."""
+        (a training loop that has consumed the previous gradient; at M = 2048 the first touch of 33 MB of new pages costs ~2 ms).
+        inputs = True: also d elbo / d x of the batch as dict["x"], a host array in the data's layout (ColVecs (d, n), RowVecs and
+        wrapped device data (n, d), a vector (n,)); inputs = (device_ptr, ld): written to device memory, element (f, j) at
+        device_ptr[f * ld + j] on the context's stream (svgp_elbo_grad_inputs / svgp_elbo_grad_ext_inputs)."""
         length = data.n - off if length is None else length
+        gx, xb = None, None
+        if inputs is not None and inputs is not False:
+            if shard is not None:
+                raise ValueError("d elbo / d x is not available for the shard form (svgp_elbo_grad_shard)")
+            if inputs is True:
+                layout = getattr(data, "layout", COLVECS)
+                if layout == VEC:
+                    xb = np.zeros(length, dtype=np_dtype(self.dtype))
+                elif layout == COLVECS:
+                    xb = np.zeros((data.d, length), dtype=np_dtype(self.dtype))              # C order: feature-major, ld = length
+                else:
+                    xb = np.zeros((length, data.d), dtype=np_dtype(self.dtype), order="F")   # F order: feature-major, ld = length
+                gx = InputGrad(_ptr(xb), length, 0, 0)
+            else:
+                ptr, ld = inputs
+                gx = InputGrad(C.c_void_p(int(ptr)), int(ld), 1, 0)
         dt = np_dtype(self.dtype)
         zshape = z_shape if z_shape is not None else ((self.M,) if self.d == 1 else (self.d, self.M))
         if out is not None:
@@ -395,8 +426,15 @@ class DeviceModel:
             gmu, gv = (np.ascontiguousarray(a, dtype=np.float64) for a in ext[1:])
             if gmu.shape != (length,) or gv.shape != (length,):
                 raise ValueError("one point gradient per point of the batch")
-            rc = self.ctx.lib.svgp_elbo_grad_ext(self.ctx.h, self.h, data.h, off, length, float(num_data), float(ext[0]),
-                                                 _ptr(gmu), _ptr(gv), C.byref(out), C.byref(terms), C.byref(g))
+            if gx is not None:
+                rc = self.ctx.lib.svgp_elbo_grad_ext_inputs(self.ctx.h, self.h, data.h, off, length, float(num_data), float(ext[0]),
+                                                            _ptr(gmu), _ptr(gv), C.byref(out), C.byref(terms), C.byref(g), C.byref(gx))
+            else:
+                rc = self.ctx.lib.svgp_elbo_grad_ext(self.ctx.h, self.h, data.h, off, length, float(num_data), float(ext[0]),
+                                                     _ptr(gmu), _ptr(gv), C.byref(out), C.byref(terms), C.byref(g))
+        elif gx is not None:
+            rc = self.ctx.lib.svgp_elbo_grad_inputs(self.ctx.h, self.h, data.h, off, length, float(num_data), C.byref(out),
+                                                    C.byref(terms), C.byref(g), C.byref(gx))
         elif shard is None:
             rc = self.ctx.lib.svgp_elbo_grad(self.ctx.h, self.h, data.h, off, length, float(num_data), C.byref(out),
                                              C.byref(terms), C.byref(g))
@@ -404,8 +442,10 @@ class DeviceModel:
             rc = self.ctx.lib.svgp_elbo_grad_shard(self.ctx.h, self.h, data.h, off, length, float(shard[0]), float(shard[1]),
                                                    C.byref(out), C.byref(terms), C.byref(g))
         self.ctx.check(rc, terms)
-        return out.value, terms, dict(variance=g.variance, inv_lengthscale=il, z=zb, m=mb, Lq=Lb,
-                                      lik_sigma2=g.lik_sigma2, mean_const=g.mean_const)
+        res = dict(variance=g.variance, inv_lengthscale=il, z=zb, m=mb, Lq=Lb, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const)
+        if xb is not None:
+            res["x"] = xb
+        return out.value, terms, res
 
     def prior_kl(self):
         kl, ld = C.c_double(), C.c_double()

@@ -156,7 +156,7 @@ def elbo(sva: SparseVariationalApproximation, fx, y, *, num_data=None, quadratur
     return (val, terms) if return_terms else val
 
 
-def _elbo_host_likelihood(sva, lfx, y, num_data, quadrature, ctx, dtype, want_grad):
+def _elbo_host_likelihood(sva, lfx, y, num_data, quadrature, ctx, dtype, want_grad, wrt_inputs=False):
     """The route of a likelihood outside the ABI's enumeration: marginals(f_post(x)) (SVA:354) from the device, SVA:355 on the
     host, KL / backward pass on the device.  Value: E num_data / n - KL (SVA:357-359)."""
     if quadrature is not None and not isinstance(quadrature, (GaussHermiteExpectation, DefaultExpectationMethod)):
@@ -173,7 +173,8 @@ def _elbo_host_likelihood(sva, lfx, y, num_data, quadrature, ctx, dtype, want_gr
         nd = float(num_data) if num_data is not None else float(n)
         if not want_grad:
             return sum_e * nd / n - model.prior_kl()[0], None
-        val, _, grads = model.elbo_grad(data, 0, n, nd, z_shape=np.asarray(sva.fz.x).shape, ext=(sum_e, gmu, gv))
+        val, _, grads = model.elbo_grad(data, 0, n, nd, z_shape=np.asarray(sva.fz.x).shape, ext=(sum_e, gmu, gv),
+                                        inputs=True if wrt_inputs else None)
         return val, grads
     finally:
         model.free()
@@ -181,10 +182,11 @@ def _elbo_host_likelihood(sva, lfx, y, num_data, quadrature, ctx, dtype, want_gr
 
 
 def elbo_and_gradient(sva: SparseVariationalApproximation, fx, y, *, num_data=None, quadrature=None, ctx=None, dtype=None,
-                      small_problems="run"):
+                      small_problems="run", wrt_inputs=False):
     """ELBO and its gradient w.r.t. (kernel variance, inverse lengthscales, inducing inputs z, mean(q) m, the lower factor
     Lq of cov(q), Gaussian noise σ², ConstMean) — what `Zygote.gradient(-elbo, ...)` yields for the reference's training
-    loops (examples/a-regression/script.jl:188-194); the Julia shim wraps it as a ChainRulesCore.rrule."""
+    loops (examples/a-regression/script.jl:188-194); the Julia shim wraps it as a ChainRulesCore.rrule.
+    wrt_inputs=True: the dict also holds "x", d elbo / d x shaped like fx.x (for a learned feature map in front of the GP)."""
     if isinstance(fx, FiniteGP):
         if not fx.is_isotropic():
             raise RuntimeError("The observation noise fx.Σy must be homoscedastic.")
@@ -196,14 +198,14 @@ def elbo_and_gradient(sva: SparseVariationalApproximation, fx, y, *, num_data=No
     _decline_if_small(sva, lfx, y, small_problems, True, ctx)
     ctx = ctx or _ffi.default_context()
     if isinstance(lfx.lik, CallerLikelihood):
-        return _elbo_host_likelihood(sva, lfx, y, num_data, quadrature, ctx, dtype, True)
+        return _elbo_host_likelihood(sva, lfx, y, num_data, quadrature, ctx, dtype, True, wrt_inputs)
     desc, keep = _desc(sva, lfx.lik, quadrature, dtype)
     y = np.asarray(y)
     data = _ffi.DeviceData(ctx, lfx.fx.x, y, _ffi.np_dtype(desc.dtype))
     model = _ffi.DeviceModel(ctx, desc, keep)
     try:
         val, _, grads = model.elbo_grad(data, 0, y.shape[0], float(num_data) if num_data is not None else 0.0,
-                                        z_shape=np.asarray(sva.fz.x).shape)
+                                        z_shape=np.asarray(sva.fz.x).shape, inputs=True if wrt_inputs else None)
     finally:
         model.free()
         data.free()

@@ -1371,6 +1371,8 @@ struct GradCall {
   // host-evaluated likelihood (svgp_elbo_grad_ext): per-point dE/dmu, dE/dv (host, fp64, [len] each) and the host's sum E
   const double *ext_gmu = nullptr, *ext_gv = nullptr;
   double ext_sum_e = 0.0;
+  // svgp_elbo_grad_inputs / svgp_elbo_grad_ext_inputs: where d elbo / d x goes (NULL: not requested, nothing more is launched)
+  const svgp_input_grad* gx = nullptr;
 };
 
 // out = Xt' Yt for M x M operands ("k-major": Xt[k][r] at Xt[k Mp + r]; a row-major matrix Z is the operand Z, a column-major
@@ -1628,6 +1630,12 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
     launch_kgrad(dt, s, kp, m->zs, Mp, M, data->x, data->ldx, off + c0, 0, clen, clen, w->Pt, w->gmu, w->gv, w->alpha, ksl, w->ns_uf,
                  w->rp_uf, w->sp_uf, 1);
     KCHECK(ctx, "kgrad uf");
+    if (gc.gx) {   // d elbo / d x of the chunk's points, from the same P while Pt holds the chunk (host output: into w->xg, [d][len])
+      const bool dev = gc.gx->on_device != 0;
+      launch_xgrad(dt, s, kp, m->zs, Mp, M, data->x, data->ldx, off + c0, clen, w->Pt, w->gmu, w->gv, w->alpha, dev ? gc.gx->x : w->xg,
+                   dev ? gc.gx->ld : len, c0);
+      KCHECK(ctx, "xgrad");
+    }
     launch_sum5(s, w->partial5, n5, w->sums);
     int64_t sl = ((ncp + ns_syrk - 1) / ns_syrk + 15) / 16 * 16;   // as even as the 16-point k-step allows
     // W (+)= A diag(2 g_v) A' (lower tiles, split-K slices): the first chunk overwrites, so the slice buffer needs no zeroing
@@ -1890,9 +1898,11 @@ int grad_finish(svgp_ctx* ctx, svgp_model* m, GradCall& gc, double* elbo_out, sv
 
 int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double scale, double klw,
                    double num_data, bool collective, double* elbo_out, svgp_terms* terms_out, svgp_grads* g,
-                   const double* ext_gmu = nullptr, const double* ext_gv = nullptr, double ext_sum_e = 0.0) {
+                   const double* ext_gmu = nullptr, const double* ext_gv = nullptr, double ext_sum_e = 0.0,
+                   const svgp_input_grad* gx = nullptr) {
   GradCall gc;
   gc.ext_gmu = ext_gmu; gc.ext_gv = ext_gv; gc.ext_sum_e = ext_sum_e;
+  gc.gx = gx;
   gc.collective = collective && ctx && ctx->comm;
   gc.scale = scale;
   gc.klw = gc.collective ? 1.0 / double(ctx->world) : klw;
@@ -1902,6 +1912,17 @@ int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
   if (rc == SVGP_OK && (!(scale > 0.0) || !(klw >= 0.0))) rc = fail(ctx, SVGP_INVALID_ARG, "scale must be positive and kl_weight non-negative");
   if (rc == SVGP_OK && hipSetDevice(ctx->device) != hipSuccess) rc = fail(ctx, SVGP_HIP_ERROR, "hipSetDevice failed");
   if (rc == SVGP_OK) rc = grad_workspace(ctx, m, len, &gc.w);
+  if (rc == SVGP_OK && gx && !gx->on_device) {   // host output: the kernel writes [d][len] on the device, one copy brings it over
+    const size_t xb = size_t(m->d) * size_t(len) * m->es;
+    GradWs* w = gc.w;
+    if (w->xg_b < xb) {
+      if (w->xg) (void)hipFree(w->xg);
+      w->xg = nullptr;
+      w->xg_b = 0;
+      if (hipMalloc(&w->xg, xb) != hipSuccess) { w->xg = nullptr; rc = fail(ctx, SVGP_OOM, "hipMalloc failed for d elbo / d x"); }
+      else w->xg_b = xb;
+    }
+  }
   if (rc != SVGP_OK) return (ctx && gc.collective) ? grad_fail_collective(ctx, rc) : rc;
   if (gc.collective) {
     rc = grad_handshake(ctx, gc, len, false);
@@ -1922,7 +1943,25 @@ int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
   }
   rc = grad_collective(ctx, m, gc, rc);
   if (rc) return rc;
+  if (gx && !gx->on_device)   // (never all-reduced: this rank's points; the stream synchronisation of grad_finish covers the copy)
+    HIPC(ctx, hipMemcpy2DAsync(gx->x, size_t(gx->ld) * m->es, gc.w->xg, size_t(len) * m->es, size_t(len) * m->es, size_t(m->d),
+                               hipMemcpyDeviceToHost, ctx->stream));
   return grad_finish(ctx, m, gc, elbo_out, terms_out, g);
+}
+
+// argument checks of the `_inputs` calls (before anything is enqueued; a NULL or inconsistent data handle is check_batch's to report)
+int check_input_grad(svgp_ctx* ctx, const svgp_data* data, int64_t len, const svgp_input_grad* gx) {
+  if (!gx || !gx->x) return fail(ctx, SVGP_INVALID_ARG, "null input-gradient output");
+  if (gx->ld < len) return fail(ctx, SVGP_INVALID_ARG, "input-gradient leading dimension smaller than the batch");
+  if ((gx->on_device != 0 && gx->on_device != 1) || gx->reserved != 0)
+    return fail(ctx, SVGP_INVALID_ARG, "input-gradient on_device must be 0 or 1 and reserved 0");
+  if (gx->on_device && data && data->x && len >= 1 && data->d >= 1) {
+    const size_t es = data->dtype == SVGP_F64 ? 8 : 4;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(gx->x), a1 = a0 + (size_t(data->d - 1) * size_t(gx->ld) + size_t(len)) * es;
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(data->x), b1 = b0 + (size_t(data->d - 1) * size_t(data->ldx) + size_t(data->n)) * es;
+    if (a0 < b1 && b0 < a1) return fail(ctx, SVGP_INVALID_ARG, "input-gradient output overlaps the data's x");
+  }
+  return SVGP_OK;
 }
 }  // namespace
 
@@ -2000,6 +2039,28 @@ extern "C" int32_t svgp_elbo_grad_ext(svgp_ctx* ctx, svgp_model* m, const svgp_d
   }
   const double scale = len >= 1 ? (num_data > 0 ? num_data : double(len)) / double(len) : 1.0;
   return elbo_grad_impl(ctx, m, data, off, len, scale, 1.0, num_data, true, elbo_out, terms_out, g, g_mu, g_v, sum_e);
+}
+
+// svgp_elbo_grad / svgp_elbo_grad_ext + d elbo / d x (include/svgp_mi355x.h): the same launches, plus one xgrad_mfma_kernel per gradient chunk
+extern "C" int32_t svgp_elbo_grad_inputs(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len,
+                                         double num_data, double* elbo_out, svgp_terms* terms_out, svgp_grads* g,
+                                         const svgp_input_grad* gx) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  const int rc = check_input_grad(ctx, data, len, gx);
+  if (rc) return ctx->comm ? grad_fail_collective(ctx, rc) : rc;
+  const double scale = len >= 1 ? (num_data > 0 ? num_data : double(len)) / double(len) : 1.0;
+  return elbo_grad_impl(ctx, m, data, off, len, scale, 1.0, num_data, true, elbo_out, terms_out, g, nullptr, nullptr, 0.0, gx);
+}
+
+extern "C" int32_t svgp_elbo_grad_ext_inputs(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len,
+                                             double num_data, double sum_e, const double* g_mu, const double* g_v,
+                                             double* elbo_out, svgp_terms* terms_out, svgp_grads* g, const svgp_input_grad* gx) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  int rc = (!g_mu || !g_v) ? fail(ctx, SVGP_INVALID_ARG, "null point gradients") : SVGP_OK;
+  if (rc == SVGP_OK) rc = check_input_grad(ctx, data, len, gx);
+  if (rc) return ctx->comm ? grad_fail_collective(ctx, rc) : rc;
+  const double scale = len >= 1 ? (num_data > 0 ? num_data : double(len)) / double(len) : 1.0;
+  return elbo_grad_impl(ctx, m, data, off, len, scale, 1.0, num_data, true, elbo_out, terms_out, g, g_mu, g_v, sum_e, gx);
 }
 
 // ================================================================================================

@@ -77,10 +77,15 @@ struct GradWs {
          *invl_d = nullptr, *scal_out = nullptr, *avec = nullptr, *kred = nullptr, *gemv_part = nullptr;
   int64_t part5_strips = 0;
   size_t rp_uf_b = 0, sp_uf_b = 0, rp_uu_b = 0, sp_uu_b = 0, g_b = 0;
+  void* xg = nullptr;   // d elbo / d x of a host-output svgp_elbo_grad_inputs call, [d][len], allocated on first use (xg_b bytes)
+  size_t xg_b = 0;
   void release() {
     for (void* p : all)
       if (p) (void)hipFree(p);
     all.clear();
+    if (xg) (void)hipFree(xg);
+    xg = nullptr;
+    xg_b = 0;
   }
 };
 

@@ -857,6 +857,220 @@ void launch_kgrad_f(hipStream_t s, const KernelParams& kp, const T* zs, int64_t 
 #undef SVGP_KGM
 }
 
+// ---- d elbo / d x: the point-wise reduction of the same W (svgp_elbo_grad_inputs) ---------------------------------------------
+// With s = lambda o x, r2_ij = |s_j - zs_i|^2 and W_ij = P_ij dK/dr2 (P = Kuf_bar, as in kgrad_mfma_kernel):
+//     x_bar_fj = 2 lambda_f sum_i W_ij (s_fj - zs_fi) = 2 lambda_f ((s_fj - c_f) S_j - Y_fj),   S_j = sum_i W_ij,  Y_fj = sum_i W_ij (zs_fi - c_f)
+// - kgrad_mfma_kernel with the roles of points and inducing rows swapped.  A wave owns 16 points for all Mp inducing rows (a workgroup 64
+// points), walking them in 16-row tiles staged through LDS 64 rows at a time:
+//   (1) r2 tile D[inducing row][point] on the MFMA (A = the staged z rows, B = the wave's x fragments times -2 (SE: 1), held in registers;
+//       accumulator preloaded with the norms);
+//   (2) VALU: kernel derivative, P = alpha_i g_mu_j + 2 g_v_j (R A)_ij, W; S_j accumulates in the lane that owns column j;
+//   (3) Y (16 points x 16 features) += W' (16 points x 4 rows) Z (4 rows x 16 features): register r of the D tile, as it stands, is the A
+//       operand of a 16x16x4 MFMA whose k-slots are the rows held in register r of the four lane groups.
+// The D slots are permuted (f64: slot g + 4 r <- row 4 g + r) so that the four registers of a lane are four CONSECUTIVE inducing rows of its
+// point: the P tile is read as one 4-element vector per lane.  No sum crosses points: the result does not depend on the grid, and needs
+// no atomics.  Centre c = the middle of the range of the workgroup's points (the expansion cancels where |x - z| << |x - c|; same reasoning
+// as kgrad_mfma_kernel's centres).  fp32: per 64-row block sums in fp32 (MFMA accumulators included), totals in fp64.
+template <typename T, int FAMILY, int DL>
+__global__ void __launch_bounds__(k256, 2) xgrad_mfma_kernel(KernelParams kp, const T* __restrict__ zs, int64_t Mp, int64_t M,
+                                                             const T* __restrict__ x, int64_t ldx, int64_t xoff, int64_t n,
+                                                             const T* __restrict__ Pt, const T* __restrict__ gmu,
+                                                             const T* __restrict__ gv, const T* __restrict__ alpha,
+                                                             T* __restrict__ out, int64_t ldo, int64_t ooff) {
+  using M16 = Mfma16<T>;
+  using acc_t = typename M16::acc_t;
+  using v4 = T __attribute__((ext_vector_type(4)));
+  constexpr bool kF64 = (sizeof(T) == 8);
+  constexpr int IB = 64, KS = DL / 4, CT = (DL + 15) / 16, NTILE = IB / 16;
+  constexpr int NQ = (CT <= 2) ? 2 : 1;             // independent accumulator sets of step (3)
+  constexpr int ZLD = DL + (kF64 ? 6 : 4);          // staged row stride; column DL holds c1 |z_i - c|^2
+  constexpr int OLD = 65;                           // output transposition: [feature][64 points + 1]
+  static_assert(IB * ZLD >= DL * OLD, "the output transposition reuses the z tile");
+  constexpr T c1 = (FAMILY == KSE) ? T(-0.5) : T(1);      // SE: the tile holds -r2 / 2, the argument of exp
+  constexpr T ascale = (FAMILY == KSE) ? T(1) : T(-2);
+  __shared__ __attribute__((aligned(16))) T zt[IB * ZLD];
+  __shared__ T al_s[IB];
+  __shared__ T cx[DL];
+  __shared__ double sS[4][16];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), l15 = lane & 15, g = lane >> 4;
+  const int d = kp.d;
+  const T* __restrict__ invl = static_cast<const T*>(kp.invl);
+  const int64_t jw0 = int64_t(blockIdx.x) * 64 + wave * 16;   // the wave's first point (chunk-relative)
+  if (int(threadIdx.x) < DL) cx[threadIdx.x] = T(0);
+  __syncthreads();
+  for (int f = wave; f < d; f += 4) {   // range of feature f over the workgroup's valid points (a wave per feature, a lane per point)
+    const int64_t p = int64_t(blockIdx.x) * 64 + lane;
+    const T v = p < n ? x[int64_t(f) * ldx + xoff + p] * invl[f] : T(0);
+    const bool ok = p < n && v == v;   // (a NaN point leaves the centre of the others alone)
+    T lo = ok ? v : T(INFINITY), hi = ok ? v : T(-INFINITY);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      lo = fmin(lo, __shfl_xor(lo, o));
+      hi = fmax(hi, __shfl_xor(hi, o));
+    }
+    if (!(lo <= hi)) lo = hi = T(0);
+    if (lane == 0) cx[f] = T(0.5) * (lo + hi);
+  }
+  __syncthreads();
+  // this lane's point (B-operand column of step (1), A-operand row of step (3)); points beyond n repeat the last one with P = 0
+  const int64_t j = jw0 + l15;
+  const bool jok = j < n;
+  const int64_t jj = jok ? j : n - 1;
+  T xb[KS], xn = T(0);
+#pragma unroll
+  for (int q = 0; q < KS; ++q) {
+    const int f = 4 * q + g;
+    const T v = (f < d) ? x[int64_t(f) * ldx + xoff + jj] * invl[f] - cx[f] : T(0);
+    xb[q] = ascale * v;
+    xn = fma(v, v, xn);
+  }
+  xn += __shfl_xor(xn, 16);
+  xn += __shfl_xor(xn, 32);
+  xn *= c1;
+  const T gm = jok ? gmu[jj] : T(0), gv2 = jok ? T(2) * gv[jj] : T(0);
+  // the staged row a lane reads as A operand of step (1): D slot s must be row 4 g + r where the lane holding it is (g, register r)
+  const int zrow = kF64 ? (4 * (l15 & 3) + (l15 >> 2)) : l15;
+  const T* __restrict__ prow = Pt + jj * Mp + 4 * g;
+  acc_t Y[NQ][CT];
+  double Yd[kF64 ? 1 : CT][4], Sd = 0.0;
+  T Sl = T(0);
+#pragma unroll
+  for (int c = 0; c < CT; ++c) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) Y[q][c] = acc_t{0, 0, 0, 0};
+    if constexpr (!kF64) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Yd[c][r] = 0.0;
+    }
+  }
+  for (int64_t ib = 0; ib < Mp; ib += IB) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < IB * DL; e += k256) {   // rows of the block, centred (zeros in the unused feature slots)
+      const int r = e % IB, f = e / IB;
+      zt[r * ZLD + f] = f < d ? zs[int64_t(f) * Mp + ib + r] - cx[f] : T(0);
+    }
+    if (threadIdx.x < IB) al_s[threadIdx.x] = alpha[ib + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x < IB) {
+      const T* __restrict__ zp = zt + threadIdx.x * ZLD;
+      T s = T(0);
+#pragma unroll
+      for (int f = 0; f < DL; ++f) s = fma(zp[f], zp[f], s);
+      zt[threadIdx.x * ZLD + DL] = c1 * s;
+    }
+    __syncthreads();
+    v4 pn = *reinterpret_cast<const v4*>(prow + ib);
+#pragma unroll 1
+    for (int t = 0; t < NTILE; ++t) {
+      const v4 pv = pn;
+      if (t + 1 < NTILE) pn = *reinterpret_cast<const v4*>(prow + ib + 16 * (t + 1));
+      const T* __restrict__ zr = zt + (16 * t) * ZLD;
+      // (1) the distance tile
+      acc_t a, a2 = {0, 0, 0, 0};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a[r] = zr[(4 * g + r) * ZLD + DL] + xn;
+      const T* __restrict__ za = zr + zrow * ZLD + g;
+      if constexpr (KS >= 4) {   // two chains
+#pragma unroll
+        for (int q = 0; q < KS; q += 2) {
+          a = M16::mma(za[4 * q], xb[q], a);
+          a2 = M16::mma(za[4 * q + 4], xb[q + 1], a2);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) a[r] += a2[r];
+      } else {
+#pragma unroll
+        for (int q = 0; q < KS; ++q) a = M16::mma(za[4 * q], xb[q], a);
+      }
+      // (2) kernel derivative, P, W (rows beyond M: W = 0)
+      T w[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rl = 16 * t + 4 * g + r;
+        const T p = fma(gv2, pv[r], al_s[rl] * gm);
+        T wr;
+        if constexpr (FAMILY == KSE) {
+          wr = p * kexp(a[r] > T(0) ? T(0) : a[r]);   // unit variance, without the -1/2 of dK/dr2 (applied at the end)
+        } else {
+          T k, dk;
+          kappa_and_d<T, FAMILY>(a[r] < T(0) ? T(0) : a[r], T(1), k, dk);
+          wr = p * dk;
+        }
+        w[r] = (ib + rl < M) ? wr : T(0);
+        Sl += w[r];
+      }
+      // (3) Y += W' Z
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const T* __restrict__ zb = zr + (4 * g + r) * ZLD + l15;
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+          const T zv = (DL >= 16 || l15 < DL) ? zb[16 * c] : T(0);
+          Y[r % NQ][c] = M16::mma(w[r], zv, Y[r % NQ][c]);
+        }
+      }
+    }
+    if constexpr (!kF64) {   // the block's fp32 sums join the fp64 totals
+      Sd += double(Sl);
+      Sl = T(0);
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          T v = Y[0][c][r];
+          if constexpr (NQ == 2) v += Y[1][c][r];
+          Yd[c][r] += double(v);
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) Y[q][c] = acc_t{0, 0, 0, 0};
+      }
+    }
+  }
+  // ---- closing: S_j over the four lane groups, then x_bar in the D layout of step (3): lane (feature l15 + 16 c, g), register r <-> point
+  // M16::row(lane, r) of the wave's 16
+  double S = kF64 ? double(Sl) : Sd;
+  S += __shfl_xor(S, 16);
+  S += __shfl_xor(S, 32);
+  if (g == 0) sS[wave][l15] = S;
+  __syncthreads();   // (also: every wave is done with zt)
+  const double wsc = (FAMILY == KSE) ? -0.5 * kp.variance : kp.variance;
+#pragma unroll
+  for (int c = 0; c < CT; ++c) {
+    const int f = l15 + 16 * c;
+    if (f >= d) continue;
+    const double c2 = 2.0 * double(invl[f]) * wsc;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int pj = M16::row(lane, r);
+      const int64_t jp = jw0 + pj;
+      double y;
+      if constexpr (kF64) { y = double(Y[0][c][r]); if constexpr (NQ == 2) y += double(Y[1][c][r]); }
+      else y = Yd[c][r];
+      const T xs = x[int64_t(f) * ldx + xoff + (jp < n ? jp : n - 1)] * invl[f] - cx[f];
+      zt[f * OLD + wave * 16 + pj] = T(c2 * (double(xs) * sS[wave][pj] - y));
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < d * 64; e += k256) {   // feature-major out, 64 consecutive points per feature
+    const int f = e >> 6, p = e & 63;
+    const int64_t jp = int64_t(blockIdx.x) * 64 + p;
+    if (jp < n) out[int64_t(f) * ldo + ooff + jp] = zt[f * OLD + p];
+  }
+}
+
+template <typename T, int FAMILY>
+void launch_xgrad_f(hipStream_t s, const KernelParams& kp, const T* zs, int64_t Mp, int64_t M, const T* x, int64_t ldx, int64_t xoff,
+                    int64_t n, const T* Pt, const T* gmu, const T* gv, const T* alpha, T* out, int64_t ldo, int64_t ooff) {
+  const dim3 grid((unsigned)((n + 63) / 64));
+#define SVGP_XGM(DL) hipLaunchKernelGGL((xgrad_mfma_kernel<T, FAMILY, DL>), grid, dim3(k256), 0, s, kp, zs, Mp, M, x, ldx, xoff, n, Pt, \
+                                        gmu, gv, alpha, out, ldo, ooff)
+  if (kp.d <= 8) SVGP_XGM(8);
+  else if (kp.d <= 16) SVGP_XGM(16);
+  else if (kp.d <= 32) SVGP_XGM(32);
+  else SVGP_XGM(64);
+#undef SVGP_XGM
+}
+
 }  // namespace
 
 // ---- launchers -----------------------------------------------------------------------------------------------
@@ -1007,6 +1221,22 @@ void launch_kgrad(int dtype, hipStream_t s, const KernelParams& kp, const void* 
     else
       launch_kgrad_f<T, KM52>(s, kp, (const T*)zs, Mp, (const T*)x, ldx, xoff, prescaled, n, nvalid, (const T*)Pt,
                               (const T*)gmu, (const T*)gv, (const T*)alpha, slice_len, nslices, rowpart, scalpart, kmb, M);
+  });
+}
+
+void launch_xgrad(int dtype, hipStream_t s, const KernelParams& kp, const void* zs, int64_t Mp, int64_t M, const void* x, int64_t ldx,
+                  int64_t xoff, int64_t n, const void* Pt, const void* gmu, const void* gv, const void* alpha, void* out, int64_t ldo,
+                  int64_t ooff) {
+  GD(dtype, T, {
+    if (kp.family == KSE)
+      launch_xgrad_f<T, KSE>(s, kp, (const T*)zs, Mp, M, (const T*)x, ldx, xoff, n, (const T*)Pt, (const T*)gmu, (const T*)gv,
+                             (const T*)alpha, (T*)out, ldo, ooff);
+    else if (kp.family == KM32)
+      launch_xgrad_f<T, KM32>(s, kp, (const T*)zs, Mp, M, (const T*)x, ldx, xoff, n, (const T*)Pt, (const T*)gmu, (const T*)gv,
+                              (const T*)alpha, (T*)out, ldo, ooff);
+    else
+      launch_xgrad_f<T, KM52>(s, kp, (const T*)zs, Mp, M, (const T*)x, ldx, xoff, n, (const T*)Pt, (const T*)gmu, (const T*)gv,
+                              (const T*)alpha, (T*)out, ldo, ooff);
   });
 }
 

@@ -184,6 +184,10 @@ void launch_linv_t_gemv(int dtype, hipStream_t s, const void* LinvRM, const void
 void launch_kgrad(int dtype, hipStream_t s, const KernelParams& kp, const void* zs, int64_t Mp, int64_t M, const void* x, int64_t ldx,
                   int64_t xoff, int prescaled, int64_t n, int64_t nvalid, const void* Pt, const void* gmu,
                   const void* gv, const void* alpha, int64_t slice_len, int nslices, double* rowpart, double* scalpart, int kmb = 0);
+// d elbo / d x of the chunk's n points from the same P (launch_kgrad's data part): out[f * ldo + ooff + j], j < n, feature-major
+void launch_xgrad(int dtype, hipStream_t s, const KernelParams& kp, const void* zs, int64_t Mp, int64_t M, const void* x, int64_t ldx,
+                  int64_t xoff, int64_t n, const void* Pt, const void* gmu, const void* gv, const void* alpha, void* out, int64_t ldo,
+                  int64_t ooff);
 // fused gradient path: sums of the per-strip partials, W = A diag(2 g_v) A' from its split-K lower tiles, (A g_mu), and the
 // assembly of Lq_bar / Lk_bar from G1 = 2 W Lq, G2 = 2 R W and the rank-one term alpha (A g_mu)'
 void launch_sum5(hipStream_t s, const double* partial, int nblocks, double* sums);

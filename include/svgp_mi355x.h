@@ -36,7 +36,9 @@ extern "C" {
 #define SVGP_ABI_VERSION 5 /* 3 = 2 + svgp_marginals, svgp_elbo_grad_ext, SVGP_LIK_BERNOULLI_NORMCDF; 4 = 3 + svgp_offload_advice /
                               svgp_offload_work and svgp_timing.ms_chol; 5 = 4 + svgp_last_timing_sized: svgp_last_timing writes the
                               48-byte v2 / v3 layout again (v4 let it write 56 bytes into a buffer a v3 host sized at 48), the
-                              fields appended since are read through the sized call.  Additions only: v2 / v3 callers keep working */
+                              fields appended since are read through the sized call.  Additions only: v2 / v3 callers keep working.
+                              Entry points added without a version step (hosts find them by symbol: dlsym / hasattr): svgp_elbo_grad_inputs,
+                              svgp_elbo_grad_ext_inputs */
 
 /* status codes -> Julia exceptions raised by the shim */
 enum {
@@ -285,6 +287,31 @@ int32_t svgp_marginals(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, 
 int32_t svgp_elbo_grad_ext(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
                            double num_data, double sum_e, const double* g_mu, const double* g_v, double* elbo_out,
                            svgp_terms* terms_out, svgp_grads* grads_out);
+
+/* ---- d elbo / d x: the gradient with respect to the data inputs (what Zygote gives the reference's elbo for lfx.fx.x) ----------
+ * For a learned feature map in front of the GP (x = NN(theta)(raw)): the host back-propagates x_bar into theta.
+ *   svgp_elbo_grad_inputs      = svgp_elbo_grad     + x_bar
+ *   svgp_elbo_grad_ext_inputs  = svgp_elbo_grad_ext + x_bar
+ * Every other output is the one the call without `_inputs` returns, bitwise, on the same context and inputs.  x_bar covers the batch
+ * [batch_off, batch_off + batch_len): element (f, j) at gx->x[f * gx->ld + j] (feature-major: the storage of RowVecs and of
+ * svgp_data_wrap_device), in the dtype of the data.  x_bar_j depends on point j alone (and on the model): a NaN coordinate of point j
+ * gives NaN in column j only.  On a context with a communicator both calls are collective like their counterparts, and x_bar is NEVER
+ * all-reduced: each rank gets its own shard's, with the scale of the global batch size.  fp32: within 5e-4 of the fp64 x_bar relative
+ * to its largest entry (the z / inverse-lengthscale tolerance above).  SVGP_INVALID_ARG, before anything is enqueued, for a NULL gx or
+ * gx->x, ld < batch_len, on_device not 0 / 1, reserved != 0, or a device gx->x overlapping the data's x storage. */
+typedef struct svgp_input_grad {
+  void* x;           /* d elbo / d x, d rows of ld elements (columns j >= batch_len are not touched) */
+  int64_t ld;        /* >= batch_len */
+  int32_t on_device; /* 0: host memory, written before the call returns; 1: device memory of the context's GPU, written on the context's stream */
+  int32_t reserved;  /* must be 0 */
+} svgp_input_grad;   /* 24 bytes */
+int32_t svgp_elbo_grad_inputs(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off,
+                              int64_t batch_len, double num_data, double* elbo_out, svgp_terms* terms_out,
+                              svgp_grads* grads_out, const svgp_input_grad* gx);
+int32_t svgp_elbo_grad_ext_inputs(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off,
+                                  int64_t batch_len, double num_data, double sum_e, const double* g_mu,
+                                  const double* g_v, double* elbo_out, svgp_terms* terms_out,
+                                  svgp_grads* grads_out, const svgp_input_grad* gx);
 
 /* ---- posterior(sva)  replaces SVA:115-136 (Centered) / SVA:160-187 (NonCentered) -------------
  * fills ApproxPosteriorGP.data = (Kuu = Cholesky(Lk), B, α): Lk_out M×M lower (upper zeroed),

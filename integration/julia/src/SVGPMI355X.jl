@@ -17,9 +17,10 @@
 #
 # AD: `try_elbo` carries a `ChainRulesCore.rrule` whose pullback returns STRUCTURAL tangents for `sva` (kernel variance,
 # inverse lengthscales, inducing inputs, constant mean, mean(q), the Cholesky factor of cov(q)) and for the likelihood
-# parameter, from ONE svgp_elbo_grad call.  When the hook declines, its rrule returns `nothing` with zero tangents and
-# Zygote differentiates the reference body as before.  Gradients with respect to the DATA inputs `x`, `y` and the jitter
-# `fz.Σy` are not computed by the library (zero tangents): the reference's callers never ask for them.
+# parameter, and for the data inputs `lfx.fx.x` (what a learned feature map in front of the GP back-propagates: x = NN(θ)(raw)),
+# from ONE svgp_elbo_grad_inputs call (svgp_elbo_grad_ext_inputs for a likelihood evaluated here).  When the hook declines, its
+# rrule returns `nothing` with zero tangents and Zygote differentiates the reference body as before.  Gradients with respect to
+# the observations `y` and the jitter `fz.Σy` are not computed by the library (zero tangents).
 #
 # NOT EXECUTED IN THIS REPOSITORY: the build image has no Julia.  The identical C symbols, struct layouts and status
 # conventions are exercised by the Python ctypes mirror (approximategps.jl_amd/approxgp/_ffi.py) that tests/ call;
@@ -65,6 +66,13 @@ end
 mutable struct Grads                  # svgp_grads
     variance::Float64; lik_sigma2::Float64; mean_const::Float64
     inv_lengthscale::Ptr{Float64}; z::Ptr{Cvoid}; m::Ptr{Cvoid}; Lq::Ptr{Cvoid}
+end
+
+struct InputGrad                      # svgp_input_grad (24 bytes): d elbo / d x, element (f, j) at x[f * ld + j]
+    x::Ptr{Cvoid}
+    ld::Int64
+    on_device::Int32
+    reserved::Int32
 end
 
 # ---------------------------------------------------------------------------------------------------------
@@ -289,9 +297,11 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
     d, M = Int(p.desc.d), length(p.m)
     gl, gz, gm, gLq = zeros(Float64, d), similar(p.Z), similar(p.m), similar(p.Lq)
     g = Grads(0, 0, 0, pointer(gl), pointer(gz), pointer(gm), pointer(gLq))
+    gxf = Matrix{T}(undef, n, d)           # d elbo / d x, feature-major (ld = n): RowVecs storage; ColVecs takes its transpose
+    gx = InputGrad(pointer(gxf), n, 0, 0)
     st = Int32(0)
     Δlik = nothing
-    GC.@preserve p Xd yd gl gz gm gLq begin
+    GC.@preserve p Xd yd gl gz gm gLq gxf begin
         if p.ext
             # host-evaluated likelihood: marginals from the device, SVA:355 here, the backward pass on the device again
             want && config === nothing && return nothing
@@ -315,10 +325,10 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
                 sumE, pb = host_expectation(want ? config : nothing, quadrature, lfx.lik, μ, v, y)
                 if want
                     Δlik, gμ, gv = pb
-                    st = ccall((:svgp_elbo_grad_ext, lib), Int32,
+                    st = ccall((:svgp_elbo_grad_ext_inputs, lib), Int32,
                                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Ptr{Float64}, Ptr{Float64},
-                                Ref{Float64}, Ref{Terms}, Ref{Grads}),
-                               ctx(), hm[], hd[], 0, n, Float64(num_data), Float64(sumE), gμ, gv, out, terms, g)
+                                Ref{Float64}, Ref{Terms}, Ref{Grads}, Ref{InputGrad}),
+                               ctx(), hm[], hd[], 0, n, Float64(num_data), Float64(sumE), gμ, gv, out, terms, g, gx)
                 else
                     kl = Ref{Float64}()
                     st = ccall((:svgp_prior_kl, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Float64}, Ptr{Float64}), ctx(), hm[], kl, C_NULL)
@@ -343,9 +353,9 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
                            ctx(), p.desc.dtype, lx, p.desc.d, n, Xd, yd, hd)
             end
             if st == 0
-                st = ccall((:svgp_elbo_grad, lib), Int32,
-                           (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Ref{Float64}, Ref{Terms}, Ref{Grads}),
-                           ctx(), hm[], hd[], 0, n, Float64(num_data), out, terms, g)
+                st = ccall((:svgp_elbo_grad_inputs, lib), Int32,
+                           (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Ref{Float64}, Ref{Terms}, Ref{Grads}, Ref{InputGrad}),
+                           ctx(), hm[], hd[], 0, n, Float64(num_data), out, terms, g, gx)
             end
             ccall((:svgp_data_free, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx(), hd[])
             ccall((:svgp_model_free, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx(), hm[])
@@ -354,7 +364,8 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
     st == 4 && return nothing            # SVGP_UNSUPPORTED: decline
     check(st, terms)
     # `Δlik`: the likelihood's own tangent from the host pullback (host-evaluated route), to be scaled by num_data / n
-    return out[], (σ²=g.variance, invl=gl, z=gz, m=gm, Lq=gLq, lik=g.lik_sigma2, c=g.mean_const, Δlik=Δlik, scale=Float64(num_data) / n)
+    gxl = lx == 0 ? permutedims(gxf) : (lx == 1 ? gxf : vec(gxf))      # in the layout of lfx.fx.x's storage
+    return out[], (σ²=g.variance, invl=gl, z=gz, m=gm, Lq=gLq, lik=g.lik_sigma2, c=g.mean_const, x=gxl, Δlik=Δlik, scale=Float64(num_data) / n)
 end
 
 # ---- structural tangents -------------------------------------------------------------------------------------------
@@ -410,8 +421,9 @@ function ChainRulesCore.rrule(config::RuleConfig{>:HasReverseMode}, ::typeof(MI3
         Δf = Tangent{typeof(f)}(; mean=mean_tangent(f.mean, Δ * g.c), kernel=kernel_tangent(f.kernel, Δ * g.σ², s(g.invl)))
         Δfz = Tangent{typeof(sva.fz)}(; f=Δf, x=inputs_tangent(sva.fz.x, s(g.z)))      # Σy (jitter): not differentiated
         Δsva = Tangent{typeof(sva)}(; fz=Δfz, q=q_tangent(sva.q, s(g.m), s(g.Lq)))
-        # the prior of lfx is the SAME object (SVA:347-351), its tangent is already on sva.fz.f; data inputs: none
-        Δlfx = Tangent{typeof(lfx)}(; lik=g.Δlik === nothing ? lik_tangent(lfx.lik, Δ * g.lik) : (Δ * g.scale) * g.Δlik)
+        # the prior of lfx is the SAME object (SVA:347-351), its tangent is already on sva.fz.f; the data inputs lfx.fx.x: d elbo / d x
+        Δfx = Tangent{typeof(lfx.fx)}(; x=inputs_tangent(lfx.fx.x, s(g.x)))
+        Δlfx = Tangent{typeof(lfx)}(; fx=Δfx, lik=g.Δlik === nothing ? lik_tangent(lfx.lik, Δ * g.lik) : (Δ * g.scale) * g.Δlik)
         return (NoTangent(), Δsva, Δlfx, NoTangent(), NoTangent(), NoTangent())
     end
     return val, try_elbo_pullback
