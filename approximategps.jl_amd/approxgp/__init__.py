@@ -7,7 +7,7 @@
 """
 from ._ffi import (Context, DeclinedError, DeviceData, DeviceModel, DomainError, PosDefException, SvgpError, UnsupportedError,
                    default_context, gausshermite, load_library, offload_advice, offload_work)
-from .gp import (GP, BernoulliLikelihood, DefaultExpectationMethod, FiniteGP, GaussHermiteExpectation,
+from .gp import (GP, BernoulliLikelihood, CustomMean, DefaultExpectationMethod, FiniteGP, GaussHermiteExpectation,
                  GaussianLikelihood, LatentFiniteGP, LatentGP, MvNormal, PoissonLikelihood, ExponentialLikelihood,
                  GammaLikelihood, CallerLikelihood, LogisticLink, NormalCDFLink, ProbitLink)
 from .kernels import (ARDTransform, Matern32Kernel, Matern52Kernel, ScaledKernel, ScaleTransform, SEKernel,

@@ -47,6 +47,16 @@ class InputGrad(C.Structure):
     _fields_ = [("x", C.c_void_p), ("ld", C.c_int64), ("on_device", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PointMean(C.Structure):
+    """svgp_point_mean: the batch's prior mean offsets mux (data dtype; on_device 0: host, 1: device)."""
+    _fields_ = [("mu", C.c_void_p), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PointMeanGrad(C.Structure):
+    """svgp_point_mean_grad: where d elbo / d mux goes (data dtype; on_device 0: host, 1: device)."""
+    _fields_ = [("mu_bar", C.c_void_p), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_prep", C.c_double), ("ms_strip", C.c_double), ("ms_expect", C.c_double),
                 ("ms_kuf", C.c_double),
@@ -84,6 +94,13 @@ SYMBOLS = {
                                           C.POINTER(Grads), C.POINTER(InputGrad)]),
     "svgp_elbo_grad_ext_inputs": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, _P,
                                               C.POINTER(C.c_double), C.POINTER(Terms), C.POINTER(Grads), C.POINTER(InputGrad)]),
+    "svgp_model_set_mean_z": (C.c_int32, [_P, _P, _P]),
+    "svgp_elbo_with_mean": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.POINTER(PointMean), C.POINTER(C.c_double),
+                                        C.POINTER(Terms)]),
+    "svgp_marginals_with_mean": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), _P, _P]),
+    "svgp_elbo_grad_with_mean": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.POINTER(PointMean), C.c_double, _P, _P,
+                                             C.POINTER(C.c_double), C.POINTER(Terms), C.POINTER(Grads), C.POINTER(InputGrad),
+                                             C.POINTER(PointMeanGrad)]),
     "svgp_prior_kl": (C.c_int32, [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "svgp_elbo_host": (C.c_int32, [_P, C.POINTER(ModelDesc), C.c_int32, C.c_int64, _P, _P, C.c_double,
                                    C.POINTER(C.c_double), C.POINTER(Terms)]),
@@ -184,6 +201,36 @@ def dtype_code(dt) -> int:
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _is_device_tensor(a):
+    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+
+
+def point_mean_grad_ptr(dst, n, dtype):
+    """Device address for d elbo / d mux of n points: a device tensor (checked: CUDA, contiguous, floating, the data dtype's element
+    size, at least n elements - the library writes n of them) or a raw device pointer (the caller's to size: n x dtype size bytes)."""
+    if hasattr(dst, "data_ptr"):
+        if (not _is_device_tensor(dst) or not dst.is_contiguous() or not dst.is_floating_point()
+                or dst.element_size() != np.dtype(np_dtype(dtype)).itemsize or dst.numel() < n):
+            raise ValueError("mean_grad: a contiguous device tensor of the data dtype with at least one entry per point of the batch")
+        return int(dst.data_ptr())
+    if isinstance(dst, (bool, np.bool_)) or not isinstance(dst, (int, np.integer)):
+        raise ValueError("mean_grad: True, a device tensor or a device pointer (int)")
+    return int(dst)
+
+
+def point_mean(mu, n, dtype):
+    """-> (PointMean, what keeps its memory alive) for prior mean offsets of n points: a host array (converted to the data dtype) or a
+    contiguous device tensor of the data dtype (read on the context's stream)."""
+    if _is_device_tensor(mu):
+        if mu.numel() != n or not mu.is_contiguous() or mu.element_size() != np.dtype(np_dtype(dtype)).itemsize or not mu.is_floating_point():
+            raise ValueError("prior_mean: a contiguous device tensor of the data dtype with one entry per point of the batch")
+        return PointMean(C.c_void_p(mu.data_ptr()), 1, 0), mu
+    buf = np.ascontiguousarray(np.asarray(mu, dtype=np_dtype(dtype)).reshape(-1))
+    if buf.shape != (n,):
+        raise ValueError("prior_mean: one entry per point of the batch")
+    return PointMean(_ptr(buf), 0, 0), buf
 
 
 class Context:
@@ -360,10 +407,26 @@ class DeviceModel:
         self.ctx.check(self.ctx.lib.svgp_model_update(self.ctx.h, self.h, C.byref(desc)))
         del keep
 
-    def elbo(self, data: DeviceData, off=0, length=None, num_data=0.0):
+    def set_mean_z(self, mu_z):
+        """mean(fz) = mean_const + mu_z (M host values; None removes them): svgp_model_set_mean_z.  Centered models only depend on it."""
+        if mu_z is None:
+            self.ctx.check(self.ctx.lib.svgp_model_set_mean_z(self.ctx.h, self.h, None))
+            return
+        buf = np.ascontiguousarray(np.asarray(mu_z, dtype=np_dtype(self.dtype)).reshape(-1))
+        if buf.shape != (self.M,):
+            raise ValueError("mu_z must have M entries")
+        self.ctx.check(self.ctx.lib.svgp_model_set_mean_z(self.ctx.h, self.h, _ptr(buf)))
+
+    def elbo(self, data: DeviceData, off=0, length=None, num_data=0.0, prior_mean=None):
+        """prior_mean: the batch's prior mean offsets mux (host array or device tensor; svgp_elbo_with_mean)."""
         length = data.n - off if length is None else length
         out, terms = C.c_double(), Terms()
-        rc = self.ctx.lib.svgp_elbo(self.ctx.h, self.h, data.h, off, length, float(num_data), C.byref(out), C.byref(terms))
+        if prior_mean is not None:
+            pm, _keep = point_mean(prior_mean, length, self.dtype)
+            rc = self.ctx.lib.svgp_elbo_with_mean(self.ctx.h, self.h, data.h, off, length, float(num_data), C.byref(pm), C.byref(out),
+                                                  C.byref(terms))
+        else:
+            rc = self.ctx.lib.svgp_elbo(self.ctx.h, self.h, data.h, off, length, float(num_data), C.byref(out), C.byref(terms))
         self.ctx.check(rc, terms)
         return out.value, terms
 
@@ -373,15 +436,20 @@ class DeviceModel:
         self.ctx.check(self.ctx.lib.svgp_elbo_partial(self.ctx.h, self.h, data.h, off, length, buf))
         return np.array(buf[:], dtype=np.float64)
 
-    def marginals(self, data: DeviceData, off=0, length=None):
-        """marginals(f_post(x)) of SVA:354 for the batch: (mu, v + 1e-18) as fp64 arrays (svgp_marginals)."""
+    def marginals(self, data: DeviceData, off=0, length=None, prior_mean=None):
+        """marginals(f_post(x)) of SVA:354 for the batch: (mu, v + 1e-18) as fp64 arrays (svgp_marginals; with prior_mean, the
+        batch's prior mean offsets: svgp_marginals_with_mean)."""
         length = data.n - off if length is None else length
         mu, var = np.zeros(length), np.zeros(length)
-        self.ctx.check(self.ctx.lib.svgp_marginals(self.ctx.h, self.h, data.h, off, length, _ptr(mu), _ptr(var)))
+        if prior_mean is not None:
+            pm, _keep = point_mean(prior_mean, length, self.dtype)
+            self.ctx.check(self.ctx.lib.svgp_marginals_with_mean(self.ctx.h, self.h, data.h, off, length, C.byref(pm), _ptr(mu), _ptr(var)))
+        else:
+            self.ctx.check(self.ctx.lib.svgp_marginals(self.ctx.h, self.h, data.h, off, length, _ptr(mu), _ptr(var)))
         return mu, var
 
     def elbo_grad(self, data: DeviceData, off=0, length=None, num_data=0.0, z_shape=None, shard=None, ext=None, out=None,
-                  inputs=None):
+                  inputs=None, prior_mean=None, mean_grad=None):
         """-> (elbo, terms, dict(variance, inv_lengthscale, z, m, Lq, lik_sigma2, mean_const)); z in the layout it was given.
         shard = (scale, kl_weight) evaluates the data-parallel shard form svgp_elbo_grad_shard instead.
         ext = (sum_e, g_mu, g_v): a likelihood the host evaluated on `marginals` (svgp_elbo_grad_ext).
@@ -389,8 +457,14 @@ class DeviceModel:
         (a training loop that has consumed the previous gradient; at M = 2048 the first touch of 33 MB of new pages costs ~2 ms).
         inputs = True: also d elbo / d x of the batch as dict["x"], a host array in the data's layout (ColVecs (d, n), RowVecs and
         wrapped device data (n, d), a vector (n,)); inputs = (device_ptr, ld): written to device memory, element (f, j) at
-        device_ptr[f * ld + j] on the context's stream (svgp_elbo_grad_inputs / svgp_elbo_grad_ext_inputs)."""
+        device_ptr[f * ld + j] on the context's stream (svgp_elbo_grad_inputs / svgp_elbo_grad_ext_inputs).
+        prior_mean = the batch's prior mean offsets mux (host array or device tensor); mean_grad = True: also d elbo / d mux as
+        dict["mean_x"] (host, data dtype); mean_grad = a device tensor or pointer: written there on the context's stream
+        (svgp_elbo_grad_with_mean, which also serves ext and inputs then)."""
         length = data.n - off if length is None else length
+        with_mean = prior_mean is not None or (mean_grad is not None and mean_grad is not False)
+        if with_mean and shard is not None:
+            raise ValueError("prior mean offsets are not available for the shard form (svgp_elbo_grad_shard)")
         gx, xb = None, None
         if inputs is not None and inputs is not False:
             if shard is not None:
@@ -422,7 +496,26 @@ class DeviceModel:
             Lb = np.zeros((self.M, self.M), dtype=dt, order="F")
         g = Grads(0.0, 0.0, 0.0, il.ctypes.data_as(C.POINTER(C.c_double)), _ptr(zb), _ptr(mb), _ptr(Lb))
         out, terms = C.c_double(), Terms()
-        if ext is not None:
+        mxb = None
+        if with_mean:
+            pm, _keep = point_mean(prior_mean, length, self.dtype) if prior_mean is not None else (None, None)
+            gpm = None
+            if mean_grad is True:
+                mxb = np.zeros(length, dtype=dt)
+                gpm = PointMeanGrad(_ptr(mxb), 0, 0)
+            elif mean_grad is not None and mean_grad is not False:
+                gpm = PointMeanGrad(C.c_void_p(point_mean_grad_ptr(mean_grad, length, self.dtype)), 1, 0)
+            sum_e, gmu, gv = 0.0, None, None
+            if ext is not None:
+                gmu, gv = (np.ascontiguousarray(a, dtype=np.float64) for a in ext[1:])
+                if gmu.shape != (length,) or gv.shape != (length,):
+                    raise ValueError("one point gradient per point of the batch")
+                sum_e = float(ext[0])
+            rc = self.ctx.lib.svgp_elbo_grad_with_mean(self.ctx.h, self.h, data.h, off, length, float(num_data),
+                                                       C.byref(pm) if pm is not None else None, sum_e, _ptr(gmu), _ptr(gv),
+                                                       C.byref(out), C.byref(terms), C.byref(g), C.byref(gx) if gx is not None else None,
+                                                       C.byref(gpm) if gpm is not None else None)
+        elif ext is not None:
             gmu, gv = (np.ascontiguousarray(a, dtype=np.float64) for a in ext[1:])
             if gmu.shape != (length,) or gv.shape != (length,):
                 raise ValueError("one point gradient per point of the batch")
@@ -445,6 +538,8 @@ class DeviceModel:
         res = dict(variance=g.variance, inv_lengthscale=il, z=zb, m=mb, Lq=Lb, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const)
         if xb is not None:
             res["x"] = xb
+        if mxb is not None:
+            res["mean_x"] = mxb
         return out.value, terms, res
 
     def prior_kl(self):

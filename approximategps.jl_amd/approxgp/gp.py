@@ -15,21 +15,42 @@ def _as_dn(x):
     return x[None, :] if x.ndim == 1 else x
 
 
+@dataclass(frozen=True)
+class CustomMean:
+    """AbstractGPs.CustomMean(f): mean(x_j) = f(x)[j].  `f` maps the inputs, in the layout they are given (ColVecs (d, n), a plain
+    vector (n,)), to a vector of n values - a physics trend, a linear trend, a learned (torch) mean.  The caller evaluates it (O(n));
+    the library takes the values as offsets (include/svgp_mi355x.h: svgp_*_with_mean, svgp_model_set_mean_z)."""
+    f: object
+
+
 @dataclass(eq=False)
 class GP:
-    """GP(kernel) with ZeroMean, or GP(c, kernel) with ConstMean(c).  Identity (`is`) matters:
+    """GP(kernel) with ZeroMean, GP(c, kernel) with ConstMean(c), or GP(CustomMean(fn), kernel).  Identity (`is`) matters:
     elbo checks `sva.fz.f === lfx.fx.f` (SVA:347-351)."""
 
     kernel: object
     mean_const: float = 0.0
+    mean_fn: object = None   # CustomMean's function, None for ZeroMean / ConstMean
 
     def __init__(self, *args):
+        self.mean_fn = None
         if len(args) == 1:
             self.kernel, self.mean_const = args[0], 0.0
+        elif len(args) == 2 and isinstance(args[0], CustomMean):
+            self.mean_const, self.mean_fn, self.kernel = 0.0, args[0].f, args[1]
         elif len(args) == 2:
             self.mean_const, self.kernel = float(args[0]), args[1]
         else:
-            raise TypeError("GP(kernel) or GP(mean_const, kernel)")
+            raise TypeError("GP(kernel), GP(mean_const, kernel) or GP(CustomMean(fn), kernel)")
+
+    def mean_offsets(self, x):
+        """The CustomMean's values at x as a float64 vector (None without one)."""
+        if self.mean_fn is None:
+            return None
+        v = self.mean_fn(x)
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        return np.asarray(v, dtype=np.float64).reshape(-1)
 
     def __call__(self, x, Sigma_y=DEFAULT_SIGMA2):
         return FiniteGP(self, np.asarray(x), Sigma_y)

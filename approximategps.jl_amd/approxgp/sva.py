@@ -92,6 +92,25 @@ def _desc(sva: SparseVariationalApproximation, lik=None, quadrature=None, dtype=
                           neg_var_policy=neg_var_policy)
 
 
+def _device_model(ctx, sva, desc, keep):
+    """DeviceModel of `sva`; a CustomMean prior also gets its values at z (mean(fz), svgp_model_set_mean_z)."""
+    model = _ffi.DeviceModel(ctx, desc, keep)
+    muz = sva.fz.f.mean_offsets(sva.fz.x)
+    if muz is not None:
+        try:
+            model.set_mean_z(muz)
+        except BaseException:
+            model.free()
+            raise
+    return model
+
+
+def _mean_z_grad(sva, grads):
+    """d elbo / d mean(fz) offsets: -m_bar (Centered: m enters only through m - mean(fz)), 0 (NonCentered)."""
+    m_bar = np.asarray(grads["m"], dtype=np.float64)
+    return -m_bar if sva.is_centered else np.zeros_like(m_bar)
+
+
 # ------------------------------------------------------------------------------------------------
 # elbo / approx_lml
 # ------------------------------------------------------------------------------------------------
@@ -146,10 +165,11 @@ def elbo(sva: SparseVariationalApproximation, fx, y, *, num_data=None, quadratur
     desc, keep = _desc(sva, lfx.lik, quadrature, dtype)
     y = np.asarray(y)
     n = y.shape[0]
+    mux = lfx.fx.f.mean_offsets(lfx.fx.x)
     data = _ffi.DeviceData(ctx, lfx.fx.x, y, _ffi.np_dtype(desc.dtype))
-    model = _ffi.DeviceModel(ctx, desc, keep)
+    model = _device_model(ctx, sva, desc, keep)
     try:
-        val, terms = model.elbo(data, 0, n, float(num_data) if num_data is not None else 0.0)
+        val, terms = model.elbo(data, 0, n, float(num_data) if num_data is not None else 0.0, prior_mean=mux)
     finally:
         model.free()
         data.free()
@@ -165,16 +185,19 @@ def _elbo_host_likelihood(sva, lfx, y, num_data, quadrature, ctx, dtype, want_gr
     desc, keep = _desc(sva, None, None, dtype)
     y = np.asarray(y, dtype=np.float64)
     n = y.shape[0]
+    mux = lfx.fx.f.mean_offsets(lfx.fx.x)
     data = _ffi.DeviceData(ctx, lfx.fx.x, None, _ffi.np_dtype(desc.dtype))
-    model = _ffi.DeviceModel(ctx, desc, keep)
+    model = _device_model(ctx, sva, desc, keep)
     try:
-        mu, var = model.marginals(data, 0, n)
+        mu, var = model.marginals(data, 0, n, prior_mean=mux)
         sum_e, gmu, gv = lfx.lik.expectation(mu, var, y, qn, want_grad)   # the caller's code (SVA:355)
         nd = float(num_data) if num_data is not None else float(n)
         if not want_grad:
             return sum_e * nd / n - model.prior_kl()[0], None
         val, _, grads = model.elbo_grad(data, 0, n, nd, z_shape=np.asarray(sva.fz.x).shape, ext=(sum_e, gmu, gv),
-                                        inputs=True if wrt_inputs else None)
+                                        inputs=True if wrt_inputs else None, prior_mean=mux, mean_grad=True if mux is not None else None)
+        if mux is not None:
+            grads["mean_z"] = _mean_z_grad(sva, grads)
         return val, grads
     finally:
         model.free()
@@ -186,7 +209,9 @@ def elbo_and_gradient(sva: SparseVariationalApproximation, fx, y, *, num_data=No
     """ELBO and its gradient w.r.t. (kernel variance, inverse lengthscales, inducing inputs z, mean(q) m, the lower factor
     Lq of cov(q), Gaussian noise σ², ConstMean) — what `Zygote.gradient(-elbo, ...)` yields for the reference's training
     loops (examples/a-regression/script.jl:188-194); the Julia shim wraps it as a ChainRulesCore.rrule.
-    wrt_inputs=True: the dict also holds "x", d elbo / d x shaped like fx.x (for a learned feature map in front of the GP)."""
+    wrt_inputs=True: the dict also holds "x", d elbo / d x shaped like fx.x (for a learned feature map in front of the GP).
+    GP(CustomMean(fn), k): the dict also holds "mean_x" = d elbo / d fn(x) (n,) and "mean_z" = d elbo / d fn(z) (M,), for the
+    caller to pull back through fn; "mean_const" is then their total."""
     if isinstance(fx, FiniteGP):
         if not fx.is_isotropic():
             raise RuntimeError("The observation noise fx.Σy must be homoscedastic.")
@@ -201,14 +226,18 @@ def elbo_and_gradient(sva: SparseVariationalApproximation, fx, y, *, num_data=No
         return _elbo_host_likelihood(sva, lfx, y, num_data, quadrature, ctx, dtype, True, wrt_inputs)
     desc, keep = _desc(sva, lfx.lik, quadrature, dtype)
     y = np.asarray(y)
+    mux = lfx.fx.f.mean_offsets(lfx.fx.x)
     data = _ffi.DeviceData(ctx, lfx.fx.x, y, _ffi.np_dtype(desc.dtype))
-    model = _ffi.DeviceModel(ctx, desc, keep)
+    model = _device_model(ctx, sva, desc, keep)
     try:
         val, _, grads = model.elbo_grad(data, 0, y.shape[0], float(num_data) if num_data is not None else 0.0,
-                                        z_shape=np.asarray(sva.fz.x).shape, inputs=True if wrt_inputs else None)
+                                        z_shape=np.asarray(sva.fz.x).shape, inputs=True if wrt_inputs else None,
+                                        prior_mean=mux, mean_grad=True if mux is not None else None)
     finally:
         model.free()
         data.free()
+    if mux is not None:
+        grads["mean_z"] = _mean_z_grad(sva, grads)
     return val, grads
 
 
@@ -229,22 +258,27 @@ class ApproxPosteriorGP:
         self.prior = approx.fz.f
         self.ctx = ctx or _ffi.default_context()
         desc, keep = _desc(approx, None, None, dtype)
-        self._model = _ffi.DeviceModel(self.ctx, desc, keep)
+        self._model = _device_model(self.ctx, approx, desc, keep)
         Lk, alpha, B = self._model.posterior()
         self.data = {"Kuu": Lk, "B": B, "α": alpha, "alpha": alpha}
 
     def inducing_points(self):  # SVA:270
         return self.approx.fz.x
 
+    def _plus_mean(self, m, x):
+        """svgp_predict returns mean_const + K*u alpha: a CustomMean prior adds its own values at x (SVA:211)."""
+        mux = self.prior.mean_offsets(x)
+        return m if mux is None else (np.asarray(m, dtype=np.float64) + mux).astype(np.asarray(m).dtype)
+
     def mean(self, x):  # SVA:208-212
-        return self._model.predict(x, True, False, False)[0]
+        return self._plus_mean(self._model.predict(x, True, False, False)[0], x)
 
     def var(self, x):  # SVA:230-235
         return self._model.predict(x, False, True, False)[1]
 
     def mean_and_var(self, x):  # SVA:246-253
         m, v, _ = self._model.predict(x, True, True, False)
-        return m, v
+        return self._plus_mean(m, x), v
 
     def cov(self, x, y=None):  # SVA:223-228 and :255-264
         if y is None:
@@ -253,7 +287,7 @@ class ApproxPosteriorGP:
 
     def mean_and_cov(self, x):  # SVA:237-244
         m, _, c = self._model.predict(x, True, False, True)
-        return m, c
+        return self._plus_mean(m, x), c
 
     def rand(self, x, n_samples=1, jitter=DEFAULT_SIGMA2, rng=None):
         """rand(f_post(x, jitter), n_samples) (examples/b-classification/script.jl:153) [dep AbstractGPs: mean +
@@ -291,7 +325,7 @@ def prior_kl(sva: SparseVariationalApproximation, *, ctx=None, dtype=None):
     """_prior_kl(sva) (SVA:362-373)."""
     ctx = ctx or _ffi.default_context()
     desc, keep = _desc(sva, None, None, dtype)
-    model = _ffi.DeviceModel(ctx, desc, keep)
+    model = _device_model(ctx, sva, desc, keep)
     try:
         return model.prior_kl()[0]
     finally:

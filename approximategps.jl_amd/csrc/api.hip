@@ -236,7 +236,10 @@ int enqueue_prep(svgp_ctx* ctx, svgp_model* m, bool overlap = false, const RowHo
     // and KL(q || p(u)) = ½(ΣB² + m~'m~ − M − logdet(BB')) — the NonCentered expression evaluated at (m~, B).
     launch_pad_lower(m->dtype, s, m->Lq_raw, m->M, m->Mp, m->B);
     launch_trsm_mat(m->dtype, s, m->T, m->Mp, m->B);
-    launch_shift_vec(m->dtype, s, m->m_raw, -m->desc.mean_const, m->M, m->Mp, m->mp);
+    if (m->mu_z)   // mean(fz) = mean_const + muz (svgp_model_set_mean_z)
+      launch_shift_sub_vec(m->dtype, s, m->m_raw, -m->desc.mean_const, m->mu_z, m->M, m->Mp, m->mp);
+    else
+      launch_shift_vec(m->dtype, s, m->m_raw, -m->desc.mean_const, m->M, m->Mp, m->mp);
     launch_trsv2(m->dtype, s, m->L, m->T, m->Mp, 0, m->mp);
     launch_pack_q_ld(m->dtype, s, m->B, m->Mp, nullptr, m->Mp, m->Mp, m->U, nullptr);
     launch_kl_terms_ld(m->dtype, s, m->B, m->Mp, m->mp, m->L, m->M, m->Mp, m->scal);
@@ -344,6 +347,7 @@ struct StripOuts {
   void* Ct = nullptr;
   int64_t lda = 0;
   bool skip_expect = false;   // svgp_marginals: the caller wants the moments themselves
+  const void* mux = nullptr;  // the batch's prior mean offsets (device, data dtype; svgp_*_with_mean)
 };
 
 // enqueue the fused strip kernel + final reduce over points [off, off+len) of (x, y)
@@ -388,6 +392,7 @@ int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, con
   a.M = m->M;
   a.kp = kparams(m);
   a.mean_const = m->desc.mean_const;
+  a.mux = o.mux;
   LikParams lp{};
   lp.lik = m->desc.likelihood;
   lp.gh_n = m->gh_n;
@@ -413,6 +418,7 @@ int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, con
     at.len = len - sh;
     at.mom_mu = a.mom_mu + sh;
     at.mom_var = a.mom_var + sh;
+    if (a.mux) at.mux = static_cast<const char*>(a.mux) + size_t(sh) * es;
     if (a.A_out) at.A_out = static_cast<char*>(a.A_out) + size_t(sh) * es;
     if (a.C_out) at.C_out = static_cast<char*>(a.C_out) + size_t(sh) * es;
     if (a.At_out) at.At_out = static_cast<char*>(a.At_out) + size_t(sh) * size_t(m->Mp) * es;
@@ -605,6 +611,36 @@ int check_batch(svgp_ctx* ctx, const svgp_model* m, const svgp_data* data, int64
   return SVGP_OK;
 }
 
+// a context buffer that grows on demand (contents not kept)
+int grow_buffer(svgp_ctx* ctx, void** p, size_t* cap, size_t bytes) {
+  if (bytes <= *cap) return SVGP_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return fail(ctx, SVGP_OOM, "hipMalloc failed for the prior mean offsets"); }
+  *cap = bytes;
+  return SVGP_OK;
+}
+
+// argument checks of the prior mean offsets (svgp_*_with_mean), before anything is enqueued
+int check_point_mean(svgp_ctx* ctx, const svgp_point_mean* pm) {
+  if (!pm) return SVGP_OK;
+  if (!pm->mu) return fail(ctx, SVGP_INVALID_ARG, "null prior mean offsets");
+  if ((pm->on_device != 0 && pm->on_device != 1) || pm->reserved != 0)
+    return fail(ctx, SVGP_INVALID_ARG, "prior mean offsets: on_device must be 0 or 1 and reserved 0");
+  return SVGP_OK;
+}
+
+// the batch's offsets on the device: a device pointer as it is, host memory by one copy into ctx->pm_x (bytes = batch_len x dtype size)
+int stage_point_mean(svgp_ctx* ctx, const svgp_point_mean* pm, size_t bytes, const void** dev) {
+  if (pm->on_device) { *dev = pm->mu; return SVGP_OK; }
+  const int rc = grow_buffer(ctx, &ctx->pm_x, &ctx->pm_x_bytes, bytes);
+  if (rc) return rc;
+  HIPC(ctx, hipMemcpyAsync(ctx->pm_x, pm->mu, bytes, hipMemcpyHostToDevice, ctx->stream));
+  *dev = ctx->pm_x;
+  return SVGP_OK;
+}
+
 // One evaluation = three stages, so that a process driving several GPUs (svgp_group_*) can enqueue every device before
 // it waits for any:  elbo_enqueue (prep + strips + reduce, asynchronous)  ->  elbo_collective (ONE ncclAllReduce of the
 // device-resident 8-vector d_res on the context's stream; nothing without a communicator)  ->  elbo_finish (read back).
@@ -612,7 +648,7 @@ struct ElboRead {
   double E = 0, n_points = 0, n_neg = 0, bad_chol = 0, failed = 0;
 };
 
-int elbo_enqueue(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len) {
+int elbo_enqueue(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, const void* mux = nullptr) {
   hipStream_t s = ctx->stream;
   HIPC(ctx, hipSetDevice(ctx->device));
   const OverlapPlan op = overlap_plan(ctx, m, len, StripOuts{});
@@ -627,6 +663,7 @@ int elbo_enqueue(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t of
   if (op.on) {
     rc = seg_prepare_forward(ctx, m, data->x, data->ldx, off, len, op, seg);
     if (rc) return rc;
+    seg.a.mux = mux;
   }
   TREC(ctx, ctx->ev[0], s);
   rc = enqueue_prep(ctx, m, op.on, op.on ? &hook : nullptr);
@@ -637,8 +674,10 @@ int elbo_enqueue(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t of
     return rc;
   }
   TREC(ctx, ctx->ev[1], s);
-  rc = op.on ? seg_finish_forward(ctx, m, data->y, off, len, StripOuts{}, seg)
-             : enqueue_strips(ctx, m, data->x, data->ldx, data->y, off, len, StripOuts{});
+  StripOuts so;
+  so.mux = mux;
+  rc = op.on ? seg_finish_forward(ctx, m, data->y, off, len, so, seg)
+             : enqueue_strips(ctx, m, data->x, data->ldx, data->y, off, len, so);
   if (rc) {
     if (op.on && ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     return rc;
@@ -706,8 +745,9 @@ int elbo_finish(svgp_ctx* ctx, svgp_model* m, ElboRead* out) {
 }
 
 // prep + strips (+ collective) + readback; refreshes the model's prep scalars
-int run_elbo(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, bool collective, ElboRead* out) {
-  int rc = elbo_enqueue(ctx, m, data, off, len);
+int run_elbo(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, bool collective, ElboRead* out,
+             const void* mux = nullptr) {
+  int rc = elbo_enqueue(ctx, m, data, off, len, mux);
   if (collective) rc = elbo_collective(ctx, rc);
   if (rc) return rc;
   return elbo_finish(ctx, m, out);
@@ -883,6 +923,8 @@ int32_t svgp_ctx_destroy(svgp_ctx* c) {
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
   if (c->kuf_buf) (void)hipFree(c->kuf_buf);
   if (c->ext_g) (void)hipFree(c->ext_g);
+  if (c->pm_x) (void)hipFree(c->pm_x);
+  if (c->pm_g) (void)hipFree(c->pm_g);
   if (c->gws) { c->gws->release(); delete c->gws; }
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
@@ -950,7 +992,7 @@ int32_t svgp_data_free(svgp_ctx* ctx, svgp_data* D) {
 int32_t svgp_model_free(svgp_ctx* ctx, svgp_model* m) {
   if (!m) return SVGP_OK;
   if (ctx) (void)hipSetDevice(ctx->device);
-  void* bufs[] = {m->z_raw, m->m_raw, m->Lq_raw, m->invl, m->zs, m->L, m->T, m->U, m->mp, m->B, m->scal, m->info, m->gh_x, m->gh_w};
+  void* bufs[] = {m->z_raw, m->m_raw, m->Lq_raw, m->invl, m->zs, m->L, m->T, m->U, m->mp, m->B, m->scal, m->info, m->gh_x, m->gh_w, m->mu_z};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   delete m;
@@ -1038,17 +1080,20 @@ void fill_terms(svgp_terms* t, const svgp_model* m, double elbo, const ElboRead&
   t->chol_info = m->chol_info;
   t->reserved = 0;
 }
-}  // namespace
 
-// With a communicator attached (svgp_ctx_attach_comm / svgp_group_create) this call is COLLECTIVE: every rank passes
-// its own shard's batch, the ranks' {sum E, n, n_neg, flags} are summed by one ncclAllReduce on the device, and every
-// rank returns the same global ELBO = sum E * num_data / n_global - KL (SVA:355-359; the KL is replicated, not summed).
-int32_t svgp_elbo(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double num_data,
-                  double* elbo_out, svgp_terms* terms_out) {
+// svgp_elbo (pm = NULL) and svgp_elbo_with_mean
+int elbo_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double num_data, double* elbo_out,
+              svgp_terms* terms_out, const svgp_point_mean* pm) {
   int rc = check_batch(ctx, m, data, off, len, true);
+  const void* mux = nullptr;
+  if (pm) {   // (ctx is not NULL here unless check_batch failed)
+    if (rc == SVGP_OK) rc = check_point_mean(ctx, pm);
+    if (rc == SVGP_OK && hipSetDevice(ctx->device) != hipSuccess) rc = fail(ctx, SVGP_HIP_ERROR, "hipSetDevice failed");
+    if (rc == SVGP_OK) rc = stage_point_mean(ctx, pm, size_t(len) * m->es, &mux);
+  }
   if (rc) return (ctx && ctx->comm) ? elbo_collective(ctx, rc) : rc;   // keep the peers' collective matched
   ElboRead r;
-  rc = run_elbo(ctx, m, data, off, len, true, &r);
+  rc = run_elbo(ctx, m, data, off, len, true, &r, mux);
   if (rc) return rc;
   const double scale = (num_data > 0 ? num_data : r.n_points) / r.n_points;   // SVA:357-358
   const double elbo = r.E * scale - m->kl;                                     // SVA:359
@@ -1056,6 +1101,20 @@ int32_t svgp_elbo(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t o
   rc = status_of(ctx, m, r.n_neg, r.bad_chol, r.failed);
   if (elbo_out) *elbo_out = (rc == SVGP_OK) ? elbo : NAN;
   return rc;
+}
+}  // namespace
+
+// With a communicator attached (svgp_ctx_attach_comm / svgp_group_create) this call is COLLECTIVE: every rank passes
+// its own shard's batch, the ranks' {sum E, n, n_neg, flags} are summed by one ncclAllReduce on the device, and every
+// rank returns the same global ELBO = sum E * num_data / n_global - KL (SVA:355-359; the KL is replicated, not summed).
+int32_t svgp_elbo(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double num_data,
+                  double* elbo_out, svgp_terms* terms_out) {
+  return elbo_impl(ctx, m, data, off, len, num_data, elbo_out, terms_out, nullptr);
+}
+
+int32_t svgp_elbo_with_mean(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double num_data,
+                            const svgp_point_mean* pm, double* elbo_out, svgp_terms* terms_out) {
+  return elbo_impl(ctx, m, data, off, len, num_data, elbo_out, terms_out, pm);
 }
 
 int32_t svgp_prior_kl(svgp_ctx* ctx, svgp_model* m, double* kl_out, double* logdet_out) {
@@ -1373,6 +1432,10 @@ struct GradCall {
   double ext_sum_e = 0.0;
   // svgp_elbo_grad_inputs / svgp_elbo_grad_ext_inputs: where d elbo / d x goes (NULL: not requested, nothing more is launched)
   const svgp_input_grad* gx = nullptr;
+  // svgp_elbo_grad_with_mean: the batch's prior mean offsets (device, data dtype) and where their gradient goes (device; NULL: not
+  // requested - point_grad_kernel writes its g_mu a second time there)
+  const void* mux = nullptr;
+  void* mux_bar = nullptr;
 };
 
 // out = Xt' Yt for M x M operands ("k-major": Xt[k][r] at Xt[k Mp + r]; a row-major matrix Z is the operand Z, a column-major
@@ -1491,6 +1554,7 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
     a.T = m->T; a.U = m->U; a.zs = m->zs; a.mp = m->mp; a.x = data->x; a.work = ctx->work; a.counter = ctx->counter;
     a.At_out = w->At; a.ldx = data->ldx; a.off = off + c0; a.len = clen; a.Mp = Mp; a.M = M; a.kp = kp;
     a.mean_const = m->desc.mean_const;
+    if (gc.mux) a.mux = static_cast<const char*>(gc.mux) + size_t(c0) * es;   // (c0: the chunk's first point inside the batch)
     a.mom_mu = ctx->mom; a.mom_var = ctx->mom + ctx->mom_cap;   // the strips' (mu, v), read by launch_point_grads
     a.R = w->Rcm; a.alpha = w->alpha; a.Pt_out = w->Pt;
     lpc = lp;
@@ -1623,7 +1687,8 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
       KCHECK(ctx, "strip (value and gradient)");
     }
     launch_point_grads(dt, s, lpc, a.mom_mu, a.mom_var, gc.ext_gmu ? nullptr : data->y, off + c0, clen, scale, n_global_dev, gc.num_data, w->gmu, w->gv,
-                       w->partial5, gop.on ? nullptr : a.counter, ncp);
+                       w->partial5, gop.on ? nullptr : a.counter, ncp,
+                       gc.mux_bar ? static_cast<char*>(gc.mux_bar) + size_t(c0) * es : nullptr);
     KCHECK(ctx, "point gradients");
     const int n5 = point_grad_blocks(clen);   // rows of partial5: one per 256-point block
     int64_t ksl = ((clen + w->ns_uf - 1) / w->ns_uf + 127) / 128 * 128;
@@ -1899,7 +1964,7 @@ int grad_finish(svgp_ctx* ctx, svgp_model* m, GradCall& gc, double* elbo_out, sv
 int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double scale, double klw,
                    double num_data, bool collective, double* elbo_out, svgp_terms* terms_out, svgp_grads* g,
                    const double* ext_gmu = nullptr, const double* ext_gv = nullptr, double ext_sum_e = 0.0,
-                   const svgp_input_grad* gx = nullptr) {
+                   const svgp_input_grad* gx = nullptr, const svgp_point_mean* pm = nullptr, const svgp_point_mean_grad* gpm = nullptr) {
   GradCall gc;
   gc.ext_gmu = ext_gmu; gc.ext_gv = ext_gv; gc.ext_sum_e = ext_sum_e;
   gc.gx = gx;
@@ -1922,6 +1987,11 @@ int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
       if (hipMalloc(&w->xg, xb) != hipSuccess) { w->xg = nullptr; rc = fail(ctx, SVGP_OOM, "hipMalloc failed for d elbo / d x"); }
       else w->xg_b = xb;
     }
+  }
+  if (rc == SVGP_OK && pm) rc = stage_point_mean(ctx, pm, size_t(len) * m->es, &gc.mux);
+  if (rc == SVGP_OK && gpm) {   // host destination: point_grad_kernel writes ctx->pm_g, one copy brings it over
+    if (gpm->on_device) gc.mux_bar = gpm->mu_bar;
+    else if ((rc = grow_buffer(ctx, &ctx->pm_g, &ctx->pm_g_bytes, size_t(len) * m->es)) == SVGP_OK) gc.mux_bar = ctx->pm_g;
   }
   if (rc != SVGP_OK) return (ctx && gc.collective) ? grad_fail_collective(ctx, rc) : rc;
   if (gc.collective) {
@@ -1946,6 +2016,8 @@ int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
   if (gx && !gx->on_device)   // (never all-reduced: this rank's points; the stream synchronisation of grad_finish covers the copy)
     HIPC(ctx, hipMemcpy2DAsync(gx->x, size_t(gx->ld) * m->es, gc.w->xg, size_t(len) * m->es, size_t(len) * m->es, size_t(m->d),
                                hipMemcpyDeviceToHost, ctx->stream));
+  if (gpm && !gpm->on_device)   // (never all-reduced either)
+    HIPC(ctx, hipMemcpyAsync(gpm->mu_bar, ctx->pm_g, size_t(len) * m->es, hipMemcpyDeviceToHost, ctx->stream));
   return grad_finish(ctx, m, gc, elbo_out, terms_out, g);
 }
 
@@ -1986,19 +2058,27 @@ extern "C" int32_t svgp_elbo_grad_shard(svgp_ctx* ctx, svgp_model* m, const svgp
 // with ANY single-latent GPLikelihoods likelihood and quadrature.  svgp_marginals hands the host marginals(f_post(x)) of
 // SVA:354; the host evaluates expected_loglikelihood (SVA:355) and, for training, its derivatives w.r.t. (mu_i, v_i);
 // svgp_elbo_grad_ext runs the same backward pass as svgp_elbo_grad with those point gradients in place of lik.hpp's.
-extern "C" int32_t svgp_marginals(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len,
-                                  double* mean_out, double* var_out) {
+namespace {
+// svgp_marginals (pm = NULL) and svgp_marginals_with_mean
+int marginals_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double* mean_out, double* var_out,
+                   const svgp_point_mean* pm) {
   int rc = check_batch(ctx, m, data, off, len, false);
   if (rc) return rc;
   if (!mean_out || !var_out) return fail(ctx, SVGP_INVALID_ARG, "null output");
+  rc = check_point_mean(ctx, pm);
+  if (rc) return rc;
   hipStream_t s = ctx->stream;
   HIPC(ctx, hipSetDevice(ctx->device));
+  StripOuts so;
+  so.skip_expect = true;
+  if (pm) {
+    rc = stage_point_mean(ctx, pm, size_t(len) * m->es, &so.mux);
+    if (rc) return rc;
+  }
   TREC(ctx, ctx->ev[0], s);
   rc = enqueue_prep(ctx, m);
   if (rc) return rc;
   TREC(ctx, ctx->ev[1], s);
-  StripOuts so;
-  so.skip_expect = true;
   rc = enqueue_strips(ctx, m, data->x, data->ldx, nullptr, off, len, so);
   if (rc) return rc;
   PrepScalars ps;
@@ -2023,6 +2103,17 @@ extern "C" int32_t svgp_marginals(svgp_ctx* ctx, svgp_model* m, const svgp_data*
     var_out[i] = v;
   }
   return status_of(ctx, m, nneg);
+}
+}  // namespace
+
+extern "C" int32_t svgp_marginals(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len,
+                                  double* mean_out, double* var_out) {
+  return marginals_impl(ctx, m, data, off, len, mean_out, var_out, nullptr);
+}
+
+extern "C" int32_t svgp_marginals_with_mean(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len,
+                                            const svgp_point_mean* pm, double* mean_out, double* var_out) {
+  return marginals_impl(ctx, m, data, off, len, mean_out, var_out, pm);
 }
 
 // Value and gradient of  scale sum_e - kl_weight KL  with (dE_i/dmu_i, dE_i/dv_i) = (g_mu[i], g_v[i]) supplied by the host
@@ -2061,6 +2152,70 @@ extern "C" int32_t svgp_elbo_grad_ext_inputs(svgp_ctx* ctx, svgp_model* m, const
   if (rc) return ctx->comm ? grad_fail_collective(ctx, rc) : rc;
   const double scale = len >= 1 ? (num_data > 0 ? num_data : double(len)) / double(len) : 1.0;
   return elbo_grad_impl(ctx, m, data, off, len, scale, 1.0, num_data, true, elbo_out, terms_out, g, g_mu, g_v, sum_e, gx);
+}
+
+namespace {
+// argument checks of the prior mean offsets' gradient output (before anything is enqueued)
+int check_point_mean_grad(svgp_ctx* ctx, const svgp_data* data, int64_t len, const svgp_input_grad* gx, const svgp_point_mean_grad* gpm) {
+  if (!gpm) return SVGP_OK;
+  if (!gpm->mu_bar) return fail(ctx, SVGP_INVALID_ARG, "null prior-mean gradient output");
+  if ((gpm->on_device != 0 && gpm->on_device != 1) || gpm->reserved != 0)
+    return fail(ctx, SVGP_INVALID_ARG, "prior-mean gradient: on_device must be 0 or 1 and reserved 0");
+  if (gpm->on_device && data && len >= 1) {
+    const size_t es = data->dtype == SVGP_F64 ? 8 : 4;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(gpm->mu_bar), a1 = a0 + size_t(len) * es;
+    auto hits = [&](const void* p, size_t bytes) {
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(p), b1 = b0 + bytes;
+      return p && a0 < b1 && b0 < a1;
+    };
+    if (data->d >= 1 && hits(data->x, (size_t(data->d - 1) * size_t(data->ldx) + size_t(data->n)) * es))
+      return fail(ctx, SVGP_INVALID_ARG, "prior-mean gradient output overlaps the data's x");
+    if (hits(data->y, size_t(data->n) * es)) return fail(ctx, SVGP_INVALID_ARG, "prior-mean gradient output overlaps the data's y");
+    if (gx && gx->on_device && data->d >= 1 && hits(gx->x, (size_t(data->d - 1) * size_t(gx->ld) + size_t(len)) * es))
+      return fail(ctx, SVGP_INVALID_ARG, "prior-mean gradient output overlaps the input-gradient output");
+  }
+  return SVGP_OK;
+}
+}  // namespace
+
+// svgp_elbo_grad / _ext / _inputs / _ext_inputs with the batch's prior mean offsets (include/svgp_mi355x.h): the same launches; the
+// offsets enter the strips' moment epilogue, and their gradient is a second store of point_grad_kernel's g_mu
+extern "C" int32_t svgp_elbo_grad_with_mean(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len,
+                                            double num_data, const svgp_point_mean* pm, double sum_e, const double* g_mu,
+                                            const double* g_v, double* elbo_out, svgp_terms* terms_out, svgp_grads* g,
+                                            const svgp_input_grad* gx, svgp_point_mean_grad* gpm) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  int rc = ((g_mu == nullptr) != (g_v == nullptr)) ? fail(ctx, SVGP_INVALID_ARG, "exactly one of g_mu / g_v is NULL") : SVGP_OK;
+  if (rc == SVGP_OK && gx) rc = check_input_grad(ctx, data, len, gx);
+  if (rc == SVGP_OK) rc = check_point_mean(ctx, pm);
+  if (rc == SVGP_OK) rc = check_point_mean_grad(ctx, data, len, gx, gpm);
+  if (rc) return ctx->comm ? grad_fail_collective(ctx, rc) : rc;
+  const double scale = len >= 1 ? (num_data > 0 ? num_data : double(len)) / double(len) : 1.0;
+  return elbo_grad_impl(ctx, m, data, off, len, scale, 1.0, num_data, true, elbo_out, terms_out, g, g_mu, g_v, g_mu ? sum_e : 0.0, gx,
+                        pm, gpm);
+}
+
+// mean(fz) = mean_const + muz: a model-owned copy (include/svgp_mi355x.h); the next evaluation prepares the model again
+extern "C" int32_t svgp_model_set_mean_z(svgp_ctx* ctx, svgp_model* m, const void* mu_z) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!m) return fail(ctx, SVGP_INVALID_ARG, "null model");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  if (!mu_z) {
+    if (m->mu_z) {
+      HIPC(ctx, hipStreamSynchronize(ctx->stream));
+      (void)hipFree(m->mu_z);
+      m->mu_z = nullptr;
+    }
+  } else {
+    if (!m->mu_z && hipMalloc(&m->mu_z, size_t(m->M) * m->es) != hipSuccess) {
+      m->mu_z = nullptr;
+      return fail(ctx, SVGP_OOM, "hipMalloc failed for the inducing points' prior mean offsets");
+    }
+    HIPC(ctx, hipMemcpyAsync(m->mu_z, mu_z, size_t(m->M) * m->es, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));   // the host buffer may be released by the caller
+  }
+  m->prepared = false;
+  return SVGP_OK;
 }
 
 // ================================================================================================

@@ -45,6 +45,8 @@ struct svgp_ctx {
   hipEvent_t ev_piece[8] = {};                               // one behind each piece of that read-back
   void* kuf_buf = nullptr;    size_t kuf_bytes = 0;
   double* ext_g = nullptr;    size_t ext_cap = 0;           // [2][ext_cap] point gradients of a host-evaluated likelihood
+  void* pm_x = nullptr;       size_t pm_x_bytes = 0;        // host-memory prior mean offsets of a call, copied in (svgp_*_with_mean)
+  void* pm_g = nullptr;       size_t pm_g_bytes = 0;        // their gradient for a host destination, copied out (svgp_elbo_grad_with_mean)
   struct GradWs* gws = nullptr;  // gradient workspace, cached by problem shape
   // data-parallel communicator (comm.hip): one RCCL rank per context; world == 1 without one
   void* comm = nullptr;        // ncclComm_t
@@ -110,6 +112,7 @@ struct svgp_model {
   double *gh_x = nullptr, *gh_w = nullptr;
   int gh_n = 0;
   bool prepared = false;
+  void* mu_z = nullptr;    // [M] prior mean offsets at the inducing points (svgp_model_set_mean_z), model dtype; Centered prep only
   // host copies of the last prep's scalars
   double kl = 0, logdet_kuu = 0;
   int chol_info = 0;

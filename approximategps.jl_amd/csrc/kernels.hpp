@@ -62,6 +62,8 @@ void launch_trsm_mat(int dtype, hipStream_t s, const void* Tm, int64_t Mp, void*
 void launch_pad_lower(int dtype, hipStream_t s, const void* Lq, int64_t M, int64_t Mp, void* out);
 // out[i] = m[i] + shift for i < M, 0 for M <= i < Mp
 void launch_shift_vec(int dtype, hipStream_t s, const void* m, double shift, int64_t M, int64_t Mp, void* out);
+// out[i] = (m[i] + shift) - mu[i] for i < M, 0 for M <= i < Mp (Centered m - mean_const - muz: svgp_model_set_mean_z)
+void launch_shift_sub_vec(int dtype, hipStream_t s, const void* m, double shift, const void* mu, int64_t M, int64_t Mp, void* out);
 // copy the lower triangle of the leading M x M block of A (ld Mp) into out (ld M), zero the upper part
 void launch_extract_lower(int dtype, hipStream_t s, const void* A, int64_t Mp, int64_t M, void* out);
 
@@ -86,6 +88,8 @@ struct StripArgs {
   int64_t Mp, M;
   KernelParams kp;
   double mean_const;
+  const void* mux;      // nullable: [len] prior mean offsets of the batch's points (data dtype, element j <-> point off + j): the moment
+                        // epilogue writes mom_mu[j] = (mean_const + mux[j]) + qm (svgp_*_with_mean)
   // ---- value-and-gradient strips (launch_strip_grad): phase 3 of the same kernel, P = Kuf_bar for the strip's points ----
   const void* R;        // Mp x Mp col-major: Lk^-T (Lq Lq' - I)
   const void* alpha;    // [Mp] Lk^-T m
@@ -129,10 +133,11 @@ size_t strip_seg_state_doubles(int dtype, int nt);
 void launch_strip_grad(int dtype, hipStream_t s, const StripArgs& a, int nt, int grid, int64_t nstrips);
 // marginals, expected log-likelihood and d E / d (mu, v) (x scale) of the points [off, off + len) of y from their moments: gmu_out /
 // gv_out (compute dtype, [len]) and part5[point_grad_blocks(len)][5] = per-block {E, sum g_mu, sum g_v, dE/dsigma2, n_neg}
+// gmu_copy (nullable): a second copy of gmu_out[0 .. len) (the prior mean offsets' gradient of svgp_elbo_grad_with_mean)
 int point_grad_blocks(int64_t len);
 void launch_point_grads(int dtype, hipStream_t s, const LikParams& lp, const double* mom_mu, const double* mom_var, const void* y,
                         int64_t off, int64_t len, double scale, const double* n_global_dev, double num_data, void* gmu_out,
-                        void* gv_out, double* part5, unsigned* strip_queue = nullptr, int64_t pad_to = 0);
+                        void* gv_out, double* part5, unsigned* strip_queue = nullptr, int64_t pad_to = 0, void* gmu_copy = nullptr);
 // marginals + expected log-likelihood of every point (SVA:354-355): per-block sums into partial/negcnt
 int expect_blocks(int64_t len);
 void launch_expect(int dtype, hipStream_t s, const LikParams& lp, const double* mom_mu, const double* mom_var,

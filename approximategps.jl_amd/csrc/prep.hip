@@ -907,6 +907,12 @@ __global__ void shift_vec_kernel(const T* __restrict__ m, T shift, int64_t M, in
   if (i < Mp) out[i] = (i < M) ? m[i] + shift : T(0);
 }
 
+template <typename T>
+__global__ void shift_sub_vec_kernel(const T* __restrict__ m, T shift, const T* __restrict__ mu, int64_t M, int64_t Mp, T* __restrict__ out) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < Mp) out[i] = (i < M) ? (m[i] + shift) - mu[i] : T(0);
+}
+
 // ------------------------------------------------------------------------------------------------
 // cov(f, xa, xb) = k(xa, xb) - Aa'Ab + Ca'Cb  (SVA:223-228, :255-264) from the k-major factors the strip
 // kernel wrote.  Tile (j-block of xb) x (i-block of xa) so that stores run along columns of the output.
@@ -1168,6 +1174,15 @@ void launch_shift_vec(int dtype, hipStream_t s, const void* m, double shift, int
   SVGP_DISPATCH(dtype,
                 hipLaunchKernelGGL(shift_vec_kernel<double>, grid, dim3(256), 0, s, (const double*)m, shift, M, Mp, (double*)out),
                 hipLaunchKernelGGL(shift_vec_kernel<float>, grid, dim3(256), 0, s, (const float*)m, float(shift), M, Mp, (float*)out));
+}
+
+void launch_shift_sub_vec(int dtype, hipStream_t s, const void* m, double shift, const void* mu, int64_t M, int64_t Mp, void* out) {
+  dim3 grid((unsigned)((Mp + 255) / 256));
+  SVGP_DISPATCH(dtype,
+                hipLaunchKernelGGL(shift_sub_vec_kernel<double>, grid, dim3(256), 0, s, (const double*)m, shift, (const double*)mu, M, Mp,
+                                   (double*)out),
+                hipLaunchKernelGGL(shift_sub_vec_kernel<float>, grid, dim3(256), 0, s, (const float*)m, float(shift), (const float*)mu, M, Mp,
+                                   (float*)out));
 }
 
 void launch_cov_assemble(int dtype, hipStream_t s, const KernelParams& kp, const void* xa, int64_t ldxa, int64_t na,

@@ -555,7 +555,8 @@ __global__ void __launch_bounds__(NTHR, MINW) strip_kernel(StripArgs a, int64_t 
                 qm += __builtin_nontemporal_load(pp + NT + tid);
                 qc += __builtin_nontemporal_load(pp + 2 * NT + tid);
               }
-              a.mom_mu[c0 + tid] = a.mean_const + qm;
+              const double mc = a.mux ? a.mean_const + double(static_cast<const T*>(a.mux)[c0 + tid]) : a.mean_const;
+              a.mom_mu[c0 + tid] = mc + qm;
               a.mom_var[c0 + tid] = a.kp.variance - qa + qc;
             }
           }
@@ -572,7 +573,10 @@ __global__ void __launch_bounds__(NTHR, MINW) strip_kernel(StripArgs a, int64_t 
           qm += red[(1 * G::WR + w) * NT + tid];
           qc += red[(2 * G::WR + w) * NT + tid];
         }
-        a.mom_mu[c0 + tid] = a.mean_const + qm;
+        // prior mean at the point: mean_const, plus the caller's offset mux[j] (one coalesced read per point; mux = 0 gives the bits of
+        // the constant mean)
+        const double mc = a.mux ? a.mean_const + double(static_cast<const T*>(a.mux)[c0 + tid]) : a.mean_const;
+        a.mom_mu[c0 + tid] = mc + qm;
         // GRAD: qc = k_j' (R A)_.j = sum C^2 - sum A^2 (qa is not accumulated in that build, it stays 0)
         a.mom_var[c0 + tid] = a.kp.variance - qa + qc;
       }
@@ -641,7 +645,8 @@ __global__ void __launch_bounds__(k256) point_grad_kernel(LikParams lp, const do
                                                           const double* __restrict__ mom_var, const T* __restrict__ y, int64_t off,
                                                           int64_t len, double scale_host, const double* __restrict__ n_global_dev,
                                                           double num_data, T* __restrict__ gmu_out, T* __restrict__ gv_out,
-                                                          double* __restrict__ part5, unsigned* __restrict__ strip_queue, int64_t pad_to) {
+                                                          double* __restrict__ part5, unsigned* __restrict__ strip_queue, int64_t pad_to,
+                                                          T* __restrict__ gmu_copy) {
   __shared__ double sh[5][k256];
   const int64_t i = int64_t(blockIdx.x) * k256 + threadIdx.x;
   // (round 6: two fills per gradient chunk - the head of the strips' queue and the padding of g_mu | g_v - ride in this launch, which
@@ -670,6 +675,7 @@ __global__ void __launch_bounds__(k256) point_grad_kernel(LikParams lp, const do
     }
     gmu_out[i] = T(gm);
     gv_out[i] = T(gvv);
+    if (gmu_copy) gmu_copy[i] = T(gm);   // mux_bar (svgp_elbo_grad_with_mean)
   }
 #pragma unroll
   for (int q = 0; q < 5; ++q) sh[q][threadIdx.x] = e5[q];
@@ -1170,16 +1176,18 @@ int point_grad_blocks(int64_t len) { return int((len + k256 - 1) / k256); }
 
 void launch_point_grads(int dtype, hipStream_t s, const LikParams& lp, const double* mom_mu, const double* mom_var, const void* y,
                         int64_t off, int64_t len, double scale, const double* n_global_dev, double num_data, void* gmu_out,
-                        void* gv_out, double* part5, unsigned* strip_queue, int64_t pad_to) {
+                        void* gv_out, double* part5, unsigned* strip_queue, int64_t pad_to, void* gmu_copy) {
   // strip_queue (nullable): zeroed for the NEXT launch of the strips; pad_to: g_mu, g_v of the points [len, pad_to) are written as zeros
   // (pad_to <= the 256-point blocks of the launch: the weighted SYRK reads g_v over the chunk padded to 128 points)
   const int nb = point_grad_blocks(len);
   if (dtype == 0)
     hipLaunchKernelGGL(point_grad_kernel<double>, dim3(nb), dim3(k256), 0, s, lp, mom_mu, mom_var, (const double*)y, off, len, scale,
-                       n_global_dev, num_data, (double*)gmu_out, (double*)gv_out, part5, strip_queue, pad_to);
+                       n_global_dev, num_data, (double*)gmu_out, (double*)gv_out, part5, strip_queue, pad_to,
+                       (double*)gmu_copy);
   else
     hipLaunchKernelGGL(point_grad_kernel<float>, dim3(nb), dim3(k256), 0, s, lp, mom_mu, mom_var, (const float*)y, off, len, scale,
-                       n_global_dev, num_data, (float*)gmu_out, (float*)gv_out, part5, strip_queue, pad_to);
+                       n_global_dev, num_data, (float*)gmu_out, (float*)gv_out, part5, strip_queue, pad_to,
+                       (float*)gmu_copy);
 }
 
 int expect_blocks(int64_t len) {

@@ -38,7 +38,8 @@ extern "C" {
                               48-byte v2 / v3 layout again (v4 let it write 56 bytes into a buffer a v3 host sized at 48), the
                               fields appended since are read through the sized call.  Additions only: v2 / v3 callers keep working.
                               Entry points added without a version step (hosts find them by symbol: dlsym / hasattr): svgp_elbo_grad_inputs,
-                              svgp_elbo_grad_ext_inputs */
+                              svgp_elbo_grad_ext_inputs, svgp_model_set_mean_z, svgp_elbo_with_mean, svgp_marginals_with_mean,
+                              svgp_elbo_grad_with_mean */
 
 /* status codes -> Julia exceptions raised by the shim */
 enum {
@@ -312,6 +313,59 @@ int32_t svgp_elbo_grad_ext_inputs(svgp_ctx* ctx, svgp_model* model, const svgp_d
                                   int64_t batch_len, double num_data, double sum_e, const double* g_mu,
                                   const double* g_v, double* elbo_out, svgp_terms* terms_out,
                                   svgp_grads* grads_out, const svgp_input_grad* gx);
+
+/* ---- prior mean functions other than ZeroMean / ConstMean: offsets the caller evaluates --------------------------------------
+ * For GP(CustomMean(g), k) (a physics trend, a linear trend, a learned mean): the caller evaluates the O(n) mean function, the library
+ * does the O(n M^2) work and hands back the adjoint.  A model may carry an offset vector muz at the inducing points
+ * (svgp_model_set_mean_z) and a call may carry an offset vector mux at the batch's points (svgp_point_mean).  Both add to mean_const:
+ *   mean(f.prior, x_j) = mean_const + mux[j]   for the points [batch_off, batch_off + batch_len)   (SVA:211, 241, 250)
+ *   mean(fz)_k         = mean_const + muz[k]   for k < M                                          (SVA:133, 362)
+ * Effects:
+ *   - posterior marginal mean: mu_j = (mean_const + mux[j]) + (K_xu alpha)_j, in that order of additions (mux = 0: bitwise the
+ *     constant-mean mean_const + (K_xu alpha)_j);
+ *   - Centered: m~ = Lk \ (m - mean_const - muz), which changes alpha (svgp_posterior's too) and the KL;
+ *   - NonCentered: muz has no effect on any output (alpha = Lk' \ m, SVA:182); it is accepted, stored and ignored;
+ *   - variances, the 1e-18 of f_post(x) and the SVGP_NEGVAR_* policy: unchanged.
+ * Gradients: mux_bar[j] = scale * dE_j/dmu_j, rounded to the data dtype as x_bar is (fp32: within the m tolerance of svgp_elbo_grad,
+ * 5e-5 of the fp64 block's largest entry; measured 2.7e-6).  fp32 elsewhere, measured against the fp64 reference on the test problems
+ * (tests/test_gpu_prior_mean.py, M = 64): Gaussian likelihood - marginal means within 4.8e-5, m / Lq 5.3e-5, inverse lengthscales 8.2e-4
+ * of the block's largest entry; other likelihoods - as the existing calls on the same problem without offsets (up to 9e-3 on z): the
+ * rounding of the fp32 strips and adjoint, which the offsets do not change.  muz_bar = -m_bar (Centered: m enters only through m - muz) and 0 (NonCentered); the
+ * library does not return it.  grads_out->mean_const keeps its meaning and equals sum_j mux_bar[j] + sum_k muz_bar[k].
+ * Non-finite offsets follow the reference's arithmetic: a NaN in mux[j] gives a NaN marginal mean for point j only and a NaN ELBO,
+ * status SVGP_OK (the NaN-x rule of svgp_elbo).
+ * svgp_predict keeps returning mean_const + K*u alpha: a caller with a mean function adds its own offset at x*.  The group calls
+ * (svgp_group_*), svgp_elbo_host and svgp_elbo_partial take no mux: they keep the constant mean (plus muz, if set on the model). */
+typedef struct svgp_point_mean {   /* mux: batch_len values in the data's dtype, element j belongs to point batch_off + j */
+  const void* mu;
+  int32_t on_device;   /* 0: host memory (one copy per call); 1: device memory of the context's GPU, read on the context's stream */
+  int32_t reserved;    /* must be 0 */
+} svgp_point_mean;     /* 16 bytes */
+typedef struct svgp_point_mean_grad {   /* mux_bar: batch_len values in the data's dtype, element j belongs to point batch_off + j */
+  void* mu_bar;
+  int32_t on_device;   /* 0: host memory, written before the call returns; 1: device memory, written on the context's stream */
+  int32_t reserved;    /* must be 0 */
+} svgp_point_mean_grad;   /* 16 bytes */
+/* muz: M values in the model's dtype (host memory), copied into a model-owned device buffer; NULL removes it.  The model is prepared
+ * again (lazily) at its next evaluation; muz persists across svgp_model_update until it is set again. */
+int32_t svgp_model_set_mean_z(svgp_ctx* ctx, svgp_model* model, const void* mu_z);
+/* svgp_elbo / svgp_marginals with mux.  pm = NULL: exactly the call without `_with_mean` (bitwise; nothing more is launched). */
+int32_t svgp_elbo_with_mean(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                            double num_data, const svgp_point_mean* pm, double* elbo_out, svgp_terms* terms_out);
+int32_t svgp_marginals_with_mean(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                                 const svgp_point_mean* pm, double* mean_out, double* var_out);
+/* Value and gradient with mux, one entry point for four cases: g_mu = g_v = NULL is the built-in likelihood (svgp_elbo_grad), both
+ * non-NULL a likelihood the host evaluated on svgp_marginals_with_mean (svgp_elbo_grad_ext: sum_e, g_mu, g_v as there); gx = NULL: no
+ * x_bar, else svgp_input_grad as in svgp_elbo_grad_inputs; gpm = NULL: no mux_bar.  pm = NULL with gpm = NULL is exactly the
+ * corresponding existing call, bitwise.  Every output other than mux_bar is that call's, evaluated at the shifted prior mean.
+ * SVGP_INVALID_ARG, before anything is enqueued: a NULL pm->mu or gpm->mu_bar, on_device not 0 / 1 or reserved != 0 in pm or gpm,
+ * a device gpm->mu_bar overlapping the data's storage (x, y) or a device x_bar output, exactly one of g_mu / g_v NULL, and every
+ * argument error of the existing calls.  On a context with a communicator all three calls are collective like their counterparts
+ * (an argument error goes through the opening handshake); mux is the rank's own shard's, and mux_bar is NEVER all-reduced. */
+int32_t svgp_elbo_grad_with_mean(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                                 double num_data, const svgp_point_mean* pm, double sum_e, const double* g_mu, const double* g_v,
+                                 double* elbo_out, svgp_terms* terms_out, svgp_grads* grads_out, const svgp_input_grad* gx,
+                                 svgp_point_mean_grad* gpm);
 
 /* ---- posterior(sva)  replaces SVA:115-136 (Centered) / SVA:160-187 (NonCentered) -------------
  * fills ApproxPosteriorGP.data = (Kuu = Cholesky(Lk), B, α): Lk_out M×M lower (upper zeroed),

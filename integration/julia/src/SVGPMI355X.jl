@@ -75,6 +75,18 @@ struct InputGrad                      # svgp_input_grad (24 bytes): d elbo / d x
     reserved::Int32
 end
 
+struct PointMean                      # svgp_point_mean (16 bytes): the batch's prior mean offsets mux
+    mu::Ptr{Cvoid}
+    on_device::Int32
+    reserved::Int32
+end
+
+struct PointMeanGrad                  # svgp_point_mean_grad (16 bytes): d elbo / d mux
+    mu_bar::Ptr{Cvoid}
+    on_device::Int32
+    reserved::Int32
+end
+
 # ---------------------------------------------------------------------------------------------------------
 # context (one per process and GPU) and status -> exception (SURVEY §8b)
 # ---------------------------------------------------------------------------------------------------------
@@ -173,7 +185,10 @@ end
 
 unpack_mean(::AbstractGPs.ZeroMean) = 0.0
 unpack_mean(m::AbstractGPs.ConstMean) = Float64(only(m.c))
+unpack_mean(::AbstractGPs.MeanFunction) = 0.0     # any other mean (CustomMean ...): mean_const 0, its values travel as offsets
 unpack_mean(::Any) = nothing
+# a mean the library takes as caller-evaluated offsets: mux = mean_vector(m, x) at the batch, muz = mean_vector(m, z) at the inducing points
+offset_mean(m) = m isa AbstractGPs.MeanFunction && !(m isa AbstractGPs.ZeroMean) && !(m isa AbstractGPs.ConstMean)
 
 # (code, parameter, has a closed-form expectation [GPLikelihoods AnalyticExpectation])
 unpack_lik(l::GaussianLikelihood) = (Int32(0), Float64(only(l.σ²)), true)
@@ -207,6 +222,7 @@ struct Packed{T}
     invl::Vector{Float64}; Z::Array{T}; m::Vector{T}; Lq::Matrix{T}
     desc::ModelDesc
     ext::Bool        # likelihood not enumerated by the ABI: evaluated HERE on the device marginals (svgp_marginals / svgp_elbo_grad_ext)
+    offset::Bool     # an offset mean (offset_mean): desc.mean_const = 0 and the mean's values must travel with every call
 end
 
 # Any single-latent GPLikelihoods likelihood can take the host-evaluated route; the two multi-latent ones cannot.
@@ -216,7 +232,10 @@ compute_type(::Type{Float32}) = Float32
 compute_type(::Type{Float64}) = Float64
 compute_type(::Type) = nothing
 
-function pack(sva::SparseVariationalApproximation{P}, lik, quadrature, ::Type{T}) where {P,T<:FT}
+# offsets = true: the caller passes the offset mean's values with every call (svgp_model_set_mean_z, svgp_*_with_mean) - only the
+# hooks below do.  Otherwise a model with an offset mean is refused (Unsupported): the resident / group APIs (DeviceModel, update!,
+# elbo_resident, set_model!, elbo(G, ...)) have no offsets, and a zero mean in their place would be a silently wrong ELBO.
+function pack(sva::SparseVariationalApproximation{P}, lik, quadrature, ::Type{T}; offsets::Bool=false) where {P,T<:FT}
     lay = layout(sva.fz.x)
     lay === nothing && throw(Unsupported())
     lz, Z, d = lay
@@ -225,6 +244,8 @@ function pack(sva::SparseVariationalApproximation{P}, lik, quadrature, ::Type{T}
     sva.q isa MvNormal || throw(Unsupported())
     ku = unpack_kernel(sva.fz.f.kernel, d)
     c = unpack_mean(sva.fz.f.mean)
+    offset = offset_mean(sva.fz.f.mean)
+    offset && !offsets && throw(Unsupported())
     lk = unpack_lik(lik)
     ext = lk === nothing
     ext && !ext_ok(lik) && throw(Unsupported())
@@ -239,7 +260,7 @@ function pack(sva::SparseVariationalApproximation{P}, lik, quadrature, ::Type{T}
     Zd = Array{T}(Z)
     desc = ModelDesc(T === Float64 ? 0 : 1, fam, P === Centered ? 1 : 0, lk[1], qn, lz, 0, d, length(m), σ²,
                      pointer(invl), c, jit, lk[2], pointer(Zd), pointer(m), pointer(Lq))
-    return Packed{T}(invl, Zd, m, Lq, desc, ext)
+    return Packed{T}(invl, Zd, m, Lq, desc, ext, offset)
 end
 
 # ---------------------------------------------------------------------------------------------------------
@@ -280,7 +301,7 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
     T === nothing && return nothing
     local p
     try
-        p = pack(sva, lfx.lik, quadrature, T)
+        p = pack(sva, lfx.lik, quadrature, T; offsets=true)
     catch e
         e isa Unsupported || rethrow()
         return nothing
@@ -293,6 +314,15 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
     (comm_world() > 1 || worth_offloading(length(y), length(p.m), Int(p.desc.d); grad=want)) || return nothing
     Xd, yd = Array{T}(X), Vector{T}(y)
     n = length(yd)
+    # GP(CustomMean(g), k) and the like: the mean's values at x and z, evaluated here (O(n)); NULL offsets otherwise
+    pmean = offset_mean(sva.fz.f.mean)
+    μx = pmean ? Vector{T}(AbstractGPs.mean_vector(sva.fz.f.mean, lfx.fx.x)) : T[]
+    μz = pmean ? Vector{T}(AbstractGPs.mean_vector(sva.fz.f.mean, sva.fz.x)) : T[]
+    pm = Ref(PointMean(pointer(μx), 0, 0))
+    gμx = zeros(T, pmean ? n : 0)
+    gpm = Ref(PointMeanGrad(pointer(gμx), 0, 0))
+    pm_arg = pmean ? pm : Ptr{PointMean}(C_NULL)
+    gpm_arg = pmean ? gpm : Ptr{PointMeanGrad}(C_NULL)
     out, terms = Ref{Float64}(), Terms()
     d, M = Int(p.desc.d), length(p.m)
     gl, gz, gm, gLq = zeros(Float64, d), similar(p.Z), similar(p.m), similar(p.Lq)
@@ -301,7 +331,7 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
     gx = InputGrad(pointer(gxf), n, 0, 0)
     st = Int32(0)
     Δlik = nothing
-    GC.@preserve p Xd yd gl gz gm gLq gxf begin
+    GC.@preserve p Xd yd gl gz gm gLq gxf μx μz gμx pm gpm begin
         if p.ext
             # host-evaluated likelihood: marginals from the device, SVA:355 here, the backward pass on the device again
             want && config === nothing && return nothing
@@ -312,23 +342,27 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
             μ, v = zeros(Float64, n), zeros(Float64, n)
             try   # the user's likelihood / AD may throw: the handles are freed on every path
             st = ccall((:svgp_model_create, lib), Int32, (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Ptr{Cvoid}}), ctx(), p.desc, hm)
+            if st == 0 && pmean
+                st = ccall((:svgp_model_set_mean_z, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx(), hm[], μz)
+            end
             if st == 0
                 st = ccall((:svgp_data_upload, lib), Int32,
                            (Ptr{Cvoid}, Int32, Int32, Int32, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}),
                            ctx(), p.desc.dtype, lx, p.desc.d, n, Xd, C_NULL, hd)
             end
             if st == 0
-                st = ccall((:svgp_marginals, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
-                           ctx(), hm[], hd[], 0, n, μ, v)
+                st = ccall((:svgp_marginals_with_mean, lib), Int32,
+                           (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{PointMean}, Ptr{Float64}, Ptr{Float64}),
+                           ctx(), hm[], hd[], 0, n, pm_arg, μ, v)
             end
             if st == 0
                 sumE, pb = host_expectation(want ? config : nothing, quadrature, lfx.lik, μ, v, y)
                 if want
                     Δlik, gμ, gv = pb
-                    st = ccall((:svgp_elbo_grad_ext_inputs, lib), Int32,
-                               (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Ptr{Float64}, Ptr{Float64},
-                                Ref{Float64}, Ref{Terms}, Ref{Grads}, Ref{InputGrad}),
-                               ctx(), hm[], hd[], 0, n, Float64(num_data), Float64(sumE), gμ, gv, out, terms, g, gx)
+                    st = ccall((:svgp_elbo_grad_with_mean, lib), Int32,
+                               (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Ptr{PointMean}, Float64, Ptr{Float64},
+                                Ptr{Float64}, Ref{Float64}, Ref{Terms}, Ref{Grads}, Ref{InputGrad}, Ptr{PointMeanGrad}),
+                               ctx(), hm[], hd[], 0, n, Float64(num_data), pm_arg, Float64(sumE), gμ, gv, out, terms, g, gx, gpm_arg)
                 else
                     kl = Ref{Float64}()
                     st = ccall((:svgp_prior_kl, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Float64}, Ptr{Float64}), ctx(), hm[], kl, C_NULL)
@@ -339,7 +373,7 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
                 free_on_ctx(:data, hd[])
                 free_on_ctx(:model, hm[])
             end
-        elseif !want
+        elseif !want && !pmean
             # one-shot entry point: uploads x, y, evaluates, frees (resident handles below avoid the upload in loops)
             st = ccall((:svgp_elbo_host, lib), Int32,
                        (Ptr{Cvoid}, Ref{ModelDesc}, Int32, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ref{Float64}, Ref{Terms}),
@@ -347,12 +381,24 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
         else
             hm, hd = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
             st = ccall((:svgp_model_create, lib), Int32, (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Ptr{Cvoid}}), ctx(), p.desc, hm)
+            if st == 0 && pmean
+                st = ccall((:svgp_model_set_mean_z, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx(), hm[], μz)
+            end
             if st == 0
                 st = ccall((:svgp_data_upload, lib), Int32,
                            (Ptr{Cvoid}, Int32, Int32, Int32, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}),
                            ctx(), p.desc.dtype, lx, p.desc.d, n, Xd, yd, hd)
             end
-            if st == 0
+            if st == 0 && !want   # (an offset mean's value: resident handles, svgp_elbo_with_mean)
+                st = ccall((:svgp_elbo_with_mean, lib), Int32,
+                           (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Ptr{PointMean}, Ref{Float64}, Ref{Terms}),
+                           ctx(), hm[], hd[], 0, n, Float64(num_data), pm_arg, out, terms)
+            elseif st == 0 && pmean
+                st = ccall((:svgp_elbo_grad_with_mean, lib), Int32,
+                           (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Ptr{PointMean}, Float64, Ptr{Float64},
+                            Ptr{Float64}, Ref{Float64}, Ref{Terms}, Ref{Grads}, Ref{InputGrad}, Ptr{PointMeanGrad}),
+                           ctx(), hm[], hd[], 0, n, Float64(num_data), pm_arg, 0.0, C_NULL, C_NULL, out, terms, g, gx, gpm_arg)
+            elseif st == 0
                 st = ccall((:svgp_elbo_grad_inputs, lib), Int32,
                            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Ref{Float64}, Ref{Terms}, Ref{Grads}, Ref{InputGrad}),
                            ctx(), hm[], hd[], 0, n, Float64(num_data), out, terms, g, gx)
@@ -365,7 +411,10 @@ function elbo_and_grads(sva, lfx, y, num_data, quadrature, want::Bool, config=no
     check(st, terms)
     # `Δlik`: the likelihood's own tangent from the host pullback (host-evaluated route), to be scaled by num_data / n
     gxl = lx == 0 ? permutedims(gxf) : (lx == 1 ? gxf : vec(gxf))      # in the layout of lfx.fx.x's storage
-    return out[], (σ²=g.variance, invl=gl, z=gz, m=gm, Lq=gLq, lik=g.lik_sigma2, c=g.mean_const, x=gxl, Δlik=Δlik, scale=Float64(num_data) / n)
+    # offset mean: mux_bar, and muz_bar = -m_bar (Centered; m enters only through m - muz) or 0 (NonCentered) - include/svgp_mi355x.h
+    μz_bar = pmean ? (p.desc.parametrization == 1 ? -Vector{Float64}(gm) : zeros(Float64, M)) : nothing
+    return out[], (σ²=g.variance, invl=gl, z=gz, m=gm, Lq=gLq, lik=g.lik_sigma2, c=g.mean_const, x=gxl, Δlik=Δlik, scale=Float64(num_data) / n,
+                   μx=pmean ? Vector{Float64}(gμx) : nothing, μz=μz_bar)
 end
 
 # ---- structural tangents -------------------------------------------------------------------------------------------
@@ -414,15 +463,25 @@ function ChainRulesCore.rrule(config::RuleConfig{>:HasReverseMode}, ::typeof(MI3
     r = elbo_and_grads(sva, lfx, y, num_data, quadrature, true, config)
     r === nothing && return decline
     val, g = r
+    # an offset mean (CustomMean with learned parameters ...): mux_bar / muz_bar pulled back through mean_vector by the caller's AD
+    f0 = sva.fz.f
+    mx_back = g.μx === nothing ? nothing : last(rrule_via_ad(config, AbstractGPs.mean_vector, f0.mean, lfx.fx.x))
+    mz_back = g.μx === nothing ? nothing : last(rrule_via_ad(config, AbstractGPs.mean_vector, f0.mean, sva.fz.x))
     function try_elbo_pullback(Δ)
         Δ = unthunk(Δ)
         s(a) = Δ .* a
         f = sva.fz.f
-        Δf = Tangent{typeof(f)}(; mean=mean_tangent(f.mean, Δ * g.c), kernel=kernel_tangent(f.kernel, Δ * g.σ², s(g.invl)))
-        Δfz = Tangent{typeof(sva.fz)}(; f=Δf, x=inputs_tangent(sva.fz.x, s(g.z)))      # Σy (jitter): not differentiated
+        Δmean, Δxm, Δzm = mean_tangent(f.mean, Δ * g.c), NoTangent(), NoTangent()
+        if mx_back !== nothing
+            _, Δm1, Δxm = mx_back(s(g.μx))
+            _, Δm2, Δzm = mz_back(s(g.μz))
+            Δmean = unthunk(Δm1) + unthunk(Δm2)
+        end
+        Δf = Tangent{typeof(f)}(; mean=Δmean, kernel=kernel_tangent(f.kernel, Δ * g.σ², s(g.invl)))
+        Δfz = Tangent{typeof(sva.fz)}(; f=Δf, x=inputs_tangent(sva.fz.x, s(g.z)) + unthunk(Δzm))      # Σy (jitter): not differentiated
         Δsva = Tangent{typeof(sva)}(; fz=Δfz, q=q_tangent(sva.q, s(g.m), s(g.Lq)))
         # the prior of lfx is the SAME object (SVA:347-351), its tangent is already on sva.fz.f; the data inputs lfx.fx.x: d elbo / d x
-        Δfx = Tangent{typeof(lfx.fx)}(; x=inputs_tangent(lfx.fx.x, s(g.x)))
+        Δfx = Tangent{typeof(lfx.fx)}(; x=inputs_tangent(lfx.fx.x, s(g.x)) + unthunk(Δxm))
         Δlfx = Tangent{typeof(lfx)}(; fx=Δfx, lik=g.Δlik === nothing ? lik_tangent(lfx.lik, Δ * g.lik) : (Δ * g.scale) * g.Δlik)
         return (NoTangent(), Δsva, Δlfx, NoTangent(), NoTangent(), NoTangent())
     end
@@ -439,7 +498,7 @@ function MI355XHooks.try_posterior(sva::SparseVariationalApproximation{P}) where
     T === nothing && return nothing
     local p
     try
-        p = pack(sva, GaussianLikelihood(1.0), GPLikelihoods.DefaultExpectationMethod(), T)
+        p = pack(sva, GaussianLikelihood(1.0), GPLikelihoods.DefaultExpectationMethod(), T; offsets=true)
     catch e
         e isa Unsupported || rethrow()
         return nothing
@@ -449,8 +508,12 @@ function MI355XHooks.try_posterior(sva::SparseVariationalApproximation{P}) where
     Lk, α, B = Matrix{T}(undef, M, M), Vector{T}(undef, M), Matrix{T}(undef, M, M)
     hm = Ref{Ptr{Cvoid}}(C_NULL)
     st = Int32(0)
-    GC.@preserve p Lk α B begin
+    μz = offset_mean(sva.fz.f.mean) ? Vector{T}(AbstractGPs.mean_vector(sva.fz.f.mean, sva.fz.x)) : nothing   # Centered α = Kuu \ (m - mean(fz))
+    GC.@preserve p Lk α B μz begin
         st = ccall((:svgp_model_create, lib), Int32, (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Ptr{Cvoid}}), ctx(), p.desc, hm)
+        if st == 0 && μz !== nothing
+            st = ccall((:svgp_model_set_mean_z, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx(), hm[], μz)
+        end
         if st == 0
             st = ccall((:svgp_posterior, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
                        ctx(), hm[], Lk, α, B)
@@ -481,7 +544,7 @@ function MI355XHooks.try_predict(f::ApproxPosteriorGP, x::AbstractVector; want_m
     T === nothing && return nothing
     local p
     try
-        p = pack(sva, GaussianLikelihood(1.0), GPLikelihoods.DefaultExpectationMethod(), T)
+        p = pack(sva, GaussianLikelihood(1.0), GPLikelihoods.DefaultExpectationMethod(), T; offsets=true)
     catch e
         e isa Unsupported || rethrow()
         return nothing
@@ -496,8 +559,13 @@ function MI355XHooks.try_predict(f::ApproxPosteriorGP, x::AbstractVector; want_m
     ptr(a) = a === nothing ? C_NULL : pointer(a)
     hm = Ref{Ptr{Cvoid}}(C_NULL)
     st = Int32(0)
-    GC.@preserve p Xd μ v C begin
+    pmean = offset_mean(sva.fz.f.mean)
+    μz = pmean ? Vector{T}(AbstractGPs.mean_vector(sva.fz.f.mean, sva.fz.x)) : nothing
+    GC.@preserve p Xd μ v C μz begin
         st = ccall((:svgp_model_create, lib), Int32, (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Ptr{Cvoid}}), ctx(), p.desc, hm)
+        if st == 0 && pmean
+            st = ccall((:svgp_model_set_mean_z, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx(), hm[], μz)
+        end
         if st == 0
             st = ccall((:svgp_predict, lib), Int32,
                        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
@@ -507,6 +575,8 @@ function MI355XHooks.try_predict(f::ApproxPosteriorGP, x::AbstractVector; want_m
     end
     st == 4 && return nothing
     check(st)
+    # svgp_predict returns mean_const + K*u α: an offset mean adds its own values at x (SVA:211)
+    pmean && μ !== nothing && (μ .+= AbstractGPs.mean_vector(sva.fz.f.mean, x))
     return (μ, v, C)
 end
 
@@ -523,7 +593,7 @@ function MI355XHooks.try_cross_cov(f::ApproxPosteriorGP, x::AbstractVector, y::A
     (T === nothing || eltype(Y) !== eltype(X) || dx != dy) && return nothing
     local p
     try
-        p = pack(sva, GaussianLikelihood(1.0), GPLikelihoods.DefaultExpectationMethod(), T)
+        p = pack(sva, GaussianLikelihood(1.0), GPLikelihoods.DefaultExpectationMethod(), T; offsets=true)   # (cov does not depend on the mean: Lk, B only)
     catch e
         e isa Unsupported || rethrow()
         return nothing
@@ -574,13 +644,14 @@ mutable struct DeviceModel
     h::Ptr{Cvoid}
 end
 function DeviceModel(p::Packed)
+    p.offset && throw(Unsupported())     # (no offsets on the resident path: see pack)
     h = Ref{Ptr{Cvoid}}()
     GC.@preserve p check(ccall((:svgp_model_create, lib), Int32, (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Ptr{Cvoid}}), ctx(), p.desc, h))
     M = DeviceModel(h[])
     finalizer(M -> free_on_ctx(:model, M.h), M)
     return M
 end
-update!(M::DeviceModel, p::Packed) =
+update!(M::DeviceModel, p::Packed) = p.offset ? throw(Unsupported()) :
     GC.@preserve p check(ccall((:svgp_model_update, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{ModelDesc}), ctx(), M.h, p.desc))
 
 "ELBO of points off+1 : off+len of resident data (a minibatch window), SVA:340-360."
@@ -635,6 +706,7 @@ function upload!(G::Group, x, y::AbstractVector{T}) where {T<:FT}
     return G
 end
 function set_model!(G::Group, p::Packed)
+    p.offset && throw(Unsupported())     # the group calls keep constant means only (include/svgp_mi355x.h)
     GC.@preserve p begin
         if isempty(G.models)
             G.models = fill(C_NULL, G.n)

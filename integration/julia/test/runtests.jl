@@ -135,6 +135,33 @@ end
     @test on(() -> posterior(sva, f(x, T(0.3)), y)).data.α ≈ pr.data.α rtol = 100tol      # 3-argument form SVA:189-201
 end
 
+@testset "CustomMean: device == reference body, and the resident / group APIs refuse it ($T, centered = $cen)" for
+        T in (Float64, Float32), cen in (false, true)
+    rng = MersenneTwister(5)
+    x, y, θ, build, lik = problem(rng, T)
+    f0, sva0 = build(θ)
+    w = T[0.3, -0.2, 0.1]
+    trend(w) = CustomMean(xi -> w[1] * xi[1] + w[2] * xi[2] + w[3])
+    f = GP(trend(w), f0.kernel)
+    sva = cen ? SparseVariationalApproximation(Centered(), f(sva0.fz.x, sva0.fz.Σy), sva0.q) :
+                SparseVariationalApproximation(f(sva0.fz.x, sva0.fz.Σy), sva0.q)
+    lfx = LatentGP(f, lik, 1e-18)(x)
+    rtol = T === Float64 ? 1e-8 : 1e-4
+    @test on(() -> elbo(sva, lfx, y; num_data=777)) ≈ off(() -> elbo(sva, lfx, y; num_data=777)) rtol = rtol
+    # the mean's parameters: rrule_via_ad through mean_vector
+    loss(w) = elbo(cen ? SparseVariationalApproximation(Centered(), GP(trend(w), f0.kernel)(sva0.fz.x, sva0.fz.Σy), sva0.q) :
+                         SparseVariationalApproximation(GP(trend(w), f0.kernel)(sva0.fz.x, sva0.fz.Σy), sva0.q),
+                   LatentGP(GP(trend(w), f0.kernel), lik, 1e-18)(x), y; num_data=777)
+    @test on(() -> Zygote.gradient(loss, w)[1]) ≈ off(() -> Zygote.gradient(loss, w)[1]) rtol = (T === Float64 ? 1e-6 : 3e-3)
+    xs = ColVecs(randn(rng, T, size(θ.Z, 1), 40))
+    @test on(() -> mean(posterior(sva), xs)) ≈ off(() -> mean(posterior(sva), xs)) rtol = rtol
+    # without offsets a zero mean would stand in for the CustomMean: pack refuses, and so do the APIs that take a Packed
+    @test_throws MI.Unsupported MI.pack(sva, lik, GPLikelihoods.DefaultExpectationMethod(), T)
+    p = MI.pack(sva, lik, GPLikelihoods.DefaultExpectationMethod(), T; offsets=true)
+    @test p.offset && p.desc.mean_const == 0
+    @test_throws MI.Unsupported MI.DeviceModel(p)
+end
+
 @testset "reference error behaviour is preserved" begin
     rng = MersenneTwister(4)
     x, y, θ, build, lik = problem(rng, Float64)
