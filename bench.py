@@ -7,6 +7,12 @@
     python bench.py --gpus N ...        # started plainly with N > 1: launches the line above itself (N fresh children, before
                                         # this process touches the GPU) and relays rank 0's JSON line
     python bench.py ... --dump-outputs DIR                   # also write what the last timed step returned as DIR/<name>.npy
+    python bench.py ... --full                               # also everything beside the headline figure (see below)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: `value` and `ms_per_step`, with the
+roofline and breakdown its own timed steps give.  --full adds, after the timed steps, the Kuf roofline, value and gradient, the
+host training step, the C5 minibatch leg, the CPU baseline with its parity check, the N > 1 collective cross-check and the
+figures read from committed PMC profiles (--no-kuf / --no-grad / --no-c5 / --no-cpu-baseline leave single legs out of it).
 
 A step is ONE full ELBO evaluation (reference elbo(sva, lfx, y), SVA:340-360) over one batch of synthetic
 data already resident in HBM: Kuu assembly, cholesky(Kuu), diagonal-block inverses / T panels, KL, then the
@@ -15,7 +21,7 @@ Workload H: N = 1e6 points per GPU, M = 1024, d = 8, SE-ARD, Gauss
 NonCentered.  With N GPUs every rank holds its own 1e6-point shard (weak scaling) and calls the library's COLLECTIVE
 svgp_elbo: the ranks' partial sums are combined by ONE ncclAllReduce of 8 doubles issued inside the library on the
 device-resident result (csrc/comm.hip; torch.distributed only carries the 128-byte communicator id and the timing
-barrier); `value` is then whole-job 1e6-point ELBO evaluations per second.  The same line carries `c5_minibatch`:
+barrier); `value` is then whole-job 1e6-point ELBO evaluations per second.  With --full the line carries `c5_minibatch`:
 BASELINE's 8-GPU configuration C5 (fp32, 2^18 points per GPU per step, num_data = 1e8) through the same path.
 Inputs come from approxgp/synthetic.py, the one §8d recipe the parity tests use too (z = first M points of x + 1e-3 noise).
 """
@@ -651,7 +657,10 @@ def main():
     ap.add_argument("--steps", type=int, default=100)      # H: 100 x 34 ms: a timed region of > 3 s
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="H", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need (module docstring)")
     ap.add_argument("--cpu-sample", type=int, default=100000)   # ~10 s of host work at H (used when RAM is short)
+    # legs of a --full run that can be left out of it one by one
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kuf", action="store_true")
     ap.add_argument("--no-grad", action="store_true")
@@ -667,6 +676,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run measures the headline figure alone; every leg beside it needs --full
+        args.no_cpu_baseline = args.no_kuf = args.no_grad = args.no_c5 = True
 
     # `python bench.py --gpus N` with N > 1, started plainly: become the launcher of N fresh ranks (before torch / HIP are
     # even imported here), so that an N-GPU line is an N-rank RCCL run however the script was started
@@ -743,7 +754,7 @@ def main():
     }
     if use_dist:
         assert res["n_points_global"] == n * world, (res["n_points_global"], n, world)
-        if not host_comm:
+        if args.full and not host_comm:
             # cross-check of the in-library collective on this very run: every rank's LOCAL partial sums (svgp_elbo_partial,
             # never collective) all-reduced by torch.distributed must give the ELBO the library's own ncclAllReduce gave
             part, kl, err = (0.0, 0.0), 0.0, None
@@ -760,7 +771,7 @@ def main():
                 ref = float(tt[0].item()) * (num_data / float(tt[1].item())) - kl
                 out["collective_check"] = {"library_allreduce_elbo": res["elbo"], "torch_allreduce_of_local_partials": ref,
                                            "rel_err": abs(res["elbo"] - ref) / abs(ref)}
-    if rank == 0:   # the Cholesky's MFMA utilisation is a PMC figure: from the committed profile of this configuration, labelled
+    if args.full and rank == 0:   # the Cholesky's MFMA utilisation is a PMC figure: from the committed profile of this configuration, labelled
         import glob
         for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "round*", f"{name}_*_pmc.json")), reverse=True):
             try:
@@ -772,7 +783,7 @@ def main():
                                                  " (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES over every launch of the factorisation; not measured in this run)",
                                                  "ms_under_rocprof": agg["ms_per_evaluation"]})
                 break
-    tr = profile_traffic(name, "strip_kernel<") if rank == 0 else None
+    tr = profile_traffic(name, "strip_kernel<") if args.full and rank == 0 else None
     if tr:
         out["roofline"].update({k: v for k, v in tr.items() if v is not None or k == "traffic_stale"})
         out["roofline"]["traffic_note"] = ("bytes per launch at the L2<->fabric boundary (FETCH_SIZE x2 + WRITE_SIZE); includes "

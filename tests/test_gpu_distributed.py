@@ -255,7 +255,7 @@ def test_bench_two_gpu_launch_runs_two_rccl_ranks():
     import subprocess
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--config", "C2", "--no-grad", "--no-c5"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--config", "C2", "--full", "--no-grad", "--no-c5"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["rccl_world"] == 2
