@@ -15,5 +15,8 @@ from .kernels import (ARDTransform, Matern32Kernel, Matern52Kernel, ScaledKernel
 from .sva import (SVGP, ApproxPosteriorGP, Centered, NonCentered, SparseVariationalApproximation, approx_lml, elbo,
                   elbo_and_gradient,
                   inducing_points, posterior, prior_kl)
+# LaplaceApproximation; approx_lml and posterior dispatch on the approximation type (the SVGP methods above are unchanged)
+from .laplace import (DeviceLaplace, LaplaceApproximation, LaplaceObjective, LaplacePosteriorGP, approx_lml,
+                      approx_lml_and_gradient, build_laplace_objective, posterior)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

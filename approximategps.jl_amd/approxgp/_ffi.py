@@ -65,6 +65,19 @@ class Timing(C.Structure):
                 ("ms_chol", C.c_double), ("ms_overlap", C.c_double)]
 
 
+class LaplaceDesc(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("kernel", C.c_int32), ("likelihood", C.c_int32), ("d", C.c_int32),
+                ("maxiter", C.c_int32), ("warm_start", C.c_int32), ("variance", C.c_double),
+                ("inv_lengthscale", C.POINTER(C.c_double)), ("jitter", C.c_double), ("lik_sigma2", C.c_double),
+                ("reserved", C.c_int64)]
+
+
+class LaplaceInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("chol_info", C.c_int32), ("reserved", C.c_int32),
+                ("lml", C.c_double), ("ms_point", C.c_double), ("ms_chol", C.c_double), ("ms_linv", C.c_double),
+                ("ms_gemv", C.c_double)]
+
+
 # every symbol include/svgp_mi355x.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -111,6 +124,15 @@ SYMBOLS = {
     "svgp_gausshermite": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "svgp_offload_advice": (C.c_int32, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "svgp_offload_work": (C.c_double, [C.c_int64, C.c_int64, C.c_int32]),
+    # the Laplace approximation
+    "svgp_laplace_create": (C.c_int32, [_P, _P, C.POINTER(_P)]),
+    "svgp_laplace_fit": (C.c_int32, [_P, _P, C.POINTER(LaplaceDesc), _P, C.POINTER(C.c_double), C.POINTER(LaplaceInfo)]),
+    "svgp_laplace_lml_grad": (C.c_int32, [_P, _P, C.POINTER(LaplaceDesc), _P, C.POINTER(C.c_double), C.POINTER(LaplaceInfo),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "svgp_laplace_mode": (C.c_int32, [_P, _P, _P, _P, _P]),
+    "svgp_laplace_predict": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P]),
+    "svgp_laplace_predict_cross_cov": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P, _P]),
+    "svgp_laplace_free": (C.c_int32, [_P, _P]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),
     "svgp_ctx_attach_comm": (C.c_int32, [_P, _P, C.c_int32, C.c_int32]),

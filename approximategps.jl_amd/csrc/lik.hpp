@@ -75,6 +75,31 @@ __device__ __forceinline__ double dloglik_point(int lik, double f, double y, dou
   return y * exp(-f) - sigma2;
 }
 
+// d2 log p(y|f) / df2 and d3 log p(y|f) / df3 (the Laplace approximation: W = -d2, the gradient's s2 = -diag(Sigma) d3 / 2).
+// All six are log-concave in f, so d2 <= 0.  Probit: with sg = +-1 for y = 1 / 0, t = sg f and h = phi(t) / Phi(t),
+// dll = sg h, d2 = h' = -h (t + h), d3 = sg h'' with h'' = -h' (t + h) - h (1 + h').
+__device__ __forceinline__ void d23loglik_point(int lik, double f, double y, double sigma2, double& d2, double& d3) {
+  if (lik == 0) {
+    d2 = -1.0 / sigma2;
+    d3 = 0.0;
+  } else if (lik == 1) {
+    const double s = 1.0 / (1.0 + exp(-f)), v = s * (1.0 - s);
+    d2 = -v;
+    d3 = -v * (1.0 - 2.0 * s);
+  } else if (lik == 2) {
+    d2 = -exp(f);
+    d3 = d2;
+  } else if (lik == 5) {
+    const double sg = y > 0.5 ? 1.0 : -1.0, t = sg * f, h = ndtr_hazard_d(t);
+    const double h1 = -h * (t + h);
+    d2 = h1;
+    d3 = sg * (-h1 * (t + h) - h * (1.0 + h1));
+  } else {   // Exponential and Gamma with the exp link (scale e^f): the f-dependence is -y e^-f in both
+    d3 = y * exp(-f);
+    d2 = -d3;
+  }
+}
+
 // (dE/dmu, dE/dv, dE/dsigma2) of expected_loglik_point: closed forms, or Gauss-Hermite with
 // dE/dmu = sum w g'(f_q), dE/dv = sum w g'(f_q) x_q / sqrt(2 v)
 __device__ __forceinline__ void expected_loglik_grad_point(const LikParams& lp, double mu, double v, double y, double& gmu,

@@ -401,6 +401,66 @@ int32_t svgp_gausshermite(int32_t n, double* nodes_out, double* weights_out);
 int32_t svgp_offload_advice(int64_t n_points, int64_t M, int32_t d, int32_t dtype, int32_t want_gradient);
 double svgp_offload_work(int64_t n_points, int64_t M, int32_t d);
 
+/* ---- the Laplace approximation: LaplaceApproximation / posterior / approx_lml  (src/LaplaceApproximationModule.jl) -------------
+ * A handle over the x and y of an existing data handle (which must outlive it) holding the N x N work of Newton mode finding
+ * (_newton_inner_loop :256-276, RW Alg. 3.1): K = kernelmatrix(k, x) + jitter I, B = I + sW K sW, its Cholesky factor and inverse.
+ * The prior mean is zero (_check_laplace_inputs :167-178 asserts it); one latent function per observation.
+ *   svgp_laplace_fit       Newton from f_init (NULL: zeros, the reference's mean(fx); else N host values in the data's dtype), or
+ *                          with warm_start = 1 and f_init = NULL from the mode of the previous successful fit on the handle (the warm
+ *                          start of build_laplace_objective :95-132).  Convergence is isapprox(f, fnew) in the compute dtype,
+ *                          |f - fnew| <= sqrt(eps) max(|f|, |fnew|); the loop then KEEPS f, otherwise f = fnew, after maxiter steps f
+ *                          is the last fnew.  lml_out = -a'f / 2 + sum log p(y|f) - sum log diag L at that f (laplace_lml :157-165,
+ *                          _laplace_lml :250-254).  The handle caches the intermediates at f for the predictions.
+ *   svgp_laplace_lml_grad  the same fit, then d lml / d variance and d lml / d inv_lengthscale (d entries): the closed form of RW
+ *                          Alg. 5.1 with d3 log p, the total derivative along the Newton fixed point that the reference's
+ *                          implicit-function rrule (:330-369) gives Zygote.  Likelihood parameters, y and x are not differentiated.
+ *   svgp_laplace_mode      f_opt, d log p / df and W = -d2 log p / df2 at it (N each, data dtype, host; any may be NULL).
+ *   svgp_laplace_predict   mean = k(x, x*)' dll (RW 3.21), var = k(x*, x*) - colsum(v.^2), cov = k(x*, x*) - v'v with
+ *                          v = L \ (sW k(x, x*)) (RW 3.29, :425-463); n values (mean, var) / n x n column-major (cov), data dtype,
+ *                          any may be NULL.  x* in `layout` (SVGP_COLVECS / ROWVECS / VEC) with the data's d.
+ *   svgp_laplace_predict_cross_cov  cov(f, x*, y*) = k(x*, y*) - vx' vy, nx x ny column-major (:458-463).
+ * fp64 and fp32; SE / Matern-3/2 / Matern-5/2 with ARD, d <= SVGP_MAX_D; 1 <= N <= 8192 (fp64) / 16384 (fp32), the sizes the
+ * device Cholesky is tested at - beyond them svgp_laplace_create returns SVGP_UNSUPPORTED.  SVGP_INVALID_ARG, before anything is
+ * enqueued: NULL required pointers, data without y, a descriptor whose dtype / d differ from the data's, maxiter < 1, warm_start
+ * not 0 / 1, jitter < 0, variance <= 0, a Gaussian sigma^2 or Gamma alpha <= 0, reserved != 0; mode / predict before a successful
+ * fit.  SVGP_NOT_POSDEF when cholesky(B) fails (info in svgp_laplace_info.chol_info).  Never collective: on a context with a
+ * communicator these calls stay local.  Found by symbol (no ABI version step). */
+typedef struct svgp_laplace svgp_laplace;
+typedef struct svgp_laplace_desc {
+  int32_t dtype;            /* SVGP_F64 | SVGP_F32: must be the data's */
+  int32_t kernel;           /* SVGP_KERNEL_* */
+  int32_t likelihood;       /* SVGP_LIK_* */
+  int32_t d;                /* must be the data's */
+  int32_t maxiter;          /* >= 1 (newton_kwargs maxiter, default 100) */
+  int32_t warm_start;       /* 1: start from the previous fit's mode when f_init is NULL */
+  double variance;          /* kernel variance */
+  const double* inv_lengthscale; /* d entries */
+  double jitter;            /* cov(fx) = K + jitter I */
+  double lik_sigma2;        /* Gaussian sigma^2, Gamma shape alpha; unused otherwise */
+  int64_t reserved;         /* must be 0 */
+} svgp_laplace_desc;        /* 64 bytes */
+typedef struct svgp_laplace_info {
+  int32_t iterations;       /* Newton steps taken */
+  int32_t converged;        /* 1 when isapprox(f, fnew) stopped the loop */
+  int32_t chol_info;        /* 0, or the order of the first non-positive leading minor of B */
+  int32_t reserved;
+  double lml;
+  /* device time of the steps (HIP events; 0 when the context runs without timing): point kernel and B assembly, cholesky(B),
+     L^-1, the GEMVs and the convergence reduction */
+  double ms_point, ms_chol, ms_linv, ms_gemv;
+} svgp_laplace_info;        /* 56 bytes */
+int32_t svgp_laplace_create(svgp_ctx* ctx, const svgp_data* data, svgp_laplace** out);
+int32_t svgp_laplace_fit(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* desc, const void* f_init, double* lml_out,
+                         svgp_laplace_info* info);
+int32_t svgp_laplace_lml_grad(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* desc, const void* f_init, double* lml_out,
+                              svgp_laplace_info* info, double* d_variance, double* d_inv_lengthscale);
+int32_t svgp_laplace_mode(svgp_ctx* ctx, svgp_laplace* la, void* f_out, void* dll_out, void* W_out);
+int32_t svgp_laplace_predict(svgp_ctx* ctx, svgp_laplace* la, int32_t layout, int64_t n, const void* x_host, void* mean_out,
+                             void* var_out, void* cov_out);
+int32_t svgp_laplace_predict_cross_cov(svgp_ctx* ctx, svgp_laplace* la, int32_t layout, int64_t nx, const void* x_host, int64_t ny,
+                                       const void* y_host, void* cov_out);
+int32_t svgp_laplace_free(svgp_ctx* ctx, svgp_laplace* la);
+
 #ifdef __cplusplus
 }
 #endif

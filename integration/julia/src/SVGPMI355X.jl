@@ -728,4 +728,79 @@ function elbo(G::Group, num_data::Real; offs=zeros(Int64, G.n), lens=G.shard)
     return out[]
 end
 
+# ---------------------------------------------------------------------------------------------------------
+# LaplaceApproximation (src/LaplaceApproximationModule.jl): a resident handle over DeviceData (svgp_laplace_*).  Newton mode
+# finding, laplace_lml (:157-165), its kernel-parameter gradient and the predictions (:425-463) on the device.  Not hooked into
+# the reference's methods (they differentiate through Zygote's rrule of newton_inner_loop); a host calls these directly.
+# ---------------------------------------------------------------------------------------------------------
+struct LaplaceDesc                    # svgp_laplace_desc (64 bytes)
+    dtype::Int32; kernel::Int32; likelihood::Int32; d::Int32; maxiter::Int32; warm_start::Int32
+    variance::Float64; inv_lengthscale::Ptr{Float64}; jitter::Float64; lik_sigma2::Float64; reserved::Int64
+end
+mutable struct LaplaceInfo            # svgp_laplace_info (56 bytes)
+    iterations::Int32; converged::Int32; chol_info::Int32; reserved::Int32
+    lml::Float64; ms_point::Float64; ms_chol::Float64; ms_linv::Float64; ms_gemv::Float64
+    LaplaceInfo() = new(0, 0, 0, 0, 0, 0, 0, 0, 0)
+end
+mutable struct DeviceLaplace
+    h::Ptr{Cvoid}; data::DeviceData
+end
+function DeviceLaplace(D::DeviceData)
+    h = Ref{Ptr{Cvoid}}()
+    check(ccall((:svgp_laplace_create, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), ctx(), D.h, h))
+    L = DeviceLaplace(h[], D)
+    finalizer(L -> (CTX[] == C_NULL || L.h == C_NULL) ||
+                   ccall((:svgp_laplace_free, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), CTX[], L.h), L)
+    return L
+end
+"laplace_lml at the Newton mode (desc.warm_start = 1: from the previous call's mode, build_laplace_objective :95-132)."
+function laplace_lml!(L::DeviceLaplace, desc::LaplaceDesc; f_init=nothing)
+    out, info = Ref{Float64}(), LaplaceInfo()
+    GC.@preserve f_init check(ccall((:svgp_laplace_fit, lib), Int32,
+                                    (Ptr{Cvoid}, Ptr{Cvoid}, Ref{LaplaceDesc}, Ptr{Cvoid}, Ref{Float64}, Ref{LaplaceInfo}),
+                                    ctx(), L.h, desc, f_init === nothing ? C_NULL : pointer(f_init), out, info))
+    return out[], info
+end
+"laplace_lml and its gradient with respect to (variance, inv_lengthscale): what Zygote gets from the rrule of :330-369."
+function laplace_lml_and_grad!(L::DeviceLaplace, desc::LaplaceDesc; f_init=nothing)
+    out, info, gv = Ref{Float64}(), LaplaceInfo(), Ref{Float64}()
+    gl = zeros(Float64, desc.d)
+    GC.@preserve f_init gl check(ccall((:svgp_laplace_lml_grad, lib), Int32,
+                                       (Ptr{Cvoid}, Ptr{Cvoid}, Ref{LaplaceDesc}, Ptr{Cvoid}, Ref{Float64}, Ref{LaplaceInfo}, Ref{Float64},
+                                        Ptr{Float64}),
+                                       ctx(), L.h, desc, f_init === nothing ? C_NULL : pointer(f_init), out, info, gv, gl))
+    return out[], gv[], gl, info
+end
+"(f_opt, d_loglik, W) of the cached intermediates (LaplaceCache :180-199)."
+function laplace_mode(L::DeviceLaplace, ::Type{T}) where {T<:FT}
+    f, g, w = zeros(T, L.data.n), zeros(T, L.data.n), zeros(T, L.data.n)
+    check(ccall((:svgp_laplace_mode, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx(), L.h, f, g, w))
+    return f, g, w
+end
+npoints(lx, X) = lx == 1 ? size(X, 1) : (lx == 0 ? size(X, 2) : length(X))
+"mean_and_var / mean_and_cov of the LaplacePosteriorGP at x (:437-447)."
+function laplace_predict(L::DeviceLaplace, x, ::Type{T}; want_cov::Bool=false) where {T<:FT}
+    lx, X, _ = layout(x)
+    Xd = Array{T}(X)
+    n = npoints(lx, Xd)
+    μ, v = zeros(T, n), zeros(T, n)
+    C = want_cov ? zeros(T, n, n) : nothing
+    GC.@preserve Xd check(ccall((:svgp_laplace_predict, lib), Int32,
+                                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                                ctx(), L.h, lx, n, Xd, μ, v, C === nothing ? C_NULL : C))
+    return μ, v, C
+end
+"cov(f, x, y) of the LaplacePosteriorGP (:458-463)."
+function laplace_cross_cov(L::DeviceLaplace, x, y, ::Type{T}) where {T<:FT}
+    lx, X, _ = layout(x)
+    _, Y, _ = layout(y)
+    Xd, Yd = Array{T}(X), Array{T}(Y)
+    nx, ny = npoints(lx, Xd), npoints(lx, Yd)
+    C = zeros(T, nx, ny)
+    GC.@preserve Xd Yd check(ccall((:svgp_laplace_predict_cross_cov, lib), Int32,
+                                   (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                                   ctx(), L.h, lx, nx, Xd, ny, Yd, C))
+    return C
+end
+
 end # module
