@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <memory>
 #include <cmath>
 #include <cstdio>
 #include <cstddef>
@@ -158,31 +159,36 @@ int upload_params(svgp_ctx* ctx, svgp_model* m, const svgp_model_desc* d) {
   m->invl_host.assign(d->inv_lengthscale, d->inv_lengthscale + d->d);
   m->desc.inv_lengthscale = m->invl_host.data();
   m->desc.z = m->desc.m = m->desc.Lq = nullptr;  // host pointers are borrowed for the call only
-  HIPC(ctx, hipMemcpyAsync(m->z_raw, d->z, size_t(m->M) * m->d * es, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(ctx, hipMemcpyAsync(m->m_raw, d->m, size_t(m->M) * es, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(ctx, hipMemcpyAsync(m->Lq_raw, d->Lq, size_t(m->M) * m->M * es, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(ctx, hipMemcpyAsync(m->z_raw.p, d->z, size_t(m->M) * m->d * es, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(ctx, hipMemcpyAsync(m->m_raw.p, d->m, size_t(m->M) * es, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(ctx, hipMemcpyAsync(m->Lq_raw.p, d->Lq, size_t(m->M) * m->M * es, hipMemcpyHostToDevice, ctx->stream));
   if (m->dtype == SVGP_F64) {
-    HIPC(ctx, hipMemcpyAsync(m->invl, m->invl_host.data(), m->d * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(m->invl.p, m->invl_host.data(), m->d * 8, hipMemcpyHostToDevice, ctx->stream));
   } else {
     std::vector<float> f(m->invl_host.begin(), m->invl_host.end());
-    HIPC(ctx, hipMemcpyAsync(m->invl, f.data(), m->d * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(m->invl.p, f.data(), m->d * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
   }
   const int gh = effective_gh(*d);
-  if (gh != m->gh_n) {
-    if (m->gh_x) (void)hipFree(m->gh_x);
-    if (m->gh_w) (void)hipFree(m->gh_w);
-    m->gh_x = m->gh_w = nullptr;
-    m->gh_n = gh;
+  if (gh != m->gh_n) {   // gh_n names the rule on the device only once both arrays hold it: a failure leaves 0 and no arrays
+    m->gh_x.release();
+    m->gh_w.release();
+    m->gh_n = 0;
     if (gh > 0) {
       std::vector<double> xs(gh), ws(gh);
       if (gauss_hermite(gh, xs.data(), ws.data()) != SVGP_OK) return fail(ctx, SVGP_INVALID_ARG, "Gauss-Hermite rule failed to converge");
       for (auto& w : ws) w /= 1.7724538509055160273;
-      HIPC(ctx, hipMalloc(&m->gh_x, gh * 8));
-      HIPC(ctx, hipMalloc(&m->gh_w, gh * 8));
-      HIPC(ctx, hipMemcpy(m->gh_x, xs.data(), gh * 8, hipMemcpyHostToDevice));
-      HIPC(ctx, hipMemcpy(m->gh_w, ws.data(), gh * 8, hipMemcpyHostToDevice));
+      hipError_t e = m->gh_x.alloc(gh * 8);
+      if (e == hipSuccess) e = m->gh_w.alloc(gh * 8);
+      if (e == hipSuccess) e = hipMemcpy(m->gh_x.p, xs.data(), gh * 8, hipMemcpyHostToDevice);
+      if (e == hipSuccess) e = hipMemcpy(m->gh_w.p, ws.data(), gh * 8, hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        m->gh_x.release();
+        m->gh_w.release();
+        return fail(ctx, e == hipErrorOutOfMemory ? SVGP_OOM : SVGP_HIP_ERROR, std::string("upload of the Gauss-Hermite rule: ") + hipGetErrorString(e));
+      }
     }
+    m->gh_n = gh;
   }
   HIPC(ctx, hipStreamSynchronize(ctx->stream));  // host buffers may be released by the caller
   m->prepared = false;
@@ -194,7 +200,7 @@ KernelParams kparams(const svgp_model* m) {
   kp.family = m->desc.kernel;
   kp.d = m->d;
   kp.variance = m->desc.variance;
-  kp.invl = m->invl;
+  kp.invl = m->invl.p;
   return kp;
 }
 
@@ -209,40 +215,42 @@ int ensure_overlap(svgp_ctx* ctx, size_t state_doubles);   // (below) second str
 int enqueue_prep(svgp_ctx* ctx, svgp_model* m, bool overlap = false, const RowHook* hook = nullptr) {
   hipStream_t s = ctx->stream;
   const KernelParams kp = kparams(m);
-  HIPC(ctx, hipMemsetAsync(m->info, 0, info_bytes(m->Mp), s));   // info + the factorisation's hand-over counters and flags
-  launch_scale_inputs(m->dtype, s, m->z_raw, m->desc.layout_z, m->d, m->M, m->Mp, m->invl, m->zs);
+  HIPC(ctx, hipMemsetAsync(m->info.as<int>(), 0, info_bytes(m->Mp), s));   // info + the factorisation's hand-over counters and flags
+  launch_scale_inputs(m->dtype, s, m->z_raw.p, m->desc.layout_z, m->d, m->M, m->Mp, m->invl.p, m->zs.p);
   KCHECK(ctx, "scale_inputs");
   if (overlap) {
-    launch_pack_q(m->dtype, s, m->Lq_raw, m->m_raw, m->M, m->Mp, m->U, m->mp);          // B = Lq      SVA:183-184
+    launch_pack_q(m->dtype, s, m->Lq_raw.p, m->m_raw.p, m->M, m->Mp, m->U.p, m->mp.p);          // B = Lq      SVA:183-184
     KCHECK(ctx, "pack_q");
     HIPC(ctx, hipEventRecord(ctx->ev_fork, s));
     TREC(ctx, ctx->ev_ov[0], s);
     if (hook && hook->fn) hook->fn(hook->user, -1);   // the strips' pre-generation: behind the fork, before the chain is enqueued
   }
-  launch_kuu(m->dtype, s, kp, m->zs, m->M, m->Mp, m->desc.jitter, m->L);
+  launch_kuu(m->dtype, s, kp, m->zs.p, m->M, m->Mp, m->desc.jitter, m->L.p);
   KCHECK(ctx, "kuu");
   TREC(ctx, ctx->ev_chol[0], s);
-  launch_potrf(m->dtype, s, m->L, m->T, m->Mp, m->info, reinterpret_cast<unsigned*>(m->info + 1), ctx->num_cus, overlap ? ctx->ev_row : nullptr,
+  hipEvent_t rows[16] = {};   // the row events as the plain handles launch_potrf takes
+  if (overlap) std::copy(std::begin(ctx->ev_row), std::end(ctx->ev_row), rows);
+  launch_potrf(m->dtype, s, m->L.p, m->T.p, m->Mp, m->info.as<int>(), reinterpret_cast<unsigned*>(m->info.as<int>() + 1), ctx->num_cus, overlap ? rows : nullptr,
                overlap ? hook : nullptr);   // T panels included
   KCHECK(ctx, "potrf");
   TREC(ctx, ctx->ev_chol[1], s);
   if (overlap) {
-    launch_kl_terms(m->dtype, s, m->Lq_raw, m->m_raw, m->L, m->M, m->Mp, m->scal);        // SVA:364-373
+    launch_kl_terms(m->dtype, s, m->Lq_raw.p, m->m_raw.p, m->L.p, m->M, m->Mp, m->scal.as<double>());        // SVA:364-373
   } else if (m->desc.parametrization == SVGP_NONCENTERED) {
-    launch_pack_q(m->dtype, s, m->Lq_raw, m->m_raw, m->M, m->Mp, m->U, m->mp);          // B = Lq      SVA:183-184
-    launch_kl_terms(m->dtype, s, m->Lq_raw, m->m_raw, m->L, m->M, m->Mp, m->scal);        // SVA:364-373
+    launch_pack_q(m->dtype, s, m->Lq_raw.p, m->m_raw.p, m->M, m->Mp, m->U.p, m->mp.p);          // B = Lq      SVA:183-184
+    launch_kl_terms(m->dtype, s, m->Lq_raw.p, m->m_raw.p, m->L.p, m->M, m->Mp, m->scal.as<double>());        // SVA:364-373
   } else {
     // Centered (SVA:115-136): B = Lk \ Lq, whitened mean m~ = Lk \ (m - mean(fz)); then α = Lk' \ m~ = Kuu \ (m - μ)
     // and KL(q || p(u)) = ½(ΣB² + m~'m~ − M − logdet(BB')) — the NonCentered expression evaluated at (m~, B).
-    launch_pad_lower(m->dtype, s, m->Lq_raw, m->M, m->Mp, m->B);
-    launch_trsm_mat(m->dtype, s, m->T, m->Mp, m->B);
-    if (m->mu_z)   // mean(fz) = mean_const + muz (svgp_model_set_mean_z)
-      launch_shift_sub_vec(m->dtype, s, m->m_raw, -m->desc.mean_const, m->mu_z, m->M, m->Mp, m->mp);
+    launch_pad_lower(m->dtype, s, m->Lq_raw.p, m->M, m->Mp, m->B.p);
+    launch_trsm_mat(m->dtype, s, m->T.p, m->Mp, m->B.p);
+    if (m->mu_z.p)   // mean(fz) = mean_const + muz (svgp_model_set_mean_z)
+      launch_shift_sub_vec(m->dtype, s, m->m_raw.p, -m->desc.mean_const, m->mu_z.p, m->M, m->Mp, m->mp.p);
     else
-      launch_shift_vec(m->dtype, s, m->m_raw, -m->desc.mean_const, m->M, m->Mp, m->mp);
-    launch_trsv2(m->dtype, s, m->L, m->T, m->Mp, 0, m->mp);
-    launch_pack_q_ld(m->dtype, s, m->B, m->Mp, nullptr, m->Mp, m->Mp, m->U, nullptr);
-    launch_kl_terms_ld(m->dtype, s, m->B, m->Mp, m->mp, m->L, m->M, m->Mp, m->scal);
+      launch_shift_vec(m->dtype, s, m->m_raw.p, -m->desc.mean_const, m->M, m->Mp, m->mp.p);
+    launch_trsv2(m->dtype, s, m->L.p, m->T.p, m->Mp, 0, m->mp.p);
+    launch_pack_q_ld(m->dtype, s, m->B.p, m->Mp, nullptr, m->Mp, m->Mp, m->U.p, nullptr);
+    launch_kl_terms_ld(m->dtype, s, m->B.p, m->Mp, m->mp.p, m->L.p, m->M, m->Mp, m->scal.as<double>());
   }
   KCHECK(ctx, "pack_q/kl");
   return SVGP_OK;
@@ -259,38 +267,24 @@ void finish_prep(svgp_model* m, const PrepScalars& ps) {
 }
 
 int ensure_scratch(svgp_ctx* ctx, size_t work_bytes, size_t npoints) {
-  if (work_bytes > ctx->work_bytes) {
-    if (ctx->work) (void)hipFree(ctx->work);
-    ctx->work = nullptr;
-    ctx->work_bytes = 0;
-    HIPC(ctx, hipMalloc(&ctx->work, work_bytes));
-    ctx->work_bytes = work_bytes;
-  }
-  if (npoints > ctx->mom_cap) {
-    if (ctx->mom) (void)hipFree(ctx->mom);
-    ctx->mom = nullptr;
-    ctx->mom_cap = 0;
-    HIPC(ctx, hipMalloc(&ctx->mom, 2 * npoints * sizeof(double)));
-    ctx->mom_cap = npoints;
-  }
-  return SVGP_OK;
+  const int rc = ctx->work.reserve(ctx, work_bytes, "the strips' scratch");
+  return rc ? rc : ctx->mom.reserve(ctx, 2 * npoints * sizeof(double), "the moments");
 }
 
 // second stream (+ fork / join events, its own strip queue head) for launches that run BESIDE the main stream's
 int ensure_stream2(svgp_ctx* ctx) {
-  if (ctx->stream2) return SVGP_OK;
+  if (ctx->counter2.p) return SVGP_OK;   // made last: a call that failed half-way is completed by the next one
   // the second stream carries work that runs BESIDE the main stream's (the ragged tail of a large batch, the segmented strips beside
   // the factorisation): lowest priority, so that where both have workgroups to dispatch the main stream's serial chain goes first
   static const int prio_knob = exp_int("SVGP_STREAM2_LOW_PRIO", 1);   // A/B knob (experiments build)
   int least = 0, greatest = 0;
-  if (prio_knob && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-    HIPC(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, least));
-  } else {
-    HIPC(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+  if (!ctx->stream2) {
+    const bool low = prio_knob && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest;
+    HIPC(ctx, low ? ctx->stream2.create(hipStreamNonBlocking, least) : ctx->stream2.create(hipStreamNonBlocking));
   }
-  HIPC(ctx, hipEventCreateWithFlags(&ctx->ev_fork, kSyncEvent));
-  HIPC(ctx, hipEventCreateWithFlags(&ctx->ev_join, kSyncEvent));
-  HIPC(ctx, hipMalloc(&ctx->counter2, 64));
+  HIPC(ctx, ctx->ev_fork.create(kSyncEvent));
+  HIPC(ctx, ctx->ev_join.create(kSyncEvent));
+  HIPC(ctx, ctx->counter2.alloc(64));
   return SVGP_OK;
 }
 
@@ -308,7 +302,7 @@ int seg_split_factor(const svgp_ctx* ctx, int nP, int64_t nstrips) {
 }
 // points the split closing launch at its partials and counters (behind the saved sums) and zeroes the counters on the second stream
 int seg_split_setup(svgp_ctx* ctx, StripArgs& a, int S, int64_t nstrips) {
-  double* extra = ctx->seg_state + (ctx->seg_state_doubles - kSegSplitDoubles);
+  double* extra = ctx->seg_state.as<double>() + (ctx->seg_state.cap / sizeof(double) - kSegSplitDoubles);
   a.seg_split = S;
   a.seg_part = extra;
   a.seg_cnt = reinterpret_cast<unsigned*>(extra + kSegSplitSlots * kSegSplitPart);
@@ -319,23 +313,14 @@ int ensure_overlap(svgp_ctx* ctx, size_t state_doubles) {
   int rc = ensure_stream2(ctx);
   if (rc) return rc;
   if (!ctx->ev_row_ready) {
-    for (auto& e : ctx->ev_row)
-      if (!e) HIPC(ctx, hipEventCreateWithFlags(&e, kSyncEvent));
-    for (auto& e : ctx->ev_ov)
-      if (!e) HIPC(ctx, hipEventCreateWithFlags(&e, kTimingEvent));
-    if (!ctx->ev_R) HIPC(ctx, hipEventCreateWithFlags(&ctx->ev_R, kSyncEvent));
-    if (!ctx->ev_S) HIPC(ctx, hipEventCreateWithFlags(&ctx->ev_S, kSyncEvent));
+    for (auto& e : ctx->ev_row) HIPC(ctx, e.create(kSyncEvent));
+    for (auto& e : ctx->ev_ov) HIPC(ctx, e.create(kTimingEvent));
+    HIPC(ctx, ctx->ev_R.create(kSyncEvent));
+    HIPC(ctx, ctx->ev_S.create(kSyncEvent));
     ctx->ev_row_ready = true;
   }
   state_doubles += kSegSplitDoubles;   // behind the saved sums: the split closing launch's partials and its per-strip counters
-  if (state_doubles > ctx->seg_state_doubles) {
-    if (ctx->seg_state) (void)hipFree(ctx->seg_state);
-    ctx->seg_state = nullptr;
-    ctx->seg_state_doubles = 0;
-    HIPC(ctx, hipMalloc(&ctx->seg_state, state_doubles * sizeof(double)));
-    ctx->seg_state_doubles = state_doubles;
-  }
-  return SVGP_OK;
+  return ctx->seg_state.reserve(ctx, state_doubles * sizeof(double), "the segmented strips' saved sums");
 }
 
 struct StripOuts {
@@ -362,24 +347,19 @@ int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, con
   if (plan.concurrent_tail) {
     rc = ensure_stream2(ctx);
     if (rc) return rc;
-    if (wb_tail > ctx->work2_bytes) {
-      if (ctx->work2) (void)hipFree(ctx->work2);
-      ctx->work2 = nullptr;
-      ctx->work2_bytes = 0;
-      HIPC(ctx, hipMalloc(&ctx->work2, wb_tail));
-      ctx->work2_bytes = wb_tail;
-    }
+    rc = ctx->work2.reserve(ctx, wb_tail, "the concurrent tail's scratch");
+    if (rc) return rc;
   }
   StripArgs a{};
-  a.T = m->T;
-  a.U = m->U;
-  a.zs = m->zs;
-  a.mp = m->mp;
+  a.T = m->T.p;
+  a.U = m->U.p;
+  a.zs = m->zs.p;
+  a.mp = m->mp.p;
   a.x = x;
-  a.work = ctx->work;
-  a.counter = ctx->counter;
-  a.mom_mu = ctx->mom;
-  a.mom_var = ctx->mom + ctx->mom_cap;
+  a.work = ctx->work.p;
+  a.counter = ctx->counter.as<unsigned>();
+  a.mom_mu = ctx->mom_mu();
+  a.mom_var = ctx->mom_var();
   a.A_out = o.A;
   a.C_out = o.C;
   a.At_out = o.At;
@@ -398,15 +378,15 @@ int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, con
   lp.gh_n = m->gh_n;
   lp.sigma2 = lik_param(m->desc);
   lp.digamma_alpha = m->desc.likelihood == SVGP_LIK_GAMMA_EXP ? digamma_d(m->desc.lik_sigma2) : 0.0;
-  lp.gh_x = m->gh_x;
-  lp.gh_w = m->gh_w;
+  lp.gh_x = m->gh_x.as<double>();
+  lp.gh_w = m->gh_w.as<double>();
   lp.clamp_neg_var = (m->desc.neg_var_policy == SVGP_NEGVAR_CLAMP);
   lp.mean_const = m->desc.mean_const;
   if (plan.concurrent_tail) HIPC(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
   if (plan.grid) {
     StripArgs am = a;
     am.len = plan.points;
-    HIPC(ctx, hipMemsetAsync(ctx->counter, 0, sizeof(unsigned), ctx->stream));
+    HIPC(ctx, hipMemsetAsync(ctx->counter.as<unsigned>(), 0, sizeof(unsigned), ctx->stream));
     launch_strip(m->dtype, ctx->stream, am, plan.nt, plan.grid, plan.nstrips);
     KCHECK(ctx, "strip");
   }
@@ -426,16 +406,16 @@ int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, con
     if (plan.concurrent_tail) {
       // fork: the tail may start as soon as everything before this point on the main stream is done (the prep kernels,
       // recorded BEFORE the main launch); join: the main stream continues after both launches
-      at.work = ctx->work2;
-      at.counter = ctx->counter2;
+      at.work = ctx->work2.p;
+      at.counter = ctx->counter2.as<unsigned>();
       HIPC(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-      HIPC(ctx, hipMemsetAsync(ctx->counter2, 0, sizeof(unsigned), ctx->stream2));
+      HIPC(ctx, hipMemsetAsync(ctx->counter2.as<unsigned>(), 0, sizeof(unsigned), ctx->stream2));
       launch_strip(m->dtype, ctx->stream2, at, plan.nt_tail, plan.grid_tail, plan.nstrips_tail);
       KCHECK(ctx, "strip tail (concurrent)");
       HIPC(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
       HIPC(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     } else {
-      HIPC(ctx, hipMemsetAsync(ctx->counter, 0, sizeof(unsigned), ctx->stream));
+      HIPC(ctx, hipMemsetAsync(ctx->counter.as<unsigned>(), 0, sizeof(unsigned), ctx->stream));
       launch_strip(m->dtype, ctx->stream, at, plan.nt_tail, plan.grid_tail, plan.nstrips_tail);
       KCHECK(ctx, "strip tail");
     }
@@ -443,9 +423,9 @@ int enqueue_strips(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx, con
   ctx->timing.strip_launches = (plan.grid ? 1 : 0) + (plan.nt_tail ? 1 : 0);
   TREC(ctx, ctx->ev[2], ctx->stream);
   if (o.skip_expect) return SVGP_OK;
-  launch_expect(m->dtype, ctx->stream, lp, a.mom_mu, a.mom_var, y, off, len, ctx->partial, ctx->negcnt, o.mu, o.var);
+  launch_expect(m->dtype, ctx->stream, lp, a.mom_mu, a.mom_var, y, off, len, ctx->partial.as<double>(), ctx->negcnt.as<unsigned>(), o.mu, o.var);
   KCHECK(ctx, "expect");
-  launch_final_reduce(ctx->stream, ctx->partial, ctx->negcnt, expect_blocks(len), m->info, double(len), ctx->d_res, m->scal);
+  launch_final_reduce(ctx->stream, ctx->partial.as<double>(), ctx->negcnt.as<unsigned>(), expect_blocks(len), m->info.as<int>(), double(len), ctx->d_res.as<double>(), m->scal.as<double>());
   KCHECK(ctx, "final_reduce");
   HIPC(ctx, hipGetLastError());
   return SVGP_OK;
@@ -543,24 +523,18 @@ int seg_prepare_forward(svgp_ctx* ctx, svgp_model* m, const void* x, int64_t ldx
   // (A checkpointed phase 2 beside the factorisation - bitwise-tested, measured in round 4, profiles/round4/overlap.md: the factorisation
   // slows by what the strips' extra work beside it occupies, 16 384 / 1024 f64 1.046 -> 1.06-1.07 ms, M = 2048 1.94 -> 2.11 - left the
   // tree in round 6.)
-  if (wb > ctx->work_seg_bytes) {
-    if (ctx->work_seg) (void)hipFree(ctx->work_seg);
-    ctx->work_seg = nullptr;
-    ctx->work_seg_bytes = 0;
-    HIPC(ctx, hipMalloc(&ctx->work_seg, wb));
-    ctx->work_seg_bytes = wb;
-  }
-  const int rc = ensure_scratch(ctx, 0, size_t(len));
+  int rc = ctx->work_seg.reserve(ctx, wb, "the segmented strips' scratch");
+  if (rc == SVGP_OK) rc = ensure_scratch(ctx, 0, size_t(len));
   if (rc) return rc;
   r.ctx = ctx; r.m = m; r.op = op; r.grad = false; r.nP = nP; r.wb1 = wb1;
   // A small batch (fewer strips than workgroup slots): phase 2 - one panel C_J after the other inside a strip's
   // workgroup - is latency-bound on the few CUs it reaches, and its panels are independent: a closing launch with S workgroups per strip
   r.split = seg_split_factor(ctx, nP, op.nstrips);
   StripArgs& a = r.a;
-  a.T = m->T; a.U = m->U; a.zs = m->zs; a.mp = m->mp; a.x = x; a.work = ctx->work_seg; a.counter = ctx->counter2;
-  a.mom_mu = ctx->mom; a.mom_var = ctx->mom + ctx->mom_cap;
+  a.T = m->T.p; a.U = m->U.p; a.zs = m->zs.p; a.mp = m->mp.p; a.x = x; a.work = ctx->work_seg.p; a.counter = ctx->counter2.as<unsigned>();
+  a.mom_mu = ctx->mom_mu(); a.mom_var = ctx->mom_var();
   a.ldx = ldx; a.off = off; a.len = len; a.Mp = m->Mp; a.M = m->M; a.kp = kparams(m); a.mean_const = m->desc.mean_const;
-  a.seg_state = ctx->seg_state;
+  a.seg_state = ctx->seg_state.as<double>();
   return SVGP_OK;
 }
 
@@ -589,13 +563,13 @@ int seg_finish_forward(svgp_ctx* ctx, svgp_model* m, const void* y, int64_t off,
   lp.gh_n = m->gh_n;
   lp.sigma2 = lik_param(m->desc);
   lp.digamma_alpha = m->desc.likelihood == SVGP_LIK_GAMMA_EXP ? digamma_d(m->desc.lik_sigma2) : 0.0;
-  lp.gh_x = m->gh_x;
-  lp.gh_w = m->gh_w;
+  lp.gh_x = m->gh_x.as<double>();
+  lp.gh_w = m->gh_w.as<double>();
   lp.clamp_neg_var = (m->desc.neg_var_policy == SVGP_NEGVAR_CLAMP);
   lp.mean_const = m->desc.mean_const;
-  launch_expect(m->dtype, s, lp, r.a.mom_mu, r.a.mom_var, y, off, len, ctx->partial, ctx->negcnt, o.mu, o.var);
+  launch_expect(m->dtype, s, lp, r.a.mom_mu, r.a.mom_var, y, off, len, ctx->partial.as<double>(), ctx->negcnt.as<unsigned>(), o.mu, o.var);
   KCHECK(ctx, "expect");
-  launch_final_reduce(s, ctx->partial, ctx->negcnt, expect_blocks(len), m->info, double(len), ctx->d_res, m->scal);
+  launch_final_reduce(s, ctx->partial.as<double>(), ctx->negcnt.as<unsigned>(), expect_blocks(len), m->info.as<int>(), double(len), ctx->d_res.as<double>(), m->scal.as<double>());
   KCHECK(ctx, "final_reduce");
   HIPC(ctx, hipGetLastError());
   return SVGP_OK;
@@ -607,18 +581,7 @@ int check_batch(svgp_ctx* ctx, const svgp_model* m, const svgp_data* data, int64
   if (data->dtype != m->dtype) return fail(ctx, SVGP_INVALID_ARG, "data and model dtypes differ");
   if (data->d != m->d) return fail(ctx, SVGP_INVALID_ARG, "data and model input dimensions differ");
   if (off < 0 || len < 1 || off + len > data->n) return fail(ctx, SVGP_INVALID_ARG, "batch range outside the data");
-  if (need_y && !data->y) return fail(ctx, SVGP_INVALID_ARG, "data has no observations y");
-  return SVGP_OK;
-}
-
-// a context buffer that grows on demand (contents not kept)
-int grow_buffer(svgp_ctx* ctx, void** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return SVGP_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return fail(ctx, SVGP_OOM, "hipMalloc failed for the prior mean offsets"); }
-  *cap = bytes;
+  if (need_y && !data->y.p) return fail(ctx, SVGP_INVALID_ARG, "data has no observations y");
   return SVGP_OK;
 }
 
@@ -634,10 +597,10 @@ int check_point_mean(svgp_ctx* ctx, const svgp_point_mean* pm) {
 // the batch's offsets on the device: a device pointer as it is, host memory by one copy into ctx->pm_x (bytes = batch_len x dtype size)
 int stage_point_mean(svgp_ctx* ctx, const svgp_point_mean* pm, size_t bytes, const void** dev) {
   if (pm->on_device) { *dev = pm->mu; return SVGP_OK; }
-  const int rc = grow_buffer(ctx, &ctx->pm_x, &ctx->pm_x_bytes, bytes);
+  const int rc = ctx->pm_x.reserve(ctx, bytes, "the prior mean offsets");
   if (rc) return rc;
-  HIPC(ctx, hipMemcpyAsync(ctx->pm_x, pm->mu, bytes, hipMemcpyHostToDevice, ctx->stream));
-  *dev = ctx->pm_x;
+  HIPC(ctx, hipMemcpyAsync(ctx->pm_x.p, pm->mu, bytes, hipMemcpyHostToDevice, ctx->stream));
+  *dev = ctx->pm_x.p;
   return SVGP_OK;
 }
 
@@ -661,7 +624,7 @@ int elbo_enqueue(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t of
   SegRun seg;
   RowHook hook{seg_row_hook, &seg};
   if (op.on) {
-    rc = seg_prepare_forward(ctx, m, data->x, data->ldx, off, len, op, seg);
+    rc = seg_prepare_forward(ctx, m, data->x.p, data->ldx, off, len, op, seg);
     if (rc) return rc;
     seg.a.mux = mux;
   }
@@ -676,8 +639,8 @@ int elbo_enqueue(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t of
   TREC(ctx, ctx->ev[1], s);
   StripOuts so;
   so.mux = mux;
-  rc = op.on ? seg_finish_forward(ctx, m, data->y, off, len, so, seg)
-             : enqueue_strips(ctx, m, data->x, data->ldx, data->y, off, len, so);
+  rc = op.on ? seg_finish_forward(ctx, m, data->y.p, off, len, so, seg)
+             : enqueue_strips(ctx, m, data->x.p, data->ldx, data->y.p, off, len, so);
   if (rc) {
     if (op.on && ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     return rc;
@@ -694,14 +657,14 @@ int elbo_collective(svgp_ctx* ctx, int local_rc) {
     const std::string keep = ctx->err;
     static const double poison[8] = {0, 0, 0, 0, 1, 0, 0, 0};
     if (hipSetDevice(ctx->device) != hipSuccess ||
-        hipMemcpyAsync(ctx->d_res, poison, sizeof poison, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+        hipMemcpyAsync(ctx->d_res.as<double>(), poison, sizeof poison, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
       comm_abort(ctx);
       ctx->err = keep;
       return local_rc;
     }
     ctx->err = keep;
   }
-  const int rc = comm_allreduce(ctx, ctx->d_res, 8, SVGP_F64);
+  const int rc = comm_allreduce(ctx, ctx->d_res.as<double>(), 8, SVGP_F64);
   if (rc != SVGP_OK) {
     comm_abort(ctx);
     return local_rc != SVGP_OK ? local_rc : rc;
@@ -714,7 +677,7 @@ int elbo_finish(svgp_ctx* ctx, svgp_model* m, ElboRead* out) {
   HIPC(ctx, hipSetDevice(ctx->device));
   double res[13];   // {sum E, n, n_neg, chol flag, failure flag, 0, 0, 0 | prep scalars (4), chol_info}: one copy
   PrepScalars ps;
-  HIPC(ctx, hipMemcpyAsync(res, ctx->d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(res, ctx->d_res.as<double>(), sizeof(res), hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   for (int q = 0; q < 4; ++q) ps.scal[q] = res[8 + q];
   ps.info = int(res[12]);
@@ -774,8 +737,8 @@ int ensure_prepared(svgp_ctx* ctx, svgp_model* m) {
   int rc = enqueue_prep(ctx, m);
   if (rc) return rc;
   PrepScalars ps;
-  HIPC(ctx, hipMemcpyAsync(ps.scal, m->scal, sizeof(ps.scal), hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(ctx, hipMemcpyAsync(&ps.info, m->info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(ctx, hipMemcpyAsync(ps.scal, m->scal.as<double>(), sizeof(ps.scal), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(ctx, hipMemcpyAsync(&ps.info, m->info.as<int>(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(ctx, hipStreamSynchronize(ctx->stream));
   finish_prep(m, ps);
   return status_of(ctx, m, 0);
@@ -789,30 +752,28 @@ int make_data(svgp_ctx* ctx, int dtype, int layout, int d, int64_t n, const void
   if (d < 1 || n < 1 || !x_host) return fail(ctx, SVGP_INVALID_ARG, "bad data shape");
   if (layout < 0 || layout > SVGP_VEC || (layout == SVGP_VEC && d != 1)) return fail(ctx, SVGP_INVALID_ARG, "bad layout");
   const size_t es = esize(dtype);
-  DataGuard guard;
-  guard.D = new (std::nothrow) svgp_data();
-  svgp_data* D = guard.D;
+  std::unique_ptr<svgp_data> D(new (std::nothrow) svgp_data());
   if (!D) return SVGP_OOM;
   D->dtype = dtype;
   D->d = d;
   D->n = n;
   D->ldx = n;
   hipStream_t s = ctx->stream;
-  hipError_t e = hipMalloc(&D->x, size_t(n) * d * es);
-  if (e == hipSuccess && y_host) e = hipMalloc(&D->y, size_t(n) * es);
-  if (e != hipSuccess) return fail(ctx, SVGP_OOM, "hipMalloc failed for data");
+  hipError_t e = D->x.alloc(size_t(n) * d * es);
+  if (e == hipSuccess && y_host) e = D->y.alloc(size_t(n) * es);
+  if (e != hipSuccess) return alloc_failed(ctx, "for data");
   if (layout == SVGP_COLVECS && d > 1) {
     DevBuf tmp;
     HIPC(ctx, tmp.alloc(size_t(n) * d * es));
     HIPC(ctx, hipMemcpyAsync(tmp.p, x_host, size_t(n) * d * es, hipMemcpyHostToDevice, s));
-    launch_transpose_colvecs(dtype, s, tmp.p, d, n, D->ldx, D->x);
+    launch_transpose_colvecs(dtype, s, tmp.p, d, n, D->ldx, D->x.p);
     HIPC(ctx, hipStreamSynchronize(s));
   } else {
-    HIPC(ctx, hipMemcpyAsync(D->x, x_host, size_t(n) * d * es, hipMemcpyHostToDevice, s));
+    HIPC(ctx, hipMemcpyAsync(D->x.p, x_host, size_t(n) * d * es, hipMemcpyHostToDevice, s));
   }
-  if (y_host) HIPC(ctx, hipMemcpyAsync(D->y, y_host, size_t(n) * es, hipMemcpyHostToDevice, s));
+  if (y_host) HIPC(ctx, hipMemcpyAsync(D->y.p, y_host, size_t(n) * es, hipMemcpyHostToDevice, s));
   HIPC(ctx, hipStreamSynchronize(s));
-  *out = guard.release();
+  *out = D.release();
   return SVGP_OK;
 }
 
@@ -876,17 +837,17 @@ int32_t svgp_ctx_create(int32_t device_id, void* stream, svgp_ctx** out) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) c->num_cus = prop.multiProcessorCount;
   if (stream) {
-    c->stream = static_cast<hipStream_t>(stream);
-  } else {
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return SVGP_HIP_ERROR; }
-    c->own_stream = true;
+    c->stream.borrow(stream);
+  } else if (c->stream.create(hipStreamNonBlocking) != hipSuccess) {
+    delete c;
+    return SVGP_HIP_ERROR;
   }
   for (auto& e : c->ev)
-    if (hipEventCreateWithFlags(&e, kTimingEvent) != hipSuccess) { delete c; return SVGP_HIP_ERROR; }
+    if (e.create(kTimingEvent) != hipSuccess) { delete c; return SVGP_HIP_ERROR; }
   for (auto& e : c->ev_chol)
-    if (hipEventCreateWithFlags(&e, kTimingEvent) != hipSuccess) { delete c; return SVGP_HIP_ERROR; }
-  if (hipMalloc(&c->d_res, 16 * sizeof(double)) != hipSuccess || hipMalloc(&c->d_coll, 8 * sizeof(double)) != hipSuccess || hipMalloc(&c->counter, 64) != hipSuccess || hipMalloc(&c->partial, 1024 * sizeof(double)) != hipSuccess ||
-      hipMalloc(&c->negcnt, 1024 * sizeof(unsigned)) != hipSuccess) { delete c; return SVGP_OOM; }
+    if (e.create(kTimingEvent) != hipSuccess) { delete c; return SVGP_HIP_ERROR; }
+  if (c->d_res.alloc(16 * sizeof(double)) != hipSuccess || c->d_coll.alloc(8 * sizeof(double)) != hipSuccess || c->counter.alloc(64) != hipSuccess ||
+      c->partial.alloc(1024 * sizeof(double)) != hipSuccess || c->negcnt.alloc(1024 * sizeof(unsigned)) != hipSuccess) { delete c; return SVGP_OOM; }
   *out = c;
   return SVGP_OK;
 }
@@ -895,42 +856,9 @@ int32_t svgp_ctx_destroy(svgp_ctx* c) {
   if (!c) return SVGP_OK;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  if (c->work) (void)hipFree(c->work);
-  if (c->partial) (void)hipFree(c->partial);
-  if (c->negcnt) (void)hipFree(c->negcnt);
-  if (c->mom) (void)hipFree(c->mom);
+  if (c->stream2) (void)hipStreamSynchronize(c->stream2);
   if (c->comm) (void)svgp_ctx_detach_comm(c);
-  if (c->d_res) (void)hipFree(c->d_res);
-  if (c->d_coll) (void)hipFree(c->d_coll);
-  if (c->h_open) (void)hipHostFree(c->h_open);
-  if (c->ev_open) (void)hipEventDestroy(c->ev_open);
-  if (c->counter) (void)hipFree(c->counter);
-  if (c->counter2) (void)hipFree(c->counter2);
-  if (c->work2) (void)hipFree(c->work2);
-  for (auto& e : c->ev_row)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->ev_ov)
-    if (e) (void)hipEventDestroy(e);
-  if (c->ev_R) (void)hipEventDestroy(c->ev_R);
-  if (c->ev_S) (void)hipEventDestroy(c->ev_S);
-  if (c->seg_state) (void)hipFree(c->seg_state);
-  if (c->work_seg) (void)hipFree(c->work_seg);
-  if (c->hstage) (void)hipHostFree(c->hstage);
-  for (auto& e : c->ev_piece)
-    if (e) (void)hipEventDestroy(e);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
-  if (c->kuf_buf) (void)hipFree(c->kuf_buf);
-  if (c->ext_g) (void)hipFree(c->ext_g);
-  if (c->pm_x) (void)hipFree(c->pm_x);
-  if (c->pm_g) (void)hipFree(c->pm_g);
-  if (c->gws) { c->gws->release(); delete c->gws; }
-  for (auto& e : c->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->ev_chol)
-    if (e) (void)hipEventDestroy(e);
-  if (c->own_stream) (void)hipStreamDestroy(c->stream);
+  delete c->gws;
   delete c;
   return SVGP_OK;
 }
@@ -971,9 +899,8 @@ int32_t svgp_data_wrap_device(svgp_ctx* ctx, int32_t dtype, int32_t d, int64_t n
   D->d = d;
   D->n = n;
   D->ldx = ldx;
-  D->x = const_cast<void*>(x_dev);
-  D->y = const_cast<void*>(y_dev);
-  D->own = false;
+  D->x.borrow(x_dev);
+  D->y.borrow(y_dev);
   *out = D;
   return SVGP_OK;
 }
@@ -981,10 +908,6 @@ int32_t svgp_data_wrap_device(svgp_ctx* ctx, int32_t dtype, int32_t d, int64_t n
 int32_t svgp_data_free(svgp_ctx* ctx, svgp_data* D) {
   if (!D) return SVGP_OK;
   if (ctx) (void)hipSetDevice(ctx->device);
-  if (D->own) {
-    if (D->x) (void)hipFree(D->x);
-    if (D->y) (void)hipFree(D->y);
-  }
   delete D;
   return SVGP_OK;
 }
@@ -992,9 +915,6 @@ int32_t svgp_data_free(svgp_ctx* ctx, svgp_data* D) {
 int32_t svgp_model_free(svgp_ctx* ctx, svgp_model* m) {
   if (!m) return SVGP_OK;
   if (ctx) (void)hipSetDevice(ctx->device);
-  void* bufs[] = {m->z_raw, m->m_raw, m->Lq_raw, m->invl, m->zs, m->L, m->T, m->U, m->mp, m->B, m->scal, m->info, m->gh_x, m->gh_w, m->mu_z};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
   delete m;
   return SVGP_OK;
 }
@@ -1014,21 +934,18 @@ int32_t svgp_model_create(svgp_ctx* ctx, const svgp_model_desc* desc, svgp_model
   m->d = desc->d;
   m->es = esize(desc->dtype);
   const size_t es = m->es, M = size_t(m->M), Mp = size_t(m->Mp);
-  struct { void** p; size_t bytes; } allocs[] = {
+  struct { DevBuf* b; size_t bytes; } allocs[] = {
       {&m->z_raw, M * m->d * es}, {&m->m_raw, M * es},     {&m->Lq_raw, M * M * es}, {&m->invl, size_t(m->d) * es},
       {&m->zs, Mp * m->d * es},   {&m->L, Mp * Mp * es},   {&m->T, Mp * Mp * es},    {&m->U, Mp * Mp * es},
-      {&m->mp, Mp * es},          {(void**)&m->scal, (8 + Mp) * sizeof(double)},     {(void**)&m->info, info_bytes(Mp)},
+      {&m->mp, Mp * es},          {&m->scal, (8 + Mp) * sizeof(double)},             {&m->info, info_bytes(Mp)},
+      {&m->B, desc->parametrization == SVGP_CENTERED ? Mp * Mp * es : 0},
   };
   for (auto& a : allocs)
-    if (hipMalloc(a.p, a.bytes) != hipSuccess) {
+    if (a.bytes && a.b->alloc(a.bytes) != hipSuccess) {
       svgp_model_free(ctx, m);
-      return fail(ctx, SVGP_OOM, "hipMalloc failed for model buffers");
+      return alloc_failed(ctx, "for model buffers");
     }
-  if (desc->parametrization == SVGP_CENTERED && hipMalloc(&m->B, Mp * Mp * es) != hipSuccess) {
-    svgp_model_free(ctx, m);
-    return fail(ctx, SVGP_OOM, "hipMalloc failed for model buffers");
-  }
-  if (hipMemsetAsync(m->T, 0, Mp * Mp * es, ctx->stream) != hipSuccess) {   // launch_potrf's contract: T zero above the diagonal
+  if (hipMemsetAsync(m->T.p, 0, Mp * Mp * es, ctx->stream) != hipSuccess) {   // launch_potrf's contract: T zero above the diagonal
     svgp_model_free(ctx, m);
     return fail(ctx, SVGP_HIP_ERROR, "hipMemsetAsync failed for the model's T buffer");
   }
@@ -1152,19 +1069,14 @@ int32_t svgp_kuf(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t of
   HIPC(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t bytes = size_t(m->M) * size_t(len) * m->es;
-  if (bytes > ctx->kuf_bytes) {
-    if (ctx->kuf_buf) (void)hipFree(ctx->kuf_buf);
-    ctx->kuf_buf = nullptr;
-    ctx->kuf_bytes = 0;
-    HIPC(ctx, hipMalloc(&ctx->kuf_buf, bytes));
-    ctx->kuf_bytes = bytes;
-  }
-  launch_scale_inputs(m->dtype, s, m->z_raw, m->desc.layout_z, m->d, m->M, m->Mp, m->invl, m->zs);
+  rc = ctx->kuf_buf.reserve(ctx, bytes, "Kuf");
+  if (rc) return rc;
+  launch_scale_inputs(m->dtype, s, m->z_raw.p, m->desc.layout_z, m->d, m->M, m->Mp, m->invl.p, m->zs.p);
   TREC(ctx, ctx->ev[0], s);
-  launch_kuf(m->dtype, s, kparams(m), m->zs, m->M, m->Mp, data->x, data->ldx, off, len, ctx->kuf_buf);
+  launch_kuf(m->dtype, s, kparams(m), m->zs.p, m->M, m->Mp, data->x.p, data->ldx, off, len, ctx->kuf_buf.p);
   TREC(ctx, ctx->ev[1], s);
   HIPC(ctx, hipGetLastError());
-  if (Kuf_out_host) HIPC(ctx, hipMemcpyAsync(Kuf_out_host, ctx->kuf_buf, bytes, hipMemcpyDeviceToHost, s));
+  if (Kuf_out_host) HIPC(ctx, hipMemcpyAsync(Kuf_out_host, ctx->kuf_buf.p, bytes, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   float t = 0;
   (void)elapsed_ms(ctx, &t, ctx->ev[0], ctx->ev[1]);
@@ -1187,22 +1099,22 @@ int32_t svgp_posterior(svgp_ctx* ctx, svgp_model* m, void* Lk_out, void* alpha_o
   void* tmp = tmpbuf.p;
   void* vec = static_cast<char*>(tmp) + M * M * es;
   if (Lk_out) {
-    launch_extract_lower(m->dtype, s, m->L, m->Mp, m->M, tmp);
+    launch_extract_lower(m->dtype, s, m->L.p, m->Mp, m->M, tmp);
     HIPC(ctx, hipMemcpyAsync(Lk_out, tmp, M * M * es, hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipStreamSynchronize(s));
   }
   if (alpha_out) {
     // α = Lk' \ m~ (SVA:182; for Centered m~ = Lk \ (m − μ) so α = Kuu \ (m − μ), SVA:134)
-    HIPC(ctx, hipMemcpyAsync(vec, m->mp, Mp * es, hipMemcpyDeviceToDevice, s));
-    launch_trsv2(m->dtype, s, m->L, m->T, m->Mp, 1, vec);
+    HIPC(ctx, hipMemcpyAsync(vec, m->mp.p, Mp * es, hipMemcpyDeviceToDevice, s));
+    launch_trsv2(m->dtype, s, m->L.p, m->T.p, m->Mp, 1, vec);
     HIPC(ctx, hipMemcpyAsync(alpha_out, vec, M * es, hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipStreamSynchronize(s));
   }
   if (B_out) {
     if (m->desc.parametrization == SVGP_CENTERED) {
-      launch_extract_lower(m->dtype, s, m->B, m->Mp, m->M, tmp);
+      launch_extract_lower(m->dtype, s, m->B.p, m->Mp, m->M, tmp);
     } else {
-      launch_extract_lower(m->dtype, s, m->Lq_raw, m->M, m->M, tmp);
+      launch_extract_lower(m->dtype, s, m->Lq_raw.p, m->M, m->M, tmp);
     }
     HIPC(ctx, hipMemcpyAsync(B_out, tmp, M * M * es, hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipStreamSynchronize(s));
@@ -1220,62 +1132,54 @@ static int32_t predict_impl(svgp_ctx* ctx, svgp_model* m, int32_t layout, int64_
   if (rc) return rc;
   hipStream_t s = ctx->stream;
   const size_t es = m->es;
-  svgp_data* X = nullptr;
-  svgp_data* Y = nullptr;
-  rc = make_data(ctx, m->dtype, layout, m->d, nx, x_host, nullptr, &X);
-  if (rc) return rc;
-  if (cross) {
-    rc = make_data(ctx, m->dtype, layout, m->d, ny, y_host, nullptr, &Y);
-    if (rc) { svgp_data_free(ctx, X); return rc; }
+  svgp_data *Xd = nullptr, *Yd = nullptr;
+  rc = make_data(ctx, m->dtype, layout, m->d, nx, x_host, nullptr, &Xd);
+  std::unique_ptr<svgp_data> X(Xd), Y;
+  if (rc == SVGP_OK && cross) {
+    rc = make_data(ctx, m->dtype, layout, m->d, ny, y_host, nullptr, &Yd);
+    Y.reset(Yd);
   }
+  if (rc) return rc;
   auto pad = [](int64_t n) { return (n + 127) / 128 * 128; };
   const int64_t ldax = pad(nx), lday = cross ? pad(ny) : 0;
-  void *mu = nullptr, *var = nullptr, *Ax = nullptr, *Cx = nullptr, *Ay = nullptr, *Cy = nullptr, *cov = nullptr;
+  DevBuf mu, var, Ax, Cx, Ay, Cy, cov;
   const bool want_cov = cov_out != nullptr;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess) e = hipMalloc(&mu, size_t(nx) * es);
-  if (e == hipSuccess) e = hipMalloc(&var, size_t(nx) * es);
+  hipError_t e = mu.alloc(size_t(nx) * es);
+  if (e == hipSuccess) e = var.alloc(size_t(nx) * es);
   if (want_cov) {
-    if (e == hipSuccess) e = hipMalloc(&Ax, size_t(m->Mp) * ldax * es);
-    if (e == hipSuccess) e = hipMalloc(&Cx, size_t(m->Mp) * ldax * es);
+    if (e == hipSuccess) e = Ax.alloc(size_t(m->Mp) * ldax * es);
+    if (e == hipSuccess) e = Cx.alloc(size_t(m->Mp) * ldax * es);
     if (cross) {
-      if (e == hipSuccess) e = hipMalloc(&Ay, size_t(m->Mp) * lday * es);
-      if (e == hipSuccess) e = hipMalloc(&Cy, size_t(m->Mp) * lday * es);
+      if (e == hipSuccess) e = Ay.alloc(size_t(m->Mp) * lday * es);
+      if (e == hipSuccess) e = Cy.alloc(size_t(m->Mp) * lday * es);
     }
-    if (e == hipSuccess) e = hipMalloc(&cov, size_t(nx) * size_t(cross ? ny : nx) * es);
+    if (e == hipSuccess) e = cov.alloc(size_t(nx) * size_t(cross ? ny : nx) * es);
   }
-  auto cleanup = [&]() {
-    for (void* p : {mu, var, Ax, Cx, Ay, Cy, cov})
-      if (p) (void)hipFree(p);
-    svgp_data_free(ctx, X);
-    svgp_data_free(ctx, Y);
-  };
-  if (e != hipSuccess) { cleanup(); return fail(ctx, SVGP_OOM, "hipMalloc failed in predict"); }
+  if (e != hipSuccess) return alloc_failed(ctx, "in predict");
   StripOuts o;
-  o.mu = mu; o.var = var; o.A = Ax; o.C = Cx; o.lda = ldax;
-  rc = enqueue_strips(ctx, m, X->x, X->ldx, nullptr, 0, nx, o);
+  o.mu = mu.p; o.var = var.p; o.A = Ax.p; o.C = Cx.p; o.lda = ldax;
+  rc = enqueue_strips(ctx, m, X->x.p, X->ldx, nullptr, 0, nx, o);
   if (rc == SVGP_OK && cross && want_cov) {
     StripOuts oy;
-    oy.A = Ay; oy.C = Cy; oy.lda = lday;
-    rc = enqueue_strips(ctx, m, Y->x, Y->ldx, nullptr, 0, ny, oy);
+    oy.A = Ay.p; oy.C = Cy.p; oy.lda = lday;
+    rc = enqueue_strips(ctx, m, Y->x.p, Y->ldx, nullptr, 0, ny, oy);
   }
   if (rc == SVGP_OK && want_cov) {
     if (cross)
-      launch_cov_assemble(m->dtype, s, kparams(m), X->x, X->ldx, nx, Y->x, Y->ldx, ny, Ax, Cx, ldax, Ay, Cy, lday, m->Mp, cov);
+      launch_cov_assemble(m->dtype, s, kparams(m), X->x.p, X->ldx, nx, Y->x.p, Y->ldx, ny, Ax.p, Cx.p, ldax, Ay.p, Cy.p, lday, m->Mp, cov.p);
     else
-      launch_cov_assemble(m->dtype, s, kparams(m), X->x, X->ldx, nx, X->x, X->ldx, nx, Ax, Cx, ldax, Ax, Cx, ldax, m->Mp, cov);
+      launch_cov_assemble(m->dtype, s, kparams(m), X->x.p, X->ldx, nx, X->x.p, X->ldx, nx, Ax.p, Cx.p, ldax, Ax.p, Cx.p, ldax, m->Mp, cov.p);
   }
   hipError_t le = hipGetLastError();
   if (rc == SVGP_OK && le != hipSuccess) rc = fail(ctx, SVGP_HIP_ERROR, hipGetErrorString(le));
   if (rc == SVGP_OK) {
-    if (mean_out) (void)hipMemcpyAsync(mean_out, mu, size_t(nx) * es, hipMemcpyDeviceToHost, s);
-    if (var_out) (void)hipMemcpyAsync(var_out, var, size_t(nx) * es, hipMemcpyDeviceToHost, s);
-    if (want_cov) (void)hipMemcpyAsync(cov_out, cov, size_t(nx) * size_t(cross ? ny : nx) * es, hipMemcpyDeviceToHost, s);
+    if (mean_out) (void)hipMemcpyAsync(mean_out, mu.p, size_t(nx) * es, hipMemcpyDeviceToHost, s);
+    if (var_out) (void)hipMemcpyAsync(var_out, var.p, size_t(nx) * es, hipMemcpyDeviceToHost, s);
+    if (want_cov) (void)hipMemcpyAsync(cov_out, cov.p, size_t(nx) * size_t(cross ? ny : nx) * es, hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) rc = fail(ctx, SVGP_HIP_ERROR, "stream sync failed in predict");
   } else {
     (void)hipStreamSynchronize(s);
   }
-  cleanup();
   return rc;
 }
 
@@ -1331,7 +1235,8 @@ int grad_workspace(svgp_ctx* ctx, svgp_model* m, int64_t len, GradWs** out) {
   const int64_t nc = grad_chunk_points(Mp, es, len);
   GradWs* w = ctx->gws;
   if (w && w->dtype == m->dtype && w->Mp == Mp && w->d == m->d && w->nc >= nc) { *out = w; return SVGP_OK; }
-  if (w) { w->release(); delete w; ctx->gws = nullptr; }
+  delete w;
+  ctx->gws = nullptr;
   w = new (std::nothrow) GradWs();
   if (!w) return SVGP_OOM;
   w->dtype = m->dtype; w->Mp = Mp; w->d = m->d; w->nc = nc;
@@ -1361,7 +1266,7 @@ int grad_workspace(svgp_ctx* ctx, svgp_model* m, int64_t len, GradWs** out) {
   // [rp_uf | sp_uf | rp_uu | sp_uu | sums (8) | scal_out (1 + dreg) | prep scalars (4) + info (1)]: one memset, and the tail
   // [sums .. info] is the ONE fp64 read-back of an evaluation
   w->zero_b = w->rp_uf_b + w->sp_uf_b + w->rp_uu_b + w->sp_uu_b + size_t(8 + 1 + dreg + 5) * 8;
-  struct { void** p; size_t b; } req[] = {
+  struct { DevBuf* p; size_t b; } req[] = {
       {&w->At, mn}, {&w->Pt, mn}, {&w->gmu, 2 * size_t(nc) * es + 256},   // g_mu | g_v contiguous: one memset per chunk (+ the SYRK's weight DMA reads 256 B at a time)
       {&w->Lqp, mm}, {&w->G1, w->g_b}, {&w->G2, mm}, {&w->LkRM, mm},
       {&w->LbarRM, mm}, {&w->Phi, mm}, {&w->tmp, mm}, {&w->H, mm}, {&w->LinvRM, mm}, {&w->LinvCM, mm},
@@ -1369,22 +1274,20 @@ int grad_workspace(svgp_ctx* ctx, svgp_model* m, int64_t len, GradWs** out) {
       // same (dtype, Mp, d), whatever its M (M = 45 then M = 96 on one context overran the smaller buffers)
       {&w->gblk, (size_t(Mp) * m->d + size_t(Mp)) * es + mm}, {&w->cblk, (size_t(Mp) * m->d + size_t(Mp)) * es + mm / 2 + size_t(Mp) * es},
       {&w->BbarRM, mm}, {&w->rbar, size_t(Mp) * es},
-      {&w->W2, mm}, {&w->Rcm, mm}, {&w->G1p, mm}, {&w->alpha, size_t(Mp) * es}, {(void**)&w->avec, size_t(Mp) * 8},
-      {(void**)&w->gemv_part, size_t(Mp / 128) * size_t(Mp) * 8},
+      {&w->W2, mm}, {&w->Rcm, mm}, {&w->G1p, mm}, {&w->alpha, size_t(Mp) * es}, {&w->avec, size_t(Mp) * 8},
+      {&w->gemv_part, size_t(Mp / 128) * size_t(Mp) * 8},
       {&w->zero_blk, w->zero_b},
-      {(void**)&w->partial5, size_t(w->part5_strips) * 5 * 8}, {(void**)&w->invl_d, size_t(m->d) * 8},
-      {(void**)&w->kred, (size_t(2 + dreg) * size_t(Mp) + size_t(1 + dreg)) * 8}};
+      {&w->partial5, size_t(w->part5_strips) * 5 * 8}, {&w->invl_d, size_t(m->d) * 8},
+      {&w->kred, (size_t(2 + dreg) * size_t(Mp) + size_t(1 + dreg)) * 8}};
   for (auto& r : req) {
-    if (hipMalloc(r.p, r.b) != hipSuccess) {
-      w->release();
+    if (r.p->alloc(r.b) != hipSuccess) {
       delete w;
-      return fail(ctx, SVGP_OOM, "hipMalloc failed for the gradient workspace");
+      return alloc_failed(ctx, "for the gradient workspace");
     }
-    w->all.push_back(*r.p);
   }
-  w->gv = static_cast<char*>(w->gmu) + size_t(nc) * es;
+  w->gv = static_cast<char*>(w->gmu.p) + size_t(nc) * es;
   {
-    char* z = static_cast<char*>(w->zero_blk);
+    char* z = static_cast<char*>(w->zero_blk.p);
     w->rp_uf = reinterpret_cast<double*>(z); z += w->rp_uf_b;
     w->sp_uf = reinterpret_cast<double*>(z); z += w->sp_uf_b;
     w->rp_uu = reinterpret_cast<double*>(z); z += w->rp_uu_b;
@@ -1394,16 +1297,14 @@ int grad_workspace(svgp_ctx* ctx, svgp_model* m, int64_t len, GradWs** out) {
   w->scal_out = w->sums + 8;   // contiguous with sums: the data-parallel path all-reduces [sums | scal_out] in one piece
   // Linv is written block-lower only and the products skip the tiles above the diagonal, but the stale upper part of a reused
   // buffer must at least be finite (0 x NaN): start from zeros once
-  for (void* p : {w->LinvRM, w->LinvCM})
+  for (void* p : {w->LinvRM.p, w->LinvCM.p})
     if (hipMemsetAsync(p, 0, mm, ctx->stream) != hipSuccess) {
-      w->release();
       delete w;
       return fail(ctx, SVGP_HIP_ERROR, "memset failed");
     }
   // the point-major chunk buffers are read beyond the written points of a short last chunk (against g_v = 0): start from zeros
-  for (void* p : {w->At, w->Pt})
+  for (void* p : {w->At.p, w->Pt.p})
     if (hipMemsetAsync(p, 0, mn, ctx->stream) != hipSuccess) {
-      w->release();
       delete w;
       return fail(ctx, SVGP_HIP_ERROR, "memset failed");
     }
@@ -1455,7 +1356,7 @@ void gemm_mm(svgp_ctx* ctx, GradWs* w, int dt, hipStream_t s, const void* Xt, co
     return;
   }
   const int64_t sl = ((Mp + ns - 1) / ns + 15) / 16 * 16;
-  void* sc = scratch ? scratch : w->G1;
+  void* sc = scratch ? scratch : w->G1.p;
   launch_gemm_pm(dt, s, Xt, Yt, nullptr, 1.0, Mp, Mp, sl, ns, sc, 1, flags);
   launch_sum_slices_lower(dt, s, sc, ns, Mp, out, (flags & kMmFull) ? 1 : 0, 1);
 }
@@ -1491,8 +1392,8 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   const size_t es = m->es;
   const int dreg = grad_dreg(m->d);
   // the user-layout gradient blocks of THIS model, contiguous: {z_bar | m_bar | Lq_bar}
-  w->zbar = w->gblk;
-  w->mbar = static_cast<char*>(w->gblk) + size_t(M) * m->d * es;
+  w->zbar = w->gblk.p;
+  w->mbar = static_cast<char*>(w->gblk.p) + size_t(M) * m->d * es;
   w->Lqbar = static_cast<char*>(w->mbar) + size_t(M) * es;
   // Strips beside the factorisation (round 4): a one-chunk, one-round batch runs its phase 1 as segmented strips on the second
   // stream - panel I behind the event of block row I of T - and its phase 3 behind the M-sized gradient prep (Linv, alpha, R) that
@@ -1512,21 +1413,19 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   lp.gh_n = m->gh_n;
   lp.sigma2 = lik_param(m->desc);
   lp.digamma_alpha = m->desc.likelihood == SVGP_LIK_GAMMA_EXP ? digamma_d(m->desc.lik_sigma2) : 0.0;
-  lp.gh_x = m->gh_x;
-  lp.gh_w = m->gh_w;
+  lp.gh_x = m->gh_x.as<double>();
+  lp.gh_w = m->gh_w.as<double>();
   lp.clamp_neg_var = (m->desc.neg_var_policy == SVGP_NEGVAR_CLAMP);
   lp.mean_const = m->desc.mean_const;
   const KernelParams kp = kparams(m);
+  double *ext_gmu = nullptr, *ext_gv = nullptr;   // their place on the device
   if (gc.ext_gmu) {   // the host's point gradients: one H2D copy of 2 x len doubles
-    if (size_t(len) > ctx->ext_cap) {
-      if (ctx->ext_g) (void)hipFree(ctx->ext_g);
-      ctx->ext_g = nullptr;
-      ctx->ext_cap = 0;
-      if (hipMalloc(&ctx->ext_g, 2 * size_t(len) * 8) != hipSuccess) return fail(ctx, SVGP_OOM, "hipMalloc failed for the point gradients");
-      ctx->ext_cap = size_t(len);
-    }
-    HIPC(ctx, hipMemcpyAsync(ctx->ext_g, gc.ext_gmu, size_t(len) * 8, hipMemcpyHostToDevice, s));
-    HIPC(ctx, hipMemcpyAsync(ctx->ext_g + ctx->ext_cap, gc.ext_gv, size_t(len) * 8, hipMemcpyHostToDevice, s));
+    rc = ctx->ext_g.reserve(ctx, 2 * size_t(len) * 8, "the point gradients");
+    if (rc) return rc;
+    ext_gmu = ctx->ext_g.as<double>();
+    ext_gv = ext_gmu + ctx->ext_g.cap / 16;   // [2][capacity in points]
+    HIPC(ctx, hipMemcpyAsync(ext_gmu, gc.ext_gmu, size_t(len) * 8, hipMemcpyHostToDevice, s));
+    HIPC(ctx, hipMemcpyAsync(ext_gv, gc.ext_gv, size_t(len) * 8, hipMemcpyHostToDevice, s));
   }
   // The likelihood gradients come from point_grad_kernel behind the strips (both likelihood routes); A g_mu (the data part of m_bar): the
   // kernel-gradient reductions, which evaluate the kernel anyway, sum Kuf g_mu and the tail applies Lk^-1 (one gemv with the explicit
@@ -1543,22 +1442,21 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   // workgroups and the prep's small launches slow each other, so only a quarter of the 230 us comes back (profiles/round6/minibatch_trace.md).
   static const int early_knob = exp_int("SVGP_SYRK_EARLY", 1);   // (experiments build: 0 = the SYRK behind phase 3, as rounds 3-5)
   const bool syrk_early = gop.on && uniform_w && early_knob != 0;
-  if (syrk_early && !w->Gmm) {
-    const size_t gmm_b = size_t(std::min<int64_t>(Mp / 128, w->nslices)) * size_t(Mp) * size_t(Mp) * m->es;
-    if (hipMalloc(&w->Gmm, gmm_b) != hipSuccess) { w->Gmm = nullptr; return fail(ctx, SVGP_OOM, "hipMalloc failed for the gradient workspace"); }
-    w->all.push_back(w->Gmm);
+  if (syrk_early) {   // (the size is a function of the workspace's shape: allocated once)
+    rc = w->Gmm.reserve(ctx, size_t(std::min<int64_t>(Mp / 128, w->nslices)) * size_t(Mp) * size_t(Mp) * m->es, "the gradient workspace");
+    if (rc) return rc;
   }
   // the strips' arguments for the chunk [c0, c0 + clen) (scratch / moment pointers: read after the ensure_scratch of the caller)
   auto strip_args = [&](int64_t c0, int64_t clen, LikParams& lpc) -> StripArgs {
     StripArgs a{};
-    a.T = m->T; a.U = m->U; a.zs = m->zs; a.mp = m->mp; a.x = data->x; a.work = ctx->work; a.counter = ctx->counter;
-    a.At_out = w->At; a.ldx = data->ldx; a.off = off + c0; a.len = clen; a.Mp = Mp; a.M = M; a.kp = kp;
+    a.T = m->T.p; a.U = m->U.p; a.zs = m->zs.p; a.mp = m->mp.p; a.x = data->x.p; a.work = ctx->work.p; a.counter = ctx->counter.as<unsigned>();
+    a.At_out = w->At.p; a.ldx = data->ldx; a.off = off + c0; a.len = clen; a.Mp = Mp; a.M = M; a.kp = kp;
     a.mean_const = m->desc.mean_const;
     if (gc.mux) a.mux = static_cast<const char*>(gc.mux) + size_t(c0) * es;   // (c0: the chunk's first point inside the batch)
-    a.mom_mu = ctx->mom; a.mom_var = ctx->mom + ctx->mom_cap;   // the strips' (mu, v), read by launch_point_grads
-    a.R = w->Rcm; a.alpha = w->alpha; a.Pt_out = w->Pt;
+    a.mom_mu = ctx->mom_mu(); a.mom_var = ctx->mom_var();   // the strips' (mu, v), read by launch_point_grads
+    a.R = w->Rcm.p; a.alpha = w->alpha.p; a.Pt_out = w->Pt.p;
     lpc = lp;
-    if (gc.ext_gmu) { lpc.lik = kLikExternal; lpc.gh_x = ctx->ext_g + c0; lpc.gh_w = ctx->ext_g + ctx->ext_cap + c0; }   // (launch_point_grads' arguments)
+    if (gc.ext_gmu) { lpc.lik = kLikExternal; lpc.gh_x = ext_gmu + c0; lpc.gh_w = ext_gv + c0; }   // (launch_point_grads' arguments)
     return a;
   };
   // The M-sized work of the adjoint that does NOT depend on the factorisation: the cleared accumulators, the inverse lengthscales for
@@ -1566,15 +1464,15 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   // prep on the main stream.  Strips beside the factorisation: on the second stream AHEAD of the pre-generation (that stream has
   // nothing to do until block row 0 of T exists, ~130 us into the chain), the main stream waits for ev_S before it forms R.
   // the adjoint runs on the whitened problem: (m~, B) are (m, Lq) for NonCentered and (Lk^-1 (m - c), Lk^-1 Lq) for Centered
-  const void* Bq = centered ? m->B : w->Lqp;
+  const void* Bq = centered ? m->B.p : w->Lqp.p;
   auto grad_pre_chain = [&](hipStream_t st) -> int {
-    HIPC(ctx, hipMemsetAsync(w->zero_blk, 0, w->zero_b, st));   // every accumulator of the evaluation, one fill
+    HIPC(ctx, hipMemsetAsync(w->zero_blk.p, 0, w->zero_b, st));   // every accumulator of the evaluation, one fill
     // (as kernel arguments: a hipMemcpyAsync from pageable memory blocks the host until the stream gets there - on the second stream
     // that was ~45 us during which the main stream's Kuu launch was not even enqueued)
-    launch_setvec_f64(st, w->invl_d, m->invl_host.data(), m->d);
-    if (!centered) launch_pad_lower(dt, st, m->Lq_raw, M, Mp, w->Lqp);
-    gemm_mm(ctx, w, dt, st, Bq, Bq, Mp, w->G2, kMmXUp | kMmYUp);   // lower tiles of B B' (row-major); B[r][k] = 0 for k > r
-    launch_sym_from_lower(dt, st, w->G2, 1, Mp, 1.0, w->tmp);     // S = B B' - I, full
+    launch_setvec_f64(st, w->invl_d.as<double>(), m->invl_host.data(), m->d);
+    if (!centered) launch_pad_lower(dt, st, m->Lq_raw.p, M, Mp, w->Lqp.p);
+    gemm_mm(ctx, w, dt, st, Bq, Bq, Mp, w->G2.p, kMmXUp | kMmYUp);   // lower tiles of B B' (row-major); B[r][k] = 0 for k > r
+    launch_sym_from_lower(dt, st, w->G2.p, 1, Mp, 1.0, w->tmp.p);     // S = B B' - I, full
     KCHECK(ctx, "grad prep (S)");
     return SVGP_OK;
   };
@@ -1591,8 +1489,8 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   if (gop.on) {
     gseg.ctx = ctx; gseg.m = m; gseg.op = gop; gseg.grad = true; gseg.nP = int(Mp / 128);
     gseg.a = strip_args(0, len, lpc_seg);
-    gseg.a.seg_state = ctx->seg_state;
-    gseg.a.counter = ctx->counter2;
+    gseg.a.seg_state = ctx->seg_state.as<double>();
+    gseg.a.counter = ctx->counter2.as<unsigned>();
     gseg.pre = &seg_pre;
   }
   ctx->overlapped = gop.on;
@@ -1612,13 +1510,13 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   }
   // Linv = Lk^-1 (both storage orders): every Lk^-T . below is a GEMM with it (round 2: four blocked substitutions, 0.18 ms each
   // at M = 1024 whatever the batch size)
-  launch_linv(dt, s, m->L, m->T, Mp, w->LinvRM, w->LinvCM, w->H);
+  launch_linv(dt, s, m->L.p, m->T.p, Mp, w->LinvRM.p, w->LinvCM.p, w->H.p);
   // M-sized operands of the strips' phase 3:  R = Lk^-T (B B' - I)  (column-major: the P operand of the GEMM); then, for the
   // kernel-gradient reductions behind the strips, alpha = Lk^-T m~ (no strip reads it: it follows ev_R)
-  gemm_mm(ctx, w, dt, s, w->tmp, w->LinvRM, Mp, w->Rcm, kMmFull | kMmYLow, syrk_early ? w->Gmm : nullptr); // out[c][r] = sum_k S[k][c] Linv[k][r] = R[r][c]: R column-major
+  gemm_mm(ctx, w, dt, s, w->tmp.p, w->LinvRM.p, Mp, w->Rcm.p, kMmFull | kMmYLow, syrk_early ? w->Gmm.p : nullptr); // out[c][r] = sum_k S[k][c] Linv[k][r] = R[r][c]: R column-major
   KCHECK(ctx, "grad prep");
   if (gop.on) HIPC(ctx, hipEventRecord(ctx->ev_R, s));   // R is final: the segmented strips' closing launch (phase 3) may run
-  launch_linv_t_gemv(dt, s, w->LinvRM, m->mp, Mp, w->alpha, w->gemv_part);
+  launch_linv_t_gemv(dt, s, w->LinvRM.p, m->mp.p, Mp, w->alpha.p, w->gemv_part.as<double>());
   // the strips' scratch (the A strip and, beside it, the Kuf strip) and the chunk's moments, sized for every chunk of the call BEFORE
   // anything of the loop is enqueued (ensure_scratch may reallocate): the full chunks and the shorter last one may plan differently
   auto chunk_plan = [&](int64_t clen, int& nt, int& grid, int64_t& nstrips) {
@@ -1654,7 +1552,7 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
                     // and the main stream joins before the point gradients
       hipStream_t s2 = ctx->stream2;
       const int nPn = int(Mp / 128);
-      if (a.work != ctx->work || a.mom_mu != ctx->mom) return fail(ctx, SVGP_HIP_ERROR, "internal: scratch moved under the segmented strips");
+      if (a.work != ctx->work.p || a.mom_mu != ctx->mom_mu()) return fail(ctx, SVGP_HIP_ERROR, "internal: scratch moved under the segmented strips");
       // A small batch has fewer strips than the chip has workgroup slots and phase 3 - 2 M^2 flops per point, one panel after the other
       // inside a strip's workgroup - is latency-bound on the few CUs it reaches (1024 points, M = 1024: 32 workgroups, 340 us for 27 us
       // of MFMA work).  Its output panels are independent: the closing launch runs S workgroups per strip (strip.hip: seg_split).
@@ -1669,8 +1567,8 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
       }
       if (syrk_early) {   // W = w A A' behind the last phase-1 segment, beside the main stream's Lk^-1 / R / alpha
         const int64_t n16 = (clen + 15) / 16 * 16, sl_e = ((ncp + ns_syrk - 1) / ns_syrk + 15) / 16 * 16;
-        if (n16 > clen) HIPC(ctx, hipMemsetAsync(static_cast<char*>(w->At) + size_t(clen) * size_t(Mp) * es, 0, size_t(n16 - clen) * size_t(Mp) * es, s2));
-        launch_syrk_uniform(dt, s2, w->At, -0.5 / lp.sigma2, scale, n_global_dev, gc.num_data, 2.0, Mp, n16, sl_e, ns_syrk, w->G1, 1);
+        if (n16 > clen) HIPC(ctx, hipMemsetAsync(static_cast<char*>(w->At.p) + size_t(clen) * size_t(Mp) * es, 0, size_t(n16 - clen) * size_t(Mp) * es, s2));
+        launch_syrk_uniform(dt, s2, w->At.p, -0.5 / lp.sigma2, scale, n_global_dev, gc.num_data, 2.0, Mp, n16, sl_e, ns_syrk, w->G1.p, 1);
         KCHECK(ctx, "syrk (beside the prep of phase 3)");
       }
       HIPC(ctx, hipStreamWaitEvent(s2, ctx->ev_R, 0));
@@ -1686,22 +1584,22 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
       launch_strip_grad(dt, s, a, nt, grid, nstrips);
       KCHECK(ctx, "strip (value and gradient)");
     }
-    launch_point_grads(dt, s, lpc, a.mom_mu, a.mom_var, gc.ext_gmu ? nullptr : data->y, off + c0, clen, scale, n_global_dev, gc.num_data, w->gmu, w->gv,
-                       w->partial5, gop.on ? nullptr : a.counter, ncp,
+    launch_point_grads(dt, s, lpc, a.mom_mu, a.mom_var, gc.ext_gmu ? nullptr : data->y.p, off + c0, clen, scale, n_global_dev, gc.num_data, w->gmu.p, w->gv,
+                       w->partial5.as<double>(), gop.on ? nullptr : a.counter, ncp,
                        gc.mux_bar ? static_cast<char*>(gc.mux_bar) + size_t(c0) * es : nullptr);
     KCHECK(ctx, "point gradients");
     const int n5 = point_grad_blocks(clen);   // rows of partial5: one per 256-point block
     int64_t ksl = ((clen + w->ns_uf - 1) / w->ns_uf + 127) / 128 * 128;
-    launch_kgrad(dt, s, kp, m->zs, Mp, M, data->x, data->ldx, off + c0, 0, clen, clen, w->Pt, w->gmu, w->gv, w->alpha, ksl, w->ns_uf,
+    launch_kgrad(dt, s, kp, m->zs.p, Mp, M, data->x.p, data->ldx, off + c0, 0, clen, clen, w->Pt.p, w->gmu.p, w->gv, w->alpha.p, ksl, w->ns_uf,
                  w->rp_uf, w->sp_uf, 1);
     KCHECK(ctx, "kgrad uf");
     if (gc.gx) {   // d elbo / d x of the chunk's points, from the same P while Pt holds the chunk (host output: into w->xg, [d][len])
       const bool dev = gc.gx->on_device != 0;
-      launch_xgrad(dt, s, kp, m->zs, Mp, M, data->x, data->ldx, off + c0, clen, w->Pt, w->gmu, w->gv, w->alpha, dev ? gc.gx->x : w->xg,
+      launch_xgrad(dt, s, kp, m->zs.p, Mp, M, data->x.p, data->ldx, off + c0, clen, w->Pt.p, w->gmu.p, w->gv, w->alpha.p, dev ? gc.gx->x : w->xg.p,
                    dev ? gc.gx->ld : len, c0);
       KCHECK(ctx, "xgrad");
     }
-    launch_sum5(s, w->partial5, n5, w->sums);
+    launch_sum5(s, w->partial5.as<double>(), n5, w->sums);
     int64_t sl = ((ncp + ns_syrk - 1) / ns_syrk + 15) / 16 * 16;   // as even as the 16-point k-step allows
     // W (+)= A diag(2 g_v) A' (lower tiles, split-K slices): the first chunk overwrites, so the slice buffer needs no zeroing
     if (syrk_early) {
@@ -1710,10 +1608,10 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
       // g_v is the same for every point (Gaussian: -scale / (2 sigma^2)): the unweighted loop, the weight applied to the accumulators.
       // Columns of the chunk's last strip beyond its last point hold the replicated last point: zero them up to the k-step boundary
       const int64_t n16 = (clen + 15) / 16 * 16;
-      if (n16 > clen) HIPC(ctx, hipMemsetAsync(static_cast<char*>(w->At) + size_t(clen) * size_t(Mp) * es, 0, size_t(n16 - clen) * size_t(Mp) * es, s));
-      launch_syrk_uniform(dt, s, w->At, -0.5 / lp.sigma2, scale, n_global_dev, gc.num_data, 2.0, Mp, n16, sl, ns_syrk, w->G1, c0 == 0 ? 1 : 0);
+      if (n16 > clen) HIPC(ctx, hipMemsetAsync(static_cast<char*>(w->At.p) + size_t(clen) * size_t(Mp) * es, 0, size_t(n16 - clen) * size_t(Mp) * es, s));
+      launch_syrk_uniform(dt, s, w->At.p, -0.5 / lp.sigma2, scale, n_global_dev, gc.num_data, 2.0, Mp, n16, sl, ns_syrk, w->G1.p, c0 == 0 ? 1 : 0);
     } else {
-      launch_gemm_pm(dt, s, w->At, w->At, w->gv, 2.0, Mp, ncp, sl, ns_syrk, w->G1, c0 == 0 ? 1 : 0);
+      launch_gemm_pm(dt, s, w->At.p, w->At.p, w->gv, 2.0, Mp, ncp, sl, ns_syrk, w->G1.p, c0 == 0 ? 1 : 0);
     }
     KCHECK(ctx, "syrk");
   }
@@ -1721,45 +1619,45 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   TREC(ctx, ctx->ev[2], s);
   // M-sized tail.  With W = A diag(2 g_v) A' and a = A g_mu:
   //   Lq_bar = tril(W B) - klw dKL/dB,   Lk_bar = -tril(alpha a' + R W)     (B = Lq whitened; W, R carry the factors 2)
-  launch_sym_from_lower(dt, s, w->G1, ns_syrk, Mp, 0.0, w->W2);
-  gemm_mm(ctx, w, dt, s, w->W2, m->U, Mp, w->G1p, kMmYLow);   // (W B)[r][c] = sum_i W[i][r] B[i][c]; B[i][c] = 0 for i < c
-  gemm_mm(ctx, w, dt, s, w->Rcm, w->W2, Mp, w->G2);           // (R W)[r][c] = sum_i R[r][i] W[i][c]
-  launch_avec(s, w->rp_uf, w->ns_uf, int64_t(2 + dreg) * Mp, Mp, w->avec);
+  launch_sym_from_lower(dt, s, w->G1.p, ns_syrk, Mp, 0.0, w->W2.p);
+  gemm_mm(ctx, w, dt, s, w->W2.p, m->U.p, Mp, w->G1p.p, kMmYLow);   // (W B)[r][c] = sum_i W[i][r] B[i][c]; B[i][c] = 0 for i < c
+  gemm_mm(ctx, w, dt, s, w->Rcm.p, w->W2.p, Mp, w->G2.p);           // (R W)[r][c] = sum_i R[r][i] W[i][c]
+  launch_avec(s, w->rp_uf, w->ns_uf, int64_t(2 + dreg) * Mp, Mp, w->avec.as<double>());
   // avec holds Kuf g_mu: A g_mu = Lk^-1 (Kuf g_mu)
-  launch_linv_t_gemv(dt, s, w->LinvCM, w->avec, Mp, w->avec, w->gemv_part, 1, 1);   // avec is fp64 in both builds
-  launch_finish_mm2(dt, s, w->G1p, w->G2, w->alpha, w->avec, Mp, M, centered ? m->B : m->Lq_raw, centered ? Mp : M, klw, w->Lqbar,
-                    centered ? w->BbarRM : nullptr, w->LbarRM);
+  launch_linv_t_gemv(dt, s, w->LinvCM.p, w->avec.as<double>(), Mp, w->avec.as<double>(), w->gemv_part.as<double>(), 1, 1);   // avec is fp64 in both builds
+  launch_finish_mm2(dt, s, w->G1p.p, w->G2.p, w->alpha.p, w->avec.as<double>(), Mp, M, centered ? m->B.p : m->Lq_raw.p, centered ? Mp : M, klw, w->Lqbar,
+                    centered ? w->BbarRM.p : nullptr, w->LbarRM.p);
   KCHECK(ctx, "Lq_bar / Lk_bar");
   if (centered) {
     // chain through m~ = Lk \ (m - c) and B = Lk \ Lq:  m_bar = Lk^-T m~_bar,  Rb = Lk^-T B_bar,  Lq_bar = tril(Rb),
     // Lk_bar -= tril(m_bar m~') + tril(Rb B')
-    launch_mbar(dt, s, w->avec, m->mp, klw, M, Mp, w->rbar);
-    launch_linv_t_gemv(dt, s, w->LinvRM, w->rbar, Mp, w->alpha, w->gemv_part);   // alpha is free after finish_mm2: holds m_bar (padded)
-    HIPC(ctx, hipMemcpyAsync(w->mbar, w->alpha, size_t(M) * es, hipMemcpyDeviceToDevice, s));
+    launch_mbar(dt, s, w->avec.as<double>(), m->mp.p, klw, M, Mp, w->rbar.p);
+    launch_linv_t_gemv(dt, s, w->LinvRM.p, w->rbar.p, Mp, w->alpha.p, w->gemv_part.as<double>());   // alpha is free after finish_mm2: holds m_bar (padded)
+    HIPC(ctx, hipMemcpyAsync(w->mbar, w->alpha.p, size_t(M) * es, hipMemcpyDeviceToDevice, s));
     // out[c][r] = sum_i B_bar[i][c] Linv[i][r] = Rb[r][c]: Rb column-major = the k-major operand of Rb B' below
-    gemm_mm(ctx, w, dt, s, w->BbarRM, w->LinvRM, Mp, w->tmp, kMmFull | kMmXLow | kMmYLow);
-    launch_cm_tril_to_user(dt, s, w->tmp, Mp, M, w->Lqbar);
-    gemm_mm(ctx, w, dt, s, w->tmp, m->B, Mp, w->Phi, kMmYUp);   // (Rb B')[r][c] = sum_i Rb[r][i] B[c][i]; B[c][i] = 0 for i > c
-    launch_lbar_adjust(dt, s, w->LbarRM, w->Phi, w->alpha, m->mp, Mp);
+    gemm_mm(ctx, w, dt, s, w->BbarRM.p, w->LinvRM.p, Mp, w->tmp.p, kMmFull | kMmXLow | kMmYLow);
+    launch_cm_tril_to_user(dt, s, w->tmp.p, Mp, M, w->Lqbar);
+    gemm_mm(ctx, w, dt, s, w->tmp.p, m->B.p, Mp, w->Phi.p, kMmYUp);   // (Rb B')[r][c] = sum_i Rb[r][i] B[c][i]; B[c][i] = 0 for i > c
+    launch_lbar_adjust(dt, s, w->LbarRM.p, w->Phi.p, w->alpha.p, m->mp.p, Mp);
     KCHECK(ctx, "centered chain");
   }
   // Cholesky backward: Kuu_bar = sym(Lk^-T Phi(Lk' Lk_bar) Lk^-1)
-  launch_lower_to_rowmajor(dt, s, m->L, Mp, w->LkRM);
-  gemm_mm(ctx, w, dt, s, w->LkRM, w->LbarRM, Mp, w->Phi, kMmXLow | kMmYLow);   // (Lk' Lk_bar)[r][c], lower tiles
-  launch_phi(dt, s, w->Phi, Mp);                                               // tril, diagonal halved; zero above
-  gemm_mm(ctx, w, dt, s, w->Phi, w->LinvRM, Mp, w->tmp, kMmFull | kMmXLow | kMmYLow);   // out[c][r] = sum_i Phi[i][c] Linv[i][r] = (Linv' Phi)[r][c]
-  gemm_mm(ctx, w, dt, s, w->tmp, w->LinvRM, Mp, w->G1p, kMmFull | kMmYLow);             // out[r][c] = sum_j (Linv' Phi)[r][j] Linv[j][c]
-  launch_symmetrize(dt, s, w->G1p, Mp, w->H);
+  launch_lower_to_rowmajor(dt, s, m->L.p, Mp, w->LkRM.p);
+  gemm_mm(ctx, w, dt, s, w->LkRM.p, w->LbarRM.p, Mp, w->Phi.p, kMmXLow | kMmYLow);   // (Lk' Lk_bar)[r][c], lower tiles
+  launch_phi(dt, s, w->Phi.p, Mp);                                               // tril, diagonal halved; zero above
+  gemm_mm(ctx, w, dt, s, w->Phi.p, w->LinvRM.p, Mp, w->tmp.p, kMmFull | kMmXLow | kMmYLow);   // out[c][r] = sum_i Phi[i][c] Linv[i][r] = (Linv' Phi)[r][c]
+  gemm_mm(ctx, w, dt, s, w->tmp.p, w->LinvRM.p, Mp, w->G1p.p, kMmFull | kMmYLow);             // out[r][c] = sum_j (Linv' Phi)[r][j] Linv[j][c]
+  launch_symmetrize(dt, s, w->G1p.p, Mp, w->H.p);
   KCHECK(ctx, "chol backward");
   // the Kuu part: the ns_uu slices must cover all M columns (a fixed slice of 128 covered only 1024 of them: the kernel-
   // parameter and z gradients were wrong for M > 1024 until tests/test_gpu_grad.py::test_gradient_large_m_float32_strips)
   const int64_t uu_sl = ((M + w->ns_uu - 1) / w->ns_uu + 127) / 128 * 128;
-  launch_kgrad(dt, s, kp, m->zs, Mp, M, m->zs, Mp, 0, 1, M, M, w->H, nullptr, nullptr, nullptr, uu_sl, w->ns_uu, w->rp_uu, w->sp_uu);
-  launch_finish_kgrad(dt, s, m->d, M, Mp, m->zs, w->invl_d, w->rp_uf, w->ns_uf, w->rp_uu, w->ns_uu, w->sp_uf, w->ns_uf * w->rb,
-                      w->sp_uu, w->ns_uu * w->rb, m->mp, klw, m->desc.layout_z, m->desc.variance, w->zbar, centered ? nullptr : w->mbar,
-                      w->scal_out, w->kred, w->avec);
+  launch_kgrad(dt, s, kp, m->zs.p, Mp, M, m->zs.p, Mp, 0, 1, M, M, w->H.p, nullptr, nullptr, nullptr, uu_sl, w->ns_uu, w->rp_uu, w->sp_uu);
+  launch_finish_kgrad(dt, s, m->d, M, Mp, m->zs.p, w->invl_d.as<double>(), w->rp_uf, w->ns_uf, w->rp_uu, w->ns_uu, w->sp_uf, w->ns_uf * w->rb,
+                      w->sp_uu, w->ns_uu * w->rb, m->mp.p, klw, m->desc.layout_z, m->desc.variance, w->zbar, centered ? nullptr : w->mbar,
+                      w->scal_out, w->kred.as<double>(), w->avec.as<double>());
   // status slots of the all-reduced scalars + this rank's prep scalars / info behind them: ONE fp64 read-back per evaluation
-  launch_grad_status(s, w->sums, m->info, double(len), m->scal, w->scal_out + 1 + dreg);
+  launch_grad_status(s, w->sums, m->info.as<int>(), double(len), m->scal.as<double>(), w->scal_out + 1 + dreg);
   KCHECK(ctx, "kgrad uu / finish");
   TREC(ctx, ctx->ev[3], s);
   return SVGP_OK;
@@ -1777,29 +1675,24 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
 // communicator, which does not wake the peers: a documented hang.)
 int grad_handshake(svgp_ctx* ctx, GradCall& gc, int64_t len, bool failed) {
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, SVGP_HIP_ERROR, "hipSetDevice failed");
-  if (!ctx->h_open && hipHostMalloc(reinterpret_cast<void**>(&ctx->h_open), 64, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_open = nullptr;
-    return fail(ctx, SVGP_OOM, "hipHostMalloc failed for the opening all-reduce's flag");
-  }
-  if (!ctx->ev_open && hipEventCreateWithFlags(&ctx->ev_open, hipEventDisableTiming) != hipSuccess) {
-    ctx->ev_open = nullptr;
-    return fail(ctx, SVGP_HIP_ERROR, "hipEventCreate failed");
-  }
-  launch_set2_f64(ctx->stream, ctx->d_coll, failed ? 0.0 : double(len), failed ? 1.0 : 0.0);
+  const int rch = ctx->h_open.reserve(ctx, 64, "the opening all-reduce's flag");
+  if (rch) return rch;
+  HIPC(ctx, ctx->ev_open.create(hipEventDisableTiming));
+  launch_set2_f64(ctx->stream, ctx->d_coll.as<double>(), failed ? 0.0 : double(len), failed ? 1.0 : 0.0);
   if (hipGetLastError() != hipSuccess) return fail(ctx, SVGP_HIP_ERROR, "launch failed in the opening all-reduce");
-  const int rc = comm_allreduce(ctx, ctx->d_coll, 2, SVGP_F64);
+  const int rc = comm_allreduce(ctx, ctx->d_coll.as<double>(), 2, SVGP_F64);
   if (rc != SVGP_OK) return rc;
-  *ctx->h_open = -1.0;
-  if (hipMemcpyAsync(ctx->h_open, ctx->d_coll + 1, sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+  *ctx->h_open.as<double>() = -1.0;
+  if (hipMemcpyAsync(ctx->h_open.p, ctx->d_coll.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
       hipEventRecord(ctx->ev_open, ctx->stream) != hipSuccess)
     return fail(ctx, SVGP_HIP_ERROR, "read-back of the opening all-reduce's flag failed");
-  gc.n_global_dev = ctx->d_coll;
+  gc.n_global_dev = ctx->d_coll.as<double>();
   return SVGP_OK;
 }
 // number of ranks that entered the opening all-reduce with the failure flag (blocks until that all-reduce has completed); < 0: unknown
 double grad_peers_failed(svgp_ctx* ctx) {
   if (!ctx->ev_open || hipEventSynchronize(ctx->ev_open) != hipSuccess) return -1.0;
-  return *ctx->h_open;
+  return *ctx->h_open.as<double>();
 }
 
 // A rank of a collective svgp_elbo_grad / svgp_elbo_grad_ext that failed BEFORE anything could be enqueued (argument checks, NULL model,
@@ -1839,9 +1732,9 @@ int grad_collective(svgp_ctx* ctx, svgp_model* m, GradCall& gc, int local_rc) {
   // the compute dtype, one in fp64 for the scalars, then unpacked in place
   const int64_t M = m->M, head = M * m->d + M;
   const size_t ncoll = size_t(head) + size_t(M) * size_t(M + 1) / 2;
-  if (hipSetDevice(ctx->device) == hipSuccess) launch_pack_tril(m->dtype, ctx->stream, w->gblk, w->cblk, head, M, 0);
+  if (hipSetDevice(ctx->device) == hipSuccess) launch_pack_tril(m->dtype, ctx->stream, w->gblk.p, w->cblk.p, head, M, 0);
   int rc = comm_group_start(ctx);
-  if (rc == SVGP_OK) rc = comm_allreduce(ctx, w->cblk, ncoll, m->dtype);
+  if (rc == SVGP_OK) rc = comm_allreduce(ctx, w->cblk.p, ncoll, m->dtype);
   if (rc == SVGP_OK) rc = comm_allreduce(ctx, w->sums, size_t(8 + 1 + dreg), SVGP_F64);
   const int rce = comm_group_end(ctx);
   if (rc == SVGP_OK) rc = rce;
@@ -1876,25 +1769,19 @@ int grad_finish(svgp_ctx* ctx, svgp_model* m, GradCall& gc, double* elbo_out, sv
   // copy, which also writes the zeros above the diagonal.  The C-ABI keeps its dense Lq_bar.
   const size_t nz = size_t(M) * m->d, head = nz + size_t(M), tri = size_t(M) * size_t(M + 1) / 2, nblk = head + tri;
   const size_t f64n = size_t(8 + 1 + dreg + 5), f64b = (f64n * 8 + 255) / 256 * 256, gbytes = nblk * es;
-  if (!gc.packed) launch_pack_tril(dt, s, w->gblk, w->cblk, int64_t(head), M, 0);
+  if (!gc.packed) launch_pack_tril(dt, s, w->gblk.p, w->cblk.p, int64_t(head), M, 0);
   KCHECK(ctx, "pack Lq_bar");
-  if (f64b + gbytes > ctx->hstage_bytes) {
-    if (ctx->hstage) (void)hipHostFree(ctx->hstage);
-    ctx->hstage = nullptr;
-    ctx->hstage_bytes = 0;
-    HIPC(ctx, hipHostMalloc(&ctx->hstage, f64b + gbytes, hipHostMallocDefault));
-    ctx->hstage_bytes = f64b + gbytes;
-  }
-  for (auto& e : ctx->ev_piece)
-    if (!e) HIPC(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  double* f64blk = static_cast<double*>(ctx->hstage);
-  char* gh = static_cast<char*>(ctx->hstage) + f64b;
+  const int rcs = ctx->hstage.reserve(ctx, f64b + gbytes, "the gradient read-back's staging");
+  if (rcs) return rcs;
+  for (auto& e : ctx->ev_piece) HIPC(ctx, e.create(hipEventDisableTiming));
+  double* f64blk = ctx->hstage.as<double>();
+  char* gh = ctx->hstage.as<char>() + f64b;
   HIPC(ctx, hipMemcpyAsync(f64blk, w->sums, f64n * 8, hipMemcpyDeviceToHost, s));
   const int npiece = int(std::min<size_t>(8, std::max<size_t>(1, gbytes >> 20)));   // >= 1 MiB per piece
   const size_t piece = ((gbytes + npiece - 1) / npiece + 255) / 256 * 256;
   for (int q = 0; q < npiece; ++q) {
     const size_t lo = std::min(gbytes, size_t(q) * piece), hi = std::min(gbytes, lo + piece);
-    if (hi > lo) HIPC(ctx, hipMemcpyAsync(gh + lo, static_cast<const char*>(w->cblk) + lo, hi - lo, hipMemcpyDeviceToHost, s));
+    if (hi > lo) HIPC(ctx, hipMemcpyAsync(gh + lo, static_cast<const char*>(w->cblk.p) + lo, hi - lo, hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipEventRecord(ctx->ev_piece[q], s));
   }
   struct Dst { size_t lo, hi; void* p; };
@@ -1978,20 +1865,12 @@ int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
   if (rc == SVGP_OK && hipSetDevice(ctx->device) != hipSuccess) rc = fail(ctx, SVGP_HIP_ERROR, "hipSetDevice failed");
   if (rc == SVGP_OK) rc = grad_workspace(ctx, m, len, &gc.w);
   if (rc == SVGP_OK && gx && !gx->on_device) {   // host output: the kernel writes [d][len] on the device, one copy brings it over
-    const size_t xb = size_t(m->d) * size_t(len) * m->es;
-    GradWs* w = gc.w;
-    if (w->xg_b < xb) {
-      if (w->xg) (void)hipFree(w->xg);
-      w->xg = nullptr;
-      w->xg_b = 0;
-      if (hipMalloc(&w->xg, xb) != hipSuccess) { w->xg = nullptr; rc = fail(ctx, SVGP_OOM, "hipMalloc failed for d elbo / d x"); }
-      else w->xg_b = xb;
-    }
+    rc = gc.w->xg.reserve(ctx, size_t(m->d) * size_t(len) * m->es, "d elbo / d x");
   }
   if (rc == SVGP_OK && pm) rc = stage_point_mean(ctx, pm, size_t(len) * m->es, &gc.mux);
   if (rc == SVGP_OK && gpm) {   // host destination: point_grad_kernel writes ctx->pm_g, one copy brings it over
     if (gpm->on_device) gc.mux_bar = gpm->mu_bar;
-    else if ((rc = grow_buffer(ctx, &ctx->pm_g, &ctx->pm_g_bytes, size_t(len) * m->es)) == SVGP_OK) gc.mux_bar = ctx->pm_g;
+    else if ((rc = ctx->pm_g.reserve(ctx, size_t(len) * m->es, "the prior mean offsets' gradient")) == SVGP_OK) gc.mux_bar = ctx->pm_g.p;
   }
   if (rc != SVGP_OK) return (ctx && gc.collective) ? grad_fail_collective(ctx, rc) : rc;
   if (gc.collective) {
@@ -2014,10 +1893,10 @@ int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
   rc = grad_collective(ctx, m, gc, rc);
   if (rc) return rc;
   if (gx && !gx->on_device)   // (never all-reduced: this rank's points; the stream synchronisation of grad_finish covers the copy)
-    HIPC(ctx, hipMemcpy2DAsync(gx->x, size_t(gx->ld) * m->es, gc.w->xg, size_t(len) * m->es, size_t(len) * m->es, size_t(m->d),
+    HIPC(ctx, hipMemcpy2DAsync(gx->x, size_t(gx->ld) * m->es, gc.w->xg.p, size_t(len) * m->es, size_t(len) * m->es, size_t(m->d),
                                hipMemcpyDeviceToHost, ctx->stream));
   if (gpm && !gpm->on_device)   // (never all-reduced either)
-    HIPC(ctx, hipMemcpyAsync(gpm->mu_bar, ctx->pm_g, size_t(len) * m->es, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(gpm->mu_bar, ctx->pm_g.p, size_t(len) * m->es, hipMemcpyDeviceToHost, ctx->stream));
   return grad_finish(ctx, m, gc, elbo_out, terms_out, g);
 }
 
@@ -2027,10 +1906,10 @@ int check_input_grad(svgp_ctx* ctx, const svgp_data* data, int64_t len, const sv
   if (gx->ld < len) return fail(ctx, SVGP_INVALID_ARG, "input-gradient leading dimension smaller than the batch");
   if ((gx->on_device != 0 && gx->on_device != 1) || gx->reserved != 0)
     return fail(ctx, SVGP_INVALID_ARG, "input-gradient on_device must be 0 or 1 and reserved 0");
-  if (gx->on_device && data && data->x && len >= 1 && data->d >= 1) {
+  if (gx->on_device && data && data->x.p && len >= 1 && data->d >= 1) {
     const size_t es = data->dtype == SVGP_F64 ? 8 : 4;
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(gx->x), a1 = a0 + (size_t(data->d - 1) * size_t(gx->ld) + size_t(len)) * es;
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(data->x), b1 = b0 + (size_t(data->d - 1) * size_t(data->ldx) + size_t(data->n)) * es;
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(data->x.p), b1 = b0 + (size_t(data->d - 1) * size_t(data->ldx) + size_t(data->n)) * es;
     if (a0 < b1 && b0 < a1) return fail(ctx, SVGP_INVALID_ARG, "input-gradient output overlaps the data's x");
   }
   return SVGP_OK;
@@ -2079,13 +1958,13 @@ int marginals_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
   rc = enqueue_prep(ctx, m);
   if (rc) return rc;
   TREC(ctx, ctx->ev[1], s);
-  rc = enqueue_strips(ctx, m, data->x, data->ldx, nullptr, off, len, so);
+  rc = enqueue_strips(ctx, m, data->x.p, data->ldx, nullptr, off, len, so);
   if (rc) return rc;
   PrepScalars ps;
-  HIPC(ctx, hipMemcpyAsync(mean_out, ctx->mom, size_t(len) * 8, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipMemcpyAsync(var_out, ctx->mom + ctx->mom_cap, size_t(len) * 8, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipMemcpyAsync(ps.scal, m->scal, sizeof(ps.scal), hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipMemcpyAsync(&ps.info, m->info, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(mean_out, ctx->mom_mu(), size_t(len) * 8, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(var_out, ctx->mom_var(), size_t(len) * 8, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(ps.scal, m->scal.as<double>(), sizeof(ps.scal), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(&ps.info, m->info.as<int>(), sizeof(int), hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   finish_prep(m, ps);
   float t01 = 0, t12 = 0;
@@ -2168,9 +2047,9 @@ int check_point_mean_grad(svgp_ctx* ctx, const svgp_data* data, int64_t len, con
       const uintptr_t b0 = reinterpret_cast<uintptr_t>(p), b1 = b0 + bytes;
       return p && a0 < b1 && b0 < a1;
     };
-    if (data->d >= 1 && hits(data->x, (size_t(data->d - 1) * size_t(data->ldx) + size_t(data->n)) * es))
+    if (data->d >= 1 && hits(data->x.p, (size_t(data->d - 1) * size_t(data->ldx) + size_t(data->n)) * es))
       return fail(ctx, SVGP_INVALID_ARG, "prior-mean gradient output overlaps the data's x");
-    if (hits(data->y, size_t(data->n) * es)) return fail(ctx, SVGP_INVALID_ARG, "prior-mean gradient output overlaps the data's y");
+    if (hits(data->y.p, size_t(data->n) * es)) return fail(ctx, SVGP_INVALID_ARG, "prior-mean gradient output overlaps the data's y");
     if (gx && gx->on_device && data->d >= 1 && hits(gx->x, (size_t(data->d - 1) * size_t(gx->ld) + size_t(len)) * es))
       return fail(ctx, SVGP_INVALID_ARG, "prior-mean gradient output overlaps the input-gradient output");
   }
@@ -2201,17 +2080,14 @@ extern "C" int32_t svgp_model_set_mean_z(svgp_ctx* ctx, svgp_model* m, const voi
   if (!m) return fail(ctx, SVGP_INVALID_ARG, "null model");
   HIPC(ctx, hipSetDevice(ctx->device));
   if (!mu_z) {
-    if (m->mu_z) {
+    if (m->mu_z.p) {
       HIPC(ctx, hipStreamSynchronize(ctx->stream));
-      (void)hipFree(m->mu_z);
-      m->mu_z = nullptr;
+      m->mu_z.release();
     }
   } else {
-    if (!m->mu_z && hipMalloc(&m->mu_z, size_t(m->M) * m->es) != hipSuccess) {
-      m->mu_z = nullptr;
-      return fail(ctx, SVGP_OOM, "hipMalloc failed for the inducing points' prior mean offsets");
-    }
-    HIPC(ctx, hipMemcpyAsync(m->mu_z, mu_z, size_t(m->M) * m->es, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = m->mu_z.reserve(ctx, size_t(m->M) * m->es, "the inducing points' prior mean offsets");
+    if (rc) return rc;
+    HIPC(ctx, hipMemcpyAsync(m->mu_z.p, mu_z, size_t(m->M) * m->es, hipMemcpyHostToDevice, ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));   // the host buffer may be released by the caller
   }
   m->prepared = false;

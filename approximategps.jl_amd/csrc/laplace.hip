@@ -395,32 +395,21 @@ struct svgp_laplace {
   int dtype = 0, d = 0;
   int64_t N = 0, Np = 0;
   size_t es = 8;
-  std::vector<void*> bufs;
-  void *K = nullptr, *B = nullptr, *T = nullptr, *LinvRM = nullptr, *LinvCM = nullptr, *Ytmp = nullptr;
-  void *xs = nullptr, *invl_t = nullptr, *f = nullptr, *fnew = nullptr, *g = nullptr, *W = nullptr, *sW = nullptr, *b = nullptr,
-       *d3 = nullptr, *a = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr;
-  double* part = nullptr;   // (Np / 128) x Np fp64 GEMV partials
-  double* res = nullptr;    // [16 + SVGP_MAX_D] step statistics / gradient slots (1 + d)
-  double* invl_d = nullptr; // [d] fp64 inverse lengthscales (gradient kernel)
-  double* llv = nullptr;    // [Np] log p(y_i | f_i) of the step
-  int* info = nullptr;      // chol info + the factorisation's hand-over counters
-  void *R = nullptr, *X = nullptr;   // gradient: R and K R (allocated on first use)
-  double* gpart = nullptr;  size_t gpart_bytes = 0;
-  hipEvent_t ev[5] = {};
+  DevBuf K, B, T, LinvRM, LinvCM, Ytmp;
+  DevBuf xs, invl_t, f, fnew, g, W, sW, b, d3, a, t1, t2, t3;
+  DevBuf part;     // (Np / 128) x Np fp64 GEMV partials
+  DevBuf res;      // [16 + SVGP_MAX_D] fp64 step statistics / gradient slots (1 + d)
+  DevBuf invl_d;   // [d] fp64 inverse lengthscales (gradient kernel)
+  DevBuf llv;      // [Np] fp64 log p(y_i | f_i) of the step
+  DevBuf info;     // (int) chol info + the factorisation's hand-over counters
+  DevBuf R, X;     // gradient: R and K R (allocated on first use)
+  DevBuf gpart;    // (fp64) the gradient's partial sums, grown on demand
+  Event ev[5];
   // the last fit: its parameters (predictions), whether a mode exists (warm start)
   bool have_mode = false;
   int family = 0, lik = 0;
   double variance = 1.0, jitter = 0.0, lik_sigma2 = 1.0;
   std::vector<double> invl;
-  ~svgp_laplace() {
-    for (void* p : bufs)
-      if (p) (void)hipFree(p);
-    if (R) (void)hipFree(R);
-    if (X) (void)hipFree(X);
-    if (gpart) (void)hipFree(gpart);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
 };
 
 namespace {
@@ -454,15 +443,15 @@ int lp_prepare(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* ds) {
   la->jitter = ds->jitter;
   la->lik_sigma2 = (ds->likelihood == SVGP_LIK_GAUSSIAN || ds->likelihood == SVGP_LIK_GAMMA_EXP) ? ds->lik_sigma2 : 1.0;
   la->invl.assign(ds->inv_lengthscale, ds->inv_lengthscale + la->d);
-  HIPC(ctx, hipMemcpyAsync(la->invl_d, la->invl.data(), size_t(la->d) * 8, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync(la->invl_d.as<double>(), la->invl.data(), size_t(la->d) * 8, hipMemcpyHostToDevice, s));
   const int64_t N = la->N, Np = la->Np;
   LP_DISPATCH(la->dtype, T, {
     std::vector<T> iv(la->invl.begin(), la->invl.end());
-    HIPC(ctx, hipMemcpyAsync(la->invl_t, iv.data(), size_t(la->d) * sizeof(T), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(lp_scale_kernel<T>, dim3(nblk(Np), (unsigned)la->d), dim3(256), 0, s, (const T*)la->data->x, la->data->ldx, N, Np,
-                       (const T*)la->invl_t, (T*)la->xs);
+    HIPC(ctx, hipMemcpyAsync(la->invl_t.p, iv.data(), size_t(la->d) * sizeof(T), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(lp_scale_kernel<T>, dim3(nblk(Np), (unsigned)la->d), dim3(256), 0, s, (const T*)la->data->x.p, la->data->ldx, N, Np,
+                       (const T*)la->invl_t.p, (T*)la->xs.p);
     hipLaunchKernelGGL(lp_kcross_kernel<T>, dim3(nblk(Np), (unsigned)Np), dim3(256), 0, s, la->family, la->d, T(la->variance),
-                       (const T*)la->xs, Np, N, Np, (const T*)la->xs, Np, N, T(la->jitter), 1, (T*)la->K, Np);
+                       (const T*)la->xs.p, Np, N, Np, (const T*)la->xs.p, Np, N, T(la->jitter), 1, (T*)la->K.p, Np);
     HIPC(ctx, hipStreamSynchronize(s));   // iv leaves scope
   });
   KCHECK(ctx, "lp_prepare");
@@ -477,42 +466,42 @@ int lp_step(svgp_ctx* ctx, svgp_laplace* la, double st[7], double ms[4]) {
   const bool timed = ctx->timing_on;
   if (timed) HIPC(ctx, hipEventRecord(la->ev[0], s));
   LP_DISPATCH(la->dtype, T, {
-    hipLaunchKernelGGL(lp_point_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->lik, la->lik_sigma2, (const T*)la->f, (const T*)la->data->y,
-                       N, Np, (T*)la->g, (T*)la->W, (T*)la->sW, (T*)la->b, (T*)la->d3);
-    hipLaunchKernelGGL(lp_assemble_b_kernel<T>, dim3(nblk(Np), (unsigned)Np), dim3(256), 0, s, (const T*)la->K, (const T*)la->sW, Np, (T*)la->B);
+    hipLaunchKernelGGL(lp_point_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->lik, la->lik_sigma2, (const T*)la->f.p, (const T*)la->data->y.p,
+                       N, Np, (T*)la->g.p, (T*)la->W.p, (T*)la->sW.p, (T*)la->b.p, (T*)la->d3.p);
+    hipLaunchKernelGGL(lp_assemble_b_kernel<T>, dim3(nblk(Np), (unsigned)Np), dim3(256), 0, s, (const T*)la->K.p, (const T*)la->sW.p, Np, (T*)la->B.p);
   });
   KCHECK(ctx, "lp_point / lp_assemble_b");
   if (timed) HIPC(ctx, hipEventRecord(la->ev[1], s));
-  HIPC(ctx, hipMemsetAsync(la->info, 0, lp_info_bytes(Np), s));
-  launch_potrf(la->dtype, s, la->B, la->T, Np, la->info, reinterpret_cast<unsigned*>(la->info + 1), ctx->num_cus);
+  HIPC(ctx, hipMemsetAsync(la->info.as<int>(), 0, lp_info_bytes(Np), s));
+  launch_potrf(la->dtype, s, la->B.p, la->T.p, Np, la->info.as<int>(), reinterpret_cast<unsigned*>(la->info.as<int>() + 1), ctx->num_cus);
   KCHECK(ctx, "potrf");
   if (timed) HIPC(ctx, hipEventRecord(la->ev[2], s));
-  launch_linv(la->dtype, s, la->B, la->T, Np, la->LinvRM, la->LinvCM, la->Ytmp);
+  launch_linv(la->dtype, s, la->B.p, la->T.p, Np, la->LinvRM.p, la->LinvCM.p, la->Ytmp.p);
   KCHECK(ctx, "linv");
   if (timed) HIPC(ctx, hipEventRecord(la->ev[3], s));
   LP_DISPATCH(la->dtype, T, {
     // t1 = sW (K b)
-    hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->K, (const T*)la->b, Np, la->part);
-    hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part, npan, Np, 1, (const T*)la->sW, (const T*)nullptr, (T*)la->t1);
+    hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->K.p, (const T*)la->b.p, Np, la->part.as<double>());
+    hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part.as<double>(), npan, Np, 1, (const T*)la->sW.p, (const T*)nullptr, (T*)la->t1.p);
     // t2 = L^-1 t1, t3 = L^-T t2 (= B \ t1)
-    launch_linv_t_gemv(la->dtype, s, la->LinvCM, la->t1, Np, la->t2, la->part, 1);
-    launch_linv_t_gemv(la->dtype, s, la->LinvRM, la->t2, Np, la->t3, la->part, 0);
+    launch_linv_t_gemv(la->dtype, s, la->LinvCM.p, la->t1.p, Np, la->t2.p, la->part.as<double>(), 1);
+    launch_linv_t_gemv(la->dtype, s, la->LinvRM.p, la->t2.p, Np, la->t3.p, la->part.as<double>(), 0);
     // a = b - sW t3
-    hipLaunchKernelGGL(lp_sub_scaled_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, (const T*)la->b, (const T*)la->sW, (const T*)la->t3, Np, (T*)la->a);
+    hipLaunchKernelGGL(lp_sub_scaled_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, (const T*)la->b.p, (const T*)la->sW.p, (const T*)la->t3.p, Np, (T*)la->a.p);
     // fnew = K a
-    hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->K, (const T*)la->a, Np, la->part);
-    hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part, npan, Np, 0, (const T*)nullptr, (const T*)nullptr, (T*)la->fnew);
+    hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->K.p, (const T*)la->a.p, Np, la->part.as<double>());
+    hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part.as<double>(), npan, Np, 0, (const T*)nullptr, (const T*)nullptr, (T*)la->fnew.p);
   });
   KCHECK(ctx, "solves");
   if (timed) HIPC(ctx, hipEventRecord(la->ev[4], s));
   LP_DISPATCH(la->dtype, T, {
-    hipLaunchKernelGGL(lp_ll_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, la->lik, la->lik_sigma2, (const T*)la->f, (const T*)la->data->y, N,
-                       la->llv);
-    hipLaunchKernelGGL(lp_stats_kernel<T>, dim3(1), dim3(k256), 0, s, (const T*)la->f, (const T*)la->fnew, (const T*)la->a,
-                       (const double*)la->llv, (const T*)la->B, N, Np, (const int*)la->info, la->res);
+    hipLaunchKernelGGL(lp_ll_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, la->lik, la->lik_sigma2, (const T*)la->f.p, (const T*)la->data->y.p, N,
+                       la->llv.as<double>());
+    hipLaunchKernelGGL(lp_stats_kernel<T>, dim3(1), dim3(k256), 0, s, (const T*)la->f.p, (const T*)la->fnew.p, (const T*)la->a.p,
+                       (const double*)la->llv.as<double>(), (const T*)la->B.p, N, Np, (const int*)la->info.as<int>(), la->res.as<double>());
   });
   KCHECK(ctx, "lp_stats");
-  HIPC(ctx, hipMemcpyAsync(st, la->res, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(st, la->res.as<double>(), 7 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   if (timed) {
     float e[4] = {0, 0, 0, 0};
@@ -542,8 +531,8 @@ int lp_fit(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* ds, const v
   rc = lp_prepare(ctx, la, ds);
   if (rc) return rc;
   if (!warm) {
-    HIPC(ctx, hipMemsetAsync(la->f, 0, vb, s));
-    if (f_init) HIPC(ctx, hipMemcpyAsync(la->f, f_init, size_t(la->N) * la->es, hipMemcpyHostToDevice, s));
+    HIPC(ctx, hipMemsetAsync(la->f.p, 0, vb, s));
+    if (f_init) HIPC(ctx, hipMemcpyAsync(la->f.p, f_init, size_t(la->N) * la->es, hipMemcpyHostToDevice, s));
   }
   const double rtol = std::sqrt(la->dtype == SVGP_F64 ? 2.220446049250313e-16 : 1.1920928955078125e-07);   // isapprox: sqrt(eps(T))
   double st[7] = {}, ms[4] = {0, 0, 0, 0};
@@ -556,7 +545,7 @@ int lp_fit(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* ds, const v
       converged = 1;
       break;
     }
-    std::swap(la->f, la->fnew);
+    std::swap(la->f.p, la->fnew.p);   // (equal sizes: the two buffers trade places)
   }
   if (st[6] == 0.0 && !converged) {   // f = the last fnew: its intermediates
     it = ds->maxiter;
@@ -583,20 +572,13 @@ int lp_fit(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* ds, const v
   return SVGP_OK;
 }
 
-void* lp_alloc(svgp_laplace* la, size_t bytes, hipError_t& e) {
-  void* p = nullptr;
-  if (e == hipSuccess) e = hipMalloc(&p, bytes);
-  if (e == hipSuccess) la->bufs.push_back(p);
-  return p;
-}
-
 }  // namespace
 
 extern "C" {
 
 int32_t svgp_laplace_create(svgp_ctx* ctx, const svgp_data* data, svgp_laplace** out) {
   if (!ctx || !data || !out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
-  if (!data->y) return fail(ctx, SVGP_INVALID_ARG, "the Laplace approximation needs y");
+  if (!data->y.p) return fail(ctx, SVGP_INVALID_ARG, "the Laplace approximation needs y");
   if (data->n < 1) return fail(ctx, SVGP_INVALID_ARG, "empty data");
   if (data->n > lp_max_n(data->dtype)) return fail(ctx, SVGP_UNSUPPORTED, "N beyond the tested size of the device Cholesky");
   auto* la = new (std::nothrow) svgp_laplace();
@@ -609,28 +591,22 @@ int32_t svgp_laplace_create(svgp_ctx* ctx, const svgp_data* data, svgp_laplace**
   la->es = data->dtype == SVGP_F64 ? 8 : 4;
   const size_t mb = size_t(la->Np) * la->Np * la->es, vb = size_t(la->Np) * la->es;
   hipError_t e = hipSuccess;
-  la->K = lp_alloc(la, mb, e);
-  la->B = lp_alloc(la, mb, e);
-  la->T = lp_alloc(la, mb, e);
-  la->LinvRM = lp_alloc(la, mb, e);
-  la->LinvCM = lp_alloc(la, mb, e);
-  la->Ytmp = lp_alloc(la, mb, e);
-  la->xs = lp_alloc(la, vb * la->d, e);
-  la->invl_t = lp_alloc(la, size_t(la->d) * la->es, e);
-  void** vecs[] = {&la->f, &la->fnew, &la->g, &la->W, &la->sW, &la->b, &la->d3, &la->a, &la->t1, &la->t2, &la->t3};
-  for (void** v : vecs) *v = lp_alloc(la, vb, e);
-  la->part = (double*)lp_alloc(la, size_t(la->Np / kNB) * la->Np * 8, e);
-  la->res = (double*)lp_alloc(la, (16 + SVGP_MAX_D) * 8, e);
-  la->invl_d = (double*)lp_alloc(la, size_t(la->d) * 8, e);
-  la->llv = (double*)lp_alloc(la, size_t(la->Np) * 8, e);
-  la->info = (int*)lp_alloc(la, lp_info_bytes(la->Np), e);
-  for (hipEvent_t& ev : la->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
+  struct { DevBuf* b; size_t bytes; } req[] = {
+      {&la->K, mb}, {&la->B, mb}, {&la->T, mb}, {&la->LinvRM, mb}, {&la->LinvCM, mb}, {&la->Ytmp, mb},
+      {&la->xs, vb * la->d}, {&la->invl_t, size_t(la->d) * la->es},
+      {&la->f, vb}, {&la->fnew, vb}, {&la->g, vb}, {&la->W, vb}, {&la->sW, vb}, {&la->b, vb}, {&la->d3, vb}, {&la->a, vb},
+      {&la->t1, vb}, {&la->t2, vb}, {&la->t3, vb},
+      {&la->part, size_t(la->Np / kNB) * la->Np * 8}, {&la->res, (16 + SVGP_MAX_D) * 8}, {&la->invl_d, size_t(la->d) * 8},
+      {&la->llv, size_t(la->Np) * 8}, {&la->info, lp_info_bytes(la->Np)}};
+  for (auto& r : req)
+    if (e == hipSuccess) e = r.b->alloc(r.bytes);
+  for (Event& ev : la->ev)
+    if (e == hipSuccess) e = ev.create(hipEventDefault);
   // T above the diagonal and L^-1 above its block diagonal are never written and must read as zero
-  if (e == hipSuccess) e = hipMemsetAsync(la->T, 0, mb, ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(la->LinvRM, 0, mb, ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(la->LinvCM, 0, mb, ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(la->B, 0, mb, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(la->T.p, 0, mb, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(la->LinvRM.p, 0, mb, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(la->LinvCM.p, 0, mb, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(la->B.p, 0, mb, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) {
     delete la;
@@ -669,43 +645,39 @@ int32_t svgp_laplace_lml_grad(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplac
   const int64_t N = la->N, Np = la->Np;
   const int npan = int(Np / kNB), d = la->d;
   const size_t mb = size_t(Np) * Np * la->es;
-  if (!la->R) HIPC(ctx, hipMalloc(&la->R, mb));
-  if (!la->X) HIPC(ctx, hipMalloc(&la->X, mb));
+  rc = la->R.reserve(ctx, mb, "the Laplace gradient's R");
+  if (rc == SVGP_OK) rc = la->X.reserve(ctx, mb, "the Laplace gradient's K R");
+  if (rc) return rc;
   const int nt = int(Np / 64), nfc = (d + kLpFc - 1) / kLpFc;
   const int64_t nchunk = 16, chunk = (Np + nchunk - 1) / nchunk;
   const size_t gb = std::max(size_t(nt) * nt * nfc * (1 + kLpFc), size_t(nchunk) * Np) * 8;
-  if (la->gpart_bytes < gb) {
-    if (la->gpart) (void)hipFree(la->gpart);
-    la->gpart = nullptr;
-    la->gpart_bytes = 0;
-    HIPC(ctx, hipMalloc(&la->gpart, gb));
-    la->gpart_bytes = gb;
-  }
+  rc = la->gpart.reserve(ctx, gb, "the Laplace gradient's partial sums");
+  if (rc) return rc;
   // R = sW (L^-T L^-1) sW: sum_j Linv[j][r] Linv[j][c] on the MFMA product kernel; X = K R (column-major)
   // Linv[j][r] = 0 for j < r: the contraction of tile (r, c) starts at the later of the two diagonal tiles (kMmXLow | kMmYLow)
-  launch_gemm_pm(la->dtype, s, la->LinvRM, la->LinvRM, nullptr, 1.0, Np, Np, Np, 1, la->R, 1, kMmFull | kMmXLow | kMmYLow);
+  launch_gemm_pm(la->dtype, s, la->LinvRM.p, la->LinvRM.p, nullptr, 1.0, Np, Np, Np, 1, la->R.p, 1, kMmFull | kMmXLow | kMmYLow);
   KCHECK(ctx, "gemm_pm (R)");
   LP_DISPATCH(la->dtype, T, {
-    hipLaunchKernelGGL(lp_scale_r_kernel<T>, dim3(nblk(Np), (unsigned)Np), dim3(256), 0, s, (T*)la->R, (const T*)la->sW, Np);
+    hipLaunchKernelGGL(lp_scale_r_kernel<T>, dim3(nblk(Np), (unsigned)Np), dim3(256), 0, s, (T*)la->R.p, (const T*)la->sW.p, Np);
   });
-  launch_gemm_pm(la->dtype, s, la->R, la->K, nullptr, 1.0, Np, Np, Np, 1, la->X, 1, kMmFull);
+  launch_gemm_pm(la->dtype, s, la->R.p, la->K.p, nullptr, 1.0, Np, Np, Np, 1, la->X.p, 1, kMmFull);
   KCHECK(ctx, "gemm_pm (K R)");
   LP_DISPATCH(la->dtype, T, {
-    hipLaunchKernelGGL(lp_diag_krk_kernel<T>, dim3(nblk(Np), (unsigned)nchunk), dim3(256), 0, s, (const T*)la->X, (const T*)la->K, Np, chunk, la->gpart);
-    hipLaunchKernelGGL(lp_s2_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->gpart, int(nchunk), (const T*)la->K, (const T*)la->d3, N, Np, (T*)la->t1);
+    hipLaunchKernelGGL(lp_diag_krk_kernel<T>, dim3(nblk(Np), (unsigned)nchunk), dim3(256), 0, s, (const T*)la->X.p, (const T*)la->K.p, Np, chunk, la->gpart.as<double>());
+    hipLaunchKernelGGL(lp_s2_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->gpart.as<double>(), int(nchunk), (const T*)la->K.p, (const T*)la->d3.p, N, Np, (T*)la->t1.p);
     // u = s2 - R (K s2)   (t1 = s2, t2 = K s2, t3 = u)
-    hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->K, (const T*)la->t1, Np, la->part);
-    hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part, npan, Np, 0, (const T*)nullptr, (const T*)nullptr, (T*)la->t2);
-    hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->R, (const T*)la->t2, Np, la->part);
-    hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part, npan, Np, 3, (const T*)nullptr, (const T*)la->t1, (T*)la->t3);
+    hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->K.p, (const T*)la->t1.p, Np, la->part.as<double>());
+    hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part.as<double>(), npan, Np, 0, (const T*)nullptr, (const T*)nullptr, (T*)la->t2.p);
+    hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->R.p, (const T*)la->t2.p, Np, la->part.as<double>());
+    hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part.as<double>(), npan, Np, 3, (const T*)nullptr, (const T*)la->t1.p, (T*)la->t3.p);
     hipLaunchKernelGGL(lp_kgrad_kernel<T>, dim3((unsigned)nt, (unsigned)nt, (unsigned)nfc), dim3(k256), 0, s, la->family, d, la->variance,
-                       (const double*)la->invl_d, (const T*)la->data->x, la->data->ldx, N, Np, (const T*)la->R, (const T*)la->a,
-                       (const T*)la->g, (const T*)la->t3, la->gpart);
+                       (const double*)la->invl_d.as<double>(), (const T*)la->data->x.p, la->data->ldx, N, Np, (const T*)la->R.p, (const T*)la->a.p,
+                       (const T*)la->g.p, (const T*)la->t3.p, la->gpart.as<double>());
   });
-  hipLaunchKernelGGL(lp_kgrad_finish_kernel, dim3((unsigned)(1 + d)), dim3(k256), 0, s, la->gpart, int64_t(nt) * nt, nfc, d, la->res);
+  hipLaunchKernelGGL(lp_kgrad_finish_kernel, dim3((unsigned)(1 + d)), dim3(k256), 0, s, la->gpart.as<double>(), int64_t(nt) * nt, nfc, d, la->res.as<double>());
   KCHECK(ctx, "laplace gradient");
   double out[1 + SVGP_MAX_D];
-  HIPC(ctx, hipMemcpyAsync(out, la->res, size_t(1 + d) * 8, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(out, la->res.as<double>(), size_t(1 + d) * 8, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   *d_variance = out[0];
   for (int f = 0; f < d; ++f) d_inv_lengthscale[f] = out[1 + f];
@@ -717,9 +689,9 @@ int32_t svgp_laplace_mode(svgp_ctx* ctx, svgp_laplace* la, void* f_out, void* dl
   if (!la->have_mode) return fail(ctx, SVGP_INVALID_ARG, "no successful svgp_laplace_fit on this handle yet");
   const size_t b = size_t(la->N) * la->es;
   hipStream_t s = ctx->stream;
-  if (f_out) HIPC(ctx, hipMemcpyAsync(f_out, la->f, b, hipMemcpyDeviceToHost, s));
-  if (dll_out) HIPC(ctx, hipMemcpyAsync(dll_out, la->g, b, hipMemcpyDeviceToHost, s));
-  if (W_out) HIPC(ctx, hipMemcpyAsync(W_out, la->W, b, hipMemcpyDeviceToHost, s));
+  if (f_out) HIPC(ctx, hipMemcpyAsync(f_out, la->f.p, b, hipMemcpyDeviceToHost, s));
+  if (dll_out) HIPC(ctx, hipMemcpyAsync(dll_out, la->g.p, b, hipMemcpyDeviceToHost, s));
+  if (W_out) HIPC(ctx, hipMemcpyAsync(W_out, la->W.p, b, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   return SVGP_OK;
 }
@@ -739,16 +711,16 @@ int lp_pred_v(svgp_ctx* ctx, svgp_laplace* la, const svgp_data* P, void* mean, D
   HIPC(ctx, V.alloc(size_t(Np) * n * la->es));
   if (mean) HIPC(ctx, mdev.alloc(size_t(n) * la->es));
   LP_DISPATCH(la->dtype, T, {
-    hipLaunchKernelGGL(lp_scale_kernel<T>, dim3(nblk(n), (unsigned)la->d), dim3(256), 0, s, (const T*)P->x, P->ldx, n, n,
-                       (const T*)la->invl_t, (T*)xs_out.p);
+    hipLaunchKernelGGL(lp_scale_kernel<T>, dim3(nblk(n), (unsigned)la->d), dim3(256), 0, s, (const T*)P->x.p, P->ldx, n, n,
+                       (const T*)la->invl_t.p, (T*)xs_out.p);
     hipLaunchKernelGGL(lp_kcross_kernel<T>, dim3(nblk(Np), (unsigned)n), dim3(256), 0, s, la->family, la->d, T(la->variance),
-                       (const T*)la->xs, Np, N, Np, (const T*)xs_out.p, n, n, T(0), 0, (T*)Kx.p, Np);
+                       (const T*)la->xs.p, Np, N, Np, (const T*)xs_out.p, n, n, T(0), 0, (T*)Kx.p, Np);
     if (mean)
-      hipLaunchKernelGGL(lp_colreduce_kernel<T>, dim3((unsigned)n), dim3(k256), 0, s, (const T*)Kx.p, Np, Np, (const T*)la->g, 0, 0.0, (T*)mdev.p);
-    hipLaunchKernelGGL(lp_rowscale_kernel<T>, dim3(nblk(Np), (unsigned)n), dim3(256), 0, s, (T*)Kx.p, Np, Np, (const T*)la->sW);
+      hipLaunchKernelGGL(lp_colreduce_kernel<T>, dim3((unsigned)n), dim3(k256), 0, s, (const T*)Kx.p, Np, Np, (const T*)la->g.p, 0, 0.0, (T*)mdev.p);
+    hipLaunchKernelGGL(lp_rowscale_kernel<T>, dim3(nblk(Np), (unsigned)n), dim3(256), 0, s, (T*)Kx.p, Np, Np, (const T*)la->sW.p);
     // V(i, j) = sum_k Linv(i, k) S(k, j): LinvCM column-major
     hipLaunchKernelGGL(lp_gemm_kernel<T>, dim3(unsigned((Np + 63) / 64), unsigned((n + 63) / 64)), dim3(k256), 0, s, Np, n, Np,
-                       (const T*)la->LinvCM, int64_t(1), Np, (const T*)Kx.p, int64_t(1), Np, (T*)V.p, Np, 0);
+                       (const T*)la->LinvCM.p, int64_t(1), Np, (const T*)Kx.p, int64_t(1), Np, (T*)V.p, Np, 0);
   });
   KCHECK(ctx, "laplace predict");
   if (mean) HIPC(ctx, hipMemcpyAsync(mean, mdev.p, size_t(n) * la->es, hipMemcpyDeviceToHost, s));
