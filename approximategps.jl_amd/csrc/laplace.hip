@@ -10,6 +10,7 @@
 //   L = chol(B)         the blocked MFMA factorisation of the SVGP path, in place        launch_potrf
 //   L^-1                recursive doubling from its inverted diagonal blocks              launch_linv
 //   a = b - sW L^-T L^-1 (sW K b),  fnew = K a                                           lp_gemv_kernel, launch_linv_t_gemv
+//   fp32: a += r - sW L^-T L^-1 (sW K r), r = b - a - W K a (one refinement step)        lp_resid_kernel, lp_refine_kernel
 //   isapprox(f, fnew), -a'f / 2, sum ll, sum log diag L: one workgroup, one read-back    lp_stats_kernel
 // The solves are GEMVs with the explicit inverse: every one of them runs across the chip (the one-workgroup trsv_kernel of the
 // SVGP posterior streams the triangle through one CU).  The gradient reuses that inverse:
@@ -145,6 +146,23 @@ template <typename T>
 __global__ void lp_sub_scaled_kernel(const T* __restrict__ b, const T* __restrict__ sc, const T* __restrict__ v, int64_t np, T* __restrict__ out) {
   const int64_t r = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (r < np) out[r] = T(double(b[r]) - double(sc[r]) * double(v[r]));
+}
+
+// The fp32 refinement of a (lp_step): r = b - a - W (K a), K a from the fp64 panel partials
+template <typename T>
+__global__ void lp_resid_kernel(const double* __restrict__ part, int npan, int64_t np, const T* __restrict__ b, const T* __restrict__ a,
+                                const T* __restrict__ W, T* __restrict__ r) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  double s = 0.0;
+  for (int q = 0; q < npan; ++q) s += part[int64_t(q) * np + i];
+  r[i] = T((double(b[i]) - double(a[i])) - double(W[i]) * s);
+}
+// a[i] += r[i] - sc[i] v[i]
+template <typename T>
+__global__ void lp_refine_kernel(T* __restrict__ a, const T* __restrict__ r, const T* __restrict__ sc, const T* __restrict__ v, int64_t np) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < np) a[i] = T(double(a[i]) + (double(r[i]) - double(sc[i]) * double(v[i])));
 }
 
 // ll[i] = log p(y_i | f_i) (its own launch: the lgamma / erfcx bodies stay out of the reduction's registers)
@@ -488,6 +506,18 @@ int lp_step(svgp_ctx* ctx, svgp_laplace* la, double st[7], double ms[4]) {
     launch_linv_t_gemv(la->dtype, s, la->LinvRM.p, la->t2.p, Np, la->t3.p, la->part.as<double>(), 0);
     // a = b - sW t3
     hipLaunchKernelGGL(lp_sub_scaled_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, (const T*)la->b.p, (const T*)la->sW.p, (const T*)la->t3.p, Np, (T*)la->a.p);
+    // fp32: one refinement step of a against (I + W K) a = b, the system the solve above answers.  The fp32 factor of B leaves
+    // a few 1e-6 of error in a, smooth enough in x to survive K a and then add up in the predictive mean k*' g (a cancelling sum
+    // of g); the residual comes from the fp64 GEMV partials, the correction from the same L^-1 (r lives in fnew until then).
+    if (la->dtype != SVGP_F64) {
+      hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->K.p, (const T*)la->a.p, Np, la->part.as<double>());
+      hipLaunchKernelGGL(lp_resid_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part.as<double>(), npan, Np, (const T*)la->b.p, (const T*)la->a.p, (const T*)la->W.p, (T*)la->fnew.p);
+      hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->K.p, (const T*)la->fnew.p, Np, la->part.as<double>());
+      hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part.as<double>(), npan, Np, 1, (const T*)la->sW.p, (const T*)nullptr, (T*)la->t1.p);
+      launch_linv_t_gemv(la->dtype, s, la->LinvCM.p, la->t1.p, Np, la->t2.p, la->part.as<double>(), 1);
+      launch_linv_t_gemv(la->dtype, s, la->LinvRM.p, la->t2.p, Np, la->t3.p, la->part.as<double>(), 0);
+      hipLaunchKernelGGL(lp_refine_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, (T*)la->a.p, (const T*)la->fnew.p, (const T*)la->sW.p, (const T*)la->t3.p, Np);
+    }
     // fnew = K a
     hipLaunchKernelGGL(lp_gemv_kernel<T>, dim3(unsigned(Np / 64), unsigned(npan)), dim3(k256), 0, s, (const T*)la->K.p, (const T*)la->a.p, Np, la->part.as<double>());
     hipLaunchKernelGGL(lp_gemv_finish_kernel<T>, dim3(nblk(Np)), dim3(256), 0, s, la->part.as<double>(), npan, Np, 0, (const T*)nullptr, (const T*)nullptr, (T*)la->fnew.p);
@@ -521,13 +551,15 @@ int lp_fail_null(svgp_ctx* ctx) { return fail(ctx, SVGP_INVALID_ARG, "null argum
 // (g, W, sW, a, L, L^-1, d3) belong to la->f = f_opt: when the loop converges it keeps f, whose step computed them; after maxiter
 // steps f is the last fnew and one more step recomputes them there (the reference's laplace_lml does the same).
 int lp_fit(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* ds, const void* f_init, double* lml_out, svgp_laplace_info* info) {
+  // a call that returns an error, a rejected argument included, leaves the handle without a mode: the next warm start is cold
+  const bool had_mode = la->have_mode;
+  la->have_mode = false;
   int rc = check_desc(ctx, la, ds);
   if (rc) return rc;
   if (!lml_out) return lp_fail_null(ctx);
   hipStream_t s = ctx->stream;
   const size_t vb = size_t(la->Np) * la->es;
-  const bool warm = ds->warm_start == 1 && la->have_mode && !f_init;
-  la->have_mode = false;
+  const bool warm = ds->warm_start == 1 && had_mode && !f_init;
   rc = lp_prepare(ctx, la, ds);
   if (rc) return rc;
   if (!warm) {
@@ -633,6 +665,7 @@ int32_t svgp_laplace_lml_grad(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplac
                               svgp_laplace_info* info, double* d_variance, double* d_inv_lengthscale) {
   if (!ctx || !la) return fail(ctx, SVGP_INVALID_ARG, "null argument");
   if (!d_variance || !d_inv_lengthscale) {
+    la->have_mode = false;
     if (desc) {
       const int rc = check_desc(ctx, la, desc);
       if (rc) return rc;

@@ -407,7 +407,8 @@ double svgp_offload_work(int64_t n_points, int64_t M, int32_t d);
  * The prior mean is zero (_check_laplace_inputs :167-178 asserts it); one latent function per observation.
  *   svgp_laplace_fit       Newton from f_init (NULL: zeros, the reference's mean(fx); else N host values in the data's dtype), or
  *                          with warm_start = 1 and f_init = NULL from the mode of the previous successful fit on the handle (the warm
- *                          start of build_laplace_objective :95-132).  Convergence is isapprox(f, fnew) in the compute dtype,
+ *                          start of build_laplace_objective :95-132; a call that returned an error, a rejected argument included,
+ *                          leaves the handle without a mode: the next call starts cold, mode / predict return SVGP_INVALID_ARG).  Convergence is isapprox(f, fnew) in the compute dtype,
  *                          |f - fnew| <= sqrt(eps) max(|f|, |fnew|); the loop then KEEPS f, otherwise f = fnew, after maxiter steps f
  *                          is the last fnew.  lml_out = -a'f / 2 + sum log p(y|f) - sum log diag L at that f (laplace_lml :157-165,
  *                          _laplace_lml :250-254).  The handle caches the intermediates at f for the predictions.

@@ -82,15 +82,48 @@ def fit(kernel, x, y, lik, s2=1.0, jitter=0.0, f_init=None, maxiter=100, eps=np.
     return lml, c, it, converged
 
 
-def lml_grad(kernel, x, y, lik, s2=1.0, jitter=0.0, f_init=None, maxiter=100):
-    """-> (lml, d lml / d variance, d lml / d inv_lengthscale (d,))"""
-    lml, c, _, _ = fit(kernel, x, y, lik, s2, jitter, f_init, maxiter)
-    K, sW, L, g, a, d3 = c["K"], c["sW"], c["L"], c["g"], c["a"], c["d3"]
+def round32(a):
+    """every entry rounded once to float32 (the least an fp32 evaluation does to a stored operand), float64 afterwards"""
+    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+def fit_one_rounding(kernel, x, y, lik, s2=1.0, jitter=0.0, maxiter=100):
+    """-> (cache, iterations): the forward-error model of an fp32 Newton loop from zero - fit() in float64 arithmetic, with an
+    exact solve, but K and every vector a step stores (g, W, sW, b, a, fnew) rounded once to float32, and float32's stop rule.
+    Its cache feeds predict(..., one_rounding=True): the one-rounding model of a prediction from the mode up."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    K = round32(o.kernelmatrix(kernel, x).astype(np.float64) + jitter * np.eye(y.size))
+    f, rtol = np.zeros(y.size), np.sqrt(np.finfo(np.float32).eps)
+
+    def step(f):
+        _, g, W, _ = _terms(lik, f, y, s2)
+        g, W = round32(g), round32(W)
+        sW = round32(np.sqrt(np.maximum(W, 0.0)))
+        L = np.linalg.cholesky(np.eye(K.shape[0]) + (sW[:, None] * K) * sW[None, :])
+        b = round32(W * f + g)
+        return dict(g=g, W=W, sW=sW, L=L, a=round32(b - sW * cho_solve((L, True), sW * (K @ b))), f=f, K=K)
+
+    for it in range(1, maxiter + 1):
+        c = step(f)
+        fnew = round32(K @ c["a"])
+        if np.linalg.norm(f - fnew) <= rtol * max(np.linalg.norm(f), np.linalg.norm(fnew)):
+            return c, it
+        f = fnew
+    return step(f), maxiter
+
+
+def lml_grad(kernel, x, y, lik, s2=1.0, jitter=0.0, f_init=None, maxiter=100, eps=np.finfo(np.float64).eps, one_rounding=False):
+    """-> (lml, d lml / d variance, d lml / d inv_lengthscale (d,)).  one_rounding: the forward-error model of an fp32 evaluation
+    (as tests/f32_grad_accuracy.py's for the SVGP gradient) - the same closed form in float64 arithmetic with K, R and every vector
+    the reduction reads (a, g, s2, u) rounded once to float32; pass eps of float32 with it for the format's Newton stop."""
+    lml, c, _, _ = fit(kernel, x, y, lik, s2, jitter, f_init, maxiter, eps)
+    rnd = round32 if one_rounding else (lambda v: v)
+    K, sW, L, g, a, d3 = rnd(c["K"]), rnd(c["sW"]), c["L"], rnd(c["g"]), rnd(c["a"]), rnd(c["d3"])
     Linv = solve_triangular(L, np.eye(L.shape[0]), lower=True)
-    R = sW[:, None] * (Linv.T @ Linv) * sW[None, :]
+    R = rnd(sW[:, None] * (Linv.T @ Linv) * sW[None, :])
     sigma = np.diag(K) - np.einsum("ij,ji->i", K @ R, K)
-    s2v = 0.5 * sigma * d3
-    u = s2v - R @ (K @ s2v)
+    s2v = rnd(0.5 * sigma * d3)
+    u = rnd(s2v - R @ (K @ s2v))
     P = 0.5 * np.outer(a, a) - 0.5 * R + 0.5 * (np.outer(u, g) + np.outer(g, u))
     xd = o._as_dn(np.asarray(x, dtype=np.float64))
     il = np.asarray(kernel.inv_lengthscale, dtype=np.float64)
@@ -110,18 +143,23 @@ def lml_grad(kernel, x, y, lik, s2=1.0, jitter=0.0, f_init=None, maxiter=100):
     return lml, dvar, dil
 
 
-def predict(cache, kernel, x, xs, ys=None):
-    """-> (mean, var, cov) at xs (cov(xs, ys) when ys is given): RW 3.21 / 3.29"""
-    kx = o.kernelmatrix(kernel, np.asarray(x, dtype=np.float64), np.asarray(xs, dtype=np.float64)).astype(np.float64)
-    mean = kx.T @ cache["g"]
-    v = solve_triangular(cache["L"], cache["sW"][:, None] * kx, lower=True)
+def predict(cache, kernel, x, xs, ys=None, one_rounding=False):
+    """-> (mean, var, cov) at xs (cov(xs, ys) when ys is given): RW 3.21 / 3.29.  Inputs of any float type (float32-rounded
+    x / xs for an fp32 device handle) are taken as they are, in float64 arithmetic.  one_rounding: the forward-error model of an
+    fp32 evaluation - every stored operand (k(x, x*), g, sW, L^-1 sW k(x, x*), k(x*, x*)) rounded once to float32."""
+    rnd = round32 if one_rounding else (lambda a: a)
+    x = np.asarray(x, dtype=np.float64)
+    kx = rnd(o.kernelmatrix(kernel, x, np.asarray(xs, dtype=np.float64)).astype(np.float64))
+    mean = kx.T @ rnd(cache["g"])
+    sW = rnd(cache["sW"])
+    v = rnd(solve_triangular(cache["L"], sW[:, None] * kx, lower=True))
     var = kernel.variance - np.sum(v * v, axis=0)
     if ys is None:
-        cov = o.kernelmatrix(kernel, np.asarray(xs, dtype=np.float64)).astype(np.float64) - v.T @ v
+        cov = rnd(o.kernelmatrix(kernel, np.asarray(xs, dtype=np.float64)).astype(np.float64)) - v.T @ v
     else:
-        ky = o.kernelmatrix(kernel, np.asarray(x, dtype=np.float64), np.asarray(ys, dtype=np.float64)).astype(np.float64)
-        vy = solve_triangular(cache["L"], cache["sW"][:, None] * ky, lower=True)
-        cov = o.kernelmatrix(kernel, np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64)).astype(np.float64) - v.T @ vy
+        ky = rnd(o.kernelmatrix(kernel, x, np.asarray(ys, dtype=np.float64)).astype(np.float64))
+        vy = rnd(solve_triangular(cache["L"], sW[:, None] * ky, lower=True))
+        cov = rnd(o.kernelmatrix(kernel, np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64)).astype(np.float64)) - v.T @ vy
     return mean, var, cov
 
 
