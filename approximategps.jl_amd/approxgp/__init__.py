@@ -18,5 +18,8 @@ from .sva import (SVGP, ApproxPosteriorGP, Centered, NonCentered, SparseVariatio
 # LaplaceApproximation; approx_lml and posterior dispatch on the approximation type (the SVGP methods above are unchanged)
 from .laplace import (DeviceLaplace, LaplaceApproximation, LaplaceObjective, LaplacePosteriorGP, approx_lml,
                       approx_lml_and_gradient, build_laplace_objective, posterior)
+# NearestNeighbors (Vecchia); approx_lml, approx_lml_and_gradient and posterior dispatch on it too (the methods above are unchanged)
+from .nearest_neighbors import (DeviceNearestNeighbors, NearestNeighbors, NNPosteriorGP, approx_lml, approx_lml_and_gradient,
+                                posterior)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

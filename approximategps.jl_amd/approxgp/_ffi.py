@@ -78,6 +78,16 @@ class LaplaceInfo(C.Structure):
                 ("ms_gemv", C.c_double)]
 
 
+class NNDesc(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("kernel", C.c_int32), ("d", C.c_int32), ("k", C.c_int32), ("variance", C.c_double),
+                ("inv_lengthscale", C.POINTER(C.c_double)), ("diag", C.c_double), ("mean_const", C.c_double),
+                ("reserved", C.c_int64)]
+
+
+class NNInfo(C.Structure):
+    _fields_ = [("first_bad", C.c_int64), ("n_neg_f", C.c_int64), ("lml", C.c_double)]
+
+
 # every symbol include/svgp_mi355x.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -133,6 +143,16 @@ SYMBOLS = {
     "svgp_laplace_predict": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P]),
     "svgp_laplace_predict_cross_cov": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P, _P]),
     "svgp_laplace_free": (C.c_int32, [_P, _P]),
+    # the NearestNeighbors (Vecchia) approximation
+    "svgp_nn_create": (C.c_int32, [_P, _P, C.POINTER(_P)]),
+    "svgp_nn_lml": (C.c_int32, [_P, _P, C.POINTER(NNDesc), C.POINTER(C.c_double), C.POINTER(NNInfo)]),
+    "svgp_nn_lml_grad": (C.c_int32, [_P, _P, C.POINTER(NNDesc), C.POINTER(C.c_double), C.POINTER(NNInfo), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "svgp_nn_fit": (C.c_int32, [_P, _P, C.POINTER(NNDesc), C.POINTER(C.c_double), C.POINTER(NNInfo)]),
+    "svgp_nn_factors": (C.c_int32, [_P, _P, _P, _P, _P]),
+    "svgp_nn_predict": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P]),
+    "svgp_nn_predict_cross_cov": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P, _P]),
+    "svgp_nn_free": (C.c_int32, [_P, _P]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),
     "svgp_ctx_attach_comm": (C.c_int32, [_P, _P, C.c_int32, C.c_int32]),

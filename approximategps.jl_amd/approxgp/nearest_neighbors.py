@@ -1,0 +1,233 @@
+"""Python host mirror of ApproximateGPs.jl's NearestNeighbors (Vecchia) approximation (src/NearestNeighborsModule.jl of the reference,
+NN) over the C-ABI of libsvgp_mi355x.so: the per-point factorisations, approx_lml, its gradient and the posterior's predictions all
+run on the device (include/svgp_mi355x.h, svgp_nn_*).  This file only packs parameters."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi
+from . import laplace as _laplace
+from .gp import FiniteGP
+from .kernels import unpack_kernel
+
+
+class NearestNeighbors:
+    """NearestNeighbors(k) (NN:73-75): every point is conditioned on the k points before it in the given order.
+    include_noise=False is the reference, which builds U from the kernel alone and ignores fx.Σy (NN:100-101); with
+    include_noise=True the isotropic fx.Σy joins every diagonal entry: the Vecchia approximation of logpdf(fx, y) itself."""
+
+    def __init__(self, k: int, include_noise: bool = False):
+        if int(k) != k or int(k) < 1:
+            raise ValueError("NearestNeighbors needs k >= 1")
+        self.k = int(k)
+        self.include_noise = bool(include_noise)
+
+
+def _check_inputs(nn: NearestNeighbors, fx: FiniteGP, y):
+    """-> (diag, mean_const).  A CustomMean prior and, with include_noise, a non-isotropic Σy are not supported."""
+    if fx.f.mean_fn is not None:
+        raise _ffi.UnsupportedError("NearestNeighbors takes a zero or constant prior mean, not a CustomMean")
+    diag = 0.0
+    if nn.include_noise:
+        if not fx.is_isotropic():
+            raise _ffi.UnsupportedError("include_noise needs an isotropic fx.Σy")
+        diag = float(fx.Sigma_y)
+    if np.shape(y)[0] != fx.n:
+        raise ValueError("x and y lengths differ")
+    return diag, float(fx.f.mean_const)
+
+
+class DeviceNearestNeighbors:
+    """A resident svgp_nn handle over (x, y): x a plain vector (d = 1) or a (d, n) ColVecs array; with layout = ROWVECS an (n, d)
+    RowVecs array.  The neighbours of a point are the points before it in this order."""
+
+    def __init__(self, ctx: _ffi.Context, x, y, dtype, layout=None):
+        self.ctx = ctx
+        x = np.asarray(x)
+        if layout is None:
+            layout = _ffi.VEC if x.ndim == 1 else _ffi.COLVECS
+        self.data = _ffi.DeviceData(ctx, x, y, dtype, layout)
+        self.dtype, self.d, self.n = self.data.dtype, self.data.d, self.data.n
+        h = C.c_void_p()
+        ctx.check(ctx.lib.svgp_nn_create(ctx.h, self.data.h, C.byref(h)))
+        self.h = h
+        self.kb = None   # columns of B after a fit
+
+    def desc(self, kernel, k, diag=0.0, mean_const=0.0):
+        family, variance, il = unpack_kernel(kernel, self.d)
+        il = np.ascontiguousarray(il, dtype=np.float64)
+        ds = _ffi.NNDesc(dtype=self.dtype, kernel=family, d=self.d, k=int(k), variance=float(variance),
+                         inv_lengthscale=il.ctypes.data_as(C.POINTER(C.c_double)), diag=float(diag), mean_const=float(mean_const),
+                         reserved=0)
+        return ds, il
+
+    def _check(self, rc, info):
+        if rc == _ffi.NOT_POSDEF:
+            msg = (self.ctx.lib.svgp_last_error(self.ctx.h) or b"").decode()
+            raise _ffi.PosDefException(int(info.first_bad), msg)
+        self.ctx.check(rc)
+
+    def lml(self, desc):
+        """-> (lml, NNInfo)"""
+        lml, info = C.c_double(), _ffi.NNInfo()
+        self._check(self.ctx.lib.svgp_nn_lml(self.ctx.h, self.h, C.byref(desc), C.byref(lml), C.byref(info)), info)
+        return lml.value, info
+
+    def lml_grad(self, desc):
+        """-> (lml, d / d variance, d / d inv_lengthscale (d,), d / d diag, NNInfo)"""
+        lml, info, dv, dd = C.c_double(), _ffi.NNInfo(), C.c_double(), C.c_double()
+        dil = np.zeros(self.d)
+        self._check(self.ctx.lib.svgp_nn_lml_grad(self.ctx.h, self.h, C.byref(desc), C.byref(lml), C.byref(info), C.byref(dv),
+                                                  dil.ctypes.data_as(C.POINTER(C.c_double)), C.byref(dd)), info)
+        return lml.value, dv.value, dil, dd.value, info
+
+    def fit(self, desc):
+        """-> (lml, NNInfo); caches B, F and alpha on the device for predict / cross_cov / factors"""
+        lml, info = C.c_double(), _ffi.NNInfo()
+        self._check(self.ctx.lib.svgp_nn_fit(self.ctx.h, self.h, C.byref(desc), C.byref(lml), C.byref(info)), info)
+        self.kb = min(int(desc.k), self.n - 1)
+        return lml.value, info
+
+    def factors(self):
+        """-> (B (n, kb) with B[i, t] the coefficient of point i on point i - kb + t, F (n,), alpha (n,)) of the last fit"""
+        dt = _ffi.np_dtype(self.dtype)
+        kb = self.kb or 0
+        B = np.zeros((self.n, kb), dtype=dt, order="F")
+        F, alpha = np.zeros(self.n, dtype=dt), np.zeros(self.n, dtype=dt)
+        self.ctx.check(self.ctx.lib.svgp_nn_factors(self.ctx.h, self.h, _ffi._ptr(B) if kb else None, _ffi._ptr(F), _ffi._ptr(alpha)))
+        return B, F, alpha
+
+    def _x(self, x):
+        dt = _ffi.np_dtype(self.dtype)
+        x = np.asarray(x, dtype=dt)
+        if x.ndim == 1:
+            if self.d != 1:
+                raise ValueError("test inputs have a different dimension than the data")
+            return _ffi.VEC, x.shape[0], np.ascontiguousarray(x)
+        if x.shape[0] != self.d:
+            raise ValueError("test inputs have a different dimension than the data")
+        return _ffi.COLVECS, x.shape[1], np.asfortranarray(x)
+
+    def predict(self, x, mean=True, var=True, cov=False):
+        layout, n, xb = self._x(x)
+        dt = _ffi.np_dtype(self.dtype)
+        m = np.zeros(n, dtype=dt) if mean else None
+        v = np.zeros(n, dtype=dt) if var else None
+        c = np.zeros((n, n), dtype=dt, order="F") if cov else None
+        self.ctx.check(self.ctx.lib.svgp_nn_predict(self.ctx.h, self.h, layout, n, _ffi._ptr(xb), _ffi._ptr(m), _ffi._ptr(v),
+                                                    _ffi._ptr(c)))
+        return m, v, c
+
+    def cross_cov(self, x, y):
+        lx, nx, xb = self._x(x)
+        ly, ny, yb = self._x(y)
+        if lx != ly:
+            raise ValueError("x and y must have the same layout")
+        c = np.zeros((nx, ny), dtype=_ffi.np_dtype(self.dtype), order="F")
+        self.ctx.check(self.ctx.lib.svgp_nn_predict_cross_cov(self.ctx.h, self.h, lx, nx, _ffi._ptr(xb), ny, _ffi._ptr(yb),
+                                                              _ffi._ptr(c)))
+        return c
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.svgp_nn_free(self.ctx.h, self.h)
+            self.h = None
+        if getattr(self, "data", None) is not None:
+            self.data.free()
+            self.data = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _dtype_of(fx, dtype):
+    if dtype is not None:
+        return np.dtype(dtype)
+    return np.dtype(np.float32 if np.asarray(fx.x).dtype == np.float32 else np.float64)
+
+
+def _nn_kwargs(fn, kwargs):
+    extra = set(kwargs) - {"ctx", "dtype"}
+    if extra:
+        raise TypeError(f"{fn}() with NearestNeighbors got unexpected keyword arguments {sorted(extra)}")
+    return kwargs.get("ctx"), kwargs.get("dtype")
+
+
+def _device(nn: NearestNeighbors, fx: FiniteGP, y, ctx, dtype):
+    diag, mean_const = _check_inputs(nn, fx, y)   # before the GPU is touched
+    dev = DeviceNearestNeighbors(ctx or _ffi.default_context(), fx.x, y, _dtype_of(fx, dtype))
+    desc, keep = dev.desc(fx.f.kernel, nn.k, diag, mean_const)
+    return dev, desc, keep
+
+
+def approx_lml(approx, fx, y, **kwargs):
+    """approx_lml(nn::NearestNeighbors, fx, y; ctx, dtype) (NN:108-113); any other approximation: the Laplace / SVGP methods with
+    every keyword passed on exactly as given."""
+    if not isinstance(approx, NearestNeighbors):
+        return _laplace.approx_lml(approx, fx, y, **kwargs)
+    ctx, dtype = _nn_kwargs("approx_lml", kwargs)
+    dev, desc, keep = _device(approx, fx, y, ctx, dtype)
+    try:
+        return dev.lml(desc)[0]
+    finally:
+        dev.free()
+
+
+def approx_lml_and_gradient(approx, fx, y, **kwargs):
+    """NearestNeighbors: -> (lml, {"variance", "inv_lengthscale" (d,), "diag"}), the gradient with respect to the kernel parameters
+    and to the diagonal term (the noise variance under include_noise).  LaplaceApproximation: the Laplace method, unchanged."""
+    if not isinstance(approx, NearestNeighbors):
+        return _laplace.approx_lml_and_gradient(approx, fx, y, **kwargs)
+    ctx, dtype = _nn_kwargs("approx_lml_and_gradient", kwargs)
+    dev, desc, keep = _device(approx, fx, y, ctx, dtype)
+    try:
+        lml, dv, dil, dd, _info = dev.lml_grad(desc)
+    finally:
+        dev.free()
+    return lml, {"variance": dv, "inv_lengthscale": dil, "diag": dd}
+
+
+class NNPosteriorGP:
+    """PosteriorGP(fx.f, (α, C = InvRoot(U), x, δ)) (NN:97-106) with B, F and α resident on the device.  Test inputs: a plain
+    vector (d = 1) or a (d, n) ColVecs array."""
+
+    def __init__(self, nn: NearestNeighbors, fx: FiniteGP, y, ctx=None, dtype=None):
+        self.approx, self.prior = nn, fx.f
+        self.dev, desc, keep = _device(nn, fx, y, ctx, dtype)
+        self.lml, self.info = self.dev.fit(desc)
+
+    def mean(self, x):
+        return self.dev.predict(x, mean=True, var=False)[0]
+
+    def var(self, x):
+        return self.dev.predict(x, mean=False, var=True)[1]
+
+    def mean_and_var(self, x):
+        m, v, _ = self.dev.predict(x, mean=True, var=True)
+        return m, v
+
+    def cov(self, x, y=None):
+        if y is None:
+            return self.dev.predict(x, mean=False, var=False, cov=True)[2]
+        return self.dev.cross_cov(x, y)
+
+    def mean_and_cov(self, x):
+        m, _, c = self.dev.predict(x, mean=True, var=False, cov=True)
+        return m, c
+
+    def factors(self):
+        return self.dev.factors()
+
+
+def posterior(approx, *args, **kwargs):
+    """posterior(nn::NearestNeighbors, fx, y) (NN:97-106); any other approximation: the Laplace / SVGP methods."""
+    if isinstance(approx, NearestNeighbors):
+        fx, y = args
+        ctx, dtype = _nn_kwargs("posterior", kwargs)
+        return NNPosteriorGP(approx, fx, y, ctx=ctx, dtype=dtype)
+    return _laplace.posterior(approx, *args, **kwargs)

@@ -1,0 +1,697 @@
+// nn.hip — the NearestNeighbors (Vecchia) approximation (reference src/NearestNeighborsModule.jl):
+//   posterior(nn, fx, y) :97-106      approx_lml(nn, fx, y) :108-113      make_row :27-29      make_F :46-61
+// The prior factors as p(f) = prod_i p(f_i | f_ns(i)), ns(i) = the m = min(i, k) points before i in the given order.  Per point:
+//   C = k(ns, ns) + diag I,  c = k(ns, x_i),  kd = k(x_i, x_i) + diag,  b_i = C \ c,  F_i = kd - c' b_i,  r_i = delta_i - b_i' delta_ns
+//   approx_lml = -1/2 sum_i (log 2 pi + log F_i + r_i^2 / F_i)
+// The reference packs the b_i into a sparse B and U = (I - B)' F^-1/2; nothing here is sparse or sequential: one dense solve of
+// order <= k per point, N of them independent.
+//   point kernel     one wavefront per point, lane j owns COLUMN j of the <= 64 x 64 block in registers (A[q] = C[q][j]).  The block
+//                    is symmetric, so at step p of the right-looking factorisation lane j finds C[j][p] in its own register p,
+//                    and the other factor of the update, L[q][p], is lane q's value: a v_readlane into scalar registers, uniform
+//                    over the wave.  No LDS, no barrier.  c and delta_ns ride along as two more rows of the block (one register
+//                    each), so l = L^-1 c, z = L^-1 delta_ns, F = kd - l'l and r = delta_i - l'z come out of the same sweep (F and r
+//                    in fp64 for both dtypes: kd - l'l cancels).  Lanes below the pivot keep their column of the Schur complement
+//                    frozen: scaled by their pivot it is the column of L the back-substitutions b = L^-T l, w = L^-T z read.
+//                    Templated on the k bucket (16 / 32 / 64 registers) and the mode (value / fit / gradient).          nn_point_kernel
+//   reduction        per-point slots -> per-block partials -> one block per slot, fixed order, no atomics             nn_reduce*_kernel
+//   gradient         gF = -1/(2F) + r^2/(2F^2), qv = gF b - (r/F) w:  C_bar = qv b' (the unsymmetrised form: it only meets symmetric
+//                    dK), c_bar = -2 gF b + (r/F) w; the inverse lengthscales contract them with dk/dr2 * 2 (ds_f)^2 / invl_f over a
+//                    regenerated block; d/d variance and d/d diag have closed forms in (F, b'b, w'b) (nn_point_kernel, MODE 2)
+//   fit              the same sweep stores b_i (banded N x kb column-major, data dtype), F_i and r_i / F_i; alpha = U (U' delta) is
+//                    a gather over the <= k later rows                                                                  nn_alpha_kernel
+//   predictions      V = U' k(x, x*) streamed in row tiles of at most 2048 points, never N x n*: k(x, x*) tile (nn_kx_kernel),
+//                    V tile with the column sums of the mean and of V.^2 (nn_v_kernel), V'V on the MFMA product kernel of the
+//                    gradient path (launch_gemm_pm) accumulated tile after tile in stream order
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "ctx.hpp"
+#include "device_common.hpp"
+#include "kernels.hpp"
+
+namespace svgp {
+namespace {
+
+#define NN_DISPATCH(dtype, T, ...)      \
+  do {                                  \
+    if ((dtype) == 0) {                 \
+      using T = double;                 \
+      __VA_ARGS__;                      \
+    } else {                            \
+      using T = float;                  \
+      __VA_ARGS__;                      \
+    }                                   \
+  } while (0)
+
+constexpr int kNnMaxK = 64;        // one lane per neighbour
+constexpr int kNnNone = 0x7f7f7f7f;   // "no bad point": what hipMemsetAsync(0x7f) leaves in the first-bad-point word
+constexpr int kNnSlots = 3;        // per point: log F, r^2 / F, (F <= 0)
+constexpr int kNnGradSlots = 5;    // ... + d / d variance, d / d diag; the d inverse lengthscales follow
+constexpr int kNnRows = 2048;      // most rows of one V tile
+constexpr int64_t kNnTileElems = int64_t(1) << 23;   // elements of one V tile (rows x padded columns): the workspace rule
+constexpr int64_t kNnMaxCov = 4096;                  // most test points of cov / cross-cov
+constexpr int64_t kNnMaxPred = int64_t(1) << 17;     // most test points of one mean / var call (64-row tiles at the workspace rule)
+
+struct NnParams {
+  int family, d, k;   // k: effective neighbour count min(k, N - 1)
+  int64_t n, ldx;
+  double variance, diag, mean_const;
+  double invl[SVGP_MAX_D];
+};
+
+// lane `l` (uniform) of v, through scalar registers
+__device__ __forceinline__ float nn_rl(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+__device__ __forceinline__ double nn_rl(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ double nn_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// f(integral_constant<I>) for I = I0 .. N - 1: the steps of the factorisation index the register array, so their number is a
+// compile-time constant whatever the unroller's budget
+template <int I, int N, typename Fn>
+__device__ __forceinline__ void nn_static_for(Fn&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    nn_static_for<I + 1, N>(f);
+  }
+}
+
+// d kappa / d r2 of the unit-variance kernel
+template <typename T>
+__device__ __forceinline__ T nn_dkappa(int family, T r2) {
+  if (family == KSE) return T(-0.5) * kexp(T(-0.5) * r2);
+  if (family == KM32) return T(-1.5) * kexp(-T(1.7320508075688772935) * ksqrt(r2));
+  const T s = T(2.2360679774997896964) * ksqrt(r2);
+  return -T(5.0 / 6.0) * (T(1) + s) * kexp(-s);
+}
+
+// A[q] = |s_q - s_j|^2 for the neighbours q, j = lane (s = x .* invl), cr2 = |s_i - s_j|^2; inactive lanes carry s = 0
+template <typename T, int KB>
+__device__ __forceinline__ void nn_dist2(const NnParams& P, const T* __restrict__ x, int64_t base, int64_t i, int lane, int m, T (&A)[KB],
+                                         T& cr2) {
+#pragma unroll
+  for (int q = 0; q < KB; ++q) A[q] = T(0);
+  cr2 = T(0);
+  for (int f = 0; f < P.d; ++f) {
+    const T il = T(P.invl[f]);
+    const T xj = lane < m ? x[int64_t(f) * P.ldx + base + lane] * il : T(0);
+    const T dc = xj - x[int64_t(f) * P.ldx + i] * il;
+    cr2 = fma(dc, dc, cr2);
+#pragma unroll
+    for (int g = 0; g < KB / 8; ++g)
+      if (g * 8 < m) {
+#pragma unroll
+        for (int q = g * 8; q < g * 8 + 8; ++q) {
+          const T df = nn_rl(xj, q) - xj;
+          A[q] = fma(df, df, A[q]);
+        }
+      }
+  }
+}
+
+// MODE 0: the lml slots.  MODE 1: + b_i, F_i, r_i / F_i (fit).  MODE 2: + the gradient slots.
+template <typename T, int KB, int MODE>
+__global__ void __launch_bounds__(k256) nn_point_kernel(const NnParams P, const T* __restrict__ x, const T* __restrict__ y,
+                                                        double* __restrict__ terms, int S, int* __restrict__ bad, T* __restrict__ Bd,
+                                                        double* __restrict__ Fd, double* __restrict__ rFd) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = int64_t(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  if (i >= P.n) return;
+  const int m = i < P.k ? int(i) : P.k;
+  const int64_t base = i - m;
+  const bool act = lane < m;
+  const T variance = T(P.variance);
+  T A[KB], c;
+  nn_dist2<T, KB>(P, x, base, i, lane, m, A, c);
+  // the block: C on the m x m corner, identity on the padding
+#pragma unroll
+  for (int g = 0; g < KB / 8; ++g) {
+    if (g * 8 < m) {
+#pragma unroll
+      for (int q = g * 8; q < g * 8 + 8; ++q) {
+        const T kv = kappa(P.family, A[q], variance) + (q == lane ? T(P.diag) : T(0));
+        A[q] = (act && q < m) ? kv : (q == lane ? T(1) : T(0));
+      }
+    } else {
+#pragma unroll
+      for (int q = g * 8; q < g * 8 + 8; ++q) A[q] = q == lane ? T(1) : T(0);
+    }
+  }
+  c = act ? kappa(P.family, c, variance) : T(0);
+  T dd = act ? T(double(y[base + lane]) - P.mean_const) : T(0);
+  double F = P.variance + P.diag, r = double(y[i]) - P.mean_const;
+  // "not positive": at or below the rounding noise of its own computation, 4 eps (m + 1) kd - a pivot or an F down there is a
+  // difference of equal numbers (an exactly repeated point with diag = 0 leaves +-1e-16, either sign)
+  const double floor_ = 4.0 * (sizeof(T) == 8 ? 2.220446049250313e-16 : 1.1920928955078125e-07) * double(m + 1) * F;
+  bool isbad = false;
+  T myrs = T(1), lme = T(0), zme = T(0);   // lane p keeps 1 / L[p][p], l_p, z_p
+  nn_static_for<0, KB>([&](auto pc) __attribute__((always_inline)) {
+    constexpr int p = decltype(pc)::value;
+    if (p < m) {
+      const T piv = nn_rl(A[p], p);
+      if (!(double(piv) > floor_)) isbad = true;
+      const T rs = T(1) / ksqrt(piv);
+      const T lj = A[p] * rs;                     // L[j][p] for the lanes j >= p
+      const T ljm = lane > p ? lj : T(0);
+      A[p] = lane >= p ? lj : A[p];               // lanes j < p: column j of the Schur complement stays (scaled in the back-substitution)
+      const T lm = nn_rl(c, p) * rs, zp = nn_rl(dd, p) * rs;
+      F = fma(-double(lm), double(lm), F);
+      r = fma(-double(lm), double(zp), r);
+      if (lane == p) { myrs = rs; lme = lm; zme = zp; }
+      c = fma(-lm, ljm, c);
+      dd = fma(-zp, ljm, dd);
+#pragma unroll
+      for (int g = (p + 1) / 8; g < KB / 8; ++g)
+        if (g * 8 < m) {
+#pragma unroll
+          for (int q = (g * 8 > p + 1 ? g * 8 : p + 1); q < g * 8 + 8; ++q) A[q] = fma(-nn_rl(lj, q), ljm, A[q]);
+        }
+    }
+  });
+  if (!(F > floor_)) isbad = true;
+  if (lane == 0) {
+    double* t = terms + i * S;
+    t[0] = isbad ? 0.0 : log(F);
+    t[1] = isbad ? 0.0 : r * r / F;
+    t[2] = (F <= 0.0) ? 1.0 : 0.0;
+    if (isbad) atomicMin(bad, int(i + 1 < kNnNone ? i + 1 : kNnNone - 1));
+  }
+  if (MODE == 0) return;
+  // b = L^-T l, w = L^-T z: L[p][j], j < p, is lane j's frozen register p times its own 1 / L[j][j]
+  T tb = lme, tw = zme, bme = T(0), wme = T(0);
+  nn_static_for<0, KB>([&](auto pc) __attribute__((always_inline)) {
+    constexpr int p = KB - 1 - decltype(pc)::value;
+    if (p < m) {
+      const T rsp = nn_rl(myrs, p);
+      const T bp = nn_rl(tb, p) * rsp, wp = nn_rl(tw, p) * rsp;
+      if (lane == p) { bme = bp; wme = wp; }
+      const T lpj = lane < p ? A[p] * myrs : T(0);
+      tb = fma(-lpj, bp, tb);
+      tw = fma(-lpj, wp, tw);
+    }
+  });
+  const double rF = r / F;
+  if (MODE == 1) {
+    if (act) Bd[i + int64_t(P.k - m + lane) * P.n] = bme;
+    if (lane == 0) { Fd[i] = F; rFd[i] = rF; }
+    return;
+  }
+  // ---- gradient ----
+  const double gF = -0.5 / F + 0.5 * r * r / (F * F);
+  const double btb = nn_wave_sum(double(bme) * double(bme)), wtb = nn_wave_sum(double(wme) * double(bme));
+  const T qv = T(gF * double(bme) - rF * double(wme));               // C_bar[q][j] = qv_q b_j
+  const T cb = T(-2.0 * gF * double(bme) + rF * double(wme));        // c_bar_j
+  T cr2;
+  nn_dist2<T, KB>(P, x, base, i, lane, m, A, cr2);
+  const T v2 = T(2) * variance;
+#pragma unroll
+  for (int g = 0; g < KB / 8; ++g) {
+    if (g * 8 < m) {
+#pragma unroll
+      for (int q = g * 8; q < g * 8 + 8; ++q) A[q] = (act && q < m) ? v2 * nn_dkappa(P.family, A[q]) * nn_rl(qv, q) * bme : T(0);
+    } else {
+#pragma unroll
+      for (int q = g * 8; q < g * 8 + 8; ++q) A[q] = T(0);
+    }
+  }
+  const T gc = act ? v2 * nn_dkappa(P.family, cr2) * cb : T(0);
+  double* t = terms + i * S;
+  for (int f = 0; f < P.d; ++f) {
+    const T il = T(P.invl[f]);
+    const T xj = act ? x[int64_t(f) * P.ldx + base + lane] * il : T(0);
+    const T dc = xj - x[int64_t(f) * P.ldx + i] * il;
+    T acc = gc * dc * dc;
+#pragma unroll
+    for (int g = 0; g < KB / 8; ++g)
+      if (g * 8 < m) {
+#pragma unroll
+        for (int q = g * 8; q < g * 8 + 8; ++q) {
+          const T df = nn_rl(xj, q) - xj;
+          acc = fma(A[q], df * df, acc);
+        }
+      }
+    const double sum = nn_wave_sum(double(acc));   // sum P_ab dk 2 variance (ds_f)^2 = invl_f * d / d invl_f
+    if (lane == 0) t[kNnGradSlots + f] = (isbad || P.invl[f] == 0.0) ? 0.0 : sum / P.invl[f];
+  }
+  if (lane == 0) {
+    const double tr = gF * btb - rF * wtb;   // trace of C_bar
+    t[3] = isbad ? 0.0 : (gF * (F - P.diag) - P.diag * tr) / P.variance;
+    t[4] = isbad ? 0.0 : gF + tr;
+  }
+}
+
+// part[s][b] = sum of slot s over the points of block b (contiguous ranges of `chunk` points), fixed order
+__global__ void __launch_bounds__(k256) nn_reduce1_kernel(const double* __restrict__ terms, int64_t n, int S, int64_t chunk,
+                                                          double* __restrict__ part) {
+  __shared__ double sh[k256];
+  const int t = threadIdx.x, s = blockIdx.y;
+  const int64_t i0 = int64_t(blockIdx.x) * chunk, i1 = i0 + chunk < n ? i0 + chunk : n;
+  double acc = 0.0;
+  for (int64_t i = i0 + t; i < i1; i += k256) acc += terms[i * S + s];
+  sh[t] = acc;
+  __syncthreads();
+  for (int w = k256 / 2; w > 0; w >>= 1) {
+    if (t < w) sh[t] += sh[t + w];
+    __syncthreads();
+  }
+  if (t == 0) part[int64_t(s) * gridDim.x + blockIdx.x] = sh[0];
+}
+__global__ void __launch_bounds__(k256) nn_reduce2_kernel(const double* __restrict__ part, int nb, double* __restrict__ out) {
+  __shared__ double sh[k256];
+  const int t = threadIdx.x, s = blockIdx.x;
+  double acc = 0.0;
+  for (int b = t; b < nb; b += k256) acc += part[int64_t(s) * nb + b];
+  sh[t] = acc;
+  __syncthreads();
+  for (int w = k256 / 2; w > 0; w >>= 1) {
+    if (t < w) sh[t] += sh[t + w];
+    __syncthreads();
+  }
+  if (t == 0) out[s] = sh[0];
+}
+
+// alpha = U (U' delta):  alpha_j = r_j / F_j - sum_{s = 1 .. kb, j + s < n} B(j + s, kb - s) r_{j+s} / F_{j+s}   (:103)
+template <typename T>
+__global__ void nn_alpha_kernel(const T* __restrict__ Bd, const double* __restrict__ rF, int64_t n, int kb, double* __restrict__ alpha) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  double a = rF[j];
+  for (int s = 1; s <= kb && j + s < n; ++s) a = fma(-double(Bd[(j + s) + int64_t(kb - s) * n]), rF[j + s], a);
+  alpha[j] = a;
+}
+
+template <typename T>
+__global__ void nn_cast_kernel(const double* __restrict__ in, int64_t n, double shift, double scale, T* __restrict__ out) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j < n) out[j] = T(shift + scale * in[j]);
+}
+
+// ---- predictions ---------------------------------------------------------------------------------------------
+// Kx[rr][j] = k(x_g, x*_j), g = i0 - 64 + rr, for rr < rows, j < np; 0 where g is outside [0, n) or j >= nt (row-major, ld np)
+template <typename T>
+__global__ void __launch_bounds__(k256) nn_kx_kernel(const NnParams P, const T* __restrict__ x, const T* __restrict__ xt, int64_t ldt,
+                                                     int64_t nt, int64_t np, int64_t i0, int rows, T* __restrict__ Kx) {
+  const int64_t j = int64_t(blockIdx.x) * k256 + threadIdx.x;
+  if (j >= np) return;
+  for (int rr = blockIdx.y; rr < rows; rr += gridDim.y) {
+    const int64_t g = i0 - kNnMaxK + rr;
+    T v = T(0);
+    if (g >= 0 && g < P.n && j < nt) {
+      T r2 = T(0);
+      for (int f = 0; f < P.d; ++f) {
+        const T df = (x[int64_t(f) * P.ldx + g] - xt[int64_t(f) * ldt + j]) * T(P.invl[f]);
+        r2 = fma(df, df, r2);
+      }
+      v = kappa(P.family, r2, T(P.variance));
+    }
+    Kx[int64_t(rr) * np + j] = v;
+  }
+}
+
+// Row i of V = U' k(x, x*): (k(x_i, x*) - sum_t B(i, t) k(x_{i - kb + t}, x*)) / sqrt(F_i), for the rows [i0, i0 + 64 gridDim.y) of one
+// tile (zero beyond n); per 64-row group the column sums of V.^2 and of k(x_i, x*) alpha_i (fp64).  256 threads = 64 columns x 4 rows.
+template <typename T>
+__global__ void __launch_bounds__(k256) nn_v_kernel(const T* __restrict__ Kx, int64_t np, int64_t i0, int64_t n, int kb,
+                                                    const T* __restrict__ Bd, const double* __restrict__ Fd, const double* __restrict__ alpha,
+                                                    int want_v, T* __restrict__ V, double* __restrict__ pm, double* __restrict__ pv) {
+  __shared__ double sm[4][64], sv[4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t j = int64_t(blockIdx.x) * 64 + tx;
+  double am = 0.0, av = 0.0;
+  for (int s = 0; s < 16; ++s) {
+    const int rr = blockIdx.y * 64 + ty + 4 * s;
+    const int64_t i = i0 + rr;
+    double v = 0.0;
+    if (i < n) {
+      const double kx = double(Kx[int64_t(rr + kNnMaxK) * np + j]);
+      am = fma(kx, alpha[i], am);
+      if (want_v) {
+        double acc = 0.0;
+        for (int t = 0; t < kb; ++t) acc = fma(double(Bd[i + int64_t(t) * n]), double(Kx[int64_t(rr + kNnMaxK - kb + t) * np + j]), acc);
+        v = (kx - acc) / sqrt(Fd[i]);
+        av = fma(v, v, av);
+      }
+    }
+    if (want_v) V[int64_t(rr) * np + j] = T(v);
+  }
+  sm[ty][tx] = am;
+  sv[ty][tx] = av;
+  __syncthreads();
+  if (ty == 0) {
+    pm[int64_t(blockIdx.y) * np + j] = ((sm[0][tx] + sm[1][tx]) + sm[2][tx]) + sm[3][tx];
+    pv[int64_t(blockIdx.y) * np + j] = ((sv[0][tx] + sv[1][tx]) + sv[2][tx]) + sv[3][tx];
+  }
+}
+// acc[j] += the tile's row-group partials, in order
+__global__ void nn_colacc_kernel(const double* __restrict__ pm, const double* __restrict__ pv, int groups, int64_t np,
+                                 double* __restrict__ macc, double* __restrict__ vacc) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= np) return;
+  double a = macc[j], b = vacc[j];
+  for (int g = 0; g < groups; ++g) {
+    a += pm[int64_t(g) * np + j];
+    b += pv[int64_t(g) * np + j];
+  }
+  macc[j] = a;
+  vacc[j] = b;
+}
+// out[a + b na] = k(xa_a, xb_b) - acc[a][b]   (acc row-major, ld np)
+template <typename T>
+__global__ void nn_cov_finish_kernel(const NnParams P, const T* __restrict__ xa, int64_t lda, int64_t na, const T* __restrict__ xb,
+                                     int64_t ldb, int64_t nb, const T* __restrict__ acc, int64_t np, T* __restrict__ out) {
+  const int64_t a = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (a >= na || b >= nb) return;
+  T r2 = T(0);
+  for (int f = 0; f < P.d; ++f) {
+    const T df = (xa[int64_t(f) * lda + a] - xb[int64_t(f) * ldb + b]) * T(P.invl[f]);
+    r2 = fma(df, df, r2);
+  }
+  out[a + b * na] = T(double(kappa(P.family, r2, T(P.variance))) - double(acc[a * np + b]));
+}
+
+inline unsigned nblk(int64_t n, int b = 256) { return unsigned((n + b - 1) / b); }
+
+}  // namespace
+}  // namespace svgp
+
+// ================================================================================================
+using namespace svgp;
+
+struct svgp_nn {
+  const svgp_data* data = nullptr;
+  int dtype = 0, d = 0;
+  int64_t N = 0;
+  size_t es = 8;
+  DevBuf terms;   // [N][slots] fp64 per-point terms, grown on demand
+  DevBuf part;    // [slots][blocks] fp64 block partials
+  DevBuf res;     // [kNnGradSlots + SVGP_MAX_D] fp64 sums
+  DevBuf bad;     // (int) 1-based index of the first bad point, kNnNone: none
+  DevBuf Bd, Fd, rF, alpha;   // the last fit: b_i (N x kb column-major, data dtype), F_i, r_i / F_i, alpha (fp64)
+  bool have_fit = false;
+  NnParams P{};   // ... and its parameters
+};
+
+namespace {
+
+int nn_check_desc(svgp_ctx* ctx, const svgp_nn* nn, const svgp_nn_desc* ds) {
+  if (!ds) return fail(ctx, SVGP_INVALID_ARG, "null NearestNeighbors descriptor");
+  if (ds->dtype != nn->dtype) return fail(ctx, SVGP_INVALID_ARG, "descriptor dtype differs from the data's");
+  if (ds->d != nn->d) return fail(ctx, SVGP_INVALID_ARG, "descriptor d differs from the data's");
+  if (ds->kernel < SVGP_KERNEL_SE || ds->kernel > SVGP_KERNEL_MATERN52) return fail(ctx, SVGP_INVALID_ARG, "bad kernel");
+  if (ds->k < 1) return fail(ctx, SVGP_INVALID_ARG, "k must be >= 1");
+  if (ds->reserved != 0) return fail(ctx, SVGP_INVALID_ARG, "reserved field must be 0");
+  if (!ds->inv_lengthscale) return fail(ctx, SVGP_INVALID_ARG, "null inv_lengthscale");
+  if (!(ds->variance > 0.0)) return fail(ctx, SVGP_INVALID_ARG, "variance must be > 0");
+  if (!(ds->diag >= 0.0)) return fail(ctx, SVGP_INVALID_ARG, "diag must be >= 0");
+  if (std::min<int64_t>(ds->k, nn->N - 1) > kNnMaxK) return fail(ctx, SVGP_UNSUPPORTED, "more than 64 neighbours: one lane per neighbour");   // k >= N is k = N - 1
+  return SVGP_OK;
+}
+
+NnParams nn_params(const svgp_nn* nn, const svgp_nn_desc* ds) {
+  NnParams P{};
+  P.family = ds->kernel;
+  P.d = nn->d;
+  P.k = int(std::min<int64_t>(ds->k, nn->N - 1));   // k >= N is k = N - 1
+  P.n = nn->N;
+  P.ldx = nn->data->ldx;
+  P.variance = ds->variance;
+  P.diag = ds->diag;
+  P.mean_const = ds->mean_const;
+  for (int f = 0; f < nn->d; ++f) P.invl[f] = ds->inv_lengthscale[f];
+  return P;
+}
+
+template <typename T, int MODE>
+void nn_launch_point(hipStream_t s, const NnParams& P, const svgp_nn* nn, int S) {
+  const dim3 grid(nblk(P.n, 4)), block(k256);
+  const T *x = (const T*)nn->data->x.p, *y = (const T*)nn->data->y.p;
+  double* terms = nn->terms.as<double>();
+  int* bad = nn->bad.as<int>();
+  T* Bd = (T*)nn->Bd.p;
+  double *Fd = nn->Fd.as<double>(), *rF = nn->rF.as<double>();
+  if (P.k <= 16) hipLaunchKernelGGL((nn_point_kernel<T, 16, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF);
+  else if (P.k <= 32) hipLaunchKernelGGL((nn_point_kernel<T, 32, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF);
+  else hipLaunchKernelGGL((nn_point_kernel<T, 64, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF);
+}
+
+// mode 0: lml; 1: fit; 2: lml and gradient.  out[S] = the reduced slots
+int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double* lml_out, svgp_nn_info* info, double* out) {
+  int rc = nn_check_desc(ctx, nn, ds);
+  if (rc) return rc;
+  if (!lml_out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const NnParams P = nn_params(nn, ds);
+  const int64_t N = nn->N;
+  const int S = mode == 2 ? kNnGradSlots + nn->d : kNnSlots;
+  const int nb = int(std::min<int64_t>(1024, (N + 1023) / 1024));
+  const int64_t chunk = (N + nb - 1) / nb;
+  rc = nn->terms.reserve(ctx, size_t(N) * S * 8, "the NearestNeighbors per-point terms");
+  if (rc == SVGP_OK) rc = nn->part.reserve(ctx, size_t(nb) * S * 8, "the NearestNeighbors block partials");
+  if (rc == SVGP_OK && mode == 1) {
+    nn->have_fit = false;
+    rc = nn->Bd.reserve(ctx, std::max<size_t>(size_t(N) * P.k * nn->es, 8), "the NearestNeighbors rows b_i");
+    if (rc == SVGP_OK) rc = nn->Fd.reserve(ctx, size_t(N) * 8, "F");
+    if (rc == SVGP_OK) rc = nn->rF.reserve(ctx, size_t(N) * 8, "r / F");
+    if (rc == SVGP_OK) rc = nn->alpha.reserve(ctx, size_t(N) * 8, "alpha");
+    if (rc == SVGP_OK && P.k > 0) HIPC(ctx, hipMemsetAsync(nn->Bd.p, 0, size_t(N) * P.k * nn->es, s));   // the ramp-up rows i < k are shorter
+  }
+  if (rc) return rc;
+  HIPC(ctx, hipMemsetAsync(nn->bad.p, 0x7f, sizeof(int), s));   // kNnNone
+  NN_DISPATCH(nn->dtype, T, {
+    if (mode == 0) nn_launch_point<T, 0>(s, P, nn, S);
+    else if (mode == 1) nn_launch_point<T, 1>(s, P, nn, S);
+    else nn_launch_point<T, 2>(s, P, nn, S);
+  });
+  KCHECK(ctx, "nn_point");
+  hipLaunchKernelGGL(nn_reduce1_kernel, dim3((unsigned)nb, (unsigned)S), dim3(k256), 0, s, (const double*)nn->terms.as<double>(), N, S, chunk,
+                     nn->part.as<double>());
+  hipLaunchKernelGGL(nn_reduce2_kernel, dim3((unsigned)S), dim3(k256), 0, s, (const double*)nn->part.as<double>(), nb, nn->res.as<double>());
+  if (mode == 1)
+    NN_DISPATCH(nn->dtype, T, {
+      hipLaunchKernelGGL(nn_alpha_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, (const T*)nn->Bd.p, (const double*)nn->rF.as<double>(), N, P.k,
+                         nn->alpha.as<double>());
+    });
+  KCHECK(ctx, "nn_reduce");
+  int badv = 0;
+  HIPC(ctx, hipMemcpyAsync(out, nn->res.p, size_t(S) * 8, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(&badv, nn->bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  const bool isbad = badv != kNnNone;
+  const double lml = isbad ? NAN : -0.5 * (double(N) * 1.8378770664093454836 + out[0] + out[1]);
+  *lml_out = lml;
+  if (info) {
+    std::memset(info, 0, sizeof(*info));
+    info->first_bad = isbad ? badv : 0;
+    info->n_neg_f = int64_t(out[2]);
+    info->lml = lml;
+  }
+  if (isbad)
+    return fail(ctx, SVGP_NOT_POSDEF, "NearestNeighbors: the block or F of point " + std::to_string(badv) + " is not positive");
+  if (mode == 1) {
+    nn->P = P;
+    nn->have_fit = true;
+  }
+  return SVGP_OK;
+}
+
+struct NnHold {   // test inputs uploaded for one call
+  svgp_ctx* ctx;
+  svgp_data* D = nullptr;
+  ~NnHold() { if (D) svgp_data_free(ctx, D); }
+};
+
+// mean / var / cov of the column set A, or cov(A, B) when Bset is given (then only cov_out)
+int nn_predict_impl(svgp_ctx* ctx, svgp_nn* nn, const svgp_data* Aset, const svgp_data* Bset, void* mean_out, void* var_out, void* cov_out) {
+  hipStream_t s = ctx->stream;
+  const NnParams& P = nn->P;
+  const int64_t N = nn->N, na = Aset->n, nbp = Bset ? Bset->n : 0;
+  const int64_t np = (std::max(na, nbp) + kNB - 1) / kNB * kNB;
+  const bool want_v = var_out || cov_out;
+  const int rows_max = int(std::max<int64_t>(64, std::min<int64_t>(kNnRows, kNnTileElems / np / 64 * 64)));
+  const int groups_max = rows_max / 64;
+  const size_t es = nn->es;
+  DevBuf Kx, Va, Vb, pm, pv, macc, vacc, Cacc, outb;
+  HIPC(ctx, Kx.alloc(size_t(rows_max + kNnMaxK) * np * es));
+  if (want_v) HIPC(ctx, Va.alloc(size_t(rows_max) * np * es));
+  if (Bset) HIPC(ctx, Vb.alloc(size_t(rows_max) * np * es));
+  HIPC(ctx, pm.alloc(size_t(groups_max) * np * 8));
+  HIPC(ctx, pv.alloc(size_t(groups_max) * np * 8));
+  HIPC(ctx, macc.alloc(size_t(np) * 8));
+  HIPC(ctx, vacc.alloc(size_t(np) * 8));
+  HIPC(ctx, hipMemsetAsync(macc.p, 0, size_t(np) * 8, s));
+  HIPC(ctx, hipMemsetAsync(vacc.p, 0, size_t(np) * 8, s));
+  if (cov_out) HIPC(ctx, Cacc.alloc(size_t(np) * np * es));
+  bool first = true;
+  for (int64_t i0 = 0; i0 < N; i0 += rows_max) {
+    const int rows = int(std::min<int64_t>(rows_max, N - i0));
+    const int groups = (rows + 63) / 64;
+    NN_DISPATCH(nn->dtype, T, {
+      for (int side = 0; side < (Bset ? 2 : 1); ++side) {
+        const svgp_data* D = side ? Bset : Aset;
+        hipLaunchKernelGGL(nn_kx_kernel<T>, dim3(nblk(np), 256), dim3(k256), 0, s, P, (const T*)nn->data->x.p, (const T*)D->x.p, D->ldx, D->n, np,
+                           i0, groups * 64 + kNnMaxK, (T*)Kx.p);
+        hipLaunchKernelGGL(nn_v_kernel<T>, dim3(unsigned(np / 64), unsigned(groups)), dim3(k256), 0, s, (const T*)Kx.p, np, i0, N, P.k,
+                           (const T*)nn->Bd.p, (const double*)nn->Fd.as<double>(), (const double*)nn->alpha.as<double>(), want_v ? 1 : 0,
+                           (T*)(side ? Vb.p : Va.p), pm.as<double>(), pv.as<double>());
+        if (!side)
+          hipLaunchKernelGGL(nn_colacc_kernel, dim3(nblk(np)), dim3(256), 0, s, (const double*)pm.as<double>(), (const double*)pv.as<double>(),
+                             groups, np, macc.as<double>(), vacc.as<double>());
+      }
+    });
+    KCHECK(ctx, "nn predict tile");
+    if (cov_out) {
+      launch_gemm_pm(nn->dtype, s, Va.p, Bset ? Vb.p : Va.p, nullptr, 1.0, np, int64_t(groups) * 64, int64_t(groups) * 64, 1, Cacc.p,
+                     first ? 1 : 0, kMmFull);
+      KCHECK(ctx, "gemm_pm (V'V)");
+    }
+    first = false;
+  }
+  const size_t ob = std::max(size_t(na) * (cov_out ? std::max<int64_t>(Bset ? nbp : na, 1) : 1), size_t(1)) * es;
+  HIPC(ctx, outb.alloc(ob));
+  NN_DISPATCH(nn->dtype, T, {
+    if (mean_out) {
+      hipLaunchKernelGGL(nn_cast_kernel<T>, dim3(nblk(na)), dim3(256), 0, s, (const double*)macc.as<double>(), na, P.mean_const, 1.0, (T*)outb.p);
+      HIPC(ctx, hipMemcpyAsync(mean_out, outb.p, size_t(na) * es, hipMemcpyDeviceToHost, s));
+    }
+    if (var_out) {
+      hipLaunchKernelGGL(nn_cast_kernel<T>, dim3(nblk(na)), dim3(256), 0, s, (const double*)vacc.as<double>(), na, P.variance, -1.0, (T*)outb.p);
+      HIPC(ctx, hipMemcpyAsync(var_out, outb.p, size_t(na) * es, hipMemcpyDeviceToHost, s));
+    }
+    if (cov_out) {
+      const svgp_data* D2 = Bset ? Bset : Aset;
+      hipLaunchKernelGGL(nn_cov_finish_kernel<T>, dim3(nblk(na), (unsigned)D2->n), dim3(256), 0, s, P, (const T*)Aset->x.p, Aset->ldx, na,
+                         (const T*)D2->x.p, D2->ldx, D2->n, (const T*)Cacc.p, np, (T*)outb.p);
+      HIPC(ctx, hipMemcpyAsync(cov_out, outb.p, size_t(na) * D2->n * es, hipMemcpyDeviceToHost, s));
+    }
+  });
+  KCHECK(ctx, "nn predict finish");
+  HIPC(ctx, hipStreamSynchronize(s));
+  return SVGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t svgp_nn_create(svgp_ctx* ctx, const svgp_data* data, svgp_nn** out) {
+  if (!ctx || !data || !out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (!data->y.p) return fail(ctx, SVGP_INVALID_ARG, "the NearestNeighbors approximation needs y");
+  if (data->n < 1) return fail(ctx, SVGP_INVALID_ARG, "empty data");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  auto* nn = new (std::nothrow) svgp_nn();
+  if (!nn) return SVGP_OOM;
+  nn->data = data;
+  nn->dtype = data->dtype;
+  nn->d = data->d;
+  nn->N = data->n;
+  nn->es = data->dtype == SVGP_F64 ? 8 : 4;
+  hipError_t e = nn->res.alloc((kNnGradSlots + SVGP_MAX_D) * 8);
+  if (e == hipSuccess) e = nn->bad.alloc(256);
+  if (e != hipSuccess) {
+    delete nn;
+    return fail(ctx, e == hipErrorOutOfMemory ? SVGP_OOM : SVGP_HIP_ERROR, std::string("svgp_nn_create: ") + hipGetErrorString(e));
+  }
+  *out = nn;
+  return SVGP_OK;
+}
+
+int32_t svgp_nn_free(svgp_ctx* ctx, svgp_nn* nn) {
+  if (!nn) return SVGP_OK;
+  if (ctx) {
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+  delete nn;
+  return SVGP_OK;
+}
+
+int32_t svgp_nn_lml(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info) {
+  if (!ctx || !nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  double out[kNnGradSlots + SVGP_MAX_D];
+  return nn_eval(ctx, nn, desc, 0, lml_out, info, out);
+}
+
+int32_t svgp_nn_lml_grad(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info, double* d_variance,
+                         double* d_inv_lengthscale, double* d_diag) {
+  if (!ctx || !nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (!d_variance || !d_inv_lengthscale) {
+    const int rc = nn_check_desc(ctx, nn, desc);
+    return rc ? rc : fail(ctx, SVGP_INVALID_ARG, "null argument");
+  }
+  double out[kNnGradSlots + SVGP_MAX_D];
+  const int rc = nn_eval(ctx, nn, desc, 2, lml_out, info, out);
+  if (rc) return rc;
+  *d_variance = out[3];
+  if (d_diag) *d_diag = out[4];
+  for (int f = 0; f < nn->d; ++f) d_inv_lengthscale[f] = out[kNnGradSlots + f];
+  return SVGP_OK;
+}
+
+int32_t svgp_nn_fit(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info) {
+  if (!ctx || !nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  double out[kNnGradSlots + SVGP_MAX_D];
+  return nn_eval(ctx, nn, desc, 1, lml_out, info, out);
+}
+
+int32_t svgp_nn_factors(svgp_ctx* ctx, svgp_nn* nn, void* B_out, void* F_out, void* alpha_out) {
+  if (!ctx || !nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (!nn->have_fit) return fail(ctx, SVGP_INVALID_ARG, "no successful svgp_nn_fit on this handle yet");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int64_t N = nn->N;
+  if (B_out && nn->P.k > 0) HIPC(ctx, hipMemcpyAsync(B_out, nn->Bd.p, size_t(N) * nn->P.k * nn->es, hipMemcpyDeviceToHost, s));
+  DevBuf tmp;
+  HIPC(ctx, tmp.alloc(size_t(N) * nn->es));
+  for (int q = 0; q < 2; ++q) {
+    void* dst = q ? alpha_out : F_out;
+    if (!dst) continue;
+    NN_DISPATCH(nn->dtype, T, {
+      hipLaunchKernelGGL(nn_cast_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, (const double*)(q ? nn->alpha : nn->Fd).as<double>(), N, 0.0, 1.0,
+                         (T*)tmp.p);
+    });
+    KCHECK(ctx, "nn_cast");
+    HIPC(ctx, hipMemcpyAsync(dst, tmp.p, size_t(N) * nn->es, hipMemcpyDeviceToHost, s));
+  }
+  HIPC(ctx, hipStreamSynchronize(s));
+  return SVGP_OK;
+}
+
+int32_t svgp_nn_predict(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t n, const void* x_host, void* mean_out, void* var_out,
+                        void* cov_out) {
+  if (!ctx || !nn || !x_host) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (!nn->have_fit) return fail(ctx, SVGP_INVALID_ARG, "no successful svgp_nn_fit on this handle yet");
+  if (n < 1) return fail(ctx, SVGP_INVALID_ARG, "no test points");
+  if (cov_out && n > kNnMaxCov) return fail(ctx, SVGP_UNSUPPORTED, "cov of more than 4096 test points");
+  if (n > kNnMaxPred) return fail(ctx, SVGP_UNSUPPORTED, "more than 131072 test points in one call");
+  NnHold h{ctx};
+  const int rc = svgp_data_upload(ctx, nn->dtype, layout, nn->d, n, x_host, nullptr, &h.D);
+  if (rc) return rc;
+  return nn_predict_impl(ctx, nn, h.D, nullptr, mean_out, var_out, cov_out);
+}
+
+int32_t svgp_nn_predict_cross_cov(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t nx, const void* x_host, int64_t ny,
+                                  const void* y_host, void* cov_out) {
+  if (!ctx || !nn || !x_host || !y_host || !cov_out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (!nn->have_fit) return fail(ctx, SVGP_INVALID_ARG, "no successful svgp_nn_fit on this handle yet");
+  if (nx < 1 || ny < 1) return fail(ctx, SVGP_INVALID_ARG, "no test points");
+  if (nx > kNnMaxCov || ny > kNnMaxCov) return fail(ctx, SVGP_UNSUPPORTED, "cov of more than 4096 test points");
+  NnHold hx{ctx}, hy{ctx};
+  int rc = svgp_data_upload(ctx, nn->dtype, layout, nn->d, nx, x_host, nullptr, &hx.D);
+  if (!rc) rc = svgp_data_upload(ctx, nn->dtype, layout, nn->d, ny, y_host, nullptr, &hy.D);
+  if (rc) return rc;
+  return nn_predict_impl(ctx, nn, hx.D, hy.D, nullptr, nullptr, cov_out);
+}
+
+}  // extern "C"

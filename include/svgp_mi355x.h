@@ -39,7 +39,7 @@ extern "C" {
                               fields appended since are read through the sized call.  Additions only: v2 / v3 callers keep working.
                               Entry points added without a version step (hosts find them by symbol: dlsym / hasattr): svgp_elbo_grad_inputs,
                               svgp_elbo_grad_ext_inputs, svgp_model_set_mean_z, svgp_elbo_with_mean, svgp_marginals_with_mean,
-                              svgp_elbo_grad_with_mean */
+                              svgp_elbo_grad_with_mean, svgp_laplace_*, svgp_nn_* */
 
 /* status codes -> Julia exceptions raised by the shim */
 enum {
@@ -461,6 +461,65 @@ int32_t svgp_laplace_predict(svgp_ctx* ctx, svgp_laplace* la, int32_t layout, in
 int32_t svgp_laplace_predict_cross_cov(svgp_ctx* ctx, svgp_laplace* la, int32_t layout, int64_t nx, const void* x_host, int64_t ny,
                                        const void* y_host, void* cov_out);
 int32_t svgp_laplace_free(svgp_ctx* ctx, svgp_laplace* la);
+
+/* ---- the NearestNeighbors (Vecchia) approximation: NearestNeighbors(k) / posterior / approx_lml  (src/NearestNeighborsModule.jl) ----
+ * p(f) = prod_i p(f_i | f_ns(i)), ns(i) = the m = min(i, k) points BEFORE i in the order of the data handle (the reference's index
+ * order; any reordering is the caller's).  Per point (0-based i), C = k(ns, ns) + diag I, c = k(ns, x_i), kd = k(x_i, x_i) + diag:
+ *   b_i = C \ c (make_row :27-29),  F_i = kd - c' b_i (make_F :46-61; F_0 = kd),  delta = y - mean_const,  r_i = delta_i - b_i' delta_ns
+ *   approx_lml = -1/2 sum_i (log 2 pi + log F_i + r_i^2 / F_i)   (:108-113: logdet(InvRoot(U)) = sum log F_i, alpha' delta = sum r_i^2 / F_i)
+ * one dense Cholesky of order <= k per point, one wavefront each; N is bounded by device memory only (no N x N matrix).
+ * diag: the reference builds U from the kernel alone and ignores fx.Sigma_y (:100-101): diag = 0 is the reference.  diag = sigma^2
+ * gives the Vecchia approximation of logpdf(fx, y) itself (k = N - 1: the exact GP).  The reference solves by LU; here Cholesky, and
+ * a block or an F_i that is not positive is reported: SVGP_NOT_POSDEF, svgp_nn_info.first_bad = 1-based index of the first such point,
+ * lml = NaN.  "Not positive" is: at or below 4 eps (m + 1) kd, the rounding noise of kd - c' b_i in the data dtype (an exactly repeated
+ * point with diag = 0 leaves +-1e-16 of either sign there, not an exact zero).
+ *   svgp_nn_lml        the value.  k >= N is k = N - 1; N = 1 is valid.
+ *   svgp_nn_lml_grad   value, d / d variance, d / d inv_lengthscale (d entries) and, when d_diag is not NULL, d / d diag: closed form,
+ *                      gF = -1/(2F) + r^2/(2F^2), w = C \ delta_ns: kd_bar = gF, c_bar = -2 gF b + (r/F) w,
+ *                      C_bar = gF b b' - (r/F) sym(w b').  x, y and mean_const are not differentiated.
+ *   svgp_nn_fit        the value, and caches b_i, F_i and alpha = U (U' delta) (:103) on the handle for the calls below.
+ *   svgp_nn_factors    B_out: N x kb column-major, kb = min(k, N - 1), B(i, t) = the coefficient of point i on point i - kb + t (zero
+ *                      where that index is negative: the rows i < kb are shorter); F_out, alpha_out: N.  Data dtype, any may be NULL.
+ *   svgp_nn_predict    PosteriorGP with C = InvRoot(U): mean = mean_const + k(x*, x) alpha, var = k(x*, x*) - colsumsq(V),
+ *                      cov = k(x*, x*) - V'V, V = U' k(x, x*): row i = (k(x_i, x*) - sum_j B_ij k(x_j, x*)) / sqrt(F_i).  n values
+ *                      (mean, var) / n x n column-major (cov), data dtype, any may be NULL.  x* in `layout` with the data's d.
+ *   svgp_nn_predict_cross_cov   cov(x*, y*) = k(x*, y*) - Vx' Vy, nx x ny column-major.
+ * Workspace rule of the predictions: V is streamed in row tiles of min(2048, 2^23 / n*p) points (a multiple of 64, at least 64; n*p =
+ * n* rounded up to 128) and never held at N x n*; so N * n* is not capped, n* is: 4096 for cov / cross-cov (the n*p x n*p accumulator),
+ * 131072 for mean / var in one call - beyond them SVGP_UNSUPPORTED, the caller tiles x*.
+ * fp64 and fp32 data (F_i, r_i and every sum over points in fp64 for both); SE / Matern-3/2 / Matern-5/2 with ARD, d <= SVGP_MAX_D;
+ * 1 <= min(k, N - 1) <= 64 neighbours (more: SVGP_UNSUPPORTED; k >= N counts as N - 1, so it is valid up to N = 65).  Every result is bitwise repeatable: fixed-order reductions, no floating-point atomics.
+ * SVGP_INVALID_ARG, before anything is enqueued: NULL required pointers, data without y, a descriptor whose dtype / d differ from the
+ * data's, k < 1, variance <= 0, diag < 0, reserved != 0; factors / predict before a successful fit.  Never collective: on a context
+ * with a communicator these calls stay local.  Found by symbol (no ABI version step). */
+typedef struct svgp_nn svgp_nn;
+typedef struct svgp_nn_desc {
+  int32_t dtype;            /* SVGP_F64 | SVGP_F32: must be the data's */
+  int32_t kernel;           /* SVGP_KERNEL_* */
+  int32_t d;                /* must be the data's */
+  int32_t k;                /* neighbours: >= 1, min(k, N - 1) <= 64 */
+  double variance;          /* kernel variance */
+  const double* inv_lengthscale; /* d entries */
+  double diag;              /* added to every diagonal entry (0: the reference) */
+  double mean_const;        /* ConstMean value, 0 for ZeroMean */
+  int64_t reserved;         /* must be 0 */
+} svgp_nn_desc;             /* 56 bytes */
+typedef struct svgp_nn_info {
+  int64_t first_bad;        /* 0, or the 1-based index of the first point whose block or F_i is not positive */
+  int64_t n_neg_f;          /* number of points with F_i <= 0 */
+  double lml;
+} svgp_nn_info;             /* 24 bytes */
+int32_t svgp_nn_create(svgp_ctx* ctx, const svgp_data* data, svgp_nn** out);
+int32_t svgp_nn_lml(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info);
+int32_t svgp_nn_lml_grad(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info, double* d_variance,
+                         double* d_inv_lengthscale, double* d_diag);
+int32_t svgp_nn_fit(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info);
+int32_t svgp_nn_factors(svgp_ctx* ctx, svgp_nn* nn, void* B_out, void* F_out, void* alpha_out);
+int32_t svgp_nn_predict(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t n, const void* x_host, void* mean_out, void* var_out,
+                        void* cov_out);
+int32_t svgp_nn_predict_cross_cov(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t nx, const void* x_host, int64_t ny,
+                                  const void* y_host, void* cov_out);
+int32_t svgp_nn_free(svgp_ctx* ctx, svgp_nn* nn);
 
 #ifdef __cplusplus
 }

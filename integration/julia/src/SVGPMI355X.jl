@@ -803,4 +803,84 @@ function laplace_cross_cov(L::DeviceLaplace, x, y, ::Type{T}) where {T<:FT}
     return C
 end
 
+# ---------------------------------------------------------------------------------------------------------
+# NearestNeighbors(k) (src/NearestNeighborsModule.jl): a resident handle over DeviceData (svgp_nn_*).  approx_lml (:108-113), its
+# gradient with respect to (variance, inv_lengthscale, diag), posterior (:97-106) and the predictions on the device.  The
+# neighbours of a point are the k points before it in the order of D.  Not hooked into the reference's methods; a host calls these.
+# ---------------------------------------------------------------------------------------------------------
+struct NNDesc                         # svgp_nn_desc (56 bytes)
+    dtype::Int32; kernel::Int32; d::Int32; k::Int32
+    variance::Float64; inv_lengthscale::Ptr{Float64}; diag::Float64; mean_const::Float64; reserved::Int64
+end
+mutable struct NNInfo                 # svgp_nn_info (24 bytes)
+    first_bad::Int64; n_neg_f::Int64; lml::Float64
+    NNInfo() = new(0, 0, 0)
+end
+mutable struct DeviceNN
+    h::Ptr{Cvoid}; data::DeviceData
+end
+function DeviceNN(D::DeviceData)
+    h = Ref{Ptr{Cvoid}}()
+    check(ccall((:svgp_nn_create, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), ctx(), D.h, h))
+    N = DeviceNN(h[], D)
+    finalizer(N -> (CTX[] == C_NULL || N.h == C_NULL) ||
+                   ccall((:svgp_nn_free, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), CTX[], N.h), N)
+    return N
+end
+nn_check(st, info::NNInfo) = st == 2 ? throw(PosDefException(Int(info.first_bad))) : check(st)
+"approx_lml(NearestNeighbors(desc.k), fx, y) (:108-113); desc.diag = 0 is the reference, which ignores fx.Σy."
+function nn_lml!(N::DeviceNN, desc::NNDesc)
+    out, info = Ref{Float64}(), NNInfo()
+    nn_check(ccall((:svgp_nn_lml, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{NNDesc}, Ref{Float64}, Ref{NNInfo}),
+                   ctx(), N.h, desc, out, info), info)
+    return out[], info
+end
+"approx_lml and its gradient with respect to (variance, inv_lengthscale, diag)."
+function nn_lml_and_grad!(N::DeviceNN, desc::NNDesc)
+    out, info, gv, gd = Ref{Float64}(), NNInfo(), Ref{Float64}(), Ref{Float64}()
+    gl = zeros(Float64, desc.d)
+    GC.@preserve gl nn_check(ccall((:svgp_nn_lml_grad, lib), Int32,
+                                   (Ptr{Cvoid}, Ptr{Cvoid}, Ref{NNDesc}, Ref{Float64}, Ref{NNInfo}, Ref{Float64}, Ptr{Float64}, Ref{Float64}),
+                                   ctx(), N.h, desc, out, info, gv, gl, gd), info)
+    return out[], gv[], gl, gd[], info
+end
+"posterior(NearestNeighbors(desc.k), fx, y) (:97-106): caches B, F and α on the device; returns approx_lml."
+function nn_fit!(N::DeviceNN, desc::NNDesc)
+    out, info = Ref{Float64}(), NNInfo()
+    nn_check(ccall((:svgp_nn_fit, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{NNDesc}, Ref{Float64}, Ref{NNInfo}),
+                   ctx(), N.h, desc, out, info), info)
+    return out[], info
+end
+"(B banded n × kb, F, α) of the last nn_fit!, kb = min(k, n - 1): B[i, t] is the coefficient of point i on point i - kb + t."
+function nn_factors(N::DeviceNN, k::Integer, ::Type{T}) where {T<:FT}
+    n = N.data.n
+    B, F, α = zeros(T, n, min(k, n - 1)), zeros(T, n), zeros(T, n)
+    check(ccall((:svgp_nn_factors, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx(), N.h, B, F, α))
+    return B, F, α
+end
+"mean_and_var / mean_and_cov of the PosteriorGP with C = InvRoot(U) at x."
+function nn_predict(N::DeviceNN, x, ::Type{T}; want_cov::Bool=false) where {T<:FT}
+    lx, X, _ = layout(x)
+    Xd = Array{T}(X)
+    n = npoints(lx, Xd)
+    μ, v = zeros(T, n), zeros(T, n)
+    C = want_cov ? zeros(T, n, n) : nothing
+    GC.@preserve Xd check(ccall((:svgp_nn_predict, lib), Int32,
+                                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                                ctx(), N.h, lx, n, Xd, μ, v, C === nothing ? C_NULL : C))
+    return μ, v, C
+end
+"cov(f, x, y) of the same posterior."
+function nn_cross_cov(N::DeviceNN, x, y, ::Type{T}) where {T<:FT}
+    lx, X, _ = layout(x)
+    _, Y, _ = layout(y)
+    Xd, Yd = Array{T}(X), Array{T}(Y)
+    nx, ny = npoints(lx, Xd), npoints(lx, Yd)
+    C = zeros(T, nx, ny)
+    GC.@preserve Xd Yd check(ccall((:svgp_nn_predict_cross_cov, lib), Int32,
+                                   (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                                   ctx(), N.h, lx, nx, Xd, ny, Yd, C))
+    return C
+end
+
 end # module

@@ -1,10 +1,10 @@
 #!/usr/bin/env bash
 # Builds the library of git HEAD into csrc/ablate/libsvgp_prev.so for same-box A/B timing against the working tree:
-# the six translation units and the flags of build.sh.  Needs a git checkout, so run it where the tree is one.
+# the translation units and the flags of build.sh.  Needs a git checkout, so run it where the tree is one.
 set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"; TMP=$(mktemp -d); OUT="$ROOT/approximategps.jl_amd/csrc/ablate"; mkdir -p "$OUT"
 git -C "$ROOT" archive HEAD approximategps.jl_amd/csrc include | tar -x -C "$TMP"
-UNITS="prep strip grad api comm laplace"
+UNITS="prep strip grad api comm laplace nn"
 pids=()
 for f in $UNITS; do
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function -c "$TMP/approximategps.jl_amd/csrc/$f.hip" -o "$TMP/$f.o" 2>/dev/null &

@@ -1,0 +1,112 @@
+"""NearestNeighbors (Vecchia) timings (csrc/nn.hip): approx_lml, value-and-gradient, fit and predict (n* = 1024, mean + var) for
+SE-ARD, d = 8, at N in {1e4, 1e5, 1e6}, k in {16, 32, 64}, fp64 and fp32.  Wall times by the host clock around calls that end in a
+device synchronise, after a warm-up of every shape; the median of --reps repeats, with the spread.  Beside each k the numpy
+restatement (tests/nn_ref.py lml_joint: one Cholesky per point, no N x N matrix) at --host-n points, the largest size it
+finishes well under a minute at.
+
+    python tools/nn_time.py [--sizes 10000 100000 1000000] [--ks 16 32 64] [--reps 5] [--host-n 10000] [--out profiles/nn/nn_time.jsonl]
+
+Rate: k^3 / 3 + 2 k^2 + k^2 (3 d + 20) / 2 flops per point (factorisation, the two carried rows, block generation) over the
+approx_lml wall time, against the FP64 / FP32 vector peaks 78.6 / 157.3 TFLOP/s (MI355X_MICROARCH.md, AMD's published FP64 figure).
+The device clock torch reports is noted per row when available."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "approximategps.jl_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+
+import torch  # noqa: E402,F401  (its HIP runtime first)
+
+import nn_ref as nr  # noqa: E402
+from approxgp import DeviceNearestNeighbors, _ffi  # noqa: E402
+from approxgp.kernels import ARDTransform, ScaledKernel, SEKernel, TransformedKernel  # noqa: E402
+
+PEAK_TF = {"float64": 78.6, "float32": 157.3}
+
+
+def flops_per_point(k, d):
+    return k ** 3 / 3 + 2 * k ** 2 + k ** 2 * (3 * d + 20) / 2
+
+
+def timed(fn, reps):
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return 1e3 * statistics.median(ts), 1e3 * min(ts), 1e3 * max(ts)
+
+
+def clock_mhz():
+    try:
+        return int(torch.cuda.clock_rate())
+    except Exception:
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[10_000, 100_000, 1_000_000])
+    ap.add_argument("--ks", type=int, nargs="+", default=[16, 32, 64])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--host-n", type=int, default=10_000)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    ctx = _ffi.Context(0)
+    d, var, diag = 8, 1.2, 1e-2
+    il = np.linspace(0.8, 1.1, d)
+    kern = ScaledKernel(TransformedKernel(SEKernel(), ARDTransform(il)), var)
+    out = open(a.out, "w") if a.out else None
+
+    def emit(row):
+        line = json.dumps(row)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    host = {}
+    for k in a.ks:
+        x, y = nr.synth(a.host_n, d, seed=1)
+        t0 = time.perf_counter()
+        ref = nr.lml_joint(nr.kernel_of(0, var, il), x, y, k, diag)
+        host[k] = (1e3 * (time.perf_counter() - t0), ref)
+        emit({"host_numpy": True, "n": a.host_n, "k": k, "approx_lml_ms": round(host[k][0], 1), "lml": ref})
+    for n in a.sizes:
+        x, y = nr.synth(n, d, seed=1)
+        xs = np.random.default_rng(2).uniform(-2, 2, size=(d, 1024))
+        for dt in (np.float64, np.float32):
+            dev = DeviceNearestNeighbors(ctx, x.astype(dt), y.astype(dt), dt)
+            for k in a.ks:
+                desc, keep = dev.desc(kern, k, diag)
+                lml = dev.lml(desc)[0]      # warm-up of every shape
+                dev.lml_grad(desc)
+                dev.fit(desc)
+                dev.predict(xs.astype(dt))
+                t_lml = timed(lambda: dev.lml(desc), a.reps)
+                t_grad = timed(lambda: dev.lml_grad(desc), a.reps)
+                t_fit = timed(lambda: dev.fit(desc), a.reps)
+                t_pred = timed(lambda: dev.predict(xs.astype(dt)), a.reps)
+                name = np.dtype(dt).name
+                tf = n * flops_per_point(k, d) / (t_lml[0] * 1e-3) / 1e12
+                row = {"n": n, "k": k, "dtype": name, "lml": lml, "clock_mhz": clock_mhz(), "reps": a.reps,
+                       "approx_lml_ms": [round(v, 3) for v in t_lml], "value_and_grad_ms": [round(v, 3) for v in t_grad],
+                       "fit_ms": [round(v, 3) for v in t_fit], "predict_1024_mean_var_ms": [round(v, 3) for v in t_pred],
+                       "lml_tflops": round(tf, 3), "share_of_vector_peak": round(tf / PEAK_TF[name], 4)}
+                if n == a.host_n and dt == np.float64:
+                    row["host_numpy_approx_lml_ms"] = round(host[k][0], 1)
+                    row["host_rel_diff"] = abs(lml - host[k][1]) / abs(host[k][1])
+                emit(row)
+            dev.free()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
