@@ -21,5 +21,7 @@ from .laplace import (DeviceLaplace, LaplaceApproximation, LaplaceObjective, Lap
 # NearestNeighbors (Vecchia); approx_lml, approx_lml_and_gradient and posterior dispatch on it too (the methods above are unchanged)
 from .nearest_neighbors import (DeviceNearestNeighbors, NearestNeighbors, NNPosteriorGP, approx_lml, approx_lml_and_gradient,
                                 posterior)
+# VFE(fz): the collapsed (Titsias) bound and the optimal q(u); elbo, elbo_and_gradient, approx_lml and posterior dispatch on it too
+from .vfe import VFE, approx_lml, elbo, elbo_and_gradient, optimal_variational_posterior, posterior
 
 __all__ = [n for n in dir() if not n.startswith("_")]

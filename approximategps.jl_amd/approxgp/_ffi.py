@@ -88,6 +88,13 @@ class NNInfo(C.Structure):
     _fields_ = [("first_bad", C.c_int64), ("n_neg_f", C.c_int64), ("lml", C.c_double)]
 
 
+class CollapsedTerms(C.Structure):
+    """svgp_collapsed_terms: the collapsed (Titsias) bound and its parts."""
+    _fields_ = [("bound", C.c_double), ("fit", C.c_double), ("trace", C.c_double), ("logdet_B", C.c_double),
+                ("logdet_kuu", C.c_double), ("n_points", C.c_int64), ("chol_info", C.c_int32), ("chol_info_b", C.c_int32),
+                ("reserved", C.c_int64)]
+
+
 # every symbol include/svgp_mi355x.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -153,6 +160,11 @@ SYMBOLS = {
     "svgp_nn_predict": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P]),
     "svgp_nn_predict_cross_cov": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P, _P]),
     "svgp_nn_free": (C.c_int32, [_P, _P]),
+    # the collapsed bound and the optimal q
+    "svgp_collapsed_bound": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.POINTER(CollapsedTerms)]),
+    "svgp_collapsed_q": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, C.POINTER(C.c_double)]),
+    "svgp_collapsed_grad": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.POINTER(CollapsedTerms),
+                                        C.POINTER(Grads), C.POINTER(InputGrad)]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),
     "svgp_ctx_attach_comm": (C.c_int32, [_P, _P, C.c_int32, C.c_int32]),
@@ -582,6 +594,64 @@ class DeviceModel:
             res["x"] = xb
         if mxb is not None:
             res["mean_x"] = mxb
+        return out.value, terms, res
+
+    # ---- the collapsed (Titsias) bound and the optimal q (svgp_collapsed_*) ----
+    def _collapsed_check(self, rc, terms):
+        if rc == NOT_POSDEF and terms is not None:
+            msg = (self.ctx.lib.svgp_last_error(self.ctx.h) or b"").decode()
+            raise PosDefException(terms.chol_info if terms.chol_info else terms.chol_info_b, msg)
+        self.ctx.check(rc)
+
+    def collapsed_bound(self, data: DeviceData, off=0, length=None):
+        """-> (bound, CollapsedTerms): one data pass; the model's q is neither read nor changed."""
+        length = data.n - off if length is None else length
+        out, terms = C.c_double(), CollapsedTerms()
+        self._collapsed_check(self.ctx.lib.svgp_collapsed_bound(self.ctx.h, self.h, data.h, off, length, C.byref(out), C.byref(terms)), terms)
+        return out.value, terms
+
+    def collapsed_q(self, data: DeviceData, off=0, length=None, fetch=True):
+        """Writes the optimal q into the model's device-resident m / Lq (the model's own parametrisation) -> (bound, m, Lq); m and
+        Lq are host copies in the model's dtype (Lq lower triangular), None with fetch=False."""
+        length = data.n - off if length is None else length
+        dt = np_dtype(self.dtype)
+        mb = np.zeros(self.M, dtype=dt) if fetch else None
+        Lb = np.zeros((self.M, self.M), dtype=dt, order="F") if fetch else None
+        out = C.c_double()
+        self.ctx.check(self.ctx.lib.svgp_collapsed_q(self.ctx.h, self.h, data.h, off, length, _ptr(mb), _ptr(Lb), C.byref(out)))
+        return out.value, mb, Lb
+
+    def collapsed_grad(self, data: DeviceData, off=0, length=None, z_shape=None, inputs=None):
+        """-> (bound, CollapsedTerms, dict(variance, inv_lengthscale, z, lik_sigma2, mean_const[, x])): the bound's total derivatives
+        (svgp_collapsed_q, then the value-and-gradient at that q).  inputs = True: also d bound / d x as dict["x"] (host, the data's
+        layout); inputs = (device_ptr, ld): written to device memory as in elbo_grad."""
+        length = data.n - off if length is None else length
+        dt = np_dtype(self.dtype)
+        gx, xb = None, None
+        if inputs is not None and inputs is not False:
+            if inputs is True:
+                layout = getattr(data, "layout", COLVECS)
+                if layout == VEC:
+                    xb = np.zeros(length, dtype=dt)
+                elif layout == COLVECS:
+                    xb = np.zeros((data.d, length), dtype=dt)
+                else:
+                    xb = np.zeros((length, data.d), dtype=dt, order="F")
+                gx = InputGrad(_ptr(xb), length, 0, 0)
+            else:
+                ptr, ld = inputs
+                gx = InputGrad(C.c_void_p(int(ptr)), int(ld), 1, 0)
+        zshape = z_shape if z_shape is not None else ((self.M,) if self.d == 1 else (self.d, self.M))
+        il = np.zeros(self.d)
+        zb = np.zeros(zshape, dtype=dt, order="F")
+        g = Grads(0.0, 0.0, 0.0, il.ctypes.data_as(C.POINTER(C.c_double)), _ptr(zb), None, None)
+        out, terms = C.c_double(), CollapsedTerms()
+        rc = self.ctx.lib.svgp_collapsed_grad(self.ctx.h, self.h, data.h, off, length, C.byref(out), C.byref(terms), C.byref(g),
+                                              C.byref(gx) if gx is not None else None)
+        self._collapsed_check(rc, terms)
+        res = dict(variance=g.variance, inv_lengthscale=il, z=zb, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const)
+        if xb is not None:
+            res["x"] = xb
         return out.value, terms, res
 
     def prior_kl(self):

@@ -1,0 +1,219 @@
+// collapsed.hip — the collapsed (Titsias 2009, eqs. 11 / 12) bound of sparse GP regression and the optimal q(u): the kernels that are
+// NOT the data pass (strip.hip: trsm_pm_kernel gives A = Lk \ Kuf point-major and sum A^2 per point; grad.hip: syrk_async_kernel gives
+// C = A A').  api.hip: collapsed_run is the schedule.  The reference builds the same q on the host (test/test_utils.jl:7-17,
+// optimal_variational_posterior) and compares it with AbstractGPs' VFE posterior (test/SparseVariationalApproximationModule.jl:99-134).
+//   data-sized   b = A r, rr = r'r, t = sum_j |A_j|^2 over the resident point-major chunk          collapsed_reduce_kernel
+//   M-sized      B = I + C / sigma^2 (fp64, from the SYRK's slices), c~ = b / sigma^2              collapsed_form_b_kernel
+//                cholesky(B), c = LB \ c~, m_w = LB' \ c, B^-1 = LBinv' LBinv, cholesky(B^-1)      prep.hip / grad.hip launchers, fp64
+//                sum log diag LB, c'c                                                              collapsed_scal_kernel
+//                q in the model's parametrisation and layout                                       collapsed_write_q_kernel
+// The M-sized tail runs in fp64 whatever the model's dtype: cond(B) = 1 + lambda_max(C) / sigma^2 grows with the number of points
+// (~ n variance / sigma^2: 1e7 at n = 1e6), so eps_fp32 cond(B) reaches 1 long before the headline size.
+// Every sum has a fixed split and a fixed order: results are bitwise repeatable, no floating-point atomics.
+#include "device_common.hpp"
+#include "kernels.hpp"
+
+namespace svgp {
+namespace {
+
+// bpart[s][k] (+)= sum_{j in split s} A_kj r_j,  spart[s] (+)= {sum r_j^2, sum ssq_j} over the same points; r_j = y_j - mean_const.
+// At point-major [n][Mp]: a thread owns one k, a workgroup 128 consecutive k (coalesced rows), gridDim.y = kCollapsedSplit splits of
+// the chunk's n points.  first: overwrite (the first chunk of a call), else add to what the previous chunks left - the chunks follow
+// each other on one stream, so the order of the additions is fixed.
+template <typename T>
+__global__ void __launch_bounds__(128) collapsed_reduce_kernel(const T* __restrict__ At, const T* __restrict__ y, const double* __restrict__ ssq,
+                                                               int64_t Mp, int64_t off, int64_t n, double mean_const, int first,
+                                                               double* __restrict__ bpart, double* __restrict__ spart) {
+  const int64_t k = int64_t(blockIdx.x) * 128 + threadIdx.x;
+  const int64_t per = (n + gridDim.y - 1) / gridDim.y;
+  const int64_t j0 = int64_t(blockIdx.y) * per;
+  int64_t j1 = j0 + per;
+  j1 = j1 < n ? j1 : n;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int64_t j = j0; j < j1; ++j) acc = fma(double(At[j * Mp + k]), double(y[off + j]) - mean_const, acc);
+  double* bp = bpart + int64_t(blockIdx.y) * Mp + k;
+  *bp = first ? acc : *bp + acc;
+  if (blockIdx.x == 0) {
+    __shared__ double sh[2][128];
+    double rr = 0.0, t = 0.0;
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += 128) {
+      const double r = double(y[off + j]) - mean_const;
+      rr = fma(r, r, rr);
+      t += ssq[j];
+    }
+    sh[0][threadIdx.x] = rr;
+    sh[1][threadIdx.x] = t;
+    __syncthreads();
+    for (int w = 64; w > 0; w >>= 1) {
+      if (int(threadIdx.x) < w) {
+        sh[0][threadIdx.x] += sh[0][threadIdx.x + w];
+        sh[1][threadIdx.x] += sh[1][threadIdx.x + w];
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x < 2) {
+      double* sp = spart + int64_t(blockIdx.y) * 2 + threadIdx.x;
+      *sp = first ? sh[threadIdx.x][0] : *sp + sh[threadIdx.x][0];
+    }
+  }
+}
+
+// Bm (fp64, Mp x Mp, full and exactly symmetric) = I + (sum of the SYRK's slices) / sigma^2: entry (r, c) reads the lower-tile entry
+// (max, min) of every slice in slice order.  Row 0's workgroups also close the reductions: cvec[k] = sum_s bpart[s][k] / sigma^2,
+// scal[0] = rr, scal[1] = t.
+template <typename T>
+__global__ void __launch_bounds__(k256) collapsed_form_b_kernel(const T* __restrict__ G, int nslices, int64_t Mp, double inv_sigma2,
+                                                                const double* __restrict__ bpart, const double* __restrict__ spart, int nsplit,
+                                                                double* __restrict__ Bm, double* __restrict__ cvec, double* __restrict__ scal) {
+  const int64_t c = int64_t(blockIdx.x) * k256 + threadIdx.x, r = blockIdx.y;
+  if (c >= Mp) return;
+  const int64_t hi = r > c ? r : c, lo = r > c ? c : r;
+  double v = 0.0;
+  for (int s = 0; s < nslices; ++s) v += double(G[int64_t(s) * Mp * Mp + hi * Mp + lo]);
+  Bm[r * Mp + c] = (r == c ? 1.0 : 0.0) + v * inv_sigma2;
+  if (r == 0) {
+    double b = 0.0;
+    for (int s = 0; s < nsplit; ++s) b += bpart[int64_t(s) * Mp + c];
+    cvec[c] = b * inv_sigma2;
+    if (c < 2) {
+      double q = 0.0;
+      for (int s = 0; s < nsplit; ++s) q += spart[2 * s + c];
+      scal[c] = q;
+    }
+  }
+}
+
+// scal[2] = sum log diag LB, scal[3] = c'c, scal[4] = info of cholesky(B), scal[5] = info of cholesky(B^-1) (nullable), one workgroup
+__global__ void __launch_bounds__(k256) collapsed_scal_kernel(const double* __restrict__ LB, const double* __restrict__ c, int64_t Mp,
+                                                              const int* __restrict__ info_b, const int* __restrict__ info_s,
+                                                              double* __restrict__ scal) {
+  __shared__ double sh[2][k256];
+  double ld = 0.0, cc = 0.0;
+  for (int64_t i = threadIdx.x; i < Mp; i += k256) {
+    ld += log(LB[i * (Mp + 1)]);
+    cc = fma(c[i], c[i], cc);
+  }
+  sh[0][threadIdx.x] = ld;
+  sh[1][threadIdx.x] = cc;
+  __syncthreads();
+  for (int w = k256 / 2; w > 0; w >>= 1) {
+    if (int(threadIdx.x) < w) {
+      sh[0][threadIdx.x] += sh[0][threadIdx.x + w];
+      sh[1][threadIdx.x] += sh[1][threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    scal[2] = sh[0][0];
+    scal[3] = sh[1][0];
+    scal[4] = double(*info_b);
+    scal[5] = info_s ? double(*info_s) : 0.0;
+  }
+}
+
+// *first_bad = 0, or the 1-based index of the first pivot of Lk (diagonal entry squared) at or below 4 eps (i + 1) kdiag, the rounding
+// noise of kdiag - sum_k L_ik^2 in the model's dtype (kdiag = variance + jitter), or NaN.  cholesky(Kuu) itself reports only pivots
+// <= 0, as LAPACK does; an exactly repeated inducing point at jitter 0 leaves +-1e-16 there, of either sign, and A = Lk \ Kuf built on
+// such a pivot is noise.  One workgroup.
+template <typename T>
+__global__ void __launch_bounds__(k256) collapsed_pivot_check_kernel(const T* __restrict__ Lk, int64_t M, int64_t Mp, double kdiag,
+                                                                     int* __restrict__ first_bad) {
+  __shared__ int sh[k256];
+  const double eps = sizeof(T) == 8 ? 2.220446049250313e-16 : 1.1920928955078125e-7;
+  int bad = 0x7fffffff;
+  for (int64_t i = threadIdx.x; i < M; i += k256) {
+    const double l = double(Lk[i * (Mp + 1)]);
+    if (!(l * l > 4.0 * eps * double(i + 1) * kdiag) && int(i + 1) < bad) bad = int(i + 1);
+  }
+  sh[threadIdx.x] = bad;
+  __syncthreads();
+  for (int w = k256 / 2; w > 0; w >>= 1) {
+    if (int(threadIdx.x) < w && sh[threadIdx.x + w] < sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *first_bad = sh[0] == 0x7fffffff ? 0 : sh[0];
+}
+
+// The optimal q into the model's own arrays (user layout: m [M], Lq M x M column-major, upper triangle zeroed).
+//   NonCentered: m = m_w, Lq = Lq_w;   Centered: m = mean_const + Lk m_w, Lq = Lk Lq_w (lower triangular, positive diagonal).
+// Lqw: the fp64 factor of B^-1 (column-major, ld Mp, lower part valid); Lk: the model's factor (model dtype, column-major, ld Mp).
+// Nothing is written when either factorisation failed (the model keeps its q); a NaN in the data sums (scal[0], scal[1]: a NaN
+// coordinate or observation) writes NaN, as the reference's arithmetic would.  gridDim.y = M columns, threads along the rows.
+template <typename T>
+__global__ void __launch_bounds__(k256) collapsed_write_q_kernel(const double* __restrict__ Lqw, const double* __restrict__ mw,
+                                                                 const T* __restrict__ Lk, int64_t M, int64_t Mp, int centered,
+                                                                 double mean_const, const double* __restrict__ scal,
+                                                                 const int* __restrict__ info_b, const int* __restrict__ info_s,
+                                                                 T* __restrict__ m_out, T* __restrict__ Lq_out) {
+  const int64_t i = int64_t(blockIdx.x) * k256 + threadIdx.x, j = blockIdx.y;
+  if (i >= M) return;
+  const bool nan_in = (scal[0] != scal[0]) || (scal[1] != scal[1]);
+  if (!nan_in && (*info_b != 0 || *info_s != 0)) return;
+  const double qnan = scal[0] + scal[1];   // NaN when nan_in
+  double v = 0.0;
+  if (i >= j) {
+    if (!centered) {
+      v = Lqw[i + j * Mp];
+    } else {
+      for (int64_t k = j; k <= i; ++k) v = fma(double(Lk[i + k * Mp]), Lqw[k + j * Mp], v);
+    }
+    if (nan_in) v = qnan;
+  }
+  Lq_out[i + j * M] = T(v);
+  if (j == 0) {
+    double mv = mw[i];
+    if (centered) {
+      mv = 0.0;
+      for (int64_t k = 0; k <= i; ++k) mv = fma(double(Lk[i + k * Mp]), mw[k], mv);
+      mv += mean_const;
+    }
+    m_out[i] = T(nan_in ? qnan : mv);
+  }
+}
+
+}  // namespace
+
+void launch_collapsed_reduce(int dtype, hipStream_t s, const void* At, const void* y, const double* ssq, int64_t Mp, int64_t off, int64_t n,
+                             double mean_const, int first, double* bpart, double* spart) {
+  const dim3 grid((unsigned)(Mp / 128), (unsigned)kCollapsedSplit);
+  if (dtype == 0)
+    hipLaunchKernelGGL(collapsed_reduce_kernel<double>, grid, dim3(128), 0, s, (const double*)At, (const double*)y, ssq, Mp, off, n, mean_const,
+                       first, bpart, spart);
+  else
+    hipLaunchKernelGGL(collapsed_reduce_kernel<float>, grid, dim3(128), 0, s, (const float*)At, (const float*)y, ssq, Mp, off, n, mean_const,
+                       first, bpart, spart);
+}
+
+void launch_collapsed_pivot_check(int dtype, hipStream_t s, const void* Lk, int64_t M, int64_t Mp, double kdiag, int* first_bad) {
+  if (dtype == 0) hipLaunchKernelGGL(collapsed_pivot_check_kernel<double>, dim3(1), dim3(k256), 0, s, (const double*)Lk, M, Mp, kdiag, first_bad);
+  else hipLaunchKernelGGL(collapsed_pivot_check_kernel<float>, dim3(1), dim3(k256), 0, s, (const float*)Lk, M, Mp, kdiag, first_bad);
+}
+
+void launch_collapsed_form_b(int dtype, hipStream_t s, const void* G, int nslices, int64_t Mp, double sigma2, const double* bpart,
+                             const double* spart, double* Bm, double* cvec, double* scal) {
+  const dim3 grid((unsigned)((Mp + k256 - 1) / k256), (unsigned)Mp);
+  if (dtype == 0)
+    hipLaunchKernelGGL(collapsed_form_b_kernel<double>, grid, dim3(k256), 0, s, (const double*)G, nslices, Mp, 1.0 / sigma2, bpart, spart,
+                       kCollapsedSplit, Bm, cvec, scal);
+  else
+    hipLaunchKernelGGL(collapsed_form_b_kernel<float>, grid, dim3(k256), 0, s, (const float*)G, nslices, Mp, 1.0 / sigma2, bpart, spart,
+                       kCollapsedSplit, Bm, cvec, scal);
+}
+
+void launch_collapsed_scal(hipStream_t s, const double* LB, const double* c, int64_t Mp, const int* info_b, const int* info_s, double* scal) {
+  hipLaunchKernelGGL(collapsed_scal_kernel, dim3(1), dim3(k256), 0, s, LB, c, Mp, info_b, info_s, scal);
+}
+
+void launch_collapsed_write_q(int dtype, hipStream_t s, const double* Lqw, const double* mw, const void* Lk, int64_t M, int64_t Mp, int centered,
+                              double mean_const, const double* scal, const int* info_b, const int* info_s, void* m_out, void* Lq_out) {
+  const dim3 grid((unsigned)((M + k256 - 1) / k256), (unsigned)M);
+  if (dtype == 0)
+    hipLaunchKernelGGL(collapsed_write_q_kernel<double>, grid, dim3(k256), 0, s, Lqw, mw, (const double*)Lk, M, Mp, centered, mean_const, scal,
+                       info_b, info_s, (double*)m_out, (double*)Lq_out);
+  else
+    hipLaunchKernelGGL(collapsed_write_q_kernel<float>, grid, dim3(k256), 0, s, Lqw, mw, (const float*)Lk, M, Mp, centered, mean_const, scal,
+                       info_b, info_s, (float*)m_out, (float*)Lq_out);
+}
+
+}  // namespace svgp

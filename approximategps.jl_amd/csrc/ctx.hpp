@@ -144,6 +144,7 @@ struct svgp_ctx {
   svgp::DevBuf pm_x;    // host-memory prior mean offsets of a call, copied in (svgp_*_with_mean)
   svgp::DevBuf pm_g;    // their gradient for a host destination, copied out (svgp_elbo_grad_with_mean)
   struct GradWs* gws = nullptr;  // gradient workspace, cached by problem shape (deleted by svgp_ctx_destroy)
+  struct CollapsedWs* cws = nullptr;   // fp64 M-sized tail of svgp_collapsed_*, cached by Mp (deleted by svgp_ctx_destroy)
   // data-parallel communicator (comm.hip): one RCCL rank per context; world == 1 without one
   void* comm = nullptr;        // ncclComm_t
   int world = 1, rank = 0;
@@ -177,6 +178,17 @@ struct GradWs {
   int64_t part5_strips = 0;
   size_t rp_uf_b = 0, sp_uf_b = 0, rp_uu_b = 0, sp_uu_b = 0, g_b = 0;
   svgp::DevBuf xg;   // d elbo / d x of a host-output svgp_elbo_grad_inputs call, [d][len], grown on demand
+};
+
+// device buffers of the M-sized tail of svgp_collapsed_* (fp64 whatever the model's dtype), sized by Mp
+struct CollapsedWs {
+  int64_t Mp = 0;
+  svgp::DevBuf Bm, TB, LinvRM, LinvCM, Ytmp, Sinv;   // B -> LB, its T panels, LB^-1 in both storage orders, scratch, B^-1 -> Lq_w (Mp x Mp doubles each)
+  svgp::DevBuf cvec, mw;       // c (Mp), m_w (Mp)
+  svgp::DevBuf bpart, spart;   // the split partials of b = A r and of {r'r, sum A^2}
+  svgp::DevBuf scal;           // [8] {rr, t, sum log diag LB, c'c, info_b, info_s, 0, 0}
+  svgp::DevBuf info_b, info_s; // cholesky info + hand-over counters of the two factorisations (int)
+  svgp::DevBuf gemv_part;
 };
 
 struct svgp_data {

@@ -134,6 +134,9 @@ void launch_strip_grad(int dtype, hipStream_t s, const StripArgs& a, int nt, int
 // marginals, expected log-likelihood and d E / d (mu, v) (x scale) of the points [off, off + len) of y from their moments: gmu_out /
 // gv_out (compute dtype, [len]) and part5[point_grad_blocks(len)][5] = per-block {E, sum g_mu, sum g_v, dE/dsigma2, n_neg}
 // gmu_copy (nullable): a second copy of gmu_out[0 .. len) (the prior mean offsets' gradient of svgp_elbo_grad_with_mean)
+// the collapsed bound's data pass: phase 1 ALONE (trsm_pm_kernel) - A point-major into a.At_out ([n][Mp]) and sum_k A_kj^2 (fp64) into
+// a.mom_var[j]; reads a.T, a.zs, a.x, a.work (ONE scratch strip per workgroup), a.counter; the widths and grids of launch_strip
+void launch_trsm_point_major(int dtype, hipStream_t s, const StripArgs& a, int nt, int grid, int64_t nstrips);
 int point_grad_blocks(int64_t len);
 void launch_point_grads(int dtype, hipStream_t s, const LikParams& lp, const double* mom_mu, const double* mom_var, const void* y,
                         int64_t off, int64_t len, double scale, const double* n_global_dev, double num_data, void* gmu_out,
@@ -213,5 +216,23 @@ void launch_finish_kgrad(int dtype, hipStream_t s, int d, int64_t M, int64_t Mp,
                          const double* rp_uf, int ns_uf, const double* rp_uu, int ns_uu, const double* sp_uf, int nsp_uf,
                          const double* sp_uu, int nsp_uu, const void* m, double klw, int layout_z, double variance,
                          void* z_bar, void* m_bar, double* scal_out, double* red, const double* avec);
+
+// ---- collapsed.hip (the collapsed bound and the optimal q: svgp_collapsed_*) ---------------------------------------------
+constexpr int kCollapsedSplit = 64;   // point splits of the b / rr / t reductions: a constant, so the summation order never depends on the chip
+// bpart[kCollapsedSplit][Mp] (+)= A r, spart[kCollapsedSplit][2] (+)= {r'r, sum ssq} over the n points of the resident point-major
+// chunk At ([n][Mp]); r_j = y[off + j] - mean_const; ssq[j] = sum_k A_kj^2 (fp64); first != 0 overwrites
+void launch_collapsed_reduce(int dtype, hipStream_t s, const void* At, const void* y, const double* ssq, int64_t Mp, int64_t off, int64_t n,
+                             double mean_const, int first, double* bpart, double* spart);
+// *first_bad = 0 or the 1-based index of the first pivot of Lk at or below its rounding noise 4 eps (i + 1) kdiag (model dtype's eps)
+void launch_collapsed_pivot_check(int dtype, hipStream_t s, const void* Lk, int64_t M, int64_t Mp, double kdiag, int* first_bad);
+// Bm (fp64, full) = I + sum(slices of G: the SYRK's lower tiles, model dtype) / sigma2; cvec = b / sigma2; scal[0] = r'r, scal[1] = sum A^2
+void launch_collapsed_form_b(int dtype, hipStream_t s, const void* G, int nslices, int64_t Mp, double sigma2, const double* bpart,
+                             const double* spart, double* Bm, double* cvec, double* scal);
+// scal[2] = sum log diag LB, scal[3] = c'c, scal[4] = *info_b, scal[5] = *info_s (info_s nullable)
+void launch_collapsed_scal(hipStream_t s, const double* LB, const double* c, int64_t Mp, const int* info_b, const int* info_s, double* scal);
+// the optimal q in the model's parametrisation into m_out [M] / Lq_out (M x M column-major, upper zeroed), model dtype
+void launch_collapsed_write_q(int dtype, hipStream_t s, const double* Lqw, const double* mw, const void* Lk, int64_t M, int64_t Mp, int centered,
+                              double mean_const, const double* scal, const int* info_b, const int* info_s, void* m_out, void* Lq_out);
+
 
 }  // namespace svgp

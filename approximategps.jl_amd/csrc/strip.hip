@@ -591,6 +591,126 @@ __global__ void __launch_bounds__(NTHR, MINW) strip_kernel(StripArgs a, int64_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The collapsed (Titsias) bound's data pass (api.hip: collapsed_run): phase 1 of the strips ALONE.  A strip's Kuf block is generated
+// into its scratch strip and solved against Lk through the T panels exactly as above (same pre-generation, same k-loops, same
+// arithmetic per point); A leaves point-major for the SYRK C = A A' and the reduction b = A r, and sum_k A_kj^2 (the trace term's
+// Qff_jj) per point in fp64 through a.mom_var.  No phase 2, no phase 3: 2 Mp^2 / 2 flops per point in here, the SYRK has the rest.
+// A kernel of its own rather than one more flag of the strip kernel above: nothing here reads q (U, mp, R), and the register allocation
+// of the 30 strip instantiations stays what it is.
+// ---------------------------------------------------------------------------------------------
+template <typename T, int NT, int BK, int NTHR, int MINW = 2, int PAD = 16, bool BIGD = false>
+__global__ void __launch_bounds__(NTHR, MINW) trsm_pm_kernel(StripArgs a, int64_t nstrips) {
+  using G = TileGemm<T, NT, BK, NTHR, PAD>;
+  using Acc = typename G::Acc;
+  using QRegs = typename G::QRegs;
+  constexpr int NB = G::NB, MI = G::MI, NJ = G::NJ;
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  T* smem = reinterpret_cast<T*>(smem_raw);
+  T* xs = smem;   // the strip's scaled inputs: read by the pre-generation only, so they alias the (then idle) staging buffers
+  const int pre_dl = BIGD ? (a.kp.d <= 32 ? 32 : 64) : (a.kp.d <= 8 ? 8 : 16);
+  const T* __restrict__ Tm = static_cast<const T*>(a.T);
+  const T* __restrict__ zs = static_cast<const T*>(a.zs);
+  const T* __restrict__ x = static_cast<const T*>(a.x);
+  const T* __restrict__ invl = static_cast<const T*>(a.kp.invl);
+  const int64_t Mp = a.Mp, M = a.M;
+  const int d = a.kp.d, family = a.kp.family;
+  const int nP = int(Mp / NB);
+  T* __restrict__ work = static_cast<T*>(a.work) + int64_t(blockIdx.x) * Mp * NT;
+  const int tid = threadIdx.x, lane = tid & 63;
+  [[maybe_unused]] const typename G::QOff qoff = G::q_offsets(NT);
+
+  __shared__ unsigned next_strip;
+#if SVGP_PREGEN_EXPTAB
+  __shared__ double s_exptab[64];
+  if (sizeof(T) == 8 && threadIdx.x < 64) s_exptab[threadIdx.x] = exp2(double(threadIdx.x) * 0.015625);
+  const double* exptab = s_exptab;
+#else
+  const double* exptab = nullptr;
+#endif
+  for (int64_t strip = blockIdx.x; strip < nstrips;) {
+    const int64_t c0 = strip * NT;
+    if (tid == 0) next_strip = gridDim.x + atomicAdd(a.counter, 1u);   // dynamic queue: which workgroup takes a strip does not change its arithmetic
+    const int64_t last = a.off + a.len - 1;
+    for (int e = tid; e < pre_dl * NT; e += NTHR) {   // columns past the batch end replicate the last point (their rows of A are never summed)
+      const int f = e / NT, c = e % NT;
+      int64_t g = a.off + c0 + c;
+      g = g > last ? last : g;
+      xs[e] = (f < d) ? x[int64_t(f) * a.ldx + g] * invl[f] : T(0);
+    }
+    __syncthreads();
+    if constexpr (BIGD) {
+      if (pre_dl == 32) {
+        if (family == KSE) pregen_mfma<T, NT, NTHR, KSE, 32>(xs, zs, d, Mp, M, a.kp.variance, work, exptab);
+        else if (family == KM32) pregen_mfma<T, NT, NTHR, KM32, 32>(xs, zs, d, Mp, M, a.kp.variance, work);
+        else pregen_mfma<T, NT, NTHR, KM52, 32>(xs, zs, d, Mp, M, a.kp.variance, work);
+      } else {
+        if (family == KSE) pregen_mfma<T, NT, NTHR, KSE, 64>(xs, zs, d, Mp, M, a.kp.variance, work, exptab);
+        else if (family == KM32) pregen_mfma<T, NT, NTHR, KM32, 64>(xs, zs, d, Mp, M, a.kp.variance, work);
+        else pregen_mfma<T, NT, NTHR, KM52, 64>(xs, zs, d, Mp, M, a.kp.variance, work);
+      }
+    } else if (pre_dl == 8) {
+      if (family == KSE) pregen_mfma<T, NT, NTHR, KSE, 8>(xs, zs, d, Mp, M, a.kp.variance, work, exptab);
+      else if (family == KM32) pregen_mfma<T, NT, NTHR, KM32, 8>(xs, zs, d, Mp, M, a.kp.variance, work);
+      else pregen_mfma<T, NT, NTHR, KM52, 8>(xs, zs, d, Mp, M, a.kp.variance, work);
+    } else {
+      if (family == KSE) pregen_mfma<T, NT, NTHR, KSE, 16>(xs, zs, d, Mp, M, a.kp.variance, work, exptab);
+      else if (family == KM32) pregen_mfma<T, NT, NTHR, KM32, 16>(xs, zs, d, Mp, M, a.kp.variance, work);
+      else pregen_mfma<T, NT, NTHR, KM52, 16>(xs, zs, d, Mp, M, a.kp.variance, work);
+    }
+    __syncthreads();
+
+    double sA[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) sA[j] = 0.0;
+    for (int I = 0; I < nP; ++I) {   // A_I = T[I, 0:(I+1)128] [A_<I ; K_I], K_I overwritten in place
+      Acc acc;
+      acc.zero();
+      if constexpr (SVGP_ASYNC && G::kAsync) {
+        auto qsrc = [&](int t) { return work + int64_t(t) * BK * NT; };
+        G::template loop_tri_async<(SVGP_TRI & 1) ? 1 : 0>(acc, Tm + int64_t(I) * NB, Mp, (I + 1) * (NB / BK), qsrc, smem);
+      } else {
+        auto qload = [&](int t, QRegs& r) { G::load_q(r, work + int64_t(t) * BK * NT, qoff); };
+        G::template loop_tri<(BK == 16 && (SVGP_TRI & 1)) ? 1 : 0>(acc, Tm + int64_t(I) * NB, Mp, (I + 1) * (NB / BK), qload, smem);
+      }
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = I * NB + G::acc_row(i, r);
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            const T val = acc.v[i][j][r];
+            work[int64_t(row) * NT + G::acc_col(j)] = val;
+            const double dv = double(val);
+            sA[j] = fma(dv, dv, sA[j]);
+          }
+        }
+      }
+      store_tile_point_major<G, T, NT, NTHR>(acc, smem, static_cast<T*>(a.At_out), c0, Mp, I * NB);
+      __syncthreads();  // scratch rows of panel I visible to the whole workgroup
+    }
+
+    double* red = reinterpret_cast<double*>(smem_raw);       // [WR][NT]; staging is idle here
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      double va = sA[j];
+      va += __shfl_xor(va, 16); va += __shfl_xor(va, 32);
+      if ((lane >> 4) == 0) red[((tid >> 6) / G::WC) * NT + G::acc_col(j)] = va;
+    }
+    __syncthreads();
+    if (tid < NT && c0 + tid < a.len) {
+      double qa = 0;
+#pragma unroll
+      for (int w = 0; w < G::WR; ++w) qa += red[w * NT + tid];
+      a.mom_var[c0 + tid] = qa;
+    }
+    strip = next_strip;
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // marginals + expected_loglikelihood (SVA:354-355): one point per thread, fixed-order block sums.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
@@ -1169,6 +1289,38 @@ void launch_strip_grad(int dtype, hipStream_t s, const StripArgs& a, int nt, int
     if (nt == 32) launch_strip_d<float, 32, true>(s, a, grid, nstrips);
     else if (nt == 64) launch_strip_d<float, 64, true>(s, a, grid, nstrips);
     else launch_strip_d<float, 128, true>(s, a, grid, nstrips);
+  }
+}
+
+// phase 1 alone (trsm_pm_kernel): A point-major into a.At_out, sum_k A_kj^2 into a.mom_var; the shapes of launch_strip
+namespace {
+template <typename T, int NT>
+void launch_trsm_pm_t(hipStream_t s, const StripArgs& a, int grid, int64_t nstrips) {
+  using G = TileGemm<T, NT, 16, 256, 16>;
+  const size_t lds = (SVGP_ASYNC && G::kAsync) ? G::ASYNC_LDS_BYTES : G::LDS_BYTES;
+  static_assert(G::LDS_BYTES >= size_t(64) * NT * sizeof(T) && (!(SVGP_ASYNC && G::kAsync) || G::ASYNC_LDS_BYTES >= size_t(64) * NT * sizeof(T)),
+                "x image must fit the staging buffers");
+  static_assert(G::LDS_BYTES >= size_t(G::WR) * NT * sizeof(double), "the per-strip sums reuse the staging buffers");
+  if (a.kp.d > 16) {
+    auto kern = trsm_pm_kernel<T, NT, 16, 256, 2, 16, true>;
+    set_max_lds(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, nstrips);
+  } else {
+    auto kern = trsm_pm_kernel<T, NT, 16, 256, 2, 16, false>;
+    set_max_lds(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, nstrips);
+  }
+}
+}  // namespace
+void launch_trsm_point_major(int dtype, hipStream_t s, const StripArgs& a, int nt, int grid, int64_t nstrips) {
+  if (dtype == 0) {
+    if (nt == 32) launch_trsm_pm_t<double, 32>(s, a, grid, nstrips);
+    else if (nt == 64) launch_trsm_pm_t<double, 64>(s, a, grid, nstrips);
+    else leave_note("internal: no phase-1 kernel for this (dtype, width)");
+  } else {
+    if (nt == 32) launch_trsm_pm_t<float, 32>(s, a, grid, nstrips);
+    else if (nt == 64) launch_trsm_pm_t<float, 64>(s, a, grid, nstrips);
+    else launch_trsm_pm_t<float, 128>(s, a, grid, nstrips);
   }
 }
 

@@ -39,7 +39,7 @@ extern "C" {
                               fields appended since are read through the sized call.  Additions only: v2 / v3 callers keep working.
                               Entry points added without a version step (hosts find them by symbol: dlsym / hasattr): svgp_elbo_grad_inputs,
                               svgp_elbo_grad_ext_inputs, svgp_model_set_mean_z, svgp_elbo_with_mean, svgp_marginals_with_mean,
-                              svgp_elbo_grad_with_mean, svgp_laplace_*, svgp_nn_* */
+                              svgp_elbo_grad_with_mean, svgp_laplace_*, svgp_nn_*, svgp_collapsed_* */
 
 /* status codes -> Julia exceptions raised by the shim */
 enum {
@@ -520,6 +520,54 @@ int32_t svgp_nn_predict(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t n, c
 int32_t svgp_nn_predict_cross_cov(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t nx, const void* x_host, int64_t ny,
                                   const void* y_host, void* cov_out);
 int32_t svgp_nn_free(svgp_ctx* ctx, svgp_nn* nn);
+
+/* ---- the collapsed bound of sparse GP regression and the optimal q(u)  (Titsias 2009, eqs. 11 / 12) ---------------------------------
+ * For the Gaussian likelihood the q(u) that maximises the ELBO has a closed form; the reference's tests build it on the host
+ * (test/test_utils.jl:7-17, optimal_variational_posterior), its user guide calls it "the optimal form for q(u)", and
+ * test/SparseVariationalApproximationModule.jl:99-134 ties the SVGP posterior at that q to AbstractGPs' posterior(VFE(fz), fx, y) and
+ * to exact GP regression.  With Kuu = k(z, z) + jitter I = Lk Lk', A = Lk \ Kuf over the window [batch_off, batch_off + batch_len) = n
+ * points, r = y - mean_const, C = A A', b = A r, t = tr C, rr = r'r, B = I + C / sigma^2 = LB LB', c = LB \ b / sigma^2:
+ *   bound = -n/2 log(2 pi sigma^2) - sum log diag LB - rr / (2 sigma^2) + c'c / 2 - (n variance - t) / (2 sigma^2)
+ *         = log N(r | 0, Qff + sigma^2 I)  [fit]  - tr(Kff - Qff) / (2 sigma^2)  [trace]          (the ELBO at the optimal q, num_data = n)
+ *   optimal whitened q: m_w = LB' \ c, S_w = inv(B);  Centered: m = mean_const + Lk m_w, Lq = Lk chol(S_w)
+ * One data pass (2 M^2 flops per point: a triangular solve and a SYRK, the count of svgp_elbo); only a point-major chunk of A
+ * (<= 65 536 points) lives in device memory, Kuf and A of the whole batch never exist.  The M-sized tail - B, its Cholesky factor, c,
+ * inv(B) and its factor - runs in fp64 whatever the model's dtype: cond(B) = 1 + lambda_max(C) / sigma^2 grows with n.
+ *   svgp_collapsed_bound  the bound and its terms.  The model's q is not read and not changed.
+ *   svgp_collapsed_q      also WRITES the optimal q into the model's device-resident m and Lq, in the model's own parametrisation
+ *                         (device to device; the model is prepared again, lazily): every later call on the model - svgp_elbo,
+ *                         svgp_elbo_grad*, svgp_posterior, svgp_predict*, svgp_marginals - sees it.  m_out (M) / Lq_out (M x M column-major,
+ *                         upper triangle zeroed): host arrays in the dtype and layout of the descriptor's m / Lq; either may be NULL.
+ *   svgp_collapsed_grad   svgp_collapsed_q, then the existing value-and-gradient at that q with num_data = batch_len.  d elbo / d q = 0
+ *                         there, so grads_out holds the TOTAL derivatives of the bound in variance, lik_sigma2, mean_const, the inverse
+ *                         lengthscales and z; grads_out->m and grads_out->Lq must be NULL.  gx: as in svgp_elbo_grad_inputs, NULL for no
+ *                         x_bar.  bound_out is the collapsed bound (not the second pass's ELBO, which equals it to rounding).
+ * A NaN coordinate or observation gives NaN results with SVGP_OK (the rule of svgp_elbo); svgp_collapsed_q then writes NaN.  Results
+ * are bitwise repeatable call to call: fixed splits, fixed-order sums, no floating-point atomics.
+ * SVGP_INVALID_ARG, before anything is enqueued: a likelihood other than SVGP_LIK_GAUSSIAN, a window outside the data, data without
+ * y, a dtype / d that differs from the model's, (grad) a NULL grads_out or non-NULL grads_out->m / ->Lq or a bad gx.
+ * SVGP_UNSUPPORTED: a context with a communicator attached, a model carrying muz.  Multi-GPU evaluation and prior mean offsets (the
+ * calls take no mux) are out of scope.  SVGP_NOT_POSDEF: a non-positive pivot of Kuu (chol_info) or of B (chol_info_b); the model's
+ * q is then left as it was.  For Kuu "non-positive" includes a pivot at or below its rounding noise, 4 eps (i + 1) (variance + jitter)
+ * in the model's dtype: an exactly repeated inducing point at jitter 0 leaves +-1e-16 there, not an exact zero, and A = Lk \\ Kuf
+ * built on it would be noise (the existing calls keep LAPACK's rule, pivot <= 0).  Found by symbol (no ABI version step). */
+typedef struct svgp_collapsed_terms {
+  double bound;        /* fit + trace */
+  double fit;          /* log N(r | 0, Qff + sigma^2 I) */
+  double trace;        /* -(n variance - tr C) / (2 sigma^2) */
+  double logdet_B;     /* 2 sum log diag LB */
+  double logdet_kuu;   /* 2 sum log diag Lk */
+  int64_t n_points;
+  int32_t chol_info;   /* 0, or the order of the first non-positive leading minor of Kuu */
+  int32_t chol_info_b; /* 0, or that of B (of inv(B), should its factorisation fail instead) */
+  int64_t reserved;    /* 0 */
+} svgp_collapsed_terms; /* 64 bytes */
+int32_t svgp_collapsed_bound(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                             double* bound_out, svgp_collapsed_terms* terms_out);
+int32_t svgp_collapsed_q(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len, void* m_out,
+                         void* Lq_out, double* bound_out);
+int32_t svgp_collapsed_grad(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                            double* bound_out, svgp_collapsed_terms* terms_out, svgp_grads* grads_out, const svgp_input_grad* gx);
 
 #ifdef __cplusplus
 }

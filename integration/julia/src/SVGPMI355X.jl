@@ -883,4 +883,46 @@ function nn_cross_cov(N::DeviceNN, x, y, ::Type{T}) where {T<:FT}
     return C
 end
 
+# ---------------------------------------------------------------------------------------------------------
+# The collapsed (Titsias 2009, eqs. 11 / 12) bound and the optimal q(u) on resident handles (svgp_collapsed_*): what the reference's
+# tests build on the host with optimal_variational_posterior (test/test_utils.jl:7-17) and compare with posterior(VFE(fz), fx, y)
+# (test/SparseVariationalApproximationModule.jl:99-134).  Gaussian likelihood, ZeroMean / ConstMean, one GPU.  Not hooked into the
+# reference's methods; a host calls these.
+# ---------------------------------------------------------------------------------------------------------
+mutable struct CollapsedTerms         # svgp_collapsed_terms (64 bytes)
+    bound::Float64; fit::Float64; trace::Float64; logdet_B::Float64; logdet_kuu::Float64
+    n_points::Int64; chol_info::Int32; chol_info_b::Int32; reserved::Int64
+    CollapsedTerms() = new(0, 0, 0, 0, 0, 0, 0, 0, 0)
+end
+collapsed_check(st, t::CollapsedTerms) =
+    st == 2 ? throw(PosDefException(Int(t.chol_info != 0 ? t.chol_info : t.chol_info_b))) : check(st)
+"The collapsed bound over the points off+1 : off+len of D (the model's q is neither read nor changed)."
+function collapsed_bound(Mo::DeviceModel, D::DeviceData; off::Integer=0, len::Integer=D.n - off)
+    out, t = Ref{Float64}(), CollapsedTerms()
+    collapsed_check(ccall((:svgp_collapsed_bound, lib), Int32,
+                          (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{Float64}, Ref{CollapsedTerms}),
+                          ctx(), Mo.h, D.h, off, len, out, t), t)
+    return out[], t
+end
+"Writes the optimal q into the model's device-resident m / Lq (its own parametrisation); returns (bound, m, Lq) as host arrays."
+function collapsed_q!(Mo::DeviceModel, D::DeviceData, M::Integer, ::Type{T}; off::Integer=0, len::Integer=D.n - off) where {T<:FT}
+    out = Ref{Float64}()
+    m, Lq = zeros(T, M), zeros(T, M, M)
+    check(ccall((:svgp_collapsed_q, lib), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Float64}),
+                ctx(), Mo.h, D.h, off, len, m, Lq, out))
+    return out[], m, LowerTriangular(Lq)
+end
+"The bound and its total derivatives in (variance, lik_sigma2, mean_const, inv_lengthscale, z); z_bar is d × M (ColVecs storage)."
+function collapsed_bound_and_grad!(Mo::DeviceModel, D::DeviceData, M::Integer, d::Integer, ::Type{T};
+                                   off::Integer=0, len::Integer=D.n - off) where {T<:FT}
+    out, t = Ref{Float64}(), CollapsedTerms()
+    gl, gz = zeros(Float64, d), zeros(T, d, M)
+    g = Grads(0.0, 0.0, 0.0, pointer(gl), pointer(gz), C_NULL, C_NULL)
+    GC.@preserve gl gz collapsed_check(ccall((:svgp_collapsed_grad, lib), Int32,
+                                             (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{Float64}, Ref{CollapsedTerms}, Ref{Grads}, Ptr{Cvoid}),
+                                             ctx(), Mo.h, D.h, off, len, out, t, g, C_NULL), t)
+    return out[], t, (variance=g.variance, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const, inv_lengthscale=gl, z=gz)
+end
+
 end # module
