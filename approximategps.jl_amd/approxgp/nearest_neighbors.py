@@ -16,13 +16,25 @@ from .kernels import unpack_kernel
 class NearestNeighbors:
     """NearestNeighbors(k) (NN:73-75): every point is conditioned on the k points before it in the given order.
     include_noise=False is the reference, which builds U from the kernel alone and ignores fx.Σy (NN:100-101); with
-    include_noise=True the isotropic fx.Σy joins every diagonal entry: the Vecchia approximation of logpdf(fx, y) itself."""
+    include_noise=True the isotropic fx.Σy joins every diagonal entry: the Vecchia approximation of logpdf(fx, y) itself.
+    neighbors: None is the reference's window of the previous k points; "nearest" conditions every point on its k nearest
+    predecessors, found on the device with the kernel's inverse lengthscales as the metric; an (n, min(k, n - 1)) integer array is
+    the caller's own table (row i: distinct indices below i, the valid ones first, -1 after them).  Gradients are taken at the
+    fixed table."""
 
-    def __init__(self, k: int, include_noise: bool = False):
+    def __init__(self, k: int, include_noise: bool = False, neighbors=None):
         if int(k) != k or int(k) < 1:
             raise ValueError("NearestNeighbors needs k >= 1")
         self.k = int(k)
         self.include_noise = bool(include_noise)
+        if isinstance(neighbors, str):
+            if neighbors != "nearest":
+                raise ValueError('neighbors is None, "nearest" or an integer array')
+        elif neighbors is not None:
+            neighbors = np.asarray(neighbors)
+            if neighbors.ndim != 2 or not np.issubdtype(neighbors.dtype, np.integer):
+                raise ValueError('neighbors is None, "nearest" or an (n, min(k, n - 1)) integer array')
+        self.neighbors = neighbors
 
 
 def _check_inputs(nn: NearestNeighbors, fx: FiniteGP, y):
@@ -90,8 +102,46 @@ class DeviceNearestNeighbors:
         self.kb = min(int(desc.k), self.n - 1)
         return lml.value, info
 
+    def set_neighbors(self, table):
+        """condition point i on the points table[i, :] ((n, kb) integers: distinct indices below i, the valid ones first, -1 after
+        them); k of the descriptors that follow must give kb = min(k, n - 1)"""
+        table = np.asarray(table)
+        if table.ndim != 2 or table.shape[0] != self.n or not np.issubdtype(table.dtype, np.integer):
+            raise ValueError("the neighbour table is an (n, kb) integer array")
+        kb = table.shape[1]
+        if kb != min(max(kb, 1), self.n - 1):
+            raise ValueError("the neighbour table has min(k, n - 1) columns, k >= 1")
+        t32 = np.asfortranarray(table, dtype=np.int32)
+        self.kb = None
+        self.ctx.check(self.ctx.lib.svgp_nn_set_neighbors(self.ctx.h, self.h, max(kb, 1), t32.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def build_neighbors(self, k, inv_lengthscale=None):
+        """the k nearest predecessors of every point under the metric inv_lengthscale ((d,), None: ones), found on the device"""
+        il = None
+        if inv_lengthscale is not None:
+            il = np.ascontiguousarray(np.broadcast_to(np.asarray(inv_lengthscale, dtype=np.float64), (self.d,)))
+        self.kb = None
+        self.ctx.check(self.ctx.lib.svgp_nn_build_neighbors(self.ctx.h, self.h, int(k),
+                                                            il.ctypes.data_as(C.POINTER(C.c_double)) if il is not None else None))
+
+    def neighbors(self):
+        """-> the handle's (n, kb) int32 table, None when it conditions on the window"""
+        kb = C.c_int32(-1)
+        self.ctx.check(self.ctx.lib.svgp_nn_get_neighbors(self.ctx.h, self.h, C.byref(kb), None))
+        if kb.value < 0:
+            return None
+        table = np.zeros((self.n, kb.value), dtype=np.int32, order="F")
+        if kb.value:
+            self.ctx.check(self.ctx.lib.svgp_nn_get_neighbors(self.ctx.h, self.h, C.byref(kb), table.ctypes.data_as(C.POINTER(C.c_int32))))
+        return table
+
+    def clear_neighbors(self):
+        self.kb = None
+        self.ctx.check(self.ctx.lib.svgp_nn_clear_neighbors(self.ctx.h, self.h))
+
     def factors(self):
-        """-> (B (n, kb) with B[i, t] the coefficient of point i on point i - kb + t, F (n,), alpha (n,)) of the last fit"""
+        """-> (B (n, kb) with B[i, t] the coefficient of point i on point i - kb + t (with a neighbour table: on point table[i, t]),
+        F (n,), alpha (n,)) of the last fit"""
         dt = _ffi.np_dtype(self.dtype)
         kb = self.kb or 0
         B = np.zeros((self.n, kb), dtype=dt, order="F")
@@ -162,6 +212,14 @@ def _device(nn: NearestNeighbors, fx: FiniteGP, y, ctx, dtype):
     diag, mean_const = _check_inputs(nn, fx, y)   # before the GPU is touched
     dev = DeviceNearestNeighbors(ctx or _ffi.default_context(), fx.x, y, _dtype_of(fx, dtype))
     desc, keep = dev.desc(fx.f.kernel, nn.k, diag, mean_const)
+    try:
+        if isinstance(nn.neighbors, str):
+            dev.build_neighbors(nn.k, keep)
+        elif nn.neighbors is not None:
+            dev.set_neighbors(nn.neighbors)
+    except Exception:
+        dev.free()
+        raise
     return dev, desc, keep
 
 

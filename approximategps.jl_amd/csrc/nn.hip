@@ -23,6 +23,7 @@
 //                    V tile with the column sums of the mean and of V.^2 (nn_v_kernel), V'V on the MFMA product kernel of the
 //                    gradient path (launch_gemm_pm) accumulated tile after tile in stream order
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
 
 #include <climits>
 #include <cmath>
@@ -96,16 +97,17 @@ __device__ __forceinline__ T nn_dkappa(int family, T r2) {
   return -T(5.0 / 6.0) * (T(1) + s) * kexp(-s);
 }
 
-// A[q] = |s_q - s_j|^2 for the neighbours q, j = lane (s = x .* invl), cr2 = |s_i - s_j|^2; inactive lanes carry s = 0
-template <typename T, int KB>
+// A[q] = |s_q - s_j|^2 for the neighbours q, j = lane (s = x .* invl), cr2 = |s_i - s_j|^2; inactive lanes carry s = 0.
+// The lane's neighbour is point base + lane (the window), or with G point `src` (a row of the neighbour table)
+template <typename T, int KB, bool G = false>
 __device__ __forceinline__ void nn_dist2(const NnParams& P, const T* __restrict__ x, int64_t base, int64_t i, int lane, int m, T (&A)[KB],
-                                         T& cr2) {
+                                         T& cr2, int64_t src = 0) {
 #pragma unroll
   for (int q = 0; q < KB; ++q) A[q] = T(0);
   cr2 = T(0);
   for (int f = 0; f < P.d; ++f) {
     const T il = T(P.invl[f]);
-    const T xj = lane < m ? x[int64_t(f) * P.ldx + base + lane] * il : T(0);
+    const T xj = lane < m ? x[int64_t(f) * P.ldx + (G ? src : base + lane)] * il : T(0);
     const T dc = xj - x[int64_t(f) * P.ldx + i] * il;
     cr2 = fma(dc, dc, cr2);
 #pragma unroll
@@ -121,19 +123,30 @@ __device__ __forceinline__ void nn_dist2(const NnParams& P, const T* __restrict_
 }
 
 // MODE 0: the lml slots.  MODE 1: + b_i, F_i, r_i / F_i (fit).  MODE 2: + the gradient slots.
-template <typename T, int KB, int MODE>
-__global__ void __launch_bounds__(k256) nn_point_kernel(const NnParams P, const T* __restrict__ x, const T* __restrict__ y,
-                                                        double* __restrict__ terms, int S, int* __restrict__ bad, T* __restrict__ Bd,
-                                                        double* __restrict__ Fd, double* __restrict__ rFd) {
+// G (gathered): lane t conditions on point nbr(i, t) of the neighbour table (N x P.k column-major, the valid entries first, -1 after
+// them) instead of point i - m + t of the window; everything after the loads is the same arithmetic in the same order.
+template <typename T, int KB, int MODE, bool G>
+__device__ __forceinline__ void nn_point_body(const NnParams& P, const T* __restrict__ x, const T* __restrict__ y,
+                                              double* __restrict__ terms, int S, int* __restrict__ bad, T* __restrict__ Bd,
+                                              double* __restrict__ Fd, double* __restrict__ rFd, const int* __restrict__ nbr) {
   const int lane = threadIdx.x & 63;
   const int64_t i = int64_t(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
   if (i >= P.n) return;
-  const int m = i < P.k ? int(i) : P.k;
-  const int64_t base = i - m;
+  int m;
+  int64_t base, src = 0;
+  if constexpr (G) {
+    const int e = lane < P.k ? nbr[i + int64_t(lane) * P.n] : -1;
+    m = __builtin_amdgcn_readfirstlane(__popcll(__ballot(e >= 0)));
+    base = 0;
+    src = e;
+  } else {
+    m = i < P.k ? int(i) : P.k;
+    base = i - m;
+  }
   const bool act = lane < m;
   const T variance = T(P.variance);
   T A[KB], c;
-  nn_dist2<T, KB>(P, x, base, i, lane, m, A, c);
+  nn_dist2<T, KB, G>(P, x, base, i, lane, m, A, c, src);
   // the block: C on the m x m corner, identity on the padding
 #pragma unroll
   for (int g = 0; g < KB / 8; ++g) {
@@ -149,7 +162,7 @@ __global__ void __launch_bounds__(k256) nn_point_kernel(const NnParams P, const 
     }
   }
   c = act ? kappa(P.family, c, variance) : T(0);
-  T dd = act ? T(double(y[base + lane]) - P.mean_const) : T(0);
+  T dd = act ? T(double(y[G ? src : base + lane]) - P.mean_const) : T(0);
   double F = P.variance + P.diag, r = double(y[i]) - P.mean_const;
   // "not positive": at or below the rounding noise of its own computation, 4 eps (m + 1) kd - a pivot or an F down there is a
   // difference of equal numbers (an exactly repeated point with diag = 0 leaves +-1e-16, either sign)
@@ -203,7 +216,7 @@ __global__ void __launch_bounds__(k256) nn_point_kernel(const NnParams P, const 
   });
   const double rF = r / F;
   if (MODE == 1) {
-    if (act) Bd[i + int64_t(P.k - m + lane) * P.n] = bme;
+    if (act) Bd[i + int64_t(G ? lane : P.k - m + lane) * P.n] = bme;
     if (lane == 0) { Fd[i] = F; rFd[i] = rF; }
     return;
   }
@@ -213,7 +226,7 @@ __global__ void __launch_bounds__(k256) nn_point_kernel(const NnParams P, const 
   const T qv = T(gF * double(bme) - rF * double(wme));               // C_bar[q][j] = qv_q b_j
   const T cb = T(-2.0 * gF * double(bme) + rF * double(wme));        // c_bar_j
   T cr2;
-  nn_dist2<T, KB>(P, x, base, i, lane, m, A, cr2);
+  nn_dist2<T, KB, G>(P, x, base, i, lane, m, A, cr2, src);
   const T v2 = T(2) * variance;
 #pragma unroll
   for (int g = 0; g < KB / 8; ++g) {
@@ -229,7 +242,7 @@ __global__ void __launch_bounds__(k256) nn_point_kernel(const NnParams P, const 
   double* t = terms + i * S;
   for (int f = 0; f < P.d; ++f) {
     const T il = T(P.invl[f]);
-    const T xj = act ? x[int64_t(f) * P.ldx + base + lane] * il : T(0);
+    const T xj = act ? x[int64_t(f) * P.ldx + (G ? src : base + lane)] * il : T(0);
     const T dc = xj - x[int64_t(f) * P.ldx + i] * il;
     T acc = gc * dc * dc;
 #pragma unroll
@@ -249,6 +262,19 @@ __global__ void __launch_bounds__(k256) nn_point_kernel(const NnParams P, const 
     t[3] = isbad ? 0.0 : (gF * (F - P.diag) - P.diag * tr) / P.variance;
     t[4] = isbad ? 0.0 : gF + tr;
   }
+}
+template <typename T, int KB, int MODE>
+__global__ void __launch_bounds__(k256) nn_point_kernel(const NnParams P, const T* __restrict__ x, const T* __restrict__ y,
+                                                        double* __restrict__ terms, int S, int* __restrict__ bad, T* __restrict__ Bd,
+                                                        double* __restrict__ Fd, double* __restrict__ rFd) {
+  nn_point_body<T, KB, MODE, false>(P, x, y, terms, S, bad, Bd, Fd, rFd, nullptr);
+}
+template <typename T, int KB, int MODE>
+__global__ void __launch_bounds__(k256) nn_point_tab_kernel(const NnParams P, const T* __restrict__ x, const T* __restrict__ y,
+                                                            double* __restrict__ terms, int S, int* __restrict__ bad, T* __restrict__ Bd,
+                                                            double* __restrict__ Fd, double* __restrict__ rFd,
+                                                            const int* __restrict__ nbr) {
+  nn_point_body<T, KB, MODE, true>(P, x, y, terms, S, bad, Bd, Fd, rFd, nbr);
 }
 
 // part[s][b] = sum of slot s over the points of block b (contiguous ranges of `chunk` points), fixed order
@@ -289,6 +315,127 @@ __global__ void nn_alpha_kernel(const T* __restrict__ Bd, const double* __restri
   double a = rF[j];
   for (int s = 1; s <= kb && j + s < n; ++s) a = fma(-double(Bd[(j + s) + int64_t(kb - s) * n]), rF[j + s], a);
   alpha[j] = a;
+}
+
+// ---- the neighbour table ---------------------------------------------------------------------------------------
+// nbr is N x kb int32 column-major: row i lists the conditioning set of point i, its m_i <= min(i, kb) valid entries first (each in
+// [0, i), distinct), -1 after them.
+
+// One wavefront per row: flag = min(flag, i + 1) over the rows that break the rule above
+__global__ void __launch_bounds__(k256) nn_check_tab_kernel(const int* __restrict__ nbr, int64_t n, int kb, int* __restrict__ flag) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = int64_t(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  if (i >= n) return;
+  const int e = lane < kb ? nbr[i + int64_t(lane) * n] : -1;
+  const unsigned long long valid = __ballot(e >= 0);
+  bool badl = e < -1 || int64_t(e) >= i;
+  if ((valid & (valid + 1)) != 0) badl = true;   // a -1 before a valid entry
+  for (int q = 0; q < kb; ++q) {
+    const int v = __shfl(e, q);
+    if (lane > q && e >= 0 && e == v) badl = true;
+  }
+  if (__ballot(badl) != 0 && lane == 0) atomicMin(flag, int(i + 1 < kNnNone ? i + 1 : kNnNone - 1));
+}
+
+// The exact k nearest predecessors: for query i the min(i, kb) points j < i with the smallest sum_f ((x_j,f - x_i,f) il_f)^2 (data
+// dtype), ties to the lower index, stored in ascending index.  One wavefront per query, four queries per workgroup in descending i
+// (block 0 holds the longest), candidates in 64-wide tiles shared through LDS.  The current best are kept one per lane, sorted by
+// (distance, index); candidates arrive in ascending index, so one beats the worst only with a strictly smaller distance, and it goes
+// in behind every entry at most as far (a wave shift).  A distance that is not finite is never chosen: that row comes out short.
+template <typename T>
+__global__ void __launch_bounds__(k256) nn_search_kernel(const NnParams P, const T* __restrict__ x, int* __restrict__ nbr) {
+  extern __shared__ double nn_search_lds[];
+  T* tile = reinterpret_cast<T*>(nn_search_lds);   // [d][64] candidates, then [4][d] queries
+  T* qs = tile + int64_t(P.d) * 64;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t top = P.n - 1 - int64_t(blockIdx.x) * 4;   // the block's largest query
+  const int64_t i = top - w;                               // may be negative in the last block
+  const int K = i < P.k ? int(i < 0 ? 0 : i) : P.k;
+  for (int e = threadIdx.x; e < 4 * P.d; e += k256) {
+    const int qw = e / P.d, f = e - qw * P.d;
+    qs[e] = top - qw >= 0 ? x[int64_t(f) * P.ldx + (top - qw)] : T(0);
+  }
+  T bd = T(INFINITY);   // lane l < K: the l-th best so far
+  int bi = INT_MAX;
+  for (int64_t j0 = 0; j0 < top; j0 += 64) {
+    __syncthreads();   // the previous tile is consumed (first round: qs is written)
+    for (int e = threadIdx.x; e < 64 * P.d; e += k256) {
+      const int f = e >> 6, c = e & 63;
+      tile[e] = j0 + c < top ? x[int64_t(f) * P.ldx + j0 + c] : T(0);
+    }
+    __syncthreads();
+    if (j0 >= i) continue;   // wave-uniform: no candidate of this tile precedes the query
+    T r2 = T(0);
+    for (int f = 0; f < P.d; ++f) {
+      const T df = (tile[f * 64 + lane] - qs[w * P.d + f]) * T(P.invl[f]);
+      r2 = fma(df, df, r2);
+    }
+    T worst = nn_rl(bd, K - 1);
+    unsigned long long mask = __ballot(j0 + lane < i && r2 < worst);
+    while (mask) {
+      const int c = __builtin_ctzll(mask);
+      mask &= mask - 1;
+      const T dc = nn_rl(r2, c);
+      if (!(dc < worst)) continue;   // the worst moved since the ballot
+      const int pos = __popcll(__ballot(lane < K && bd <= dc));
+      const T ud = __shfl_up(bd, 1);
+      const int ui = __shfl_up(bi, 1);
+      if (lane > pos) { bd = ud; bi = ui; }
+      if (lane == pos) { bd = dc; bi = int(j0 + c); }
+      worst = nn_rl(bd, K - 1);
+    }
+  }
+  if (i < 0) return;
+  // ascending index: the rank of an entry is the number of smaller ones (the unfilled places hold INT_MAX and come last)
+  const bool have = lane < K && bi != INT_MAX;
+  int rank = 0;
+  for (int q = 0; q < K; ++q) {
+    const int v = __shfl(bi, q);
+    rank += v < bi ? 1 : 0;
+  }
+  const int nv = __popcll(__ballot(have));
+  if (have) nbr[i + int64_t(rank) * P.n] = bi;
+  if (lane >= nv && lane < P.k) nbr[i + int64_t(lane) * P.n] = -1;
+}
+
+// The reverse lists: the pairs (i, t) with nbr(i, t) = j, for every j, in ascending i.  The pairs are listed row by row (p = i kb + t),
+// keyed by j (n for the -1 entries) and put through a stable radix sort; val = i + t n is the pair's place in B.
+__global__ void nn_pairs_kernel(const int* __restrict__ nbr, int64_t n, int kb, unsigned* __restrict__ key, int64_t* __restrict__ val) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p >= n * kb) return;
+  const int64_t i = p / kb;
+  const int t = int(p - i * kb);
+  const int e = nbr[i + int64_t(t) * n];
+  key[p] = e >= 0 ? unsigned(e) : unsigned(n);
+  val[p] = i + int64_t(t) * n;
+}
+// off[j] = the first place of the sorted keys that holds a key >= j, j = 0 .. n
+__global__ void nn_offsets_kernel(const unsigned* __restrict__ key, int64_t total, int64_t n, int64_t* __restrict__ off) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j > n) return;
+  int64_t lo = 0, hi = total;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (int64_t(key[mid]) < j) lo = mid + 1; else hi = mid;
+  }
+  off[j] = lo;
+}
+// alpha_j = r_j / F_j - sum over the reverse list of j of B(i, t) r_i / F_i: one wavefront per j, the lanes stride the list and a
+// fixed tree adds them (a hub's list has up to n - 1 pairs)
+template <typename T>
+__global__ void __launch_bounds__(k256) nn_alpha_tab_kernel(const T* __restrict__ Bd, const double* __restrict__ rF, int64_t n,
+                                                            const int64_t* __restrict__ off, const int64_t* __restrict__ rv,
+                                                            double* __restrict__ alpha) {
+  const int lane = threadIdx.x & 63;
+  const int64_t j = int64_t(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  if (j >= n) return;
+  double a = 0.0;
+  for (int64_t p = off[j] + lane; p < off[j + 1]; p += 64) {
+    const int64_t v = rv[p];
+    a = fma(double(Bd[v]), rF[v % n], a);
+  }
+  a = nn_wave_sum(a);
+  if (lane == 0) alpha[j] = rF[j] - a;
 }
 
 template <typename T>
@@ -353,6 +500,55 @@ __global__ void __launch_bounds__(k256) nn_v_kernel(const T* __restrict__ Kx, in
     pv[int64_t(blockIdx.y) * np + j] = ((sv[0][tx] + sv[1][tx]) + sv[2][tx]) + sv[3][tx];
   }
 }
+// The same rows with a neighbour table: (k(x_i, x*) - sum_t B(i, t) k(x_nbr(i, t), x*)) / sqrt(F_i).  The neighbours of a row are
+// anywhere before it, so their kernel values are evaluated here (kb + 1 evaluations per entry); same tiles and column sums.
+template <typename T>
+__device__ __forceinline__ T nn_kval(const NnParams& P, const T* __restrict__ x, int64_t g, const T* __restrict__ xt, int64_t ldt, int64_t j) {
+  T r2 = T(0);
+  for (int f = 0; f < P.d; ++f) {
+    const T df = (x[int64_t(f) * P.ldx + g] - xt[int64_t(f) * ldt + j]) * T(P.invl[f]);
+    r2 = fma(df, df, r2);
+  }
+  return kappa(P.family, r2, T(P.variance));
+}
+template <typename T>
+__global__ void __launch_bounds__(k256) nn_vtab_kernel(const NnParams P, const T* __restrict__ x, const T* __restrict__ xt, int64_t ldt,
+                                                       int64_t nt, int64_t np, int64_t i0, const int* __restrict__ nbr,
+                                                       const T* __restrict__ Bd, const double* __restrict__ Fd,
+                                                       const double* __restrict__ alpha, int want_v, T* __restrict__ V,
+                                                       double* __restrict__ pm, double* __restrict__ pv) {
+  __shared__ double sm[4][64], sv[4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t j = int64_t(blockIdx.x) * 64 + tx, n = P.n;
+  double am = 0.0, av = 0.0;
+  for (int s = 0; s < 16; ++s) {
+    const int rr = blockIdx.y * 64 + ty + 4 * s;
+    const int64_t i = i0 + rr;
+    double v = 0.0;
+    if (i < n && j < nt) {
+      const double kx = double(nn_kval<T>(P, x, i, xt, ldt, j));
+      am = fma(kx, alpha[i], am);
+      if (want_v) {
+        double acc = 0.0;
+        for (int t = 0; t < P.k; ++t) {
+          const int e = nbr[i + int64_t(t) * n];   // uniform over the wavefront
+          if (e < 0) break;
+          acc = fma(double(Bd[i + int64_t(t) * n]), double(nn_kval<T>(P, x, e, xt, ldt, j)), acc);
+        }
+        v = (kx - acc) / sqrt(Fd[i]);
+        av = fma(v, v, av);
+      }
+    }
+    if (want_v) V[int64_t(rr) * np + j] = T(v);
+  }
+  sm[ty][tx] = am;
+  sv[ty][tx] = av;
+  __syncthreads();
+  if (ty == 0) {
+    pm[int64_t(blockIdx.y) * np + j] = ((sm[0][tx] + sm[1][tx]) + sm[2][tx]) + sm[3][tx];
+    pv[int64_t(blockIdx.y) * np + j] = ((sv[0][tx] + sv[1][tx]) + sv[2][tx]) + sv[3][tx];
+  }
+}
 // acc[j] += the tile's row-group partials, in order
 __global__ void nn_colacc_kernel(const double* __restrict__ pm, const double* __restrict__ pv, int groups, int64_t np,
                                  double* __restrict__ macc, double* __restrict__ vacc) {
@@ -400,6 +596,10 @@ struct svgp_nn {
   DevBuf Bd, Fd, rF, alpha;   // the last fit: b_i (N x kb column-major, data dtype), F_i, r_i / F_i, alpha (fp64)
   bool have_fit = false;
   NnParams P{};   // ... and its parameters
+  // the neighbour table (svgp_nn_set_neighbors / svgp_nn_build_neighbors); tab_kb < 0: none, the window of the previous k points
+  int tab_kb = -1;
+  DevBuf nbr;        // (int) N x tab_kb column-major
+  DevBuf roff, rv;   // (int64) the reverse lists: offsets [N + 1], and the places i + t N in B of the pairs with nbr(i, t) = j
 };
 
 namespace {
@@ -415,6 +615,9 @@ int nn_check_desc(svgp_ctx* ctx, const svgp_nn* nn, const svgp_nn_desc* ds) {
   if (!(ds->variance > 0.0)) return fail(ctx, SVGP_INVALID_ARG, "variance must be > 0");
   if (!(ds->diag >= 0.0)) return fail(ctx, SVGP_INVALID_ARG, "diag must be >= 0");
   if (std::min<int64_t>(ds->k, nn->N - 1) > kNnMaxK) return fail(ctx, SVGP_UNSUPPORTED, "more than 64 neighbours: one lane per neighbour");   // k >= N is k = N - 1
+  if (nn->tab_kb >= 0 && std::min<int64_t>(ds->k, nn->N - 1) != nn->tab_kb)
+    return fail(ctx, SVGP_INVALID_ARG, "descriptor k gives " + std::to_string(std::min<int64_t>(ds->k, nn->N - 1)) +
+                                           " neighbours, the handle's neighbour table has " + std::to_string(nn->tab_kb));
   return SVGP_OK;
 }
 
@@ -440,6 +643,13 @@ void nn_launch_point(hipStream_t s, const NnParams& P, const svgp_nn* nn, int S)
   int* bad = nn->bad.as<int>();
   T* Bd = (T*)nn->Bd.p;
   double *Fd = nn->Fd.as<double>(), *rF = nn->rF.as<double>();
+  if (nn->tab_kb >= 0) {
+    const int* nbr = nn->nbr.as<int>();
+    if (P.k <= 16) hipLaunchKernelGGL((nn_point_tab_kernel<T, 16, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF, nbr);
+    else if (P.k <= 32) hipLaunchKernelGGL((nn_point_tab_kernel<T, 32, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF, nbr);
+    else hipLaunchKernelGGL((nn_point_tab_kernel<T, 64, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF, nbr);
+    return;
+  }
   if (P.k <= 16) hipLaunchKernelGGL((nn_point_kernel<T, 16, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF);
   else if (P.k <= 32) hipLaunchKernelGGL((nn_point_kernel<T, 32, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF);
   else hipLaunchKernelGGL((nn_point_kernel<T, 64, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF);
@@ -480,8 +690,12 @@ int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double
   hipLaunchKernelGGL(nn_reduce2_kernel, dim3((unsigned)S), dim3(k256), 0, s, (const double*)nn->part.as<double>(), nb, nn->res.as<double>());
   if (mode == 1)
     NN_DISPATCH(nn->dtype, T, {
-      hipLaunchKernelGGL(nn_alpha_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, (const T*)nn->Bd.p, (const double*)nn->rF.as<double>(), N, P.k,
-                         nn->alpha.as<double>());
+      if (nn->tab_kb >= 0)
+        hipLaunchKernelGGL(nn_alpha_tab_kernel<T>, dim3(nblk(N, 4)), dim3(k256), 0, s, (const T*)nn->Bd.p, (const double*)nn->rF.as<double>(), N,
+                           (const int64_t*)nn->roff.as<int64_t>(), (const int64_t*)nn->rv.as<int64_t>(), nn->alpha.as<double>());
+      else
+        hipLaunchKernelGGL(nn_alpha_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, (const T*)nn->Bd.p, (const double*)nn->rF.as<double>(), N, P.k,
+                           nn->alpha.as<double>());
     });
   KCHECK(ctx, "nn_reduce");
   int badv = 0;
@@ -523,7 +737,8 @@ int nn_predict_impl(svgp_ctx* ctx, svgp_nn* nn, const svgp_data* Aset, const svg
   const int groups_max = rows_max / 64;
   const size_t es = nn->es;
   DevBuf Kx, Va, Vb, pm, pv, macc, vacc, Cacc, outb;
-  HIPC(ctx, Kx.alloc(size_t(rows_max + kNnMaxK) * np * es));
+  const bool tab = nn->tab_kb >= 0;
+  if (!tab) HIPC(ctx, Kx.alloc(size_t(rows_max + kNnMaxK) * np * es));
   if (want_v) HIPC(ctx, Va.alloc(size_t(rows_max) * np * es));
   if (Bset) HIPC(ctx, Vb.alloc(size_t(rows_max) * np * es));
   HIPC(ctx, pm.alloc(size_t(groups_max) * np * 8));
@@ -540,11 +755,18 @@ int nn_predict_impl(svgp_ctx* ctx, svgp_nn* nn, const svgp_data* Aset, const svg
     NN_DISPATCH(nn->dtype, T, {
       for (int side = 0; side < (Bset ? 2 : 1); ++side) {
         const svgp_data* D = side ? Bset : Aset;
-        hipLaunchKernelGGL(nn_kx_kernel<T>, dim3(nblk(np), 256), dim3(k256), 0, s, P, (const T*)nn->data->x.p, (const T*)D->x.p, D->ldx, D->n, np,
-                           i0, groups * 64 + kNnMaxK, (T*)Kx.p);
-        hipLaunchKernelGGL(nn_v_kernel<T>, dim3(unsigned(np / 64), unsigned(groups)), dim3(k256), 0, s, (const T*)Kx.p, np, i0, N, P.k,
-                           (const T*)nn->Bd.p, (const double*)nn->Fd.as<double>(), (const double*)nn->alpha.as<double>(), want_v ? 1 : 0,
-                           (T*)(side ? Vb.p : Va.p), pm.as<double>(), pv.as<double>());
+        if (tab) {
+          hipLaunchKernelGGL(nn_vtab_kernel<T>, dim3(unsigned(np / 64), unsigned(groups)), dim3(k256), 0, s, P, (const T*)nn->data->x.p,
+                             (const T*)D->x.p, D->ldx, D->n, np, i0, (const int*)nn->nbr.as<int>(), (const T*)nn->Bd.p,
+                             (const double*)nn->Fd.as<double>(), (const double*)nn->alpha.as<double>(), want_v ? 1 : 0,
+                             (T*)(side ? Vb.p : Va.p), pm.as<double>(), pv.as<double>());
+        } else {
+          hipLaunchKernelGGL(nn_kx_kernel<T>, dim3(nblk(np), 256), dim3(k256), 0, s, P, (const T*)nn->data->x.p, (const T*)D->x.p, D->ldx, D->n,
+                             np, i0, groups * 64 + kNnMaxK, (T*)Kx.p);
+          hipLaunchKernelGGL(nn_v_kernel<T>, dim3(unsigned(np / 64), unsigned(groups)), dim3(k256), 0, s, (const T*)Kx.p, np, i0, N, P.k,
+                             (const T*)nn->Bd.p, (const double*)nn->Fd.as<double>(), (const double*)nn->alpha.as<double>(), want_v ? 1 : 0,
+                             (T*)(side ? Vb.p : Va.p), pm.as<double>(), pv.as<double>());
+        }
         if (!side)
           hipLaunchKernelGGL(nn_colacc_kernel, dim3(nblk(np)), dim3(256), 0, s, (const double*)pm.as<double>(), (const double*)pv.as<double>(),
                              groups, np, macc.as<double>(), vacc.as<double>());
@@ -581,9 +803,129 @@ int nn_predict_impl(svgp_ctx* ctx, svgp_nn* nn, const svgp_data* Aset, const svg
   return SVGP_OK;
 }
 
+void nn_drop_table(svgp_nn* nn) {
+  nn->tab_kb = -1;
+  nn->have_fit = false;
+}
+
+// k of a set / build call -> kb = min(k, N - 1), or a status
+int nn_table_kb(svgp_ctx* ctx, const svgp_nn* nn, int32_t k, int* kb) {
+  if (k < 1) return fail(ctx, SVGP_INVALID_ARG, "k must be >= 1");
+  if (nn->N > int64_t(INT_MAX)) return fail(ctx, SVGP_UNSUPPORTED, "a neighbour table holds int32 indices: N does not fit");
+  if (std::min<int64_t>(k, nn->N - 1) > kNnMaxK) return fail(ctx, SVGP_UNSUPPORTED, "more than 64 neighbours: one lane per neighbour");
+  *kb = int(std::min<int64_t>(k, nn->N - 1));
+  return SVGP_OK;
+}
+
+// the reverse lists of nn->nbr (N x kb): a stable radix sort of the pairs by the point they name, then the offsets
+int nn_reverse_lists(svgp_ctx* ctx, svgp_nn* nn, int kb) {
+  hipStream_t s = ctx->stream;
+  const int64_t N = nn->N, total = N * kb;
+  int rc = nn->roff.reserve(ctx, size_t(N + 1) * 8, "the reverse-list offsets");
+  if (rc == SVGP_OK) rc = nn->rv.reserve(ctx, std::max<size_t>(size_t(total) * 8, 8), "the reverse lists");
+  if (rc) return rc;
+  DevBuf key, key2, val, tmp;
+  if (total > 0) {
+    HIPC(ctx, key.alloc(size_t(total) * 4));
+    HIPC(ctx, key2.alloc(size_t(total) * 4));
+    HIPC(ctx, val.alloc(size_t(total) * 8));
+    hipLaunchKernelGGL(nn_pairs_kernel, dim3(nblk(total)), dim3(256), 0, s, (const int*)nn->nbr.as<int>(), N, kb, key.as<unsigned>(),
+                       val.as<int64_t>());
+    KCHECK(ctx, "nn_pairs");
+    unsigned bits = 1;
+    while (bits < 32 && (uint64_t(1) << bits) <= uint64_t(N)) ++bits;   // the keys are 0 .. N
+    size_t tb = 0;
+    HIPC(ctx, rocprim::radix_sort_pairs(nullptr, tb, key.as<unsigned>(), key2.as<unsigned>(), val.as<int64_t>(), nn->rv.as<int64_t>(),
+                                        size_t(total), 0u, bits, s));
+    HIPC(ctx, tmp.alloc(std::max<size_t>(tb, 8)));
+    HIPC(ctx, rocprim::radix_sort_pairs(tmp.p, tb, key.as<unsigned>(), key2.as<unsigned>(), val.as<int64_t>(), nn->rv.as<int64_t>(),
+                                        size_t(total), 0u, bits, s));
+  }
+  hipLaunchKernelGGL(nn_offsets_kernel, dim3(nblk(N + 1)), dim3(256), 0, s, (const unsigned*)key2.as<unsigned>(), total, N,
+                     nn->roff.as<int64_t>());
+  KCHECK(ctx, "nn_offsets");
+  HIPC(ctx, hipStreamSynchronize(s));   // the sort's buffers are released on return
+  return SVGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t svgp_nn_set_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t k, const int32_t* nbr_host) {
+  if (!ctx || !nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  nn_drop_table(nn);
+  int kb = 0;
+  int rc = nn_table_kb(ctx, nn, k, &kb);
+  if (rc) return rc;
+  if (!nbr_host && kb > 0) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int64_t N = nn->N;
+  rc = nn->nbr.reserve(ctx, std::max<size_t>(size_t(N) * kb * 4, 8), "the neighbour table");
+  if (rc) return rc;
+  if (kb > 0) {
+    HIPC(ctx, hipMemcpyAsync(nn->nbr.p, nbr_host, size_t(N) * kb * 4, hipMemcpyHostToDevice, s));
+    HIPC(ctx, hipMemsetAsync(nn->bad.p, 0x7f, sizeof(int), s));   // kNnNone
+    hipLaunchKernelGGL(nn_check_tab_kernel, dim3(nblk(N, 4)), dim3(k256), 0, s, (const int*)nn->nbr.as<int>(), N, kb, nn->bad.as<int>());
+    KCHECK(ctx, "nn_check_tab");
+    int badv = 0;
+    HIPC(ctx, hipMemcpyAsync(&badv, nn->bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipStreamSynchronize(s));   // also: nbr_host is the caller's again
+    if (badv != kNnNone)
+      return fail(ctx, SVGP_INVALID_ARG, "neighbour table: row " + std::to_string(badv) + " (1-based) is not a set of distinct earlier points, the valid entries first and -1 after them");
+  }
+  rc = nn_reverse_lists(ctx, nn, kb);
+  if (rc) return rc;
+  nn->tab_kb = kb;
+  return SVGP_OK;
+}
+
+int32_t svgp_nn_build_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t k, const double* inv_lengthscale) {
+  if (!ctx || !nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  nn_drop_table(nn);
+  int kb = 0;
+  int rc = nn_table_kb(ctx, nn, k, &kb);
+  if (rc) return rc;
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int64_t N = nn->N;
+  rc = nn->nbr.reserve(ctx, std::max<size_t>(size_t(N) * kb * 4, 8), "the neighbour table");
+  if (rc) return rc;
+  if (kb > 0) {
+    NnParams P{};
+    P.d = nn->d;
+    P.k = kb;
+    P.n = N;
+    P.ldx = nn->data->ldx;
+    for (int f = 0; f < nn->d; ++f) P.invl[f] = inv_lengthscale ? inv_lengthscale[f] : 1.0;
+    NN_DISPATCH(nn->dtype, T, {
+      hipLaunchKernelGGL(nn_search_kernel<T>, dim3(nblk(N, 4)), dim3(k256), size_t(68) * nn->d * sizeof(T), s, P, (const T*)nn->data->x.p,
+                         nn->nbr.as<int>());
+    });
+    KCHECK(ctx, "nn_search");
+  }
+  rc = nn_reverse_lists(ctx, nn, kb);
+  if (rc) return rc;
+  nn->tab_kb = kb;
+  return SVGP_OK;
+}
+
+int32_t svgp_nn_get_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t* k_out, int32_t* nbr_out) {
+  if (!ctx || !nn || !k_out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  *k_out = nn->tab_kb;
+  if (nn->tab_kb <= 0 || !nbr_out) return SVGP_OK;
+  HIPC(ctx, hipSetDevice(ctx->device));
+  HIPC(ctx, hipMemcpyAsync(nbr_out, nn->nbr.p, size_t(nn->N) * nn->tab_kb * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(ctx, hipStreamSynchronize(ctx->stream));
+  return SVGP_OK;
+}
+
+int32_t svgp_nn_clear_neighbors(svgp_ctx* ctx, svgp_nn* nn) {
+  if (!ctx || !nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  nn_drop_table(nn);
+  return SVGP_OK;
+}
 
 int32_t svgp_nn_create(svgp_ctx* ctx, const svgp_data* data, svgp_nn** out) {
   if (!ctx || !data || !out) return fail(ctx, SVGP_INVALID_ARG, "null argument");

@@ -491,7 +491,27 @@ int32_t svgp_laplace_free(svgp_ctx* ctx, svgp_laplace* la);
  * 1 <= min(k, N - 1) <= 64 neighbours (more: SVGP_UNSUPPORTED; k >= N counts as N - 1, so it is valid up to N = 65).  Every result is bitwise repeatable: fixed-order reductions, no floating-point atomics.
  * SVGP_INVALID_ARG, before anything is enqueued: NULL required pointers, data without y, a descriptor whose dtype / d differ from the
  * data's, k < 1, variance <= 0, diag < 0, reserved != 0; factors / predict before a successful fit.  Never collective: on a context
- * with a communicator these calls stay local.  Found by symbol (no ABI version step). */
+ * with a communicator these calls stay local.  Found by symbol (no ABI version step).
+ *
+ * Neighbour tables.  A handle may carry a table nbr: N x kb int32, column-major like B, kb = min(k, N - 1) <= 64.  Row i lists the
+ * conditioning set of point i: its m_i <= min(i, kb) valid entries first, each in [0, i) and distinct, then -1.  With a table set,
+ * ns(i) is row i in place of the window of the previous k points (the Vecchia / NNGP form: GpGp, GPvecchia, Datta et al.'s NNGP);
+ * svgp_nn_lml, _lml_grad, _fit, _factors, _predict and _predict_cross_cov use it.  desc->k must give the table's kb (min(desc->k,
+ * N - 1) == kb), else SVGP_INVALID_ARG.  svgp_nn_factors then returns B(i, t) = the coefficient of point i on point nbr(i, t), 0 where
+ * that entry is -1.  Without a table every call is what it was.  The ordering of the points stays the caller's.
+ *   svgp_nn_set_neighbors    uploads a caller's table (N x kb, k as in the descriptor) and validates it on the device; a row that breaks
+ *                            the rule above: SVGP_INVALID_ARG, svgp_last_error names the first such row (1-based).
+ *   svgp_nn_build_neighbors  the exact k nearest predecessors: for every i the min(i, kb) points j < i with the smallest
+ *                            sum_f ((x_j,f - x_i,f) il_f)^2, computed from differences in the data dtype; ties go to the lower index;
+ *                            rows in ascending index.  inv_lengthscale: d entries, NULL: ones.  Brute force, N^2 / 2 distances; for
+ *                            sorted 1-D inputs the result is the window.  A distance that is not finite is never chosen.
+ *   svgp_nn_get_neighbors    *k_out = kb of the handle's table, -1 without one; nbr_out (may be NULL) receives the N x kb table.
+ *   svgp_nn_clear_neighbors  back to the window.
+ * Setting, building or clearing a table discards the handle's fit: factors / predict return SVGP_INVALID_ARG until the next
+ * svgp_nn_fit.  A failed set or build leaves the handle with no table.  N must fit int32 (else SVGP_UNSUPPORTED).
+ * The gradient is taken at a FIXED table: a table built with the inverse lengthscales as its metric is piecewise constant in them,
+ * and svgp_nn_lml_grad does not (and cannot) differentiate the selection.  Bitwise repeatable like the rest: the search uses no
+ * atomics, the reverse lists behind alpha come from a stable sort, the validation from one integer atomicMin. */
 typedef struct svgp_nn svgp_nn;
 typedef struct svgp_nn_desc {
   int32_t dtype;            /* SVGP_F64 | SVGP_F32: must be the data's */
@@ -520,6 +540,10 @@ int32_t svgp_nn_predict(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t n, c
 int32_t svgp_nn_predict_cross_cov(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t nx, const void* x_host, int64_t ny,
                                   const void* y_host, void* cov_out);
 int32_t svgp_nn_free(svgp_ctx* ctx, svgp_nn* nn);
+int32_t svgp_nn_set_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t k, const int32_t* nbr_host);
+int32_t svgp_nn_build_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t k, const double* inv_lengthscale);
+int32_t svgp_nn_get_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t* k_out, int32_t* nbr_out);
+int32_t svgp_nn_clear_neighbors(svgp_ctx* ctx, svgp_nn* nn);
 
 /* ---- the collapsed bound of sparse GP regression and the optimal q(u)  (Titsias 2009, eqs. 11 / 12) ---------------------------------
  * For the Gaussian likelihood the q(u) that maximises the ELBO has a closed form; the reference's tests build it on the host

@@ -828,6 +828,30 @@ function DeviceNN(D::DeviceData)
     return N
 end
 nn_check(st, info::NNInfo) = st == 2 ? throw(PosDefException(Int(info.first_bad))) : check(st)
+"Condition point i on row i of `table` (n × kb Int32, 0-based indices of earlier points, the valid ones first, -1 after them)."
+function nn_set_neighbors!(N::DeviceNN, k::Integer, table::Matrix{Int32})
+    GC.@preserve table check(ccall((:svgp_nn_set_neighbors, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}),
+                                   ctx(), N.h, Int32(k), table))
+    return N
+end
+"The exact k nearest predecessors of every point under the metric `inv_lengthscale` (nothing: ones), built on the device."
+function nn_build_neighbors!(N::DeviceNN, k::Integer, inv_lengthscale::Union{Nothing,Vector{Float64}}=nothing)
+    il = inv_lengthscale === nothing ? Ptr{Float64}(C_NULL) : pointer(inv_lengthscale)
+    GC.@preserve inv_lengthscale check(ccall((:svgp_nn_build_neighbors, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}),
+                                             ctx(), N.h, Int32(k), il))
+    return N
+end
+"The handle's neighbour table (n × kb Int32), or nothing when the window of the previous k points is in use."
+function nn_neighbors(N::DeviceNN)
+    kb = Ref{Int32}(-1)
+    check(ccall((:svgp_nn_get_neighbors, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int32}, Ptr{Int32}), ctx(), N.h, kb, C_NULL))
+    kb[] < 0 && return nothing
+    table = zeros(Int32, N.data.n, kb[])
+    check(ccall((:svgp_nn_get_neighbors, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int32}, Ptr{Int32}), ctx(), N.h, kb, table))
+    return table
+end
+"Back to the window of the previous k points."
+nn_clear_neighbors!(N::DeviceNN) = (check(ccall((:svgp_nn_clear_neighbors, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx(), N.h)); N)
 "approx_lml(NearestNeighbors(desc.k), fx, y) (:108-113); desc.diag = 0 is the reference, which ignores fx.Σy."
 function nn_lml!(N::DeviceNN, desc::NNDesc)
     out, info = Ref{Float64}(), NNInfo()
@@ -851,7 +875,8 @@ function nn_fit!(N::DeviceNN, desc::NNDesc)
                    ctx(), N.h, desc, out, info), info)
     return out[], info
 end
-"(B banded n × kb, F, α) of the last nn_fit!, kb = min(k, n - 1): B[i, t] is the coefficient of point i on point i - kb + t."
+"(B banded n × kb, F, α) of the last nn_fit!, kb = min(k, n - 1): B[i, t] is the coefficient of point i on point i - kb + t, or with a
+neighbour table on point table[i, t]."
 function nn_factors(N::DeviceNN, k::Integer, ::Type{T}) where {T<:FT}
     n = N.data.n
     B, F, α = zeros(T, n, min(k, n - 1)), zeros(T, n), zeros(T, n)

@@ -57,6 +57,7 @@ def main():
     ap.add_argument("--ks", type=int, nargs="+", default=[16, 32, 64])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-n", type=int, default=10_000)
+    ap.add_argument("--table-max-n", type=int, default=100_000, help="largest N that also gets the neighbour-table rows")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ctx = _ffi.Context(0)
@@ -104,6 +105,24 @@ def main():
                     row["host_numpy_approx_lml_ms"] = round(host[k][0], 1)
                     row["host_rel_diff"] = abs(lml - host[k][1]) / abs(host[k][1])
                 emit(row)
+                if n > a.table_max_n:   # the brute-force search is N^2 / 2 distances
+                    continue
+                # the same N, k and dtype with the k nearest predecessors as a table; the window row above is the yardstick
+                dev.build_neighbors(k, il)
+                t_build = timed(lambda: dev.build_neighbors(k, il), a.reps)
+                lml_t = dev.lml(desc)[0]
+                dev.lml_grad(desc)
+                dev.fit(desc)
+                dev.predict(xs.astype(dt))
+                tt = {"approx_lml_ms": timed(lambda: dev.lml(desc), a.reps), "value_and_grad_ms": timed(lambda: dev.lml_grad(desc), a.reps),
+                      "fit_ms": timed(lambda: dev.fit(desc), a.reps), "predict_1024_mean_var_ms": timed(lambda: dev.predict(xs.astype(dt)), a.reps)}
+                rowt = {"n": n, "k": k, "dtype": name, "neighbors": "nearest", "lml": lml_t, "reps": a.reps,
+                        "build_ms": [round(v, 3) for v in t_build], "build_gdist_per_s": round(n * n / 2 / (t_build[0] * 1e-3) / 1e9, 2)}
+                for key, v in tt.items():
+                    rowt[key] = [round(u, 3) for u in v]
+                    rowt[key.replace("_ms", "_over_window")] = round(v[0] / row[key][0], 3)
+                emit(rowt)
+                dev.clear_neighbors()
             dev.free()
     ctx.close()
 
