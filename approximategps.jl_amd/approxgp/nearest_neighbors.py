@@ -170,6 +170,33 @@ class DeviceNearestNeighbors:
                                                     _ffi._ptr(c)))
         return m, v, c
 
+    def predict_local(self, x, k, neighbors=False, layout=None):
+        """nearest-neighbour kriging: every test point conditioned on its min(k, n) nearest training points under the fit's inverse
+        lengthscales -> (mean, var), with neighbors=True (mean, var, table): the (n*, min(k, n)) int32 table of those points, a
+        short row ending in -1.  x as for predict; with layout = ROWVECS an (n*, d) RowVecs array.  A test point whose block is not
+        positive raises PosDefException(its 1-based index) carrying .mean and .var: NaN there, every other point as computed."""
+        dt = _ffi.np_dtype(self.dtype)
+        if layout == _ffi.ROWVECS:
+            xb = np.asfortranarray(np.asarray(x, dtype=dt))
+            if xb.ndim != 2 or xb.shape[1] != self.d:
+                raise ValueError("test inputs have a different dimension than the data")
+            n, finite = xb.shape[0], np.isfinite(xb).all(axis=1)
+        else:
+            layout, n, xb = self._x(x)
+            finite = np.isfinite(xb) if xb.ndim == 1 else np.isfinite(xb).all(axis=0)
+        m, v = np.zeros(n, dtype=dt), np.zeros(n, dtype=dt)
+        table = np.zeros((n, min(int(k), self.n)), dtype=np.int32, order="F") if neighbors and int(k) >= 1 else None
+        rc = self.ctx.lib.svgp_nn_predict_local(self.ctx.h, self.h, layout, n, _ffi._ptr(xb), int(k), _ffi._ptr(m), _ffi._ptr(v),
+                                                table.ctypes.data_as(C.POINTER(C.c_int32)) if table is not None else None)
+        if rc == _ffi.NOT_POSDEF:
+            msg = (self.ctx.lib.svgp_last_error(self.ctx.h) or b"").decode()
+            bad = np.flatnonzero(np.isnan(m) & finite)   # a test point that is not finite is NaN too, and no error
+            err = _ffi.PosDefException(int(bad[0]) + 1 if len(bad) else 0, msg)
+            err.mean, err.var = m, v
+            raise err
+        self.ctx.check(rc)
+        return (m, v, table) if neighbors else (m, v)
+
     def cross_cov(self, x, y):
         lx, nx, xb = self._x(x)
         ly, ny, yb = self._x(y)
@@ -280,6 +307,17 @@ class NNPosteriorGP:
 
     def factors(self):
         return self.dev.factors()
+
+    def local_mean_and_var(self, x, k=None):
+        """nearest-neighbour kriging (GpGp `predictions`): every test point conditioned on its k nearest observed points, k
+        defaulting to the approximation's; the latent mean and variance, test points independent of each other"""
+        return self.dev.predict_local(x, self.approx.k if k is None else k)
+
+    def local_mean(self, x, k=None):
+        return self.local_mean_and_var(x, k)[0]
+
+    def local_var(self, x, k=None):
+        return self.local_mean_and_var(x, k)[1]
 
 
 def posterior(approx, *args, **kwargs):

@@ -22,6 +22,9 @@
 //   predictions      V = U' k(x, x*) streamed in row tiles of at most 2048 points, never N x n*: k(x, x*) tile (nn_kx_kernel),
 //                    V tile with the column sums of the mean and of V.^2 (nn_v_kernel), V'V on the MFMA product kernel of the
 //                    gradient path (launch_gemm_pm) accumulated tile after tile in stream order
+//   local predictions   nearest-neighbour kriging: per test point the min(k, N) nearest training points (nn_query_search_kernel: one
+//                    wavefront per query, 16 per workgroup, double-buffered 64-wide LDS tiles), then the point kernel's sweep over the
+//                    gathered block with the query read from the test array (nn_local_kernel); rounds of 32768 test points
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -59,6 +62,7 @@ constexpr int kNnRows = 2048;      // most rows of one V tile
 constexpr int64_t kNnTileElems = int64_t(1) << 23;   // elements of one V tile (rows x padded columns): the workspace rule
 constexpr int64_t kNnMaxCov = 4096;                  // most test points of cov / cross-cov
 constexpr int64_t kNnMaxPred = int64_t(1) << 17;     // most test points of one mean / var call (64-row tiles at the workspace rule)
+constexpr int64_t kNnLocalChunk = int64_t(1) << 15;  // test points of one round of svgp_nn_predict_local: its whole workspace
 
 struct NnParams {
   int family, d, k;   // k: effective neighbour count min(k, N - 1)
@@ -263,6 +267,86 @@ __device__ __forceinline__ void nn_point_body(const NnParams& P, const T* __rest
     t[4] = isbad ? 0.0 : gF + tr;
   }
 }
+// ---- the sweep of a local prediction: nn_point_body's distances, block and factorisation with the query read from a second array.
+// A sibling, not a shared body: with the three pieces below factored out of nn_point_body its instantiations did not keep their
+// register counts (f64 KB = 16 value 74 -> 84 VGPRs, 6 -> 5 waves per SIMD; the fp32 ones moved by up to 110), so nn_point_body stays
+// as it was, and the arithmetic and its order are repeated here line for line.
+// nn_dist2 with the lane's neighbour point `src` of x and the query column i of xq (ld ldq)
+template <typename T, int KB>
+__device__ __forceinline__ void nn_dist2_query(const NnParams& P, const T* __restrict__ x, const T* __restrict__ xq, int64_t ldq, int64_t i,
+                                               int lane, int m, T (&A)[KB], T& cr2, int64_t src) {
+#pragma unroll
+  for (int q = 0; q < KB; ++q) A[q] = T(0);
+  cr2 = T(0);
+  for (int f = 0; f < P.d; ++f) {
+    const T il = T(P.invl[f]);
+    const T xj = lane < m ? x[int64_t(f) * P.ldx + src] * il : T(0);
+    const T dc = xj - xq[int64_t(f) * ldq + i] * il;
+    cr2 = fma(dc, dc, cr2);
+#pragma unroll
+    for (int g = 0; g < KB / 8; ++g)
+      if (g * 8 < m) {
+#pragma unroll
+        for (int q = g * 8; q < g * 8 + 8; ++q) {
+          const T df = nn_rl(xj, q) - xj;
+          A[q] = fma(df, df, A[q]);
+        }
+      }
+  }
+}
+// The block from its squared distances: C = k(ns, ns) + diag I on the m x m corner, identity on the padding; c = k(ns, x_i)
+template <typename T, int KB>
+__device__ __forceinline__ void nn_block(const NnParams& P, int lane, int m, T (&A)[KB], T& c) {
+  const bool act = lane < m;
+  const T variance = T(P.variance);
+#pragma unroll
+  for (int g = 0; g < KB / 8; ++g) {
+    if (g * 8 < m) {
+#pragma unroll
+      for (int q = g * 8; q < g * 8 + 8; ++q) {
+        const T kv = kappa(P.family, A[q], variance) + (q == lane ? T(P.diag) : T(0));
+        A[q] = (act && q < m) ? kv : (q == lane ? T(1) : T(0));
+      }
+    } else {
+#pragma unroll
+      for (int q = g * 8; q < g * 8 + 8; ++q) A[q] = q == lane ? T(1) : T(0);
+    }
+  }
+  c = act ? kappa(P.family, c, variance) : T(0);
+}
+
+// The right-looking factorisation of the block with c and dd = delta_ns riding along: F -= l'l, r -= l'z (fp64), lane p keeps
+// 1 / L[p][p], l_p, z_p.  -> a pivot was "not positive": at or below floor_
+template <typename T, int KB>
+__device__ __forceinline__ bool nn_factor(int lane, int m, double floor_, T (&A)[KB], T& c, T& dd, double& F, double& r, T& myrs, T& lme,
+                                          T& zme) {
+  bool isbad = false;
+  nn_static_for<0, KB>([&](auto pc) __attribute__((always_inline)) {
+    constexpr int p = decltype(pc)::value;
+    if (p < m) {
+      const T piv = nn_rl(A[p], p);
+      if (!(double(piv) > floor_)) isbad = true;
+      const T rs = T(1) / ksqrt(piv);
+      const T lj = A[p] * rs;                     // L[j][p] for the lanes j >= p
+      const T ljm = lane > p ? lj : T(0);
+      A[p] = lane >= p ? lj : A[p];               // lanes j < p: column j of the Schur complement stays (scaled in the back-substitution)
+      const T lm = nn_rl(c, p) * rs, zp = nn_rl(dd, p) * rs;
+      F = fma(-double(lm), double(lm), F);
+      r = fma(-double(lm), double(zp), r);
+      if (lane == p) { myrs = rs; lme = lm; zme = zp; }
+      c = fma(-lm, ljm, c);
+      dd = fma(-zp, ljm, dd);
+#pragma unroll
+      for (int g = (p + 1) / 8; g < KB / 8; ++g)
+        if (g * 8 < m) {
+#pragma unroll
+          for (int q = (g * 8 > p + 1 ? g * 8 : p + 1); q < g * 8 + 8; ++q) A[q] = fma(-nn_rl(lj, q), ljm, A[q]);
+        }
+    }
+  });
+  return isbad;
+}
+
 template <typename T, int KB, int MODE>
 __global__ void __launch_bounds__(k256) nn_point_kernel(const NnParams P, const T* __restrict__ x, const T* __restrict__ y,
                                                         double* __restrict__ terms, int S, int* __restrict__ bad, T* __restrict__ Bd,
@@ -275,6 +359,47 @@ __global__ void __launch_bounds__(k256) nn_point_tab_kernel(const NnParams P, co
                                                             double* __restrict__ Fd, double* __restrict__ rFd,
                                                             const int* __restrict__ nbr) {
   nn_point_body<T, KB, MODE, true>(P, x, y, terms, S, bad, Bd, Fd, rFd, nbr);
+}
+
+// Local (nearest-neighbour kriging) prediction: query q (column q of xq, ld ldq) is conditioned on the points of row q of its own table
+// (nq x P.k column-major, P.k = min(k, N), -1 after the valid entries); the block, its factorisation and the two riding rows are
+// nn_point_body's (the sibling pieces above).  kd = k(x*, x*) carries no diag (the latent variance), so F starts from the variance and r from 0:
+//   var = F = variance - l'l,   mean = mean_const + l'z = mean_const - r.
+// Only a pivot is "not positive" here (floor: 4 eps (m + 1) of the block's diagonal, variance + diag); F is returned as computed.
+// A query with a coordinate that is not finite gives NaN, and is no error.
+template <typename T, int KB>
+__global__ void __launch_bounds__(k256) nn_local_kernel(const NnParams P, const T* __restrict__ x, const T* __restrict__ y,
+                                                        const T* __restrict__ xq, int64_t ldq, int64_t nq, int64_t q0,
+                                                        const int* __restrict__ nbr, int* __restrict__ bad, T* __restrict__ mean,
+                                                        T* __restrict__ var) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = int64_t(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  if (i >= nq) return;
+  bool qnan = false;
+  for (int f = lane; f < P.d; f += 64) qnan = qnan || !isfinite(double(xq[int64_t(f) * ldq + i]));
+  if (__ballot(qnan) != 0) {
+    if (lane == 0) {
+      if (mean) mean[i] = T(NAN);
+      if (var) var[i] = T(NAN);
+    }
+    return;
+  }
+  const int e = lane < P.k ? nbr[i + int64_t(lane) * nq] : -1;
+  const int m = __builtin_amdgcn_readfirstlane(__popcll(__ballot(e >= 0)));
+  const bool act = lane < m;
+  T A[KB], c;
+  nn_dist2_query<T, KB>(P, x, xq, ldq, i, lane, m, A, c, e);
+  nn_block<T, KB>(P, lane, m, A, c);
+  T dd = act ? T(double(y[e]) - P.mean_const) : T(0);
+  double F = P.variance, r = 0.0;
+  const double floor_ = 4.0 * (sizeof(T) == 8 ? 2.220446049250313e-16 : 1.1920928955078125e-07) * double(m + 1) * (P.variance + P.diag);
+  T myrs = T(1), lme = T(0), zme = T(0);
+  const bool isbad = nn_factor<T, KB>(lane, m, floor_, A, c, dd, F, r, myrs, lme, zme);
+  if (lane == 0) {
+    if (mean) mean[i] = isbad ? T(NAN) : T(P.mean_const - r);
+    if (var) var[i] = isbad ? T(NAN) : T(F);
+    if (isbad) atomicMin(bad, int(q0 + i + 1 < kNnNone ? q0 + i + 1 : kNnNone - 1));
+  }
 }
 
 // part[s][b] = sum of slot s over the points of block b (contiguous ranges of `chunk` points), fixed order
@@ -337,11 +462,45 @@ __global__ void __launch_bounds__(k256) nn_check_tab_kernel(const int* __restric
   if (__ballot(badl) != 0 && lane == 0) atomicMin(flag, int(i + 1 < kNnNone ? i + 1 : kNnNone - 1));
 }
 
+// The current best of a search are kept one per lane (lane l < K: the l-th best so far), sorted by (distance, index).  Candidates
+// arrive in ascending index (lane c of this tile is point j0 + c, `ok`: it is a candidate), so one beats the worst only with a
+// strictly smaller distance, and it goes in behind every entry at most as far (a wave shift).  A distance that is not finite is
+// never chosen.
+template <typename T>
+__device__ __forceinline__ void nn_best_insert(T r2, bool ok, int64_t j0, int K, int lane, T& bd, int& bi) {
+  T worst = nn_rl(bd, K - 1);
+  unsigned long long mask = __ballot(ok && r2 < worst);
+  while (mask) {
+    const int c = __builtin_ctzll(mask);
+    mask &= mask - 1;
+    const T dc = nn_rl(r2, c);
+    if (!(dc < worst)) continue;   // the worst moved since the ballot
+    const int pos = __popcll(__ballot(lane < K && bd <= dc));
+    const T ud = __shfl_up(bd, 1);
+    const int ui = __shfl_up(bi, 1);
+    if (lane > pos) { bd = ud; bi = ui; }
+    if (lane == pos) { bd = dc; bi = int(j0 + c); }
+    worst = nn_rl(bd, K - 1);
+  }
+}
+// Row i of a table (ld rows, kb columns) from the best K: ascending index - the rank of an entry is the number of smaller ones (the
+// unfilled places hold INT_MAX and come last) - and -1 after them
+__device__ __forceinline__ void nn_store_row(int* __restrict__ nbr, int64_t i, int64_t ld, int K, int kb, int lane, int bi) {
+  const bool have = lane < K && bi != INT_MAX;
+  int rank = 0;
+  for (int q = 0; q < K; ++q) {
+    const int v = __shfl(bi, q);
+    rank += v < bi ? 1 : 0;
+  }
+  const int nv = __popcll(__ballot(have));
+  if (have) nbr[i + int64_t(rank) * ld] = bi;
+  if (lane >= nv && lane < kb) nbr[i + int64_t(lane) * ld] = -1;
+}
+
 // The exact k nearest predecessors: for query i the min(i, kb) points j < i with the smallest sum_f ((x_j,f - x_i,f) il_f)^2 (data
 // dtype), ties to the lower index, stored in ascending index.  One wavefront per query, four queries per workgroup in descending i
-// (block 0 holds the longest), candidates in 64-wide tiles shared through LDS.  The current best are kept one per lane, sorted by
-// (distance, index); candidates arrive in ascending index, so one beats the worst only with a strictly smaller distance, and it goes
-// in behind every entry at most as far (a wave shift).  A distance that is not finite is never chosen: that row comes out short.
+// (block 0 holds the longest), candidates in 64-wide tiles shared through LDS.  A distance that is not finite is never chosen: that
+// row comes out short.
 template <typename T>
 __global__ void __launch_bounds__(k256) nn_search_kernel(const NnParams P, const T* __restrict__ x, int* __restrict__ nbr) {
   extern __shared__ double nn_search_lds[];
@@ -370,32 +529,68 @@ __global__ void __launch_bounds__(k256) nn_search_kernel(const NnParams P, const
       const T df = (tile[f * 64 + lane] - qs[w * P.d + f]) * T(P.invl[f]);
       r2 = fma(df, df, r2);
     }
-    T worst = nn_rl(bd, K - 1);
-    unsigned long long mask = __ballot(j0 + lane < i && r2 < worst);
-    while (mask) {
-      const int c = __builtin_ctzll(mask);
-      mask &= mask - 1;
-      const T dc = nn_rl(r2, c);
-      if (!(dc < worst)) continue;   // the worst moved since the ballot
-      const int pos = __popcll(__ballot(lane < K && bd <= dc));
-      const T ud = __shfl_up(bd, 1);
-      const int ui = __shfl_up(bi, 1);
-      if (lane > pos) { bd = ud; bi = ui; }
-      if (lane == pos) { bd = dc; bi = int(j0 + c); }
-      worst = nn_rl(bd, K - 1);
-    }
+    nn_best_insert<T>(r2, j0 + lane < i, j0, K, lane, bd, bi);
   }
   if (i < 0) return;
-  // ascending index: the rank of an entry is the number of smaller ones (the unfilled places hold INT_MAX and come last)
-  const bool have = lane < K && bi != INT_MAX;
-  int rank = 0;
-  for (int q = 0; q < K; ++q) {
-    const int v = __shfl(bi, q);
-    rank += v < bi ? 1 : 0;
+  nn_store_row(nbr, i, P.n, K, P.k, lane, bi);
+}
+
+// The k nearest training points of a test point: for query q (column q of xq, ld ldq) the P.k = min(k, N) points j with the smallest
+// sum_f ((x_j,f - x*_f) il_f)^2, by the rules above, as row q of an nq x P.k table.  Every query scans all N candidates, so the scans
+// of a workgroup have one length and a tile serves every wavefront for all of its life: kNnQw = 16 queries per workgroup (one
+// wavefront each), four times the reuse of a tile and a quarter of the barriers per query of the predecessor search.  The tiles are
+// double buffered - the next one is fetched into registers before the distances of the current one and stored behind them, one
+// barrier per tile - because at one workgroup per compute unit nothing else hides the fetch.  The query's d <= 64 coordinates sit
+// one per lane and are read through scalar registers.
+constexpr int kNnQw = 16;
+template <typename T>
+__global__ void __launch_bounds__(kNnQw * 64) nn_query_search_kernel(const NnParams P, const T* __restrict__ x, const T* __restrict__ xq,
+                                                                     int64_t ldq, int64_t nq, int* __restrict__ nbr) {
+  extern __shared__ double nn_search_lds[];
+  T* tile = reinterpret_cast<T*>(nn_search_lds);   // [2][d][64] candidates
+  constexpr int kPre = 64 * SVGP_MAX_D / (kNnQw * 64);   // elements of a tile per thread
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t i = int64_t(blockIdx.x) * kNnQw + w;   // may be beyond nq in the last block: that wavefront only moves tiles
+  const int te = 64 * P.d;
+  const T qx = (i < nq && lane < P.d) ? xq[int64_t(lane) * ldq + i] : T(0);
+  T pre[kPre];
+  auto fetch = [&](int64_t j0) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < kPre; ++u) {
+      const int e = int(threadIdx.x) + u * kNnQw * 64, f = e >> 6, c = e & 63;
+      pre[u] = (e < te && j0 + c < P.n) ? x[int64_t(f) * P.ldx + j0 + c] : T(0);
+    }
+  };
+  auto stash = [&](T* buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < kPre; ++u) {
+      const int e = int(threadIdx.x) + u * kNnQw * 64;
+      if (e < te) buf[e] = pre[u];
+    }
+  };
+  fetch(0);
+  stash(tile);
+  __syncthreads();
+  T bd = T(INFINITY);
+  int bi = INT_MAX, cur = 0;
+  for (int64_t j0 = 0; j0 < P.n; j0 += 64) {
+    const bool more = j0 + 64 < P.n;
+    if (more) fetch(j0 + 64);
+    if (i < nq) {   // wave-uniform
+      const T* tb = tile + cur * te;
+      T r2 = T(0);
+      for (int f = 0; f < P.d; ++f) {
+        const T df = (tb[f * 64 + lane] - nn_rl(qx, f)) * T(P.invl[f]);
+        r2 = fma(df, df, r2);
+      }
+      nn_best_insert<T>(r2, j0 + lane < P.n, j0, P.k, lane, bd, bi);
+    }
+    cur ^= 1;
+    if (more) stash(tile + cur * te);
+    __syncthreads();   // the next tile is whole, and this one is consumed before the round after next overwrites it
   }
-  const int nv = __popcll(__ballot(have));
-  if (have) nbr[i + int64_t(rank) * P.n] = bi;
-  if (lane >= nv && lane < P.k) nbr[i + int64_t(lane) * P.n] = -1;
+  if (i >= nq) return;
+  nn_store_row(nbr, i, nq, P.k, P.k, lane, bi);
 }
 
 // The reverse lists: the pairs (i, t) with nbr(i, t) = j, for every j, in ascending i.  The pairs are listed row by row (p = i kb + t),
@@ -1034,6 +1229,68 @@ int32_t svgp_nn_predict_cross_cov(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, in
   if (!rc) rc = svgp_data_upload(ctx, nn->dtype, layout, nn->d, ny, y_host, nullptr, &hy.D);
   if (rc) return rc;
   return nn_predict_impl(ctx, nn, hx.D, hy.D, nullptr, nullptr, cov_out);
+}
+
+int32_t svgp_nn_predict_local(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t n, const void* x_host, int32_t k, void* mean_out,
+                              void* var_out, int32_t* nbr_out) {
+  if (!ctx || !nn || !x_host) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (!nn->have_fit) return fail(ctx, SVGP_INVALID_ARG, "no successful svgp_nn_fit on this handle yet");
+  if (n < 1) return fail(ctx, SVGP_INVALID_ARG, "no test points");
+  if (k < 1) return fail(ctx, SVGP_INVALID_ARG, "k must be >= 1");
+  if (layout < 0 || layout > SVGP_VEC || (layout == SVGP_VEC && nn->d != 1)) return fail(ctx, SVGP_INVALID_ARG, "bad layout");
+  if (std::min<int64_t>(k, nn->N) > kNnMaxK) return fail(ctx, SVGP_UNSUPPORTED, "more than 64 neighbours: one lane per neighbour");
+  if (nn->N > int64_t(INT_MAX)) return fail(ctx, SVGP_UNSUPPORTED, "a neighbour table holds int32 indices: N does not fit");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  NnParams P = nn->P;
+  P.k = int(std::min<int64_t>(k, nn->N));   // k > N is N
+  const int d = nn->d, kq = P.k;
+  const size_t es = nn->es;
+  const int64_t cmax = std::min(n, kNnLocalChunk);
+  const bool colvecs = layout == SVGP_COLVECS && d > 1;
+  DevBuf xq, xt, tab, mo, vo;
+  HIPC(ctx, xq.alloc(size_t(cmax) * d * es));
+  if (colvecs) HIPC(ctx, xt.alloc(size_t(cmax) * d * es));
+  HIPC(ctx, tab.alloc(size_t(cmax) * kq * 4));
+  if (mean_out) HIPC(ctx, mo.alloc(size_t(cmax) * es));
+  if (var_out) HIPC(ctx, vo.alloc(size_t(cmax) * es));
+  HIPC(ctx, hipMemsetAsync(nn->bad.p, 0x7f, sizeof(int), s));   // kNnNone
+  const char* xh = static_cast<const char*>(x_host);
+  for (int64_t q0 = 0; q0 < n; q0 += kNnLocalChunk) {
+    const int64_t c = std::min(kNnLocalChunk, n - q0);   // this round's queries: feature-major [d][c] in xq
+    if (colvecs) {
+      HIPC(ctx, hipMemcpyAsync(xt.p, xh + size_t(q0) * d * es, size_t(c) * d * es, hipMemcpyHostToDevice, s));
+      launch_transpose_colvecs(nn->dtype, s, xt.p, d, c, c, xq.p);
+      KCHECK(ctx, "transpose_colvecs");
+    } else {
+      for (int f = 0; f < d; ++f)   // n x d column-major: a round's rows are strided
+        HIPC(ctx, hipMemcpyAsync(static_cast<char*>(xq.p) + size_t(f) * c * es, xh + (size_t(f) * n + q0) * es, size_t(c) * es,
+                                 hipMemcpyHostToDevice, s));
+    }
+    NN_DISPATCH(nn->dtype, T, {
+      const T *x = (const T*)nn->data->x.p, *y = (const T*)nn->data->y.p, *q = (const T*)xq.p;
+      hipLaunchKernelGGL(nn_query_search_kernel<T>, dim3(nblk(c, kNnQw)), dim3(kNnQw * 64), size_t(2) * 64 * d * sizeof(T), s, P, x, q, c, c,
+                         tab.as<int>());
+      const dim3 grid(nblk(c, 4)), block(k256);
+      const int* nbr = tab.as<int>();
+      int* bad = nn->bad.as<int>();
+      if (kq <= 16) hipLaunchKernelGGL((nn_local_kernel<T, 16>), grid, block, 0, s, P, x, y, q, c, c, q0, nbr, bad, (T*)mo.p, (T*)vo.p);
+      else if (kq <= 32) hipLaunchKernelGGL((nn_local_kernel<T, 32>), grid, block, 0, s, P, x, y, q, c, c, q0, nbr, bad, (T*)mo.p, (T*)vo.p);
+      else hipLaunchKernelGGL((nn_local_kernel<T, 64>), grid, block, 0, s, P, x, y, q, c, c, q0, nbr, bad, (T*)mo.p, (T*)vo.p);
+    });
+    KCHECK(ctx, "nn_local");
+    if (mean_out) HIPC(ctx, hipMemcpyAsync(static_cast<char*>(mean_out) + size_t(q0) * es, mo.p, size_t(c) * es, hipMemcpyDeviceToHost, s));
+    if (var_out) HIPC(ctx, hipMemcpyAsync(static_cast<char*>(var_out) + size_t(q0) * es, vo.p, size_t(c) * es, hipMemcpyDeviceToHost, s));
+    if (nbr_out)
+      for (int t = 0; t < kq; ++t)
+        HIPC(ctx, hipMemcpyAsync(nbr_out + size_t(t) * n + q0, tab.as<int>() + size_t(t) * c, size_t(c) * 4, hipMemcpyDeviceToHost, s));
+  }
+  int badv = 0;
+  HIPC(ctx, hipMemcpyAsync(&badv, nn->bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));   // also: the round buffers are released on return
+  if (badv != kNnNone)
+    return fail(ctx, SVGP_NOT_POSDEF, "NearestNeighbors: the block of test point " + std::to_string(badv) + " is not positive");
+  return SVGP_OK;
 }
 
 }  // extern "C"

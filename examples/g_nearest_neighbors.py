@@ -70,6 +70,12 @@ def main():
         mean, var = post.mean_and_var(grid)
         print(f"{name}: grid of {grid.shape[1]} points: rmse against the noise-free function {np.sqrt(np.mean((mean - truth(grid)) ** 2)):.4f}, "
               f"mean latent sd {np.mean(np.sqrt(np.maximum(var, 0.0))):.4f}")
+        if neighbors == "nearest":
+            # the same model predicted locally: every grid point conditioned on its K nearest observed points (svgp_nn_predict_local),
+            # N distances and one K x K block per grid point in place of N kernel evaluations through the global U
+            lmean, lvar = post.local_mean_and_var(grid)
+            print(f"local:   grid of {grid.shape[1]} points: rmse against the noise-free function {np.sqrt(np.mean((lmean - truth(grid)) ** 2)):.4f}, "
+                  f"mean latent sd {np.mean(np.sqrt(np.maximum(lvar, 0.0))):.4f}")
         post.dev.free()
 
 

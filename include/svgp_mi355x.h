@@ -511,7 +511,32 @@ int32_t svgp_laplace_free(svgp_ctx* ctx, svgp_laplace* la);
  * svgp_nn_fit.  A failed set or build leaves the handle with no table.  N must fit int32 (else SVGP_UNSUPPORTED).
  * The gradient is taken at a FIXED table: a table built with the inverse lengthscales as its metric is piecewise constant in them,
  * and svgp_nn_lml_grad does not (and cannot) differentiate the selection.  Bitwise repeatable like the rest: the search uses no
- * atomics, the reverse lists behind alpha come from a stable sort, the validation from one integer atomicMin. */
+ * atomics, the reverse lists behind alpha come from a stable sort, the validation from one integer atomicMin.
+ *
+ * Local predictions (nearest-neighbour kriging: GpGp `predictions`, GPvecchia, spNNGP).  svgp_nn_predict is PosteriorGP with the
+ * global U: N kernel evaluations per test point ((kb + 1) N with a table).  svgp_nn_predict_local conditions every test point on
+ * its own kq = min(k, N) nearest OBSERVED points instead:
+ *   ns* = the kq training points j with the smallest sum_f ((x_j,f - x*_f) il_f)^2 (il: the fit's inverse lengthscales; differences in
+ *         the data dtype, ties to the lower index, ascending index, a distance that is not finite is never chosen)
+ *   C = k(ns*, ns*) + diag I,  c = k(ns*, x*)
+ *   mean(x*) = mean_const + c' C^-1 (y_ns* - mean_const),   var(x*) = k(x*, x*) - c' C^-1 c
+ * var is the latent variance like svgp_nn_predict's (k(x*, x*) carries no diag) and is returned as computed: a test point on top of
+ * a training point at diag = 0 leaves +- rounding noise there.  The test points are independent of each other (no joint covariance).
+ * Cost per test point: N distances (3 d flops, no exp) and one block of order kq, ~ kq^2 (3 d + 20) / 2 + kq^3 / 3; no N x n* object
+ * and no fit-time state beyond the data: the call uses the last successful svgp_nn_fit's kernel, variance, inverse lengthscales,
+ * diag and mean_const, and neither the handle's table nor B, F or alpha (k is this call's own; setting, building or clearing a
+ * table still discards the fit, the rule above, and with it this call).
+ *   k >= 1, min(k, N) <= 64 (more: SVGP_UNSUPPORTED; k > N counts as N); N must fit int32 (else SVGP_UNSUPPORTED).
+ *   mean_out / var_out: n values, data dtype, either may be NULL.  nbr_out (may be NULL): the n x kq table of the ns*, int32
+ *   column-major like the training table, a short row (fewer than kq finite distances) ends in -1.  x* in `layout` with the data's d.
+ *   The test points are processed in rounds of 32768, which is the whole workspace (32768 (d + 2) elements and 32768 kq int32):
+ *   n is bounded by host memory only, and the rounds change no result bit.
+ *   A test point with a coordinate that is not finite: mean = var = NaN for that point (never the prior), SVGP_OK.
+ *   A block with a pivot at or below 4 eps (m + 1) (variance + diag) - repeated training points at diag = 0 - is "not positive":
+ *   mean = var = NaN for that test point, every other one is still written, SVGP_NOT_POSDEF, and svgp_last_error names the first such
+ *   test point (1-based; one integer atomicMin).
+ *   SVGP_INVALID_ARG, before anything is enqueued: NULL ctx / nn / x_host, n < 1, k < 1, no successful fit, a bad layout.
+ * Never collective.  Bitwise repeatable: the search uses no atomics, F and the mean's sum are accumulated in fp64 in a fixed order. */
 typedef struct svgp_nn svgp_nn;
 typedef struct svgp_nn_desc {
   int32_t dtype;            /* SVGP_F64 | SVGP_F32: must be the data's */
@@ -544,6 +569,8 @@ int32_t svgp_nn_set_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t k, const int32
 int32_t svgp_nn_build_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t k, const double* inv_lengthscale);
 int32_t svgp_nn_get_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t* k_out, int32_t* nbr_out);
 int32_t svgp_nn_clear_neighbors(svgp_ctx* ctx, svgp_nn* nn);
+int32_t svgp_nn_predict_local(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t n, const void* x_host, int32_t k, void* mean_out,
+                              void* var_out, int32_t* nbr_out);
 
 /* ---- the collapsed bound of sparse GP regression and the optimal q(u)  (Titsias 2009, eqs. 11 / 12) ---------------------------------
  * For the Gaussian likelihood the q(u) that maximises the ELBO has a closed form; the reference's tests build it on the host

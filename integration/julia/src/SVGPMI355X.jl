@@ -895,6 +895,19 @@ function nn_predict(N::DeviceNN, x, ::Type{T}; want_cov::Bool=false) where {T<:F
                                 ctx(), N.h, lx, n, Xd, μ, v, C === nothing ? C_NULL : C))
     return μ, v, C
 end
+"Nearest-neighbour kriging at x: every test point conditioned on its min(k, n) nearest training points under the fit's inverse
+lengthscales (no N × n* object).  -> (μ, v, table), table n* × min(k, n) zero-based indices (-1 after a short row) when want_table."
+function predict_local(N::DeviceNN, x, k::Integer, ::Type{T}; want_table::Bool=false) where {T<:FT}
+    lx, X, _ = layout(x)
+    Xd = Array{T}(X)
+    n = npoints(lx, Xd)
+    μ, v = zeros(T, n), zeros(T, n)
+    table = want_table ? zeros(Int32, n, min(k, N.data.n)) : nothing
+    GC.@preserve Xd check(ccall((:svgp_nn_predict_local, lib), Int32,
+                                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}),
+                                ctx(), N.h, lx, n, Xd, k, μ, v, table === nothing ? C_NULL : table))
+    return μ, v, table
+end
 "cov(f, x, y) of the same posterior."
 function nn_cross_cov(N::DeviceNN, x, y, ::Type{T}) where {T<:FT}
     lx, X, _ = layout(x)

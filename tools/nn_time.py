@@ -8,7 +8,13 @@ finishes well under a minute at.
 
 Rate: k^3 / 3 + 2 k^2 + k^2 (3 d + 20) / 2 flops per point (factorisation, the two carried rows, block generation) over the
 approx_lml wall time, against the FP64 / FP32 vector peaks 78.6 / 157.3 TFLOP/s (MI355X_MICROARCH.md, AMD's published FP64 figure).
-The device clock torch reports is noted per row when available."""
+The device clock torch reports is noted per row when available.
+
+    python tools/nn_time.py --local [--local-n 200000] [--local-nq 4096] [--ks 16 64] [--local-ds 2 8] [--out ...]
+
+times the local predictions (svgp_nn_predict_local, mean + var) beside svgp_nn_predict (window, and with the nearest table unless
+--local-no-table) at the same N, n*, k and dtype, and writes their ratio; --out appends in this mode.  Cost model: global n* N
+kernel evaluations (n* N (kb + 1) with a table), local n* N distances of 3 d flops plus n* (k^2 (3 d + 20) / 2 + k^3 / 3)."""
 import argparse
 import json
 import os
@@ -51,8 +57,49 @@ def clock_mhz():
         return None
 
 
+def local_rows(a, emit):
+    """predict_local beside predict at one N, n*: a row per (d, dtype, k)"""
+    ctx = _ffi.Context(0)
+    var, diag, n, nq = 1.2, 1e-2, a.local_n, a.local_nq
+    for d in a.local_ds:
+        il = np.linspace(0.8, 1.1, d)
+        kern = ScaledKernel(TransformedKernel(SEKernel(), ARDTransform(il)), var)
+        x, y = nr.synth(n, d, seed=1)
+        xs = np.random.default_rng(2).uniform(-2, 2, size=(d, nq))
+        for dt in (np.float64, np.float32):
+            dev = DeviceNearestNeighbors(ctx, x.astype(dt), y.astype(dt), dt)
+            xq = xs.astype(dt)
+            for k in a.ks:
+                desc, keep = dev.desc(kern, k, diag)
+                dev.fit(desc)
+                dev.predict(xq, cov=False)      # warm-up of every shape
+                dev.predict_local(xq, k)
+                t_glob = timed(lambda: dev.predict(xq, cov=False), a.reps)
+                t_loc = timed(lambda: dev.predict_local(xq, k), a.reps)
+                row = {"local": True, "n": n, "nq": nq, "k": k, "d": d, "dtype": np.dtype(dt).name, "clock_mhz": clock_mhz(), "reps": a.reps,
+                       "predict_window_ms": [round(v, 3) for v in t_glob], "predict_local_ms": [round(v, 3) for v in t_loc],
+                       "window_over_local": round(t_glob[0] / t_loc[0], 3),
+                       "local_gdist_per_s": round(n * nq / (t_loc[0] * 1e-3) / 1e9, 2)}
+                if not a.local_no_table:
+                    dev.build_neighbors(k, il)
+                    dev.fit(desc)
+                    dev.predict(xq, cov=False)
+                    t_tab = timed(lambda: dev.predict(xq, cov=False), a.reps)
+                    row["predict_table_ms"] = [round(v, 3) for v in t_tab]
+                    row["table_over_local"] = round(t_tab[0] / t_loc[0], 3)
+                    dev.clear_neighbors()
+                emit(row)
+            dev.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--local", action="store_true", help="only the predict_local rows")
+    ap.add_argument("--local-n", type=int, default=200_000)
+    ap.add_argument("--local-nq", type=int, default=4096)
+    ap.add_argument("--local-ds", type=int, nargs="+", default=[2, 8])
+    ap.add_argument("--local-no-table", action="store_true", help="skip the table-mode svgp_nn_predict (its search is N^2 / 2 distances)")
     ap.add_argument("--sizes", type=int, nargs="+", default=[10_000, 100_000, 1_000_000])
     ap.add_argument("--ks", type=int, nargs="+", default=[16, 32, 64])
     ap.add_argument("--reps", type=int, default=5)
@@ -60,11 +107,7 @@ def main():
     ap.add_argument("--table-max-n", type=int, default=100_000, help="largest N that also gets the neighbour-table rows")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    ctx = _ffi.Context(0)
-    d, var, diag = 8, 1.2, 1e-2
-    il = np.linspace(0.8, 1.1, d)
-    kern = ScaledKernel(TransformedKernel(SEKernel(), ARDTransform(il)), var)
-    out = open(a.out, "w") if a.out else None
+    out = open(a.out, "a" if a.local else "w") if a.out else None
 
     def emit(row):
         line = json.dumps(row)
@@ -73,6 +116,13 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if a.local:
+        local_rows(a, emit)
+        return
+    ctx = _ffi.Context(0)
+    d, var, diag = 8, 1.2, 1e-2
+    il = np.linspace(0.8, 1.1, d)
+    kern = ScaledKernel(TransformedKernel(SEKernel(), ARDTransform(il)), var)
     host = {}
     for k in a.ks:
         x, y = nr.synth(a.host_n, d, seed=1)
