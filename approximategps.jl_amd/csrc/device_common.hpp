@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include <utility>
 
 #include "diag.hpp"
 #include <stdint.h>
@@ -563,9 +564,10 @@ struct TileGemm {
       r.q[q] = uint32_t((int64_t((wave + q * NW) * QR + qrow) * ldq + (qslot ^ (qrow * 16))) * sizeof(T));
     return r;
   }
+  static __device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)); }
   static __device__ __forceinline__ void dma_tile(const T* __restrict__ psrc, const T* __restrict__ qsrc, const AOff& off,
                                                   T* __restrict__ Pb, T* __restrict__ Qb) {
-    const int wv = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+    const int wv = wave_index();
     if constexpr (!diag::ablate<1>) {   // (diagnostic builds: bit 1 no P-tile DMA, bit 2 no Q-tile DMA - timing only)
 #pragma unroll
       for (int q = 0; q < DP; ++q) glds16(psrc, off.p[q], Pb + (wv + q * NW) * (kPairP ? PPP : PLD));
@@ -665,6 +667,117 @@ struct TileGemm {
     }
     mma_frag<ILO, IHI>(acc, f[1]);
   }
+  // ---- the same step with the buffer rotation at COMPILE time (round 7; SVGP_ASYNC_ROT = 1, the product).
+  // astep above takes the buffer index b as a run-time value, so every LDS address of a step is rebuilt with vector adds
+  // (fr.a + b * PA_TILE, ...: 10 v_add_u32 + 1 v_readfirstlane per 32 f64 MFMAs, and an f64 MFMA never co-executes with VALU work).
+  // Here B is a template parameter and a step's ds_reads address one of three per-lane bases plus an immediate that holds the
+  // buffer offset, the slab offset and, for the slab-0 fragments read behind the barrier, the NEXT buffer's offset:
+  //   * the bases are LDS byte addresses the compiler cannot look into (lds_opaque): left to itself it keeps the constant
+  //     NBUF * PA_TILE of the Q origin in the immediate (0xd800 bytes, f64) and 2 * QA_TILE no longer fits the 16-bit field;
+  //   * the reads are volatile: otherwise pairs of them are merged into ds_read2_b64, whose two 8-bit offsets reach 2 KiB, and
+  //     every slab gets a v_add_u32 for a new base (HEAD did that too: it is where 4 of its 10 adds came from);
+  //   * the LDS destinations of the DMA are one per-wave scalar base per operand plus an immediate (s_add_u32 into M0), not 18
+  //     hoisted scalars, and the wave index is read once per loop.
+  // Same MFMAs in the same order, same waits and barriers as astep: results are bit for bit the same.
+#ifndef SVGP_ASYNC_ROT
+#define SVGP_ASYNC_ROT 1   // 1 = compile-time rotation (rstep), 0 = run-time buffer index (astep); A/B builds (tools/build_variant.sh)
+#endif
+  using LdsP = const volatile __attribute__((address_space(3))) T*;
+  struct RFrag { LdsP a, b0, b1; };
+  static __device__ __forceinline__ LdsP lds_opaque(const T* p) {
+    uint32_t v = uint32_t(uintptr_t((const __attribute__((address_space(3))) T*)(p)));
+    asm("" : "+v"(v));
+    return (LdsP)(uintptr_t(v));
+  }
+  static __device__ __forceinline__ RFrag rfrag(const T* smem) {
+    const AFrag fr = afrag(smem);   // the Q origins carry NBUF * PA_TILE
+    return RFrag{lds_opaque(fr.a), lds_opaque(fr.b0), lds_opaque(fr.b1)};
+  }
+  static constexpr int kMaxRotImmP = ((NBUF - 1) * PA_TILE + (kPairP ? 3 * 2 * PPP : 3 * 4 * PLD) + (MI - 1) * 32) * int(sizeof(T));
+  static constexpr int kMaxRotImmQ = ((NBUF - 1) * QA_TILE + 3 * QSLAB + (NJ - 2) * 16) * int(sizeof(T));
+  static_assert(!kAsync || (kMaxRotImmP < 65536 && kMaxRotImmQ < 65536), "a fragment read's offset must fit the ds_read immediate");
+  template <int B, int KSLAB, int ILO = 0, int IHI = MI - 1>
+  static __device__ __forceinline__ void load_rfrag(Frag& f, const RFrag& fr) {
+    constexpr int AOFF = B * PA_TILE + (kPairP ? KSLAB * 2 * PPP : KSLAB * 4 * PLD);
+    constexpr int QOFF = B * QA_TILE + KSLAB * QSLAB;
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+      if (i >= ILO && i <= IHI) f.a[i] = fr.a[AOFF + i * 32];
+    if (ILO <= IHI) {
+      static_assert(NJ % 2 == 0, "column tiles come in even / odd pairs");
+      static_assert(QR == 2 || NJ == 2, "the quad image is written for two column tiles per wave");
+#pragma unroll
+      for (int j = 0; j < NJ; j += 2) {
+        f.b[j] = fr.b0[QOFF + j * 16];
+        f.b[j + 1] = fr.b1[QOFF + j * 16];
+      }
+    }
+  }
+  // this wave's first DMA destination row (unit) of buffer 0, as LDS byte addresses in scalar registers
+  struct ADst { uint32_t p, q; };
+  static __device__ __forceinline__ ADst a_dst(const T* smem, int wv) {
+    const uint32_t l = uint32_t(uintptr_t((const __attribute__((address_space(3))) T*)(smem)));
+    return ADst{l + uint32_t(wv * (kPairP ? PPP : PLD) * int(sizeof(T))),
+                l + uint32_t((NBUF * PA_TILE + wv * QPP) * int(sizeof(T)))};
+  }
+  template <int IMM>
+  static __device__ __forceinline__ void glds16_at(const void* sbase, uint32_t voff, uint32_t lds) {
+    asm volatile("s_add_u32 m0, %0, %3\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(sbase), "n"(IMM) : "memory", "scc");
+  }
+  // dma_tile into buffer B of a destination pair that may itself be displaced by whole buffers (the loop's prologue)
+  template <int B>
+  static __device__ __forceinline__ void dma_tile_at(const T* __restrict__ psrc, const T* __restrict__ qsrc, const AOff& off,
+                                                     const ADst& dst) {
+    if constexpr (!diag::ablate<1>) dma_rows<B * PA_TILE, NW * (kPairP ? PPP : PLD)>(psrc, off.p, dst.p, std::make_integer_sequence<int, DP>{});
+    if constexpr (!diag::ablate<2>) dma_rows<B * QA_TILE, NW * QPP>(qsrc, off.q, dst.q, std::make_integer_sequence<int, DQ>{});
+  }
+  template <int BASE, int STRIDE, int N, int... Q>
+  static __device__ __forceinline__ void dma_rows(const T* __restrict__ src, const uint32_t (&voff)[N], uint32_t dst,
+                                                  std::integer_sequence<int, Q...>) {
+    (glds16_at<(BASE + Q * STRIDE) * int(sizeof(T))>(src, voff[Q], dst), ...);
+  }
+  // one k-step on tile t, which lives in buffer B (= t % NBUF up to the loop's displacement: the caller's business).
+  // MORE: how many tiles follow tile t where the caller knows it (3: at least three, 2, 1, 0: the loop's last step), else kAskT.
+  // The written-out tail says it this way and passes the loop counter as t: numbered nreg + k, its steps' DMA source pointers are
+  // invariants of the trips before them, get computed ahead of the loop and come back as 16 scalar-register reloads in the tail.
+  static constexpr int kAskT = -1;
+  template <int B, int ILO, int IHI, int MORE = kAskT, typename QSrc, typename WSrc>
+  static __device__ __forceinline__ void rstep(Acc& acc, Frag (&f)[2], const T* __restrict__ Pbase, int64_t pstride,
+                                               const AOff& off, int t, int nsteps, QSrc& qsrc, WSrc& wsrc, T* __restrict__ smem,
+                                               const ADst& dst, const RFrag& fr) {
+    constexpr int KS = BK / 4;
+    constexpr bool W = WSrc::on;
+    constexpr int PER_TILE = DMA_PER_TILE + (W ? 1 : 0);
+    constexpr int BN = (B + 1) % NBUF;
+    static_assert(KS == 4, "written for 16-deep steps");
+    static_assert(B >= 0 && B < NBUF, "buffer index");
+    T* Ws = smem + NBUF * (PA_TILE + QA_TILE);
+    const T* wl = Ws + B * W_TILE + ((threadIdx.x & 63) >> 4);   // this lane's k-row of slab 0
+    load_rfrag<B, 1, ILO, IHI>(f[1], fr);
+    mma_frag<ILO, IHI>(acc, f[0]);
+    scale_b<1, W>(f[1], wl);
+    load_rfrag<B, 2, ILO, IHI>(f[0], fr);
+    mma_frag<ILO, IHI>(acc, f[1]);
+    scale_b<2, W>(f[0], wl);
+    load_rfrag<B, 3, ILO, IHI>(f[1], fr);
+    mma_frag<ILO, IHI>(acc, f[0]);
+    scale_b<3, W>(f[1], wl);
+    const bool more1 = (MORE == kAskT) ? (t + 1 < nsteps) : (MORE >= 1);
+    const bool more2 = (MORE == kAskT) ? (t + 2 < nsteps) : (MORE >= 2);
+    const bool more3 = (MORE == kAskT) ? (t + 3 < nsteps) : (MORE >= 3);
+    if (more1) {
+      // tile t + 1 must be in LDS for every wave: of this wave's DMAs only the newest group (tile t + 2) may still fly
+      if (more2) wait_barrier<PER_TILE>();
+      else wait_barrier<0>();
+      load_rfrag<BN, 0>(f[0], fr);   // all tiles: next range unknown here
+      scale_b<0, W>(f[0], Ws + BN * W_TILE + ((threadIdx.x & 63) >> 4));
+      if (more3) {   // buffer B (tile t) is free now
+        dma_tile_at<B>(Pbase + int64_t(t + 3) * pstride, qsrc(t + 3), off, dst);
+        if constexpr (W) dma_w(wsrc(t + 3), Ws + B * W_TILE);
+      }
+    }
+    mma_frag<ILO, IHI>(acc, f[1]);
+  }
   // ---- a weighted twin of astep (the SYRK W = A diag(w) A'), round 4, MEASURED AND REJECTED (kept as an A/B build, SVGP_WSTEP).
   // A separate function, NOT a branch of astep: the strips' kernels, which instantiate the unweighted step, change their register
   // allocation with any edit of it (212 -> 255 VGPRs + 4 spills when this was first written as one function).  The idea: fetch
@@ -729,6 +842,7 @@ struct TileGemm {
     }
   }
 #define SVGP_ASTEP(LO, HI, TT) astep<LO, HI>(acc, f, Pbase, pstride, off, (TT), nsteps, qsrc, wsrc, smem, b, fr)
+#define SVGP_RSTEP(B, LO, HI, TT, ...) rstep<B, LO, HI, ##__VA_ARGS__>(acc, f, Pbase, pstride, off, (TT), nsteps, qsrc, wsrc, smem, dst, fr)
   template <int TRI, typename QSrc>
   static __device__ __forceinline__ void loop_tri_async(Acc& acc, const T* __restrict__ Pbase, int64_t ldp, int nsteps,
                                                         QSrc&& qsrc, T* __restrict__ smem, int64_t ldq = NT) {
@@ -745,45 +859,119 @@ struct TileGemm {
     static_assert(TRI == 0 || (ND == 8 && MI == 4), "triangular steps are written out for BK = 16, 128-row panels");
     const AOff off = a_offsets(ldp, ldq);
     const int64_t pstride = int64_t(BK) * ldp;
-    const AFrag fr = afrag(smem);
-    T* Qs = smem + NBUF * PA_TILE;
-    T* Ws = smem + NBUF * (PA_TILE + QA_TILE);
-    dma_tile(Pbase, qsrc(0), off, smem, Qs);
-    if constexpr (W) dma_w(wsrc(0), Ws);
-    if (nsteps > 1) {
-      dma_tile(Pbase + pstride, qsrc(1), off, smem + PA_TILE, Qs + QA_TILE);
-      if constexpr (W) dma_w(wsrc(1), Ws + W_TILE);
-    }
-    if (nsteps > 2) {
-      dma_tile(Pbase + 2 * pstride, qsrc(2), off, smem + 2 * PA_TILE, Qs + 2 * QA_TILE);
-      if constexpr (W) dma_w(wsrc(2), Ws + 2 * W_TILE);
-    }
-    if (nsteps > 2) wait_barrier<2 * PER_TILE>();
-    else if (nsteps > 1) wait_barrier<PER_TILE>();
-    else wait_barrier<0>();
-    Frag f[2];
-    load_afrag<0>(f[0], fr.a, fr.b0, fr.b1);
-    scale_b<0, W>(f[0], Ws + ((threadIdx.x & 63) >> 4));
-    int b = 0, t = 0;
-    if (TRI < 0) {
-      SVGP_ASTEP(0, 0, 0); SVGP_ASTEP(0, 0, 1); SVGP_ASTEP(0, 1, 2); SVGP_ASTEP(0, 1, 3);
-      SVGP_ASTEP(0, 2, 4); SVGP_ASTEP(0, 2, 5); SVGP_ASTEP(0, 3, 6); SVGP_ASTEP(0, 3, 7);
-      t = ND;
-    }
     const int nreg = (TRI > 0) ? nsteps - ND : nsteps;
-    if constexpr (W && TRI == 0 && SVGP_WSTEP != 0) {
-      WRegs wr;
-      load_w(wr, Ws + ((threadIdx.x & 63) >> 4));   // f[0] was scaled above through scale_b (once per loop)
-      for (; t < nreg; ++t) astep_w(acc, f, wr, Pbase, pstride, off, t, nsteps, qsrc, wsrc, smem, b, fr);
+    Frag f[2];
+    constexpr bool kTwin = W && TRI == 0 && SVGP_WSTEP != 0;   // the weighted twin (A/B builds) keeps the run-time buffer index
+    if constexpr (SVGP_ASYNC_ROT && !kTwin) {
+      // Compile-time rotation: three regular steps per trip, buffers 0, 1, 2.  The 0 / 1 / 2 regular steps that do not fill a trip
+      // cost no dispatch inside the loop:
+      //   TRI >= 0: they run FIRST.  The loop's tiles are displaced by s0 = (3 - nreg % 3) % 3 buffers (tile t in buffer (t + s0) % 3),
+      //     which only the prologue's DMA destinations (scalar) and one wave-uniform branch at the loop's entry see: the steps left
+      //     over run in buffers 1, 2 or 2, the trips follow from buffer 0, and the eight written-out triangular steps of TRI > 0
+      //     always start at buffer 0 - ONE instance of them.  (Three instances entered by a branch behind the trips, and the left-over
+      //     steps behind the trips, were built first: the f64 strips went from 212 to 256 VGPRs with 284 bytes of scratch.)
+      //   TRI < 0: the eight head steps have the buffers 0, 1, 2, 0, 1, 2, 0, 1, the trips start at buffer 2 and the left-over
+      //     steps follow them, each behind its own wave-uniform branch (two per loop, not per step).
+      constexpr bool kRemFirst = TRI >= 0;
+      const int rem = kRemFirst ? nreg % NBUF : 0;
+      const int s0 = (rem == 0) ? 0 : NBUF - rem, s1 = (s0 + 1 == NBUF) ? 0 : s0 + 1, s2 = (s1 + 1 == NBUF) ? 0 : s1 + 1;
+      const ADst dst = a_dst(smem, wave_index());
+      auto displaced = [&](int sb) { return ADst{dst.p + uint32_t(sb * PA_TILE * int(sizeof(T))), dst.q + uint32_t(sb * QA_TILE * int(sizeof(T)))}; };
+      T* Ws = smem + NBUF * (PA_TILE + QA_TILE);
+      dma_tile_at<0>(Pbase, qsrc(0), off, displaced(s0));
+      if constexpr (W) dma_w(wsrc(0), Ws + s0 * W_TILE);
+      if (nsteps > 1) {
+        dma_tile_at<0>(Pbase + pstride, qsrc(1), off, displaced(s1));
+        if constexpr (W) dma_w(wsrc(1), Ws + s1 * W_TILE);
+      }
+      if (nsteps > 2) {
+        dma_tile_at<0>(Pbase + 2 * pstride, qsrc(2), off, displaced(s2));
+        if constexpr (W) dma_w(wsrc(2), Ws + s2 * W_TILE);
+      }
+      if (nsteps > 2) wait_barrier<2 * PER_TILE>();
+      else if (nsteps > 1) wait_barrier<PER_TILE>();
+      else wait_barrier<0>();
+      const RFrag fr = rfrag(smem);
+      const T* wl0 = Ws + ((threadIdx.x & 63) >> 4);
+      if constexpr (kRemFirst) {
+        // the left-over steps' tile numbers 0 and 1 as a value the compiler cannot see: as literals, their DMA source pointers are
+        // invariants of the CALLER's loop over panels, get hoisted out of it and come back as scalar-register spills inside the steps
+        int zt = 0;
+        asm volatile("" : "+s"(zt));
+        int t = rem;
+        if (rem == 0) {
+          load_rfrag<0, 0>(f[0], fr);
+          scale_b<0, W>(f[0], wl0);
+        } else if (rem == 1) {
+          load_rfrag<2, 0>(f[0], fr);
+          scale_b<0, W>(f[0], wl0 + 2 * W_TILE);
+          SVGP_RSTEP(2, 0, MI - 1, zt);
+        } else {
+          load_rfrag<1, 0>(f[0], fr);
+          scale_b<0, W>(f[0], wl0 + W_TILE);
+          SVGP_RSTEP(1, 0, MI - 1, zt); SVGP_RSTEP(2, 0, MI - 1, zt + 1);
+        }
+        for (; t < nreg; t += 3) {
+          SVGP_RSTEP(0, 0, MI - 1, t); SVGP_RSTEP(1, 0, MI - 1, t + 1); SVGP_RSTEP(2, 0, MI - 1, t + 2);
+        }
+        if constexpr (TRI > 0) {   // the lower-triangular tail, tile ranges as in loop_tri; t == nreg here
+          SVGP_RSTEP(0, 0, 3, t + 0, 3); SVGP_RSTEP(1, 0, 3, t + 1, 3); SVGP_RSTEP(2, 1, 3, t + 2, 3); SVGP_RSTEP(0, 1, 3, t + 3, 3);
+          SVGP_RSTEP(1, 2, 3, t + 4, 3); SVGP_RSTEP(2, 2, 3, t + 5, 2); SVGP_RSTEP(0, 3, 3, t + 6, 1); SVGP_RSTEP(1, 3, 3, t + 7, 0);
+        }
+      } else {
+        load_rfrag<0, 0>(f[0], fr);
+        scale_b<0, W>(f[0], wl0);
+        SVGP_RSTEP(0, 0, 0, 0); SVGP_RSTEP(1, 0, 0, 1); SVGP_RSTEP(2, 0, 1, 2); SVGP_RSTEP(0, 0, 1, 3);
+        SVGP_RSTEP(1, 0, 2, 4); SVGP_RSTEP(2, 0, 2, 5); SVGP_RSTEP(0, 0, 3, 6); SVGP_RSTEP(1, 0, 3, 7);
+        constexpr int B0 = ND % NBUF, B1 = (B0 + 1) % NBUF, B2 = (B0 + 2) % NBUF;
+        int t = ND;
+        for (; t + 2 < nreg; t += 3) {
+          SVGP_RSTEP(B0, 0, MI - 1, t); SVGP_RSTEP(B1, 0, MI - 1, t + 1); SVGP_RSTEP(B2, 0, MI - 1, t + 2);
+        }
+        if (t < nreg) SVGP_RSTEP(B0, 0, MI - 1, t);
+        if (t + 1 < nreg) SVGP_RSTEP(B1, 0, MI - 1, t + 1);
+      }
+      __builtin_amdgcn_sched_barrier(0);   // the caller's epilogue arithmetic stays out of the last step's MFMAs
     } else {
-      for (; t < nreg; ++t) astep<0, MI - 1>(acc, f, Pbase, pstride, off, t, nsteps, qsrc, wsrc, smem, b, fr);
-    }
-    if (TRI > 0) {
-      SVGP_ASTEP(0, 3, nreg + 0); SVGP_ASTEP(0, 3, nreg + 1); SVGP_ASTEP(1, 3, nreg + 2); SVGP_ASTEP(1, 3, nreg + 3);
-      SVGP_ASTEP(2, 3, nreg + 4); SVGP_ASTEP(2, 3, nreg + 5); SVGP_ASTEP(3, 3, nreg + 6); SVGP_ASTEP(3, 3, nreg + 7);
+      const AFrag fr = afrag(smem);
+      T* Qs = smem + NBUF * PA_TILE;
+      T* Ws = smem + NBUF * (PA_TILE + QA_TILE);
+      dma_tile(Pbase, qsrc(0), off, smem, Qs);
+      if constexpr (W) dma_w(wsrc(0), Ws);
+      if (nsteps > 1) {
+        dma_tile(Pbase + pstride, qsrc(1), off, smem + PA_TILE, Qs + QA_TILE);
+        if constexpr (W) dma_w(wsrc(1), Ws + W_TILE);
+      }
+      if (nsteps > 2) {
+        dma_tile(Pbase + 2 * pstride, qsrc(2), off, smem + 2 * PA_TILE, Qs + 2 * QA_TILE);
+        if constexpr (W) dma_w(wsrc(2), Ws + 2 * W_TILE);
+      }
+      if (nsteps > 2) wait_barrier<2 * PER_TILE>();
+      else if (nsteps > 1) wait_barrier<PER_TILE>();
+      else wait_barrier<0>();
+      load_afrag<0>(f[0], fr.a, fr.b0, fr.b1);
+      scale_b<0, W>(f[0], Ws + ((threadIdx.x & 63) >> 4));
+      int b = 0, t = 0;
+      if (TRI < 0) {
+        SVGP_ASTEP(0, 0, 0); SVGP_ASTEP(0, 0, 1); SVGP_ASTEP(0, 1, 2); SVGP_ASTEP(0, 1, 3);
+        SVGP_ASTEP(0, 2, 4); SVGP_ASTEP(0, 2, 5); SVGP_ASTEP(0, 3, 6); SVGP_ASTEP(0, 3, 7);
+        t = ND;
+      }
+      if constexpr (kTwin) {
+        WRegs wr;
+        load_w(wr, Ws + ((threadIdx.x & 63) >> 4));   // f[0] was scaled above through scale_b (once per loop)
+        for (; t < nreg; ++t) astep_w(acc, f, wr, Pbase, pstride, off, t, nsteps, qsrc, wsrc, smem, b, fr);
+      } else {
+        for (; t < nreg; ++t) astep<0, MI - 1>(acc, f, Pbase, pstride, off, t, nsteps, qsrc, wsrc, smem, b, fr);
+      }
+      if (TRI > 0) {
+        SVGP_ASTEP(0, 3, nreg + 0); SVGP_ASTEP(0, 3, nreg + 1); SVGP_ASTEP(1, 3, nreg + 2); SVGP_ASTEP(1, 3, nreg + 3);
+        SVGP_ASTEP(2, 3, nreg + 4); SVGP_ASTEP(2, 3, nreg + 5); SVGP_ASTEP(3, 3, nreg + 6); SVGP_ASTEP(3, 3, nreg + 7);
+      }
     }
     __syncthreads();  // callers reuse the LDS right away; also drains nothing (every DMA was waited for)
   }
+#undef SVGP_RSTEP
 #undef SVGP_ASTEP
 };
 

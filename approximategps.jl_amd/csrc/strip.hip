@@ -75,6 +75,9 @@ __device__ __forceinline__ void pregen_mfma(const T* __restrict__ xs, const T* _
   }
   for (int kb = wave; kb < int(Mp / 16); kb += NW) {
     const int64_t k0 = int64_t(kb) * 16;
+    // rows >= M are padding and stored as zeros; the test is uniform over the block except in the one block that straddles M,
+    // so it is a wave-uniform branch around the masked store form and not 2-3 v_cndmask per generated element
+    const bool inside = __builtin_amdgcn_readfirstlane(int(k0 + 16 <= M)) != 0;
     T za[KS];
     T s = T(0);
 #pragma unroll
@@ -110,14 +113,23 @@ __device__ __forceinline__ void pregen_mfma(const T* __restrict__ xs, const T* _
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] += acc2[r];
       }
+      T out[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int64_t k = k0 + M16::row(lane, r);
         const T v = acc[r];
-        T out;
-        if constexpr (SVGP_PREGEN_EXPTAB && F == KSE && sizeof(T) == 8) out = T(kexp_tab(double(v > c0 ? c0 : v), exptab));
-        else out = (F == KSE) ? kexp(v > c0 ? c0 : v) : kappa<T>(F, v < T(0) ? T(0) : v, variance);
-        work[k * NT + jt * 16 + l15] = (k < M) ? out : T(0);
+        if constexpr (SVGP_PREGEN_EXPTAB && F == KSE && sizeof(T) == 8) out[r] = T(kexp_tab(double(v > c0 ? c0 : v), exptab));
+        else out[r] = (F == KSE) ? kexp(v > c0 ? c0 : v) : kappa<T>(F, v < T(0) ? T(0) : v, variance);
+      }
+      if (inside) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) work[(k0 + M16::row(lane, r)) * NT + jt * 16 + l15] = out[r];
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t k = k0 + M16::row(lane, r);
+          work[k * NT + jt * 16 + l15] = (k < M) ? out[r] : T(0);
+        }
+        asm volatile("" ::: "memory");   // keeps the two store forms apart (merged, the mask is back on every block)
       }
     }
   }
