@@ -23,5 +23,7 @@ from .nearest_neighbors import (DeviceNearestNeighbors, NearestNeighbors, NNPost
                                 posterior)
 # VFE(fz): the collapsed (Titsias) bound and the optimal q(u); elbo, elbo_and_gradient, approx_lml and posterior dispatch on it too
 from .vfe import VFE, approx_lml, elbo, elbo_and_gradient, optimal_variational_posterior, posterior
+# natural-gradient steps on q(u) (GPflow's NaturalGradient / GPyTorch's NGD); DeviceModel.natgrad_step / update_keep_q for resident loops
+from .natgrad import natural_gradient_step
 
 __all__ = [n for n in dir() if not n.startswith("_")]

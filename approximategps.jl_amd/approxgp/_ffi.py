@@ -170,6 +170,12 @@ SYMBOLS = {
     "svgp_collapsed_q": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, C.POINTER(C.c_double)]),
     "svgp_collapsed_grad": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.POINTER(CollapsedTerms),
                                         C.POINTER(Grads), C.POINTER(InputGrad)]),
+    # natural-gradient steps on q
+    "svgp_natgrad_step": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(Terms),
+                                      C.POINTER(Grads), _P, _P]),
+    "svgp_natgrad_step_ext": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _P, _P,
+                                          C.POINTER(C.c_double), C.POINTER(Terms), C.POINTER(Grads), _P, _P]),
+    "svgp_model_update_keep_q": (C.c_int32, [_P, _P, C.POINTER(ModelDesc)]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),
     "svgp_ctx_attach_comm": (C.c_int32, [_P, _P, C.c_int32, C.c_int32]),
@@ -466,6 +472,12 @@ class DeviceModel:
         self.ctx.check(self.ctx.lib.svgp_model_update(self.ctx.h, self.h, C.byref(desc)))
         del keep
 
+    def update_keep_q(self, desc: ModelDesc, keep):
+        """svgp_model_update_keep_q: new kernel parameters, z, likelihood parameters, jitter and mean_const go up; desc.m / desc.Lq are
+        ignored (they may be NULL) and the device-resident q - e.g. what natgrad_step wrote - stays."""
+        self.ctx.check(self.ctx.lib.svgp_model_update_keep_q(self.ctx.h, self.h, C.byref(desc)))
+        del keep
+
     def set_mean_z(self, mu_z):
         """mean(fz) = mean_const + mu_z (M host values; None removes them): svgp_model_set_mean_z.  Centered models only depend on it."""
         if mu_z is None:
@@ -658,6 +670,41 @@ class DeviceModel:
         if xb is not None:
             res["x"] = xb
         return out.value, terms, res
+
+    # ---- natural-gradient steps on q (svgp_natgrad_step / _ext) ----
+    def natgrad_step(self, data: DeviceData, off=0, length=None, num_data=0.0, gamma=1.0, ext=None, want_grads=False, fetch=True,
+                     z_shape=None):
+        """One natural-gradient step of length gamma in (0, 1] on the model's device-resident q -> (elbo, terms, grads, m, Lq).
+        elbo, terms and grads (the dict of elbo_grad with want_grads=True, else None) are the values at the q the call started from;
+        m and Lq are host copies of the NEW q in the model's dtype and parametrisation (None with fetch=False).
+        ext = (sum_e, g_mu, g_v): a likelihood the host evaluated on `marginals` (svgp_natgrad_step_ext)."""
+        length = data.n - off if length is None else length
+        dt = np_dtype(self.dtype)
+        mb = np.zeros(self.M, dtype=dt) if fetch else None
+        Lb = np.zeros((self.M, self.M), dtype=dt, order="F") if fetch else None
+        g, res = None, None
+        if want_grads:
+            zshape = z_shape if z_shape is not None else ((self.M,) if self.d == 1 else (self.d, self.M))
+            il = np.zeros(self.d)
+            zb = np.zeros(zshape, dtype=dt, order="F")
+            gm = np.zeros(self.M, dtype=dt)
+            gL = np.zeros((self.M, self.M), dtype=dt, order="F")
+            g = Grads(0.0, 0.0, 0.0, il.ctypes.data_as(C.POINTER(C.c_double)), _ptr(zb), _ptr(gm), _ptr(gL))
+        out, terms = C.c_double(), Terms()
+        gref = C.byref(g) if g is not None else None
+        if ext is not None:
+            gmu, gv = (np.ascontiguousarray(a, dtype=np.float64) for a in ext[1:])
+            if gmu.shape != (length,) or gv.shape != (length,):
+                raise ValueError("one point gradient per point of the batch")
+            rc = self.ctx.lib.svgp_natgrad_step_ext(self.ctx.h, self.h, data.h, off, length, float(num_data), float(gamma), float(ext[0]),
+                                                    _ptr(gmu), _ptr(gv), C.byref(out), C.byref(terms), gref, _ptr(mb), _ptr(Lb))
+        else:
+            rc = self.ctx.lib.svgp_natgrad_step(self.ctx.h, self.h, data.h, off, length, float(num_data), float(gamma), C.byref(out),
+                                                C.byref(terms), gref, _ptr(mb), _ptr(Lb))
+        self.ctx.check(rc, terms)
+        if g is not None:
+            res = dict(variance=g.variance, inv_lengthscale=il, z=zb, m=gm, Lq=gL, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const)
+        return out.value, terms, res, mb, Lb
 
     def prior_kl(self):
         kl, ld = C.c_double(), C.c_double()

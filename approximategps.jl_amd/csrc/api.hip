@@ -123,7 +123,7 @@ int gauss_hermite(int n, double* xs, double* ws) {
   return SVGP_OK;
 }
 
-int validate_desc(svgp_ctx* ctx, const svgp_model_desc* d) {
+int validate_desc(svgp_ctx* ctx, const svgp_model_desc* d, bool need_q = true) {   // need_q false: d->m / d->Lq are not read (svgp_model_update_keep_q)
   if (!d) return fail(ctx, SVGP_INVALID_ARG, "null model descriptor");
   if (d->dtype != SVGP_F64 && d->dtype != SVGP_F32) return fail(ctx, SVGP_INVALID_ARG, "dtype must be SVGP_F64 or SVGP_F32");
   if (d->kernel < 0 || d->kernel > SVGP_KERNEL_MATERN52) return fail(ctx, SVGP_UNSUPPORTED, "unsupported kernel family");
@@ -135,7 +135,7 @@ int validate_desc(svgp_ctx* ctx, const svgp_model_desc* d) {
   if (d->layout_z < 0 || d->layout_z > SVGP_VEC) return fail(ctx, SVGP_INVALID_ARG, "bad layout_z");
   if (d->layout_z == SVGP_VEC && d->d != 1) return fail(ctx, SVGP_INVALID_ARG, "SVGP_VEC layout requires d == 1");
   if (d->quadrature_n < 0 || d->quadrature_n > 512) return fail(ctx, SVGP_INVALID_ARG, "quadrature_n must be in 0..512");
-  if (!d->inv_lengthscale || !d->z || !d->m || !d->Lq) return fail(ctx, SVGP_INVALID_ARG, "null parameter array");
+  if (!d->inv_lengthscale || !d->z || (need_q && (!d->m || !d->Lq))) return fail(ctx, SVGP_INVALID_ARG, "null parameter array");
   if (!(d->variance > 0)) return fail(ctx, SVGP_INVALID_ARG, "kernel variance must be positive");
   if (d->likelihood == SVGP_LIK_GAUSSIAN && !(d->lik_sigma2 > 0)) return fail(ctx, SVGP_INVALID_ARG, "Gaussian likelihood needs sigma2 > 0");
   if (d->likelihood == SVGP_LIK_GAMMA_EXP && !(d->lik_sigma2 > 0)) return fail(ctx, SVGP_INVALID_ARG, "Gamma likelihood needs shape alpha > 0");
@@ -153,15 +153,17 @@ int effective_gh(const svgp_model_desc& d) {
   return 20;  // DefaultExpectationMethod -> GaussHermiteExpectation(20)  [GPLikelihoods]
 }
 
-int upload_params(svgp_ctx* ctx, svgp_model* m, const svgp_model_desc* d) {
+int upload_params(svgp_ctx* ctx, svgp_model* m, const svgp_model_desc* d, bool keep_q = false) {   // keep_q: the device-resident m / Lq stay
   const size_t es = m->es;
   m->desc = *d;
   m->invl_host.assign(d->inv_lengthscale, d->inv_lengthscale + d->d);
   m->desc.inv_lengthscale = m->invl_host.data();
   m->desc.z = m->desc.m = m->desc.Lq = nullptr;  // host pointers are borrowed for the call only
   HIPC(ctx, hipMemcpyAsync(m->z_raw.p, d->z, size_t(m->M) * m->d * es, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(ctx, hipMemcpyAsync(m->m_raw.p, d->m, size_t(m->M) * es, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(ctx, hipMemcpyAsync(m->Lq_raw.p, d->Lq, size_t(m->M) * m->M * es, hipMemcpyHostToDevice, ctx->stream));
+  if (!keep_q) {
+    HIPC(ctx, hipMemcpyAsync(m->m_raw.p, d->m, size_t(m->M) * es, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(m->Lq_raw.p, d->Lq, size_t(m->M) * m->M * es, hipMemcpyHostToDevice, ctx->stream));
+  }
   if (m->dtype == SVGP_F64) {
     HIPC(ctx, hipMemcpyAsync(m->invl.p, m->invl_host.data(), m->d * 8, hipMemcpyHostToDevice, ctx->stream));
   } else {
@@ -970,6 +972,19 @@ int32_t svgp_model_update(svgp_ctx* ctx, svgp_model* m, const svgp_model_desc* d
   return upload_params(ctx, m, desc);
 }
 
+// svgp_model_update without the upload of q: desc->m / desc->Lq are ignored (they may be NULL), the device-resident q - what the model
+// was created or last updated with, or what svgp_collapsed_q / svgp_natgrad_step wrote - stays
+int32_t svgp_model_update_keep_q(svgp_ctx* ctx, svgp_model* m, const svgp_model_desc* desc) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!m) return fail(ctx, SVGP_INVALID_ARG, "null model");
+  int rc = validate_desc(ctx, desc, false);
+  if (rc) return rc;
+  if (desc->M != m->M || desc->d != m->d || desc->dtype != m->dtype || desc->parametrization != m->desc.parametrization)
+    return fail(ctx, SVGP_INVALID_ARG, "svgp_model_update_keep_q: M, d, dtype and parametrization must not change");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  return upload_params(ctx, m, desc, true);
+}
+
 int32_t svgp_elbo_partial(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len,
                           double partial_out[4]) {
   int rc = check_batch(ctx, m, data, off, len, true);
@@ -1338,7 +1353,18 @@ struct GradCall {
   // requested - point_grad_kernel writes its g_mu a second time there)
   const void* mux = nullptr;
   void* mux_bar = nullptr;
+  // svgp_natgrad_step: where W = A diag(-2 scale g_v) A' goes in fp64, gathered from the SYRK's slices before the tail reuses their
+  // buffer as split-K scratch (NULL: not requested, nothing more is launched)
+  double* ng_W = nullptr;
 };
+
+// svgp_natgrad_step / _ext: the step length and the fp64 workspace of the M-sized tail that follows the value-and-gradient's launches
+struct NatgradCall {
+  double gamma = 1.0;
+  CollapsedWs* c = nullptr;
+};
+int natgrad_enqueue(svgp_ctx* ctx, svgp_model* m, GradCall& gc, NatgradCall& ng);   // (below, beside the collapsed bound's tail)
+int natgrad_finish(svgp_ctx* ctx, svgp_model* m, NatgradCall& ng);
 
 // out = Xt' Yt for M x M operands ("k-major": Xt[k][r] at Xt[k Mp + r]; a row-major matrix Z is the operand Z, a column-major
 // one is Z').  Lower 128-tiles of the row-major result, or all tiles with kMmFull; kMm?Low / kMm?Up name triangular operands
@@ -1618,6 +1644,10 @@ int grad_enqueue_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64
   }
   if (gc.ext_gmu) launch_add_f64(s, w->sums, gc.ext_sum_e);   // sums[0] = sum E: the host's, before any collective
   TREC(ctx, ctx->ev[2], s);
+  if (gc.ng_W) {
+    launch_natgrad_gather_w(dt, s, w->G1.p, ns_syrk, Mp, gc.ng_W);
+    KCHECK(ctx, "natgrad (W in fp64)");
+  }
   // M-sized tail.  With W = A diag(2 g_v) A' and a = A g_mu:
   //   Lq_bar = tril(W B) - klw dKL/dB,   Lk_bar = -tril(alpha a' + R W)     (B = Lq whitened; W, R carry the factors 2)
   launch_sym_from_lower(dt, s, w->G1.p, ns_syrk, Mp, 0.0, w->W2.p);
@@ -1852,8 +1882,10 @@ int grad_finish(svgp_ctx* ctx, svgp_model* m, GradCall& gc, double* elbo_out, sv
 int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double scale, double klw,
                    double num_data, bool collective, double* elbo_out, svgp_terms* terms_out, svgp_grads* g,
                    const double* ext_gmu = nullptr, const double* ext_gv = nullptr, double ext_sum_e = 0.0,
-                   const svgp_input_grad* gx = nullptr, const svgp_point_mean* pm = nullptr, const svgp_point_mean_grad* gpm = nullptr) {
+                   const svgp_input_grad* gx = nullptr, const svgp_point_mean* pm = nullptr, const svgp_point_mean_grad* gpm = nullptr,
+                   NatgradCall* ng = nullptr) {   // ng (never collective): the natural-gradient tail behind the same launches
   GradCall gc;
+  if (ng) gc.ng_W = ng->c->Wm.as<double>();
   gc.ext_gmu = ext_gmu; gc.ext_gv = ext_gv; gc.ext_sum_e = ext_sum_e;
   gc.gx = gx;
   gc.collective = collective && ctx && ctx->comm;
@@ -1882,6 +1914,7 @@ int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
     }
   }
   rc = grad_enqueue(ctx, m, data, off, len, gc);
+  if (rc == SVGP_OK && ng) rc = natgrad_enqueue(ctx, m, gc, *ng);
   if (gc.collective) {
     const double nfail = grad_peers_failed(ctx);
     if (nfail != 0.0) {   // a peer failed before its backward pass (or the flag could not be read): it will not enter the closing all-reduce
@@ -1898,7 +1931,9 @@ int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
                                hipMemcpyDeviceToHost, ctx->stream));
   if (gpm && !gpm->on_device)   // (never all-reduced either)
     HIPC(ctx, hipMemcpyAsync(gpm->mu_bar, ctx->pm_g.p, size_t(len) * m->es, hipMemcpyDeviceToHost, ctx->stream));
-  return grad_finish(ctx, m, gc, elbo_out, terms_out, g);
+  rc = grad_finish(ctx, m, gc, elbo_out, terms_out, g);
+  if (rc == SVGP_OK && ng) rc = natgrad_finish(ctx, m, *ng);
+  return rc;
 }
 
 // argument checks of the `_inputs` calls (before anything is enqueued; a NULL or inconsistent data handle is check_batch's to report)
@@ -2329,6 +2364,129 @@ extern "C" int32_t svgp_collapsed_grad(svgp_ctx* ctx, svgp_model* m, const svgp_
   if (rc) return rc;
   if (bound_out) *bound_out = bound;
   return SVGP_OK;
+}
+
+// ================================================================================================
+// One natural-gradient step on q(u): svgp_natgrad_step / _ext (natgrad.hip has the formulas and the kernels).  The launches of
+// svgp_elbo_grad, unchanged, then the M-sized fp64 tail on the same stream: the value-and-gradient's read-back (grad_finish) follows the
+// tail's enqueue, so the two overlap and the call synchronises once more only for the tail's 64 status bytes.
+namespace {
+
+int natgrad_enqueue(svgp_ctx* ctx, svgp_model* m, GradCall& gc, NatgradCall& ng) {
+  hipStream_t s = ctx->stream;
+  GradWs* w = gc.w;
+  CollapsedWs* c = ng.c;
+  const int dt = m->dtype;
+  const int64_t Mp = m->Mp, M = m->M;
+  const double gamma = ng.gamma;
+  const bool full = gamma == 1.0;   // Lambda' = I + W: Lambda is neither formed nor read
+  double* Wm = c->Wm.as<double>();
+  double* Bw = full ? nullptr : c->Bw.as<double>();
+  double* mw = c->mw.as<double>();
+  double* scal = c->scal.as<double>();
+  int* info_b = c->info_b.as<int>();
+  int* info_s = c->info_s.as<int>();
+  int* info_q = c->info_q.as<int>();
+  // the prep of this very call left the whitened q on the model: m->mp = m_w, m->U = B' (both parametrisations)
+  launch_natgrad_widen(dt, s, m->U.p, m->mp.p, M, Mp, Bw, mw);
+  const double* Lam = nullptr;
+  if (!full) {
+    // Lambda = B^-T B^-1 from the explicit inverse of the triangular B (never inv(B B'): that squares cond(B))
+    launch_natgrad_diag_check(s, Bw, M, Mp, info_q);
+    launch_natgrad_diag_inv(s, Bw, Mp, c->TB.as<double>());
+    launch_linv(SVGP_F64, s, Bw, c->TB.p, Mp, c->LinvRM.p, c->LinvCM.p, c->Ytmp.p);
+    launch_gemm_pm(SVGP_F64, s, c->LinvRM.p, c->LinvRM.p, nullptr, 1.0, Mp, Mp, Mp, 1, c->Sinv.p, 1, kMmFull | kMmXLow | kMmYLow);
+    Lam = c->Sinv.as<double>();
+    KCHECK(ctx, "natgrad tail (Lambda)");
+  }
+  launch_natgrad_form(s, Lam, Wm, Mp, gamma, c->Bm.as<double>());
+  launch_natgrad_rhs(s, c->Bm.as<double>(), mw, w->avec.as<double>(), Mp, gamma, c->cvec.as<double>());
+  HIPC(ctx, hipMemsetAsync(info_b, 0, info_bytes(Mp), s));
+  launch_potrf(SVGP_F64, s, c->Bm.p, c->TB.p, Mp, info_b, reinterpret_cast<unsigned*>(info_b + 1), ctx->num_cus);
+  launch_trsv2(SVGP_F64, s, c->Bm.p, c->TB.p, Mp, 0, c->cvec.p);
+  HIPC(ctx, hipMemcpyAsync(c->mw.p, c->cvec.p, size_t(Mp) * 8, hipMemcpyDeviceToDevice, s));
+  launch_trsv2(SVGP_F64, s, c->Bm.p, c->TB.p, Mp, 1, c->mw.p);   // m_w' = Lambda'^-1 rhs
+  KCHECK(ctx, "natgrad tail (cholesky(Lambda'), m_w)");
+  // S_w' = inv(Lambda') = L^-T L^-1 from the explicit triangular inverse; Lq_w = its lower Cholesky factor (the collapsed bound's tail)
+  launch_linv(SVGP_F64, s, c->Bm.p, c->TB.p, Mp, c->LinvRM.p, c->LinvCM.p, c->Ytmp.p);
+  launch_gemm_pm(SVGP_F64, s, c->LinvRM.p, c->LinvRM.p, nullptr, 1.0, Mp, Mp, Mp, 1, c->Sinv.p, 1, kMmFull | kMmXLow | kMmYLow);
+  HIPC(ctx, hipMemsetAsync(info_s, 0, info_bytes(Mp), s));
+  launch_potrf(SVGP_F64, s, c->Sinv.p, c->TB.p, Mp, info_s, reinterpret_cast<unsigned*>(info_s + 1), ctx->num_cus);
+  launch_natgrad_status(s, Wm, w->avec.as<double>(), Mp, info_b, info_s, full ? nullptr : info_q, m->info.as<int>(), w->sums,
+                        m->desc.neg_var_policy == SVGP_NEGVAR_ERROR ? 1 : 0, scal);
+  KCHECK(ctx, "natgrad tail (inv(Lambda'), its factor)");
+  // device to device into the model's own m / Lq; nothing is written when a factorisation failed or the value-and-gradient itself fails
+  launch_collapsed_write_q(dt, s, c->Sinv.as<double>(), mw, m->L.p, M, Mp, m->desc.parametrization == SVGP_CENTERED ? 1 : 0,
+                           m->desc.mean_const, scal, info_b, info_s, m->m_raw.p, m->Lq_raw.p);
+  KCHECK(ctx, "natgrad q");
+  return SVGP_OK;
+}
+
+// after grad_finish returned SVGP_OK: the tail's status; the model is prepared again, lazily, once q was written
+int natgrad_finish(svgp_ctx* ctx, svgp_model* m, NatgradCall& ng) {
+  double h[8] = {};
+  HIPC(ctx, hipMemcpyAsync(h, ng.c->scal.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(ctx, hipStreamSynchronize(ctx->stream));
+  const bool nan_in = std::isnan(h[0]) || std::isnan(h[1]);   // a NaN coordinate / observation: q is written NaN, SVGP_OK (the rule of svgp_collapsed_q)
+  if (!nan_in) {
+    const int ib = int(h[4]), is = int(h[5]), iq = int(h[6]);
+    char buf[240];
+    if (iq != 0) {
+      snprintf(buf, sizeof buf, "the whitened Cholesky factor of q has a non-positive diagonal entry: leading minor of order %d (PosDefException); q is unchanged", iq);
+      return fail(ctx, SVGP_NOT_POSDEF, buf);
+    }
+    if (ib != 0 || is != 0) {
+      snprintf(buf, sizeof buf, "%s is not positive definite: leading minor of order %d (PosDefException); q is unchanged",
+               ib ? "the precision of the natural-gradient step, (1 - gamma) inv(S_w) + gamma (I + W)," : "the covariance of the natural-gradient step", ib ? ib : is);
+      return fail(ctx, SVGP_NOT_POSDEF, buf);
+    }
+    if (h[7] != 0.0) return SVGP_OK;   // (unreachable behind an SVGP_OK of grad_finish: q was not written)
+  }
+  m->prepared = false;
+  return SVGP_OK;
+}
+
+int natgrad_step_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double num_data, double gamma, bool ext,
+                      double sum_e, const double* g_mu, const double* g_v, double* elbo_out, svgp_terms* terms_out, svgp_grads* g,
+                      void* m_out, void* Lq_out) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!(gamma > 0.0 && gamma <= 1.0)) return fail(ctx, SVGP_INVALID_ARG, "svgp_natgrad_step: the step length gamma must lie in (0, 1]");
+  if (ext && (!g_mu || !g_v)) return fail(ctx, SVGP_INVALID_ARG, "null point gradients");
+  int rc = check_batch(ctx, m, data, off, len, !ext);
+  if (rc) return rc;
+  if (ctx->comm) return fail(ctx, SVGP_UNSUPPORTED, "the natural-gradient step is not collective: detach the communicator");
+  if (m->mu_z.p) return fail(ctx, SVGP_UNSUPPORTED, "the natural-gradient step takes no prior mean offsets (svgp_model_set_mean_z)");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  NatgradCall ng;
+  ng.gamma = gamma;
+  rc = collapsed_workspace(ctx, m->Mp, &ng.c);
+  if (rc) return rc;
+  const size_t mm = size_t(m->Mp) * size_t(m->Mp) * 8;
+  if ((rc = ng.c->Wm.reserve(ctx, mm, "the natural-gradient step's workspace")) != SVGP_OK) return rc;
+  if (gamma != 1.0 && (rc = ng.c->Bw.reserve(ctx, mm, "the natural-gradient step's workspace")) != SVGP_OK) return rc;
+  if ((rc = ng.c->info_q.reserve(ctx, 256, "the natural-gradient step's workspace")) != SVGP_OK) return rc;
+  svgp_grads none{};   // the gradient is computed whether or not it is wanted: grads_out NULL reads none of its blocks back
+  const double scale = (num_data > 0 ? num_data : double(len)) / double(len);
+  rc = elbo_grad_impl(ctx, m, data, off, len, scale, 1.0, num_data, false, elbo_out, terms_out, g ? g : &none, ext ? g_mu : nullptr,
+                      ext ? g_v : nullptr, ext ? sum_e : 0.0, nullptr, nullptr, nullptr, &ng);
+  if (rc) return rc;
+  if (m_out) HIPC(ctx, hipMemcpyAsync(m_out, m->m_raw.p, size_t(m->M) * m->es, hipMemcpyDeviceToHost, ctx->stream));
+  if (Lq_out) HIPC(ctx, hipMemcpyAsync(Lq_out, m->Lq_raw.p, size_t(m->M) * size_t(m->M) * m->es, hipMemcpyDeviceToHost, ctx->stream));
+  if (m_out || Lq_out) HIPC(ctx, hipStreamSynchronize(ctx->stream));
+  return SVGP_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t svgp_natgrad_step(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double num_data,
+                                     double gamma, double* elbo_out, svgp_terms* terms_out, svgp_grads* g, void* m_out, void* Lq_out) {
+  return natgrad_step_impl(ctx, m, data, off, len, num_data, gamma, false, 0.0, nullptr, nullptr, elbo_out, terms_out, g, m_out, Lq_out);
+}
+
+extern "C" int32_t svgp_natgrad_step_ext(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, double num_data,
+                                         double gamma, double sum_e, const double* g_mu, const double* g_v, double* elbo_out,
+                                         svgp_terms* terms_out, svgp_grads* g, void* m_out, void* Lq_out) {
+  return natgrad_step_impl(ctx, m, data, off, len, num_data, gamma, true, sum_e, g_mu, g_v, elbo_out, terms_out, g, m_out, Lq_out);
 }
 
 // ================================================================================================

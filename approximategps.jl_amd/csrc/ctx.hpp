@@ -189,6 +189,9 @@ struct CollapsedWs {
   svgp::DevBuf scal;           // [8] {rr, t, sum log diag LB, c'c, info_b, info_s, 0, 0}
   svgp::DevBuf info_b, info_s; // cholesky info + hand-over counters of the two factorisations (int)
   svgp::DevBuf gemv_part;
+  // svgp_natgrad_step* only (allocated by its first call): W = A diag(-2 scale g_v) A' and the whitened factor B of q in fp64
+  // (Mp x Mp doubles each), the index of B's first non-positive diagonal entry (int)
+  svgp::DevBuf Wm, Bw, info_q;
 };
 
 struct svgp_data {

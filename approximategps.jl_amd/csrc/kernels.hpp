@@ -234,5 +234,22 @@ void launch_collapsed_scal(hipStream_t s, const double* LB, const double* c, int
 void launch_collapsed_write_q(int dtype, hipStream_t s, const double* Lqw, const double* mw, const void* Lk, int64_t M, int64_t Mp, int centered,
                               double mean_const, const double* scal, const int* info_b, const int* info_s, void* m_out, void* Lq_out);
 
+// ---- natgrad.hip (one natural-gradient step on q: svgp_natgrad_step*) -----------------------------------------------------
+// Wm (fp64, full, symmetric) = - sum(slices of G: the SYRK's lower tiles of A diag(2 scale g_v) A', model dtype), in slice order
+void launch_natgrad_gather_w(int dtype, hipStream_t s, const void* G, int nslices, int64_t Mp, double* Wm);
+// Bw (fp64 column-major lower, identity on the padding; NULL: skipped) from U = B' (model dtype); mw = the padded m_w widened
+void launch_natgrad_widen(int dtype, hipStream_t s, const void* U, const void* mp, int64_t M, int64_t Mp, double* Bw, double* mw);
+// *first_bad = 0 or the 1-based index of the first diagonal entry of Bw that is not positive
+void launch_natgrad_diag_check(hipStream_t s, const double* Bw, int64_t M, int64_t Mp, int* first_bad);
+// the diagonal 128-blocks of Tm = the inverses of those of the lower-triangular Bw (zero above the diagonal): what launch_linv starts from
+void launch_natgrad_diag_inv(hipStream_t s, const double* Bw, int64_t Mp, double* Tm);
+// Bm = (1 - gamma) Lam + gamma (I + Wm), full and symmetric; Lam NULL (gamma = 1): not read
+void launch_natgrad_form(hipStream_t s, const double* Lam, const double* Wm, int64_t Mp, double gamma, double* Bm);
+// cvec = Bm mw - gamma mw + gamma a
+void launch_natgrad_rhs(hipStream_t s, const double* Bm, const double* mw, const double* a, int64_t Mp, double gamma, double* cvec);
+// scal[0..8) = {tr W, sum a (NaN probes), 0, 0, *info_b, *info_s, *info_q, blocked}; sets *info_s when q must not be written
+void launch_natgrad_status(hipStream_t s, const double* Wm, const double* a, int64_t Mp, const int* info_b, int* info_s, const int* info_q,
+                           const int* kuu_info, const double* gsums, int neg_var_is_error, double* scal);
+
 
 }  // namespace svgp

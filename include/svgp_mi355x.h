@@ -620,6 +620,50 @@ int32_t svgp_collapsed_q(svgp_ctx* ctx, svgp_model* model, const svgp_data* data
 int32_t svgp_collapsed_grad(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
                             double* bound_out, svgp_collapsed_terms* terms_out, svgp_grads* grads_out, const svgp_input_grad* gx);
 
+/* ---- natural-gradient steps on q(u) -------------------------------------------------------------------------------------------------
+ * The reference trains q = N(m, Lq Lq') with the optimiser that trains everything else: svgp_elbo_grad hands it the Euclidean
+ * m_bar / Lq_bar of the ELBO (SVA:340-373).  A natural-gradient step moves q along the ELBO's gradient in the expectation parameters
+ * instead (Hensman et al. 2013; GPflow's NaturalGradient, GPyTorch's NGD) and costs one value-and-gradient pass plus an M-sized tail.
+ * In whitened coordinates - q(v) = N(m_w, S_w), u = mean_const + Lk v, Lambda = inv(S_w) - with A = Lk \ Kuf over the window, the
+ * likelihood's point gradients g_mu = dE/dmu, g_v = dE/dv at the marginals of the current q (SVA:354-355) and
+ * scale = num_data / batch_len:
+ *     W = A diag(-2 scale g_v) A',   a = scale A g_mu
+ *     Lambda'      = (1 - gamma) Lambda     + gamma (I + W)
+ *     Lambda' m_w' = (1 - gamma) Lambda m_w + gamma (a + W m_w)
+ *     S_w'         = inv(Lambda')
+ * which is theta' = theta + gamma dL/d eta for the natural parameters theta = (Lambda m_w, -Lambda / 2) and the expectation parameters
+ * eta = (m_w, S_w + m_w m_w').  gamma = 1 with the Gaussian likelihood on the full batch is svgp_collapsed_q; any likelihood, any
+ * minibatch with num_data and any gamma in (0, 1] are covered here.
+ *   svgp_natgrad_step      the data pass of svgp_elbo_grad, unchanged, then the tail.  The new q is WRITTEN into the model's
+ *                          device-resident m and Lq, in the model's own parametrisation (NonCentered: m = m_w', Lq = chol(S_w');
+ *                          Centered: m = mean_const + Lk m_w', Lq = Lk chol(S_w')), device to device; the model is prepared again, lazily.
+ *                          elbo_out, terms_out and every block of grads_out (NULL: none wanted; grads_out->m / ->Lq are allowed) are the
+ *                          values at the q the call STARTED from, bitwise what svgp_elbo_grad returns for the same inputs on the same
+ *                          context: one call serves an optimiser step on the hyperparameters and moves q.  m_out (M) / Lq_out (M x M
+ *                          column-major, upper triangle zeroed): host arrays in the dtype and layout of the descriptor's m / Lq, the new q;
+ *                          either may be NULL.
+ *   svgp_natgrad_step_ext  the same with the caller's point gradients: the counterpart of svgp_elbo_grad_ext (sum_e, g_mu, g_v as there).
+ *   svgp_model_update_keep_q   svgp_model_update with desc->m / desc->Lq ignored (they may be NULL): kernel parameters, z, likelihood
+ *                          parameters, jitter and mean_const go up, the device-resident q stays - no M x M upload.  For a Centered model
+ *                          the stored q is in u-space and is kept as is (the same u-space q under the new kernel, not the same whitened q).
+ * The tail runs in fp64 whatever the model's dtype (cond(Lambda') grows with num_data); Lambda is formed as B^-T B^-1 from the explicit
+ * inverse of the whitened factor B, and at gamma = 1 exactly it is neither formed nor read.  Results are bitwise repeatable call to
+ * call: fixed splits, fixed-order sums, no floating-point atomics.
+ * SVGP_INVALID_ARG, before anything is enqueued: gamma outside (0, 1] or not finite, and everything svgp_elbo_grad / _ext reject.
+ * SVGP_UNSUPPORTED: a context with a communicator attached, a model carrying muz (there are no mux variants): multi-GPU evaluation and
+ * prior mean offsets are out of scope, as for the collapsed calls.  SVGP_NOT_POSDEF, with q left exactly as it was: Lambda' (or its
+ * inverse) not positive definite - possible with a caller's g_v > 0 only, the built-in likelihoods being log-concave in f - or, at
+ * gamma < 1, a non-positive diagonal entry of the whitened factor of q; svgp_last_error names the order of the failing minor.  A
+ * non-positive pivot of Kuu and SVGP_NEG_VARIANCE (the model's policy) are reported as by svgp_elbo_grad, q untouched.  A NaN coordinate
+ * or observation gives NaN outputs with SVGP_OK and q is then written NaN (the rule of svgp_collapsed_q).  Found by symbol (no ABI
+ * version step). */
+int32_t svgp_natgrad_step(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len, double num_data,
+                          double gamma, double* elbo_out, svgp_terms* terms_out, svgp_grads* grads_out, void* m_out, void* Lq_out);
+int32_t svgp_natgrad_step_ext(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len, double num_data,
+                              double gamma, double sum_e, const double* g_mu, const double* g_v, double* elbo_out, svgp_terms* terms_out,
+                              svgp_grads* grads_out, void* m_out, void* Lq_out);
+int32_t svgp_model_update_keep_q(svgp_ctx* ctx, svgp_model* model, const svgp_model_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

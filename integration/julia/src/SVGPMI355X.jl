@@ -963,4 +963,38 @@ function collapsed_bound_and_grad!(Mo::DeviceModel, D::DeviceData, M::Integer, d
     return out[], t, (variance=g.variance, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const, inv_lengthscale=gl, z=gz)
 end
 
+# ---------------------------------------------------------------------------------------------------------
+# Natural-gradient steps on q(u) on resident handles (svgp_natgrad_step / svgp_model_update_keep_q): q moves on the device along the
+# ELBO's gradient in the expectation parameters (the ELBO of SVA:340-373), the host's optimiser keeps the hyperparameters and z.  Any
+# built-in likelihood, any minibatch window with num_data, step length gamma in (0, 1]; one GPU, ZeroMean / ConstMean.
+# ---------------------------------------------------------------------------------------------------------
+"One natural-gradient step of length `gamma` on the model's device-resident q over the points off+1 : off+len of D.  Returns
+(elbo, grads, m, Lq): the ELBO and its gradient in (variance, lik_sigma2, mean_const, inv_lengthscale, z) at the q the call STARTED
+from (what svgp_elbo_grad returns), and the NEW q as host arrays in the model's parametrisation."
+function natgrad_step!(Mo::DeviceModel, D::DeviceData, M::Integer, d::Integer, ::Type{T}; gamma::Real=1.0, num_data::Real=0.0,
+                       off::Integer=0, len::Integer=D.n - off) where {T<:FT}
+    out, terms = Ref{Float64}(), Terms()
+    gl, gz = zeros(Float64, d), zeros(T, d, M)
+    m, Lq = zeros(T, M), zeros(T, M, M)
+    g = Grads(0.0, 0.0, 0.0, pointer(gl), pointer(gz), C_NULL, C_NULL)
+    GC.@preserve gl gz check(ccall((:svgp_natgrad_step, lib), Int32,
+                                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Ref{Float64}, Ref{Terms}, Ref{Grads}, Ptr{Cvoid}, Ptr{Cvoid}),
+                                   ctx(), Mo.h, D.h, off, len, Float64(num_data), Float64(gamma), out, terms, g, m, Lq), terms)
+    return out[], (variance=g.variance, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const, inv_lengthscale=gl, z=gz), m, LowerTriangular(Lq)
+end
+"The same step with the caller's point gradients (sum_e, g_mu, g_v as for svgp_elbo_grad_ext); returns (elbo, m, Lq)."
+function natgrad_step_ext!(Mo::DeviceModel, D::DeviceData, M::Integer, ::Type{T}, sum_e::Real, g_mu::Vector{Float64}, g_v::Vector{Float64};
+                           gamma::Real=1.0, num_data::Real=0.0, off::Integer=0, len::Integer=D.n - off) where {T<:FT}
+    (length(g_mu) == len && length(g_v) == len) || throw(ArgumentError("one point gradient per point of the batch"))
+    out, terms = Ref{Float64}(), Terms()
+    m, Lq = zeros(T, M), zeros(T, M, M)
+    check(ccall((:svgp_natgrad_step_ext, lib), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Terms}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                ctx(), Mo.h, D.h, off, len, Float64(num_data), Float64(gamma), Float64(sum_e), g_mu, g_v, out, terms, C_NULL, m, Lq), terms)
+    return out[], m, LowerTriangular(Lq)
+end
+"update! without the upload of q: the packed m / Lq are ignored, the device-resident q (e.g. what natgrad_step! wrote) stays."
+update_keep_q!(M::DeviceModel, p::Packed) = p.offset ? throw(Unsupported()) :
+    GC.@preserve p check(ccall((:svgp_model_update_keep_q, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{ModelDesc}), ctx(), M.h, p.desc))
+
 end # module

@@ -4,7 +4,7 @@
 set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"; TMP=$(mktemp -d); OUT="$ROOT/approximategps.jl_amd/csrc/ablate"; mkdir -p "$OUT"
 git -C "$ROOT" archive HEAD approximategps.jl_amd/csrc include | tar -x -C "$TMP"
-UNITS="prep strip grad api comm laplace nn collapsed"
+UNITS=$(cd "$TMP/approximategps.jl_amd/csrc" && for f in *.hip; do echo "${f%.hip}"; done)   # every translation unit HEAD has
 pids=()
 for f in $UNITS; do
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function -c "$TMP/approximategps.jl_amd/csrc/$f.hip" -o "$TMP/$f.o" 2>/dev/null &
