@@ -7,6 +7,9 @@
 """
 from ._ffi import (Context, DeclinedError, DeviceData, DeviceModel, DomainError, PosDefException, SvgpError, UnsupportedError,
                    default_context, gausshermite, load_library, offload_advice, offload_work)
+# the predictive distribution of the observation: DeviceModel.predictive for resident data, lik_predictive for latent marginals a caller
+# holds; predict_y / log_predictive_density on the three posterior types
+from ._ffi import PredSummary, lik_predictive
 from .gp import (GP, BernoulliLikelihood, CustomMean, DefaultExpectationMethod, FiniteGP, GaussHermiteExpectation,
                  GaussianLikelihood, LatentFiniteGP, LatentGP, MvNormal, PoissonLikelihood, ExponentialLikelihood,
                  GammaLikelihood, CallerLikelihood, LogisticLink, NormalCDFLink, ProbitLink)

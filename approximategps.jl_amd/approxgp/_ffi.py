@@ -95,6 +95,11 @@ class CollapsedTerms(C.Structure):
                 ("reserved", C.c_int64)]
 
 
+class PredSummary(C.Structure):
+    """svgp_pred_summary: the sums of svgp_predictive / svgp_lik_predictive over the points that counted."""
+    _fields_ = [("sum_lpd", C.c_double), ("sum_sq_err", C.c_double), ("n_points", C.c_int64), ("n_neg_var", C.c_int64)]
+
+
 # every symbol include/svgp_mi355x.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -176,6 +181,9 @@ SYMBOLS = {
     "svgp_natgrad_step_ext": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _P, _P,
                                           C.POINTER(C.c_double), C.POINTER(Terms), C.POINTER(Grads), _P, _P]),
     "svgp_model_update_keep_q": (C.c_int32, [_P, _P, C.POINTER(ModelDesc)]),
+    # the predictive distribution of the observation
+    "svgp_predictive": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), C.POINTER(PredSummary), _P, _P, _P]),
+    "svgp_lik_predictive": (C.c_int32, [_P, C.c_int32, C.c_double, C.c_int32, C.c_int64, _P, _P, _P, C.POINTER(PredSummary), _P, _P, _P]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),
     "svgp_ctx_attach_comm": (C.c_int32, [_P, _P, C.c_int32, C.c_int32]),
@@ -298,6 +306,58 @@ def point_mean(mu, n, dtype):
     return PointMean(_ptr(buf), 0, 0), buf
 
 
+PRED_WANTS = ("summary", "lpd", "ymean", "yvar")
+
+
+def _pred_wants(want, has_y):
+    """The outputs asked of svgp_predictive / svgp_lik_predictive, checked as the library checks them (before the GPU is touched)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in PRED_WANTS for w in want):
+        raise ValueError(f"want: a non-empty selection of {PRED_WANTS}")
+    if not has_y and ("summary" in want or "lpd" in want):
+        raise ValueError("no observations y: only ymean and yvar are available (summary and lpd need y)")
+    return want
+
+
+def _pred_call(ctx, want, n, call):
+    """Allocates the wanted outputs, runs call(summary_ref, lpd_ptr, ymean_ptr, yvar_ptr) -> status and packs the result.  Under the error
+    policy a negative variance raises DomainError carrying the (written) outputs as its `outputs` attribute: NaN at the bad points."""
+    summary = PredSummary() if "summary" in want else None
+    arrs = {k: np.zeros(n) for k in ("lpd", "ymean", "yvar") if k in want}
+    rc = call(C.byref(summary) if summary is not None else None, _ptr(arrs.get("lpd")), _ptr(arrs.get("ymean")), _ptr(arrs.get("yvar")))
+    res = dict(arrs)
+    if summary is not None:
+        res["summary"] = summary
+    try:
+        ctx.check(rc)
+    except DomainError as e:
+        e.outputs = res
+        raise
+    return res
+
+
+def lik_predictive(ctx, lik: int, param: float, quadrature_n: int, mu, var, y=None, want=None):
+    """svgp_lik_predictive: log predictive density and (E[y], Var[y]) from latent marginals N(mu_i, var_i) a caller holds (Laplace,
+    NearestNeighbors, svgp_marginals' output) -> dict of the wanted outputs (default: all four with y, ymean / yvar without)."""
+    mu = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
+    var = np.ascontiguousarray(np.asarray(var, dtype=np.float64).reshape(-1))
+    yb = None if y is None else np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+    want = _pred_wants(want if want is not None else (PRED_WANTS if yb is not None else ("ymean", "yvar")), yb is not None)
+    n = mu.shape[0]
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    if var.shape != (n,) or (yb is not None and yb.shape != (n,)):
+        raise ValueError("mu, var and y must have one entry per point")
+    if isinstance(lik, bool) or not isinstance(lik, (int, np.integer)) or not LIK_GAUSSIAN <= lik <= LIK_BERNOULLI_NORMCDF:
+        raise ValueError(f"unsupported likelihood code {lik!r}")
+    if not 0 <= int(quadrature_n) <= 512:
+        raise ValueError("quadrature_n must be in 0..512")
+    if lik in (LIK_GAUSSIAN, LIK_GAMMA_EXP) and not float(param) > 0:
+        raise ValueError("the Gaussian likelihood needs sigma2 > 0, the Gamma likelihood a shape alpha > 0")
+    return _pred_call(ctx, want, n, lambda s, a, b, c: ctx.lib.svgp_lik_predictive(ctx.h, int(lik), float(param), int(quadrature_n), n, _ptr(mu),
+                                                                                   _ptr(var), _ptr(yb), s, a, b, c))
+
+
 class Context:
     """One GPU + one HIP stream.  `stream` may be a raw hipStream_t (e.g. torch.cuda.current_stream().cuda_stream)."""
 
@@ -403,6 +463,7 @@ class DeviceData:
         if self._y is not None and self._y.shape[0] != n:
             raise ValueError("x and y lengths differ")
         self.n, self.d, self.dtype = n, d, dtype_code(dt)
+        self.has_y = self._y is not None
         h = C.c_void_p()
         ctx.check(ctx.lib.svgp_data_upload(ctx.h, self.dtype, layout, d, n, _ptr(self._x), _ptr(self._y), C.byref(h)))
         self.h = h
@@ -412,6 +473,7 @@ class DeviceData:
         self = cls.__new__(cls)
         self.ctx, self.n, self.d, self.dtype = ctx, n, d, dtype_code(dtype)
         self.layout = ROWVECS   # feature-major storage
+        self.has_y = bool(y_ptr)
         h = C.c_void_p()
         ctx.check(ctx.lib.svgp_data_wrap_device(ctx.h, self.dtype, d, n, ldx, C.c_void_p(x_ptr),
                                                 C.c_void_p(y_ptr) if y_ptr else None, C.byref(h)))
@@ -518,6 +580,20 @@ class DeviceModel:
         else:
             self.ctx.check(self.ctx.lib.svgp_marginals(self.ctx.h, self.h, data.h, off, length, _ptr(mu), _ptr(var)))
         return mu, var
+
+    def predictive(self, data: DeviceData, off=0, length=None, prior_mean=None, want=PRED_WANTS):
+        """svgp_predictive: the predictive distribution of the OBSERVATION for the batch, through the model's likelihood -> dict of the
+        wanted outputs: "summary" (PredSummary: sum of lpd, sum of (y - E[y])^2, n_points, n_neg_var), "lpd" (log p(y_i | D)), "ymean",
+        "yvar" (fp64 arrays).  One forward data pass, local even on a context with a communicator.  Data without y: ymean / yvar only.
+        prior_mean: the batch's prior mean offsets, as in marginals."""
+        length = data.n - off if length is None else length
+        want = _pred_wants(want, bool(getattr(data, "has_y", False)))
+        if off < 0 or length < 1 or off + length > data.n:
+            raise ValueError("batch range outside the data")
+        pm, _keep = point_mean(prior_mean, length, self.dtype) if prior_mean is not None else (None, None)
+        ctx = self.ctx
+        return _pred_call(ctx, want, length, lambda s, a, b, c: ctx.lib.svgp_predictive(ctx.h, self.h, data.h, off, length,
+                                                                                        C.byref(pm) if pm is not None else None, s, a, b, c))
 
     def elbo_grad(self, data: DeviceData, off=0, length=None, num_data=0.0, z_shape=None, shard=None, ext=None, out=None,
                   inputs=None, prior_mean=None, mean_grad=None):

@@ -197,7 +197,7 @@ class LaplacePosteriorGP:
     RW 3.21 / 3.29 (LA:425-463).  Test inputs: a plain vector (d = 1) or a (d, n) ColVecs array."""
 
     def __init__(self, la: LaplaceApproximation, lfx: LatentFiniteGP, ys, ctx=None, dtype=None):
-        self.approx, self.prior = la, lfx.fx.f
+        self.approx, self.prior, self.lik = la, lfx.fx.f, lfx.lik
         self.dev, (self.lml, self.info) = _fit(la, lfx, ys, ctx, dtype, grad=False)
 
     def mean(self, x):
@@ -222,6 +222,20 @@ class LaplacePosteriorGP:
     def mode(self):
         """(f_opt, d log p / df, W) of the cached intermediates"""
         return self.dev.mode()
+
+    def _lik_predictive(self, x, y, quadrature, want):
+        code, s2 = _lik_code(self.lik)
+        m, v = self.mean_and_var(x)
+        return _ffi.lik_predictive(self.dev.ctx, code, s2, _sva._quadrature_n(quadrature), m, v, y, want=want)
+
+    def predict_y(self, x, quadrature=None):
+        """(E[y*], Var[y*]) through the likelihood the approximation was fitted with: svgp_laplace_predict, then svgp_lik_predictive."""
+        r = self._lik_predictive(x, None, quadrature, ("ymean", "yvar"))
+        return r["ymean"], r["yvar"]
+
+    def log_predictive_density(self, x, y, quadrature=None):
+        """log p(y*_i | D) per point under the Gaussian (Laplace) latent marginals; NLPD = -mean of it."""
+        return self._lik_predictive(x, y, quadrature, ("lpd",))["lpd"]
 
 
 def posterior(approx, *args, **kwargs):

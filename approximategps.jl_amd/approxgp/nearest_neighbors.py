@@ -283,6 +283,9 @@ class NNPosteriorGP:
 
     def __init__(self, nn: NearestNeighbors, fx: FiniteGP, y, ctx=None, dtype=None):
         self.approx, self.prior = nn, fx.f
+        if not fx.is_isotropic():
+            raise _ffi.UnsupportedError("fx.Σy must be isotropic noise")
+        self.noise = float(fx.Sigma_y)
         self.dev, desc, keep = _device(nn, fx, y, ctx, dtype)
         self.lml, self.info = self.dev.fit(desc)
 
@@ -307,6 +310,23 @@ class NNPosteriorGP:
 
     def factors(self):
         return self.dev.factors()
+
+    def _lik_predictive(self, x, y, want):
+        """the Gaussian observation model y = f + N(0, fx.Σy) on the latent predictions, through the array form the SVGP and Laplace
+        posteriors share (svgp_lik_predictive): one definition of the three"""
+        if not self.noise > 0:
+            raise ValueError("predictions of y need observation noise fx.Σy > 0")
+        m, v = self.mean_and_var(x)
+        return _ffi.lik_predictive(self.dev.ctx, _ffi.LIK_GAUSSIAN, self.noise, 0, m, v, y, want=want)
+
+    def predict_y(self, x):
+        """(E[y*], Var[y*]) = (mean, var + noise)"""
+        r = self._lik_predictive(x, None, ("ymean", "yvar"))
+        return r["ymean"], r["yvar"]
+
+    def log_predictive_density(self, x, y):
+        """log N(y*_i; mean_i, var_i + noise) per point"""
+        return self._lik_predictive(x, y, ("lpd",))["lpd"]
 
     def local_mean_and_var(self, x, k=None):
         """nearest-neighbour kriging (GpGp `predictions`): every test point conditioned on its k nearest observed points, k

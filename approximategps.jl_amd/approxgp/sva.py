@@ -92,6 +92,14 @@ def _desc(sva: SparseVariationalApproximation, lik=None, quadrature=None, dtype=
                           neg_var_policy=neg_var_policy)
 
 
+def _quadrature_n(quadrature):
+    if isinstance(quadrature, GaussHermiteExpectation):
+        return int(quadrature.n)
+    if quadrature is not None and not isinstance(quadrature, DefaultExpectationMethod):
+        raise _ffi.UnsupportedError(f"unsupported quadrature {quadrature!r}")
+    return 0
+
+
 def _device_model(ctx, sva, desc, keep):
     """DeviceModel of `sva`; a CustomMean prior also gets its values at z (mean(fz), svgp_model_set_mean_z)."""
     model = _ffi.DeviceModel(ctx, desc, keep)
@@ -253,9 +261,11 @@ class ApproxPosteriorGP:
     """ApproxPosteriorGP(sva, prior, (Kuu = Cholesky(Lk), B, α))  (SVA:134-135, :185-186), with the model
     kept resident on the GPU for the prediction methods."""
 
-    def __init__(self, approx: SparseVariationalApproximation, ctx=None, dtype=None):
+    def __init__(self, approx: SparseVariationalApproximation, ctx=None, dtype=None, lik=None):
         self.approx = approx
         self.prior = approx.fz.f
+        self.lik = lik   # the likelihood predict_y / log_predictive_density default to (posterior(sva, lfx, y) passes lfx.lik)
+        self._dtype = dtype
         self.ctx = ctx or _ffi.default_context()
         desc, keep = _desc(approx, None, None, dtype)
         self._model = _device_model(self.ctx, approx, desc, keep)
@@ -299,6 +309,36 @@ class ApproxPosteriorGP:
         rng = rng if rng is not None else np.random.default_rng()
         return m[:, None] + L @ rng.standard_normal((c.shape[0], int(n_samples)))
 
+    def _predictive(self, x, y, lik, quadrature, want):
+        """svgp_predictive on (x, y): the forward data pass, then the likelihood on the device"""
+        lik = lik if lik is not None else self.lik
+        if lik is None:
+            raise ValueError("a likelihood is needed: pass lik=, or build the posterior with posterior(sva, lfx, y)")
+        if isinstance(lik, CallerLikelihood):
+            raise _ffi.UnsupportedError("predictions of y need one of the built-in likelihoods")
+        desc, keep = _desc(self.approx, lik, quadrature, self._dtype)
+        mux = self.prior.mean_offsets(x)
+        data = _ffi.DeviceData(self.ctx, x, y, _ffi.np_dtype(desc.dtype))
+        try:
+            model = _device_model(self.ctx, self.approx, desc, keep)
+            try:
+                return model.predictive(data, 0, data.n, prior_mean=mux, want=want)
+            finally:
+                model.free()
+        finally:
+            data.free()
+
+    def predict_y(self, x, lik=None, quadrature=None):
+        """(E[y*], Var[y*]) at x through the likelihood (GPflow's predict_y): the class-1 probability p and p (1 - p) for a Bernoulli
+        model, the log-normal moments for the exp-link count and scale models, (mean, var + σ²) for a Gaussian one."""
+        r = self._predictive(x, None, lik, quadrature, ("ymean", "yvar"))
+        return r["ymean"], r["yvar"]
+
+    def log_predictive_density(self, x, y, lik=None, quadrature=None):
+        """log p(y*_i | D) = log ∫ p(y*_i | f) N(f; μ_i, v_i) df per point (GPflow's predict_log_density); NLPD = -mean of it.  Not the
+        ELBO's E_q[log p], which bounds it from below."""
+        return self._predictive(x, np.asarray(y), lik, quadrature, ("lpd",))["lpd"]
+
     def marginals(self, x):
         """marginals(f_post(x)) (SVA:354): (μ, σ) of Normal.(μ, sqrt.(v + 1e-18))."""
         m, v = self.mean_and_var(x)
@@ -314,7 +354,12 @@ def posterior(sva: SparseVariationalApproximation, fx=None, y=None, *, ctx=None,
     if fx is not None:
         prior = fx.f if isinstance(fx, FiniteGP) else fx.fx.f
         assert sva.fz.f is prior  # SVA:192,199
-    return ApproxPosteriorGP(sva, ctx=ctx, dtype=dtype)
+    lik = None
+    if isinstance(fx, LatentFiniteGP):
+        lik = fx.lik
+    elif isinstance(fx, FiniteGP) and fx.is_isotropic() and float(fx.Sigma_y) > 0:
+        lik = GaussianLikelihood(float(fx.Sigma_y))
+    return ApproxPosteriorGP(sva, ctx=ctx, dtype=dtype, lik=lik)
 
 
 def inducing_points(f: ApproxPosteriorGP):

@@ -143,6 +143,12 @@ struct svgp_ctx {
   svgp::DevBuf ext_g;   // [2][n] point gradients of a host-evaluated likelihood (double)
   svgp::DevBuf pm_x;    // host-memory prior mean offsets of a call, copied in (svgp_*_with_mean)
   svgp::DevBuf pm_g;    // their gradient for a host destination, copied out (svgp_elbo_grad_with_mean)
+  // svgp_predictive / svgp_lik_predictive (allocated by their first call)
+  svgp::DevBuf pred_part;   // [1024][3] per-block sums of predictive_kernel, then [4] their sums (double)
+  svgp::DevBuf pred_out;    // [3][n] per-point lpd | ymean | yvar (double)
+  svgp::DevBuf pred_in;     // [3][n] a caller's mu | var | y (double; svgp_lik_predictive)
+  svgp::DevBuf pred_gh;     // [2][pred_gh_n] Gauss-Hermite nodes | weights / sqrt(pi) of the predictive rule (double)
+  int pred_gh_n = 0;
   struct GradWs* gws = nullptr;  // gradient workspace, cached by problem shape (deleted by svgp_ctx_destroy)
   struct CollapsedWs* cws = nullptr;   // fp64 M-sized tail of svgp_collapsed_*, cached by Mp (deleted by svgp_ctx_destroy)
   // data-parallel communicator (comm.hip): one RCCL rank per context; world == 1 without one

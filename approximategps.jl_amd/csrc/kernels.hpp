@@ -151,6 +151,13 @@ void launch_expect(int dtype, hipStream_t s, const LikParams& lp, const double* 
 // out[8..13) (not all-reduced) = this rank's prep scalars prep_scal[0..4) and *chol_info: one read-back per evaluation
 void launch_final_reduce(hipStream_t s, const double* partial, const unsigned* negcnt, int64_t n, const int* chol_info,
                          double n_points, double* out, const double* prep_scal);
+// predictive.hip: log predictive density and (E[y], Var[y]) of every point from its latent marginal (mom_mu, mom_var + var_shift);
+// lp.gh_n is the predictive rule (0: closed form, Gaussian / normcdf Bernoulli only).  part3: [expect_blocks(len)][3] per-block sums,
+// sums3[0..3) = {sum lpd, sum (y - E[y])^2, n_neg} in a fixed order.  y (dtype's element type, read at off + i) and each of the
+// fp64 per-point outputs may be NULL
+void launch_predictive(int dtype, hipStream_t s, const LikParams& lp, const double* mom_mu, const double* mom_var, const void* y,
+                       int64_t off, int64_t len, double var_shift, double* part3, double* sums3, double* lpd_out, double* ymean_out,
+                       double* yvar_out);
 // standalone Kuf (M x len col-major, ld = M)
 void launch_kuf(int dtype, hipStream_t s, const KernelParams& kp, const void* zs, int64_t M, int64_t Mp,
                 const void* x, int64_t ldx, int64_t off, int64_t len, void* Kuf);

@@ -64,6 +64,105 @@ __device__ __forceinline__ double expected_loglik_point(const LikParams& lp, dou
   return acc;  // weights are pre-divided by sqrt(pi)
 }
 
+// ---- the predictive distribution of the OBSERVATION (predictive.hip: svgp_predictive / svgp_lik_predictive) -----------------------
+// For both functions lp.gh_n is the PREDICTIVE rule (api.hip: predictive_gh): 0 = closed form, which exists for the Gaussian and the
+// normcdf Bernoulli only; every other likelihood arrives with a Gauss-Hermite rule (GH-20 when the model's quadrature_n is 0).
+// Poisson, Exponential and Gamma have a closed-form ELBO expectation (expected_loglik_point) but NO closed-form predictive density:
+// E[exp(-e^f)] of a log-normal has none.  They take the quadrature here.
+
+// log p(y | D) = log int p(y | f) N(f; mu, v) df, a different quantity from E_q[log p(y | f)] above (which bounds it from below, Jensen).
+//   Gaussian            log N(y; mu, v + sigma2)
+//   Bernoulli(Phi(f))   log Phi(+-mu / sqrt(1 + v))
+//   otherwise, and every likelihood with lp.gh_n > 0:  logsumexp_q(log w_q + log p(y | f_q)),  f_q = mu + sqrt(2 v) x_q, in ONE pass
+//   with a running maximum (a plain log(sum w_q exp(.)) underflows for a Poisson count of a few hundred).  Weights that underflowed to 0
+//   (the high orders) and terms at -inf are skipped.  v = 0 (a clamped point) collapses to loglik_point(mu).
+// log p(y | f) = loglik_f_part + loglik_y_part: the terms that depend on f, and the rest (lgamma, log y, the normalisations), which the
+// quadrature below adds once per point instead of once per node
+__device__ __forceinline__ double loglik_f_part(int lik, double f, double y, double sigma2) {
+  if (lik == 0) {
+    const double r = y - f;
+    return -0.5 * r * r / sigma2;
+  }
+  if (lik == 1) return -softplus_d(y > 0.5 ? -f : f);
+  if (lik == 2) return y * f - exp(f);
+  if (lik == 3) return -f - y * exp(-f);
+  if (lik == 5) return log_ndtr_d(y > 0.5 ? f : -f);
+  return -y * exp(-f) - sigma2 * f;
+}
+// (not inlined, and static so that a translation unit that does not use it emits nothing: lgamma's double-precision code is what
+// pushes expect_kernel to one wave per SIMD; behind a call predictive_kernel stays at 158 VGPRs without spills)
+static __device__ __noinline__ double loglik_y_part(int lik, double y, double sigma2) {
+  if (lik == 0) return -0.5 * (1.8378770664093453 + log(sigma2));
+  if (lik == 2) return -lgamma(y + 1.0);
+  if (lik == 4) return (sigma2 - 1.0) * log(y) - lgamma(sigma2);
+  return 0.0;
+}
+
+__device__ __forceinline__ double predictive_logdensity_point(const LikParams& lp, double mu, double v, double y) {
+  if (lp.gh_n == 0) {
+    if (lp.lik == 0) {
+      const double r = y - mu, t = v + lp.sigma2;
+      return -0.5 * (1.8378770664093453 + log(t) + r * r / t);
+    }
+    const double z = mu / sqrt(1.0 + v);
+    return log_ndtr_d(y > 0.5 ? z : -z);
+  }
+  const double s = 1.4142135623730951 * sqrt(v);
+  double mx = -INFINITY, acc = 0.0;   // sum_q exp(t_q) = exp(mx) acc
+#pragma unroll 1
+  for (int q = 0; q < lp.gh_n; ++q) {
+    const double w = lp.gh_w[q];      // pre-divided by sqrt(pi)
+    if (!(w > 0.0)) continue;
+    const double t = log(w) + loglik_f_part(lp.lik, s * lp.gh_x[q] + mu, y, lp.sigma2);
+    if (t == -INFINITY) continue;
+    if (t > mx) {
+      acc = acc * exp(mx - t) + 1.0;
+      mx = t;
+    } else {
+      acc += exp(t - mx);             // a NaN t lands here and stays
+    }
+  }
+  return mx + log(acc) + loglik_y_part(lp.lik, y, lp.sigma2);
+}
+
+// (E[y], Var[y]) under the same marginal; no y needed.  Closed forms wherever they exist, whatever lp.gh_n is.  With e1 = exp(mu + v/2):
+//   Gaussian            (mu, v + sigma2)
+//   Bernoulli           p = E[link(f)], (p, p (1 - p));  p = Phi(mu / sqrt(1 + v)) for normcdf, Gauss-Hermite of the sigmoid for logistic
+//   Poisson(e^f)        (e1, e1 + expm1(v) e1^2)
+//   Exponential(e^f)    (e1, exp(2 mu + 2 v) + expm1(v) e1^2)
+//   Gamma(alpha, e^f)   (alpha e1, alpha exp(2 mu + 2 v) + alpha^2 expm1(v) e1^2)
+__device__ __forceinline__ void predictive_moments_point(const LikParams& lp, double mu, double v, double& ymean, double& yvar) {
+  if (lp.lik == 0) {
+    ymean = mu;
+    yvar = v + lp.sigma2;
+    return;
+  }
+  if (lp.lik == 1 || lp.lik == 5) {
+    double p = 0.0;
+    if (lp.lik == 5) {
+      p = 0.5 * erfc(-0.70710678118654752440 * mu / sqrt(1.0 + v));
+    } else {
+      const double s = 1.4142135623730951 * sqrt(v);
+#pragma unroll 1
+      for (int q = 0; q < lp.gh_n; ++q) p += lp.gh_w[q] / (1.0 + exp(-(s * lp.gh_x[q] + mu)));
+    }
+    ymean = p;
+    yvar = p * (1.0 - p);
+    return;
+  }
+  const double e1 = exp(mu + 0.5 * v), spread = expm1(v) * e1 * e1, e2 = exp(2.0 * mu + 2.0 * v);
+  if (lp.lik == 2) {
+    ymean = e1;
+    yvar = e1 + spread;
+  } else if (lp.lik == 3) {
+    ymean = e1;
+    yvar = e2 + spread;
+  } else {
+    ymean = lp.sigma2 * e1;
+    yvar = lp.sigma2 * e2 + lp.sigma2 * lp.sigma2 * spread;
+  }
+}
+
 
 // d log p(y|f) / df
 __device__ __forceinline__ double dloglik_point(int lik, double f, double y, double sigma2) {

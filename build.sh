@@ -16,17 +16,17 @@ mkdir -p "$(dirname "$LOG")"
   echo "# $(hipcc --version 2>/dev/null | grep -m1 -i 'clang version' || true)"
 } > "$LOG"
 pids=()
-for f in prep strip grad api comm laplace nn collapsed natgrad; do
+for f in prep strip grad api comm laplace nn collapsed natgrad predictive; do
   echo "hipcc $FLAGS -c approximategps.jl_amd/csrc/$f.hip -o approximategps.jl_amd/csrc/$f.o" >> "$LOG"
   hipcc $FLAGS -c "$SRC/$f.hip" -o "$SRC/$f.o" &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
-echo "hipcc --offload-arch=gfx950 -shared -fPIC -o approximategps.jl_amd/csrc/libsvgp_mi355x.so {prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad}.o -ldl" >> "$LOG"
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$SRC/prep.o" "$SRC/strip.o" "$SRC/grad.o" "$SRC/api.o" "$SRC/comm.o" "$SRC/laplace.o" "$SRC/nn.o" "$SRC/collapsed.o" "$SRC/natgrad.o" -ldl
+echo "hipcc --offload-arch=gfx950 -shared -fPIC -o approximategps.jl_amd/csrc/libsvgp_mi355x.so {prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad,predictive}.o -ldl" >> "$LOG"
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$SRC/prep.o" "$SRC/strip.o" "$SRC/grad.o" "$SRC/api.o" "$SRC/comm.o" "$SRC/laplace.o" "$SRC/nn.o" "$SRC/collapsed.o" "$SRC/natgrad.o" "$SRC/predictive.o" -ldl
 {
   echo "# sha256 (sources, headers, objects, library)"
   (cd "$HERE" && sha256sum approximategps.jl_amd/csrc/*.hip approximategps.jl_amd/csrc/*.hpp include/svgp_mi355x.h \
-     approximategps.jl_amd/csrc/{prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad}.o approximategps.jl_amd/csrc/libsvgp_mi355x.so)
+     approximategps.jl_amd/csrc/{prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad,predictive}.o approximategps.jl_amd/csrc/libsvgp_mi355x.so)
 } >> "$LOG"
 echo "built $OUT"

@@ -664,6 +664,58 @@ int32_t svgp_natgrad_step_ext(svgp_ctx* ctx, svgp_model* model, const svgp_data*
                               svgp_grads* grads_out, void* m_out, void* Lq_out);
 int32_t svgp_model_update_keep_q(svgp_ctx* ctx, svgp_model* model, const svgp_model_desc* desc);
 
+/* ---- the predictive distribution of the OBSERVATION: held-out log density and predictions of y -------------------------------------
+ * What svgp_marginals / svgp_predict / svgp_laplace_predict return is the latent marginal N(mu_i, v_i) of f.  These two calls push it
+ * through the likelihood on the device (GPflow: predict_y / predict_log_density; GPyTorch: likelihood(model(x))):
+ *   lpd_i   = log p(y_i | D) = log int p(y_i | f) N(f; mu_i, v_i) df        the held-out log density; NLPD = -mean(lpd)
+ *   ymean_i = E[y_i],  yvar_i = Var[y_i]                                    no y needed
+ * lpd_i is NOT the ELBO's E_q[log p(y_i | f_i)], which bounds it from below (Jensen).  Per likelihood, with v_i including the 1e-18 of
+ * svgp_marginals and e1 = exp(mu + v / 2):
+ *   Gaussian              lpd = log N(y; mu, v + sigma2)                                  (mu, v + sigma2)
+ *   Bernoulli, normcdf    lpd = log Phi(+-mu / sqrt(1 + v))                               p = Phi(mu / sqrt(1 + v)):  (p, p (1 - p))
+ *   Bernoulli, logistic   lpd by quadrature                                               p = E[sigmoid(f)] by quadrature:  (p, p (1 - p))
+ *   Poisson, exp link     lpd by quadrature                                               (e1, e1 + expm1(v) e1^2)
+ *   Exponential(scale e^f)  lpd by quadrature                                             (e1, exp(2 mu + 2 v) + expm1(v) e1^2)
+ *   Gamma(alpha, scale e^f) lpd by quadrature                                             (alpha e1, alpha exp(2 mu + 2 v) + alpha^2 expm1(v) e1^2)
+ * Quadrature is Gauss-Hermite in the log domain, logsumexp_q(log w_q + log p(y | f_q)) with f_q = mu + sqrt(2 v) x_q and a running
+ * maximum: finite for a Poisson count of several hundred; weights that underflowed to 0 at high orders are skipped.  quadrature_n > 0
+ * forces GH-n for lpd of every likelihood; quadrature_n == 0 means the closed form where one exists (Gaussian, normcdf Bernoulli), else
+ * GH-20 - the rule svgp_model_desc documents for the ELBO, except that Poisson / Exponential / Gamma, whose ELBO term is closed, have no
+ * closed-form predictive density and take GH-20 here, and that the normcdf Bernoulli, whose ELBO term takes GH-20, is closed here.  The
+ * moments use their closed forms whenever they exist, whatever quadrature_n is (logistic: GH-n, or GH-20).
+ *   svgp_predictive       data-resident: ONE forward data pass, the one svgp_elbo runs (same prep, same strips, overlapped where svgp_elbo
+ *                         overlaps them), then the point stage.  pm: the batch's prior mean offsets as in svgp_marginals_with_mean, or NULL.
+ *                         A model carrying muz (svgp_model_set_mean_z) is honoured as svgp_elbo_with_mean honours it.
+ *   svgp_lik_predictive   array form, for Laplace / NearestNeighbors / any caller holding latent marginals: no model, no data pass.  mu, var,
+ *                         y: n host doubles each; var is the marginal variance itself (svgp_marginals' output holds the 1e-18 already).
+ *                         likelihood is a SVGP_LIK_* code, lik_param the Gaussian sigma2 / the Gamma shape alpha (ignored otherwise).
+ * Outputs (host, fp64, batch_len / n each; any may be NULL, not all): summary_out, lpd_out, ymean_out, yvar_out.  Without observations -
+ * a data object uploaded without y, or y == NULL in the array form - summary_out and lpd_out must be NULL (SVGP_INVALID_ARG before
+ * anything is enqueued); ymean_out and yvar_out still work.
+ * Both calls are ALWAYS LOCAL, like svgp_elbo_partial: on a context with a communicator nothing is all-reduced, and a data-parallel
+ * host adds the ranks' summaries itself.  svgp_elbo on the same model before and after is bitwise unchanged; both calls are bitwise
+ * repeatable (fixed-order sums, no atomics).
+ * Negative variances follow the model's neg_var_policy exactly as in svgp_elbo: a point with v_i < 0 is counted in n_neg_var; under
+ * SVGP_NEGVAR_CLAMP it is evaluated at v_i = 0 (the quadrature then collapses to log p(y_i | mu_i)); under SVGP_NEGVAR_ERROR it is left
+ * out of both sums and of n_points, its per-point outputs are NaN, every other point's are valid, and the status is SVGP_NEG_VARIANCE
+ * (outputs and summary are written all the same).  svgp_lik_predictive treats var[i] < 0 as the error policy does.  Non-finite inputs give
+ * non-finite outputs with SVGP_OK, as in svgp_elbo.  SVGP_NOT_POSDEF as in svgp_elbo.  SVGP_INVALID_ARG, before anything is enqueued:
+ * what svgp_marginals_with_mean rejects, no output requested, n < 1, NULL mu / var, quadrature_n outside 0..512, sigma2 / alpha <= 0 where
+ * the likelihood reads it; SVGP_UNSUPPORTED: a likelihood code outside SVGP_LIK_*.  svgp_last_timing reports svgp_predictive like a
+ * forward evaluation, the point stage in ms_expect; svgp_lik_predictive reports its point stage alone.  fp32 models: the data pass is
+ * fp32, the point stage fp64 on its moments.  Found by symbol (no ABI version step). */
+typedef struct svgp_pred_summary {
+  double sum_lpd;     /* sum_i log p(y_i | D) over the points that counted */
+  double sum_sq_err;  /* sum_i (y_i - E[y_i])^2 over the same points: RMSE = sqrt(sum_sq_err / n_points) */
+  int64_t n_points;
+  int64_t n_neg_var;
+} svgp_pred_summary;   /* 32 bytes */
+int32_t svgp_predictive(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                        const svgp_point_mean* pm, svgp_pred_summary* summary_out, double* lpd_out, double* ymean_out, double* yvar_out);
+int32_t svgp_lik_predictive(svgp_ctx* ctx, int32_t likelihood, double lik_param, int32_t quadrature_n, int64_t n, const double* mu,
+                            const double* var, const double* y, svgp_pred_summary* summary_out, double* lpd_out, double* ymean_out,
+                            double* yvar_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,12 @@ struct PointMeanGrad                  # svgp_point_mean_grad (16 bytes): d elbo 
     reserved::Int32
 end
 
+mutable struct PredSummary            # svgp_pred_summary (32 bytes): the sums of svgp_predictive / svgp_lik_predictive
+    sum_lpd::Float64; sum_sq_err::Float64
+    n_points::Int64; n_neg_var::Int64
+    PredSummary() = new(0, 0, 0, 0)
+end
+
 # ---------------------------------------------------------------------------------------------------------
 # context (one per process and GPU) and status -> exception (SURVEY §8b)
 # ---------------------------------------------------------------------------------------------------------
@@ -996,5 +1002,44 @@ end
 "update! without the upload of q: the packed m / Lq are ignored, the device-resident q (e.g. what natgrad_step! wrote) stays."
 update_keep_q!(M::DeviceModel, p::Packed) = p.offset ? throw(Unsupported()) :
     GC.@preserve p check(ccall((:svgp_model_update_keep_q, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{ModelDesc}), ctx(), M.h, p.desc))
+
+# ---------------------------------------------------------------------------------------------------------
+# The predictive distribution of the OBSERVATION (svgp_predictive / svgp_lik_predictive): log p(y_i | D) = log ∫ p(y_i | f) N(f; μ_i, v_i) df
+# and (E[y_i], Var[y_i]) through the model's likelihood - what AbstractGPs / GPLikelihoods leave to the caller after marginals(f_post(x)).
+# NLPD = -mean(lpd); RMSE = sqrt(summary.sum_sq_err / summary.n_points).  Always local: a data-parallel host adds the ranks' summaries.
+# ---------------------------------------------------------------------------------------------------------
+"Held-out metrics and predictions of y for the points off+1 : off+len of resident data: one forward data pass, then the likelihood on
+the device.  Returns (summary, lpd, ymean, yvar); `mux`: the batch's prior mean offsets (data eltype) or nothing.  Data without y:
+call with `with_y=false` and read ymean / yvar only."
+function predictive(Mo::DeviceModel, D::DeviceData; off::Integer=0, len::Integer=D.n - off, mux::Union{Nothing,Vector}=nothing,
+                    with_y::Bool=true)
+    s = PredSummary()
+    lpd, ymean, yvar = zeros(Float64, with_y ? len : 0), zeros(Float64, len), zeros(Float64, len)
+    mux === nothing || length(mux) == len || throw(ArgumentError("one prior mean offset per point of the batch"))
+    pm = mux === nothing ? Ref(PointMean(C_NULL, 0, 0)) : Ref(PointMean(pointer(mux), 0, 0))
+    GC.@preserve mux pm check(ccall((:svgp_predictive, lib), Int32,
+                                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{PointMean}, Ptr{PredSummary}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                    ctx(), Mo.h, D.h, off, len,
+                                    mux === nothing ? Ptr{PointMean}(C_NULL) : Base.unsafe_convert(Ptr{PointMean}, pm),
+                                    with_y ? Ptr{PredSummary}(pointer_from_objref(s)) : Ptr{PredSummary}(C_NULL),
+                                    with_y ? pointer(lpd) : Ptr{Float64}(C_NULL), ymean, yvar))
+    return s, lpd, ymean, yvar
+end
+"The same point stage on latent marginals the caller holds (Laplace, NearestNeighbors, svgp_marginals' output): no model, no data pass.
+`lik` is a SVGP_LIK_* code, `param` the Gaussian σ² / the Gamma shape; `y === nothing`: the moments alone.  Returns (summary, lpd, ymean, yvar)."
+function lik_predictive(lik::Integer, param::Real, mu::Vector{Float64}, var::Vector{Float64}, y::Union{Nothing,Vector{Float64}}=nothing;
+                        quadrature_n::Integer=0)
+    n = length(mu)
+    (length(var) == n && (y === nothing || length(y) == n)) || throw(ArgumentError("mu, var and y must have one entry per point"))
+    s = PredSummary()
+    lpd, ymean, yvar = zeros(Float64, y === nothing ? 0 : n), zeros(Float64, n), zeros(Float64, n)
+    GC.@preserve y check(ccall((:svgp_lik_predictive, lib), Int32,
+                               (Ptr{Cvoid}, Int32, Float64, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{PredSummary}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                               ctx(), Int32(lik), Float64(param), Int32(quadrature_n), n, mu, var,
+                               y === nothing ? Ptr{Float64}(C_NULL) : pointer(y),
+                               y === nothing ? Ptr{PredSummary}(C_NULL) : Ptr{PredSummary}(pointer_from_objref(s)),
+                               y === nothing ? Ptr{Float64}(C_NULL) : pointer(lpd), ymean, yvar))
+    return s, lpd, ymean, yvar
+end
 
 end # module

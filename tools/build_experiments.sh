@@ -6,10 +6,10 @@ set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"; SRC="$ROOT/approximategps.jl_amd/csrc"; OUT="$SRC/ablate"; mkdir -p "$OUT"
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function -DSVGP_EXPERIMENTS ${SVGP_EXTRA_FLAGS:-}"
 pids=()
-for f in prep strip grad api comm laplace nn collapsed natgrad; do
+for f in prep strip grad api comm laplace nn collapsed natgrad predictive; do
   hipcc $FLAGS -c "$SRC/$f.hip" -o "$OUT/${f}_exp.o" &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libsvgp_experiments.so" "$OUT"/{prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad}_exp.o -ldl
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libsvgp_experiments.so" "$OUT"/{prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad,predictive}_exp.o -ldl
 echo "$OUT/libsvgp_experiments.so"
