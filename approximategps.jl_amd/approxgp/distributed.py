@@ -128,7 +128,7 @@ class ShardedELBO:
         if self.in_library:
             val, _, g = self.model.elbo_grad(self.data, off, length, self.num_data)
             return val, g
-        # The host-side mirror of the library's protocol (csrc/api.hip: grad_handshake): the gradient all-reduce is sized by the model,
+        # The host-side mirror of the library's protocol (csrc/api_grad.hip: grad_handshake): the gradient all-reduce is sized by the model,
         # so a rank whose evaluation raised cannot simply enter it.  Every rank first enters ONE fixed-size all-reduce of its failure
         # flag; if any rank failed, all of them leave here - the failing rank with its own exception, the others with RuntimeError -
         # and nobody enters the gradient all-reduce.

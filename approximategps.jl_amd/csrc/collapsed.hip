@@ -1,6 +1,6 @@
 // collapsed.hip — the collapsed (Titsias 2009, eqs. 11 / 12) bound of sparse GP regression and the optimal q(u): the kernels that are
 // NOT the data pass (strip.hip: trsm_pm_kernel gives A = Lk \ Kuf point-major and sum A^2 per point; grad.hip: syrk_async_kernel gives
-// C = A A').  api.hip: collapsed_run is the schedule.  The reference builds the same q on the host (test/test_utils.jl:7-17,
+// C = A A').  api_qopt.hip: collapsed_run is the schedule.  The reference builds the same q on the host (test/test_utils.jl:7-17,
 // optimal_variational_posterior) and compares it with AbstractGPs' VFE posterior (test/SparseVariationalApproximationModule.jl:99-134).
 //   data-sized   b = A r, rr = r'r, t = sum_j |A_j|^2 over the resident point-major chunk          collapsed_reduce_kernel
 //   M-sized      B = I + C / sigma^2 (fp64, from the SYRK's slices), c~ = b / sigma^2              collapsed_form_b_kernel

@@ -1,4 +1,4 @@
-// ctx.hpp — internal definitions shared by the host-side translation units of libsvgp_mi355x (api.hip, comm.hip, laplace.hip):
+// ctx.hpp — internal definitions shared by the host-side translation units of libsvgp_mi355x (api.hip and its api_*.hip siblings, comm.hip, laplace.hip, nn.hip):
 // the owning types of every device resource, the opaque handles of include/svgp_mi355x.h and the error macros.  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -128,7 +128,7 @@ struct svgp_ctx {
   svgp::Event ev_fork, ev_join;
   svgp::DevBuf counter2;
   svgp::DevBuf work2;
-  // strips beside the factorisation (api.hip: SegRun): one event per block row of T, the segmented strips' saved sums
+  // strips beside the factorisation (host.hpp: SegRun): one event per block row of T, the segmented strips' saved sums
   svgp::Event ev_row[16];
   bool ev_row_ready = false, overlapped = false;
   bool timing_on = true;   // SVGP_TIMING=0 at context creation: no timing events on the stream (each record costs the stream ~5 us); svgp_last_timing then reports zeros
@@ -137,7 +137,7 @@ struct svgp_ctx {
   svgp::Event ev_ov[2];   // timed: fork point, first strip launch done (svgp_timing.ms_overlap)
   svgp::DevBuf seg_state;   // (double)
   svgp::DevBuf work_seg;    // per-strip scratch of the segmented strips
-  svgp::HostBuf hstage;     // pinned host staging of the gradient read-back (api.hip: grad_finish)
+  svgp::HostBuf hstage;     // pinned host staging of the gradient read-back (api_grad.hip: grad_finish)
   svgp::Event ev_piece[8];  // one behind each piece of that read-back
   svgp::DevBuf kuf_buf;
   svgp::DevBuf ext_g;   // [2][n] point gradients of a host-evaluated likelihood (double)
@@ -155,7 +155,7 @@ struct svgp_ctx {
   void* comm = nullptr;        // ncclComm_t
   int world = 1, rank = 0;
   bool comm_owned_by_group = false;
-  svgp::HostBuf h_open;   // pinned host word (double): the reduced failure flag of svgp_elbo_grad's opening all-reduce (api.hip: grad_handshake)
+  svgp::HostBuf h_open;   // pinned host word (double): the reduced failure flag of svgp_elbo_grad's opening all-reduce (api_grad.hip: grad_handshake)
   svgp::Event ev_open;    // ... recorded behind its copy
   svgp::DevBuf d_coll;    // [8] the all-reduced vector {sum E, n_points, n_neg_var, chol flag, failure flag, ...} (double)
 };
@@ -169,7 +169,7 @@ struct GradWs {
   void* gv = nullptr;    // ... its second half
   svgp::DevBuf Lqp, G1, G2, LkRM, LbarRM, Phi, tmp, H, BbarRM, rbar;
   svgp::DevBuf LinvRM, LinvCM;   // Lk^-1 in both storage orders (launch_linv): every Lk^-T . of the tail is a GEMM with it
-  svgp::DevBuf Gmm;   // split-K scratch of the M x M products that run BESIDE an early SYRK (api.hip: syrk_early), allocated on first use
+  svgp::DevBuf Gmm;   // split-K scratch of the M x M products that run BESIDE an early SYRK (api_grad.hip: grad_plan), allocated on first use
   svgp::DevBuf W2, Rcm, G1p, alpha;   // W = A diag(2 g_v) A', R = Lk^-T (Lq Lq' - I), 2 W Lq, Lk^-T m
   // the user-layout gradient blocks {z_bar (M d) | m_bar (M) | Lq_bar (M^2)}: ONE allocation, contiguous for the model's M, so
   // that the data-parallel sum is one ncclAllReduce and the read-back one copy; zbar / mbar / Lqbar point into it (set per call)

@@ -1,7 +1,7 @@
 // grad.hip — reverse-mode gradient of the ELBO (the reference differentiates elbo with Zygote:
 // examples/a-regression/script.jl:188-194, test/SparseVariationalApproximationModule.jl:170-175): the kernels of the parts
 // that are NOT the strip kernel's phase 3.  Hand-derived adjoint of the forward path (oracle/svgp_oracle.py: elbo_grad is
-// the same derivation; api.hip: grad_enqueue is the schedule).  With A = Lk \ Kuf, B the whitened factor, W = A diag(2 g_v) A':
+// the same derivation; api_grad.hip: grad_enqueue is the schedule).  With A = Lk \ Kuf, B the whitened factor, W = A diag(2 g_v) A':
 //   data-sized     W (SYRK over the points, split-K slices)                         gemm_pm_kernel
 //                  kernel-parameter / inducing-input reductions of P o dK           kgrad_mfma_kernel
 //                  (P = alpha g_mu' + 2 (R A) diag(g_v) is formed there from the strips' UNSCALED R A: the strips take the
@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(320) sum5_kernel(const double* __restrict__ pa
   if (lane == 0) out[q] += s;
 }
 
-// ---- M x M helpers of the fused gradient path (svgp_elbo_grad, api.hip: grad_enqueue) ---------------------------------
+// ---- M x M helpers of the fused gradient path (svgp_elbo_grad, api_grad.hip: grad_enqueue) ---------------------------------
 // out (row-major, FULL symmetric) = sum over slices of the lower triangle of G (row-major; only entries c <= r are read, also
 // inside the diagonal tiles, so the result is exactly symmetric), minus `eye` on the diagonal.  One 32 x 32 tile of the lower
 // triangle per workgroup: the slice sums are read along rows, the mirror image leaves through an LDS transposition, so both

@@ -40,7 +40,7 @@ void launch_kuu(int dtype, hipStream_t s, const KernelParams& kp, const void* zs
 // first non-positive pivot; sync: Mp / 128 zeroed counters (device) for the in-kernel hand-over of the next diagonal block.
 // row_events (nullable; Mp / 128 <= potrf_max_row_events() events): event p is recorded on `s` once block row p of T is final
 // row hook: called on the host right after row_events[p] is recorded (p = block row of T that has just become final), so that the
-// caller can enqueue the work that waits for that event BEHIND the record and still AHEAD of the device (api.hip: SegRun)
+// caller can enqueue the work that waits for that event BEHIND the record and still AHEAD of the device (host.hpp: SegRun)
 struct RowHook { void (*fn)(void* user, int row) = nullptr; void* user = nullptr; };
 void launch_potrf(int dtype, hipStream_t s, void* A, void* T, int64_t Mp, int* info, unsigned* sync, int num_cus, hipEvent_t* row_events = nullptr,
                   const RowHook* hook = nullptr);

@@ -65,7 +65,7 @@ __device__ __forceinline__ double expected_loglik_point(const LikParams& lp, dou
 }
 
 // ---- the predictive distribution of the OBSERVATION (predictive.hip: svgp_predictive / svgp_lik_predictive) -----------------------
-// For both functions lp.gh_n is the PREDICTIVE rule (api.hip: predictive_gh): 0 = closed form, which exists for the Gaussian and the
+// For both functions lp.gh_n is the PREDICTIVE rule (api_predictive.hip: predictive_gh): 0 = closed form, which exists for the Gaussian and the
 // normcdf Bernoulli only; every other likelihood arrives with a Gauss-Hermite rule (GH-20 when the model's quadrature_n is 0).
 // Poisson, Exponential and Gamma have a closed-form ELBO expectation (expected_loglik_point) but NO closed-form predictive density:
 // E[exp(-e^f)] of a log-normal has none.  They take the quadrature here.

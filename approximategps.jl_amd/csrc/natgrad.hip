@@ -1,5 +1,5 @@
 // natgrad.hip — one natural-gradient step on q(u) (svgp_natgrad_step / _ext): the M-sized kernels that are NOT the data pass.  The data
-// pass is svgp_elbo_grad's, unchanged (api.hip: grad_enqueue_impl): it leaves the split-K slices of A diag(2 scale g_v) A' in the
+// pass is svgp_elbo_grad's, unchanged (api_grad.hip: grad_enqueue_impl): it leaves the split-K slices of A diag(2 scale g_v) A' in the
 // gradient's slice buffer and scale A g_mu in its avec.  In whitened coordinates, q(v) = N(m_w, S_w), S_w = B B', Lambda = inv(S_w),
 // W = A diag(-2 scale g_v) A', a = scale A g_mu, step length gamma in (0, 1]  (the reference's ELBO, SVA:340-373, in the natural
 // parameters theta = (Lambda m_w, -Lambda / 2) and the expectation parameters eta = (m_w, S_w + m_w m_w'): theta' = theta + gamma dL/d eta):

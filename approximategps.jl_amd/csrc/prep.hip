@@ -1016,7 +1016,7 @@ void potrf_t(hipStream_t s, T* A, T* Tm, int64_t Mp, int* info, unsigned* sync, 
   auto step1 = [&](int p) {   // one-level panel step p: TRSM (+ T panels), trailing update with the next block factorisation
     const int n = nP - p - 1, nt_p = t_inside ? p : 0;
     // block row p of T (inv(L_pp) from the block factorisation, T[p, J < p] from the TRSM launch) is final behind that launch: the
-    // strips' phase 1 of panel p may start (api.hip: SegRun - the row hook below enqueues the waiter on its own stream).  The event
+    // strips' phase 1 of panel p may start (host.hpp: SegRun - the row hook below enqueues the waiter on its own stream).  The event
     // rides on the launch itself (hipExtLaunchKernelGGL's stop event = the dispatch packet's own completion signal): a separate
     // hipEventRecord is a barrier packet of its own, ~5 us of the chain per panel (kernel traces, minibatch_step.md section 8).
     // SVGP_ROW_EVENT_EXT=0: the separate record (A/B).

@@ -224,8 +224,8 @@ __device__ __noinline__ PointGrads strip_point_grads(LikParams lp, double mu, do
 // BIGD (round 4): the instantiation for 16 < d <= 64.  A separate kernel, not a branch: with the 32- / 64-feature pre-generation
 // bodies inside, the register allocation of the WHOLE kernel changed (the headline f64 kernel went from 0 to 335 spilled VGPRs) -
 // so the d <= 16 kernels stay bit for bit what they were and the wide-input kernels hold only the wide bodies.
-// SEG (round 4): the SEGMENTED form for strips that run BESIDE the factorisation of Kuu (api.hip:
-// enqueue_strips_overlapped).  Phase 1 of panel I needs nothing of the prep but block row I of T, which is final after panel
+// SEG (round 4): the SEGMENTED form for strips that run BESIDE the factorisation of Kuu (api_forward.hip:
+// seg_enqueue_row).  Phase 1 of panel I needs nothing of the prep but block row I of T, which is final after panel
 // step I of the Cholesky; so a batch of at most one round of strips is evaluated as a sequence of short launches on a second
 // stream - pre-generation, then one launch per panel (each behind the event of its T row), then phase 2 + moments - instead of
 // one launch behind the whole prep.  A launch covers the panels [seg_lo, seg_hi); between launches a strip's state is its scratch
@@ -603,7 +603,7 @@ __global__ void __launch_bounds__(NTHR, MINW) strip_kernel(StripArgs a, int64_t 
 }
 
 // ---------------------------------------------------------------------------------------------
-// The collapsed (Titsias) bound's data pass (api.hip: collapsed_run): phase 1 of the strips ALONE.  A strip's Kuf block is generated
+// The collapsed (Titsias) bound's data pass (api_qopt.hip: collapsed_run): phase 1 of the strips ALONE.  A strip's Kuf block is generated
 // into its scratch strip and solved against Lk through the T panels exactly as above (same pre-generation, same k-loops, same
 // arithmetic per point); A leaves point-major for the SYRK C = A A' and the reduction b = A r, and sum_k A_kj^2 (the trace term's
 // Qff_jj) per point in fp64 through a.mom_var.  No phase 2, no phase 3: 2 Mp^2 / 2 flops per point in here, the SYRK has the rest.

@@ -15,18 +15,20 @@ mkdir -p "$(dirname "$LOG")"
   echo "# build.sh: $(hipcc --version 2>/dev/null | grep -m1 -i 'HIP version' || echo 'hipcc version unknown')"
   echo "# $(hipcc --version 2>/dev/null | grep -m1 -i 'clang version' || true)"
 } > "$LOG"
+UNITS=$(cd "$SRC" && for f in *.hip; do echo "${f%.hip}"; done)   # every translation unit: csrc/ holds nothing else that matches
 pids=()
-for f in prep strip grad api comm laplace nn collapsed natgrad predictive; do
+for f in $UNITS; do
   echo "hipcc $FLAGS -c approximategps.jl_amd/csrc/$f.hip -o approximategps.jl_amd/csrc/$f.o" >> "$LOG"
   hipcc $FLAGS -c "$SRC/$f.hip" -o "$SRC/$f.o" &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
-echo "hipcc --offload-arch=gfx950 -shared -fPIC -o approximategps.jl_amd/csrc/libsvgp_mi355x.so {prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad,predictive}.o -ldl" >> "$LOG"
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$SRC/prep.o" "$SRC/strip.o" "$SRC/grad.o" "$SRC/api.o" "$SRC/comm.o" "$SRC/laplace.o" "$SRC/nn.o" "$SRC/collapsed.o" "$SRC/natgrad.o" "$SRC/predictive.o" -ldl
+OBJS=$(for f in $UNITS; do echo "approximategps.jl_amd/csrc/$f.o"; done)
+echo "hipcc --offload-arch=gfx950 -shared -fPIC -o approximategps.jl_amd/csrc/libsvgp_mi355x.so" $OBJS "-ldl" >> "$LOG"
+(cd "$HERE" && hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT" $OBJS -ldl)
 {
   echo "# sha256 (sources, headers, objects, library)"
   (cd "$HERE" && sha256sum approximategps.jl_amd/csrc/*.hip approximategps.jl_amd/csrc/*.hpp include/svgp_mi355x.h \
-     approximategps.jl_amd/csrc/{prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad,predictive}.o approximategps.jl_amd/csrc/libsvgp_mi355x.so)
+     $OBJS approximategps.jl_amd/csrc/libsvgp_mi355x.so)
 } >> "$LOG"
 echo "built $OUT"

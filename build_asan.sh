@@ -8,11 +8,12 @@ set -euo pipefail
 HERE="$(cd "$(dirname "$0")" && pwd)"
 SRC="$HERE/approximategps.jl_amd/csrc"; OUT="$SRC/asan"; mkdir -p "$OUT"
 FLAGS="-O1 -g -std=c++17 --offload-arch=gfx950 -fPIC -fsanitize=address -fno-gpu-sanitize -fno-omit-frame-pointer -Wno-unused-function"
+UNITS=$(cd "$SRC" && for f in *.hip; do echo "${f%.hip}"; done)   # every translation unit: csrc/ holds nothing else that matches
 pids=()
-for f in prep strip grad api comm laplace nn collapsed natgrad predictive; do
+for f in $UNITS; do
   hipcc $FLAGS -c "$SRC/$f.hip" -o "$OUT/$f.o" &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
-hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address -fno-gpu-sanitize -shared-libsan -o "$OUT/libsvgp_mi355x_asan.so" "$OUT"/{prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad,predictive}.o -ldl
+hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address -fno-gpu-sanitize -shared-libsan -o "$OUT/libsvgp_mi355x_asan.so" $(for f in $UNITS; do echo "$OUT/$f.o"; done) -ldl
 echo "built $OUT/libsvgp_mi355x_asan.so"

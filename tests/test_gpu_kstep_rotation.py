@@ -11,7 +11,7 @@ steps; phase 1 of the strips appends eight triangular steps, phase 2 starts with
     (Bernoulli); phase 3 of its strips (TRI = 0, 8 / 24 steps);
   * phase 1 alone (the collapsed bound).
 
-The slicing rule of the SYRK (csrc/api.hip: syrk_slices, grad_chunk_points; csrc/grad.hip: syrk_async_kernel), restated: a call
+The slicing rule of the SYRK (csrc/api_grad.hip: syrk_slices, grad_chunk_points; csrc/grad.hip: syrk_async_kernel), restated: a call
 of N <= 65 536 points is one chunk of ncp = ceil128(N) points; it is cut into ns = min(64, ncp / 512) slices (at least 1; for M <= 384
 on a device of >= 64 CUs) of sl = ceil16(ceil(ncp / ns)) points, the last slice takes what is left.  A slice of L points is a loop of
 ceil(L / 16) steps.

@@ -132,7 +132,7 @@ _OV = dict(SVGP_OVERLAP_MIN_PANELS="2", SVGP_TIMING="1")
                                       (100000, 512, 8, o.LIK_GAUSSIAN), (70001, 650, 4, o.LIK_BERNOULLI_LOGISTIC), (150000, 300, 2, o.LIK_GAUSSIAN)])
 def test_strips_beside_the_factorisation_are_bitwise_the_serial_result(dtype, N, M, d, lik):
     """a batch of at most one round of strips runs as segmented strips on a second stream, panel I behind the
-    event of block row I of T, beside the Cholesky of Kuu (api.hip: SegRun).  Per strip the arithmetic is the
+    event of block row I of T, beside the Cholesky of Kuu (host.hpp: SegRun).  Per strip the arithmetic is the
     one-launch kernel's, register for register: ELBO, expectation and the per-point marginals must be IDENTICAL bits with the
     overlap on and off, repeatedly (a race between the streams would show as a flaky difference), at several M / widths."""
     x, y, sva, s2 = o.synth_problem(6000 + M, N, M, d, lik=lik, dtype=dtype)
@@ -317,7 +317,7 @@ def test_gradient_strips_beside_the_factorisation_are_bitwise_the_serial_result(
 @pytest.mark.parametrize("M,d", [(130, 3), (1100, 8)])   # gradient blocks below one piece of the read-back, and of several pieces
 def test_gradient_read_back_in_pieces_and_into_reused_buffers(ctx, dtype, M, d):
     """svgp_elbo_grad returns M^2 elements of Lq_bar to host memory every step: the read-back goes through a pinned staging buffer in up
-    to 8 pieces whose host copies overlap the bus (api.hip: grad_finish).  Piece boundaries fall anywhere inside z_bar | m_bar | Lq_bar:
+    to 8 pieces whose host copies overlap the bus (api_grad.hip: grad_finish).  Piece boundaries fall anywhere inside z_bar | m_bar | Lq_bar:
     every block must equal a one-piece reference (models of different sizes sharing the context's staging buffer), and a second call
     into the SAME host arrays (`out=`) must overwrite them with identical bits."""
     N = 2000

@@ -131,7 +131,10 @@ def test_environment_knobs_are_exactly_the_documented_sets():
     missing = sorted(n for n in product | py if f"`{n}`" not in head) + sorted(n for n in experiments if f"`{n}`" not in tail)
     assert not missing, missing
     # no evaluation path reads the environment: outside knobs.hpp the only getenv calls are the process-wide statics / svgp_offload_advice
-    api = open(os.path.join(ROOT, "approximategps.jl_amd", "csrc", "api.hip")).read()
+    # (the host-only units: the C-ABI's api*.hip and what crosses them, host.hpp)
+    host = sorted(glob.glob(os.path.join(ROOT, "approximategps.jl_amd", "csrc", "api*.hip"))) + [os.path.join(ROOT, "approximategps.jl_amd", "csrc", "host.hpp")]
+    assert len(host) == 6 and all("__global__" not in open(f).read() for f in host)
+    api = "".join(open(f).read() for f in host)
     assert re.findall(r'getenv\("(SVGP_[A-Z0-9_]+)"', api) == ["SVGP_OFFLOAD_MIN_WORK"]
     from approxgp import _ffi
     if os.path.exists(_ffi.LIB_PATH) and "experiments" not in os.path.basename(_ffi.LIB_PATH):

@@ -5,11 +5,12 @@
 set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"; SRC="$ROOT/approximategps.jl_amd/csrc"; OUT="$SRC/ablate"; mkdir -p "$OUT"
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function -DSVGP_EXPERIMENTS ${SVGP_EXTRA_FLAGS:-}"
+UNITS=$(cd "$SRC" && for f in *.hip; do echo "${f%.hip}"; done)   # every translation unit: csrc/ holds nothing else that matches
 pids=()
-for f in prep strip grad api comm laplace nn collapsed natgrad predictive; do
+for f in $UNITS; do
   hipcc $FLAGS -c "$SRC/$f.hip" -o "$OUT/${f}_exp.o" &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libsvgp_experiments.so" "$OUT"/{prep,strip,grad,api,comm,laplace,nn,collapsed,natgrad,predictive}_exp.o -ldl
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libsvgp_experiments.so" $(for f in $UNITS; do echo "$OUT/${f}_exp.o"; done) -ldl
 echo "$OUT/libsvgp_experiments.so"

@@ -7,6 +7,7 @@ tag=$1; shift
 F=${FILE:-prep}
 hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function "$@" -c "$SRC/$F.hip" -o "$OUT/${F}_$tag.o"
 objs=""
-for o in prep strip grad api comm; do if [ "$o" = "$F" ]; then objs="$objs $OUT/${F}_$tag.o"; else objs="$objs $SRC/$o.o"; fi; done
+for o in $(cd "$SRC" && for f in *.hip; do echo "${f%.hip}"; done); do   # every translation unit
+  if [ "$o" = "$F" ]; then objs="$objs $OUT/${F}_$tag.o"; else objs="$objs $SRC/$o.o"; fi; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libsvgp_$tag.so" $objs -ldl
 echo "$OUT/libsvgp_$tag.so"
