@@ -28,5 +28,8 @@ from .nearest_neighbors import (DeviceNearestNeighbors, NearestNeighbors, NNPost
 from .vfe import VFE, approx_lml, elbo, elbo_and_gradient, optimal_variational_posterior, posterior
 # natural-gradient steps on q(u) (GPflow's NaturalGradient / GPyTorch's NGD); DeviceModel.natgrad_step / update_keep_q for resident loops
 from .natgrad import natural_gradient_step
+# pathwise posterior function samples: ApproxPosteriorGP.function_samples, DeviceModel.sampler; draw_basis draws their random numbers
+from ._ffi import DeviceSampler, SampleBasis
+from .pathwise import FunctionSamples, draw_basis, function_samples
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -100,6 +100,13 @@ class PredSummary(C.Structure):
     _fields_ = [("sum_lpd", C.c_double), ("sum_sq_err", C.c_double), ("n_points", C.c_int64), ("n_neg_var", C.c_int64)]
 
 
+class SampleBasis(C.Structure):
+    """svgp_sample_basis: the random numbers of S pathwise function samples, all supplied by the caller (host arrays, model dtype):
+    omega [L][d] unit-lengthscale frequencies, tau [L] phases, w [S][L] feature weights, eps [S][M] draws for q(u)."""
+    _fields_ = [("n_features", C.c_int64), ("n_samples", C.c_int64), ("omega", C.c_void_p), ("tau", C.c_void_p),
+                ("w", C.c_void_p), ("eps", C.c_void_p)]
+
+
 # every symbol include/svgp_mi355x.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -184,6 +191,11 @@ SYMBOLS = {
     # the predictive distribution of the observation
     "svgp_predictive": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), C.POINTER(PredSummary), _P, _P, _P]),
     "svgp_lik_predictive": (C.c_int32, [_P, C.c_int32, C.c_double, C.c_int32, C.c_int64, _P, _P, _P, C.POINTER(PredSummary), _P, _P, _P]),
+    # pathwise posterior function samples
+    "svgp_sampler_create": (C.c_int32, [_P, _P, C.POINTER(SampleBasis), C.POINTER(_P)]),
+    "svgp_sampler_eval": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), _P, C.c_int64, C.c_int32]),
+    "svgp_sampler_state": (C.c_int32, [_P, _P, _P, _P]),
+    "svgp_sampler_free": (C.c_int32, [_P, _P]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),
     "svgp_ctx_attach_comm": (C.c_int32, [_P, _P, C.c_int32, C.c_int32]),
@@ -823,6 +835,11 @@ class DeviceModel:
         self.ctx.check(self.ctx.lib.svgp_predict_cross_cov(self.ctx.h, self.h, layout, nx, _ptr(xb), ny, _ptr(yb), _ptr(cov)))
         return cov
 
+    def sampler(self, basis):
+        """svgp_sampler_create: S pathwise posterior function samples from `basis` = (omega (L, d), tau (L,), w (S, L), eps (S, M)) - every
+        random number is the caller's (approxgp.pathwise.draw_basis draws them).  The DeviceSampler is a snapshot of this model."""
+        return DeviceSampler(self, *basis)
+
     def kuf(self, data: DeviceData, off=0, length=None, fetch=True):
         length = data.n - off if length is None else length
         out = np.zeros((self.M, length), dtype=np_dtype(self.dtype), order="F") if fetch else None
@@ -832,6 +849,63 @@ class DeviceModel:
     def free(self):
         if getattr(self, "h", None):
             self.ctx.lib.svgp_model_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DeviceSampler:
+    """S function samples of a model's posterior, resident in HBM (svgp_sampler): evaluate them anywhere, any number of times."""
+
+    def __init__(self, model: DeviceModel, omega, tau, w, eps):
+        self.ctx = ctx = model.ctx
+        self.M, self.d, self.dtype = model.M, model.d, model.dtype
+        dt = np_dtype(self.dtype)
+        eps = np.ascontiguousarray(np.asarray(eps, dtype=dt))
+        if eps.ndim != 2 or eps.shape[1] != self.M or eps.shape[0] < 1:
+            raise ValueError("eps must be (S, M) with S >= 1")
+        S = eps.shape[0]
+        w = np.ascontiguousarray(np.asarray(np.zeros((S, 0)) if w is None else w, dtype=dt).reshape(S, -1))
+        L = w.shape[1]
+        omega = np.ascontiguousarray(np.asarray(omega, dtype=dt).reshape(L, self.d))
+        tau = np.ascontiguousarray(np.asarray(tau, dtype=dt).reshape(L))
+        self.n_samples, self.n_features = S, L
+        basis = SampleBasis(L, S, _ptr(omega) if L else None, _ptr(tau) if L else None, _ptr(w) if L else None, _ptr(eps))
+        h = C.c_void_p()
+        ctx.check(ctx.lib.svgp_sampler_create(ctx.h, model.h, C.byref(basis), C.byref(h)))
+        self.h = h
+
+    def eval(self, data: DeviceData, off=0, length=None, prior_mean=None, out=None, ldo=None):
+        """f_s at the points [off, off + length) of `data` -> (S, length) array of the model dtype (row s = sample s).  out: a device
+        pointer (int) or a contiguous device tensor to write there instead, rows ldo >= length apart; then nothing is returned."""
+        length = data.n - off if length is None else length
+        pm, _keep = point_mean(prior_mean, length, self.dtype) if prior_mean is not None else (None, None)
+        pmr = C.byref(pm) if pm is not None else None
+        ctx = self.ctx
+        if out is not None:
+            ldo = length if ldo is None else int(ldo)
+            ptr = int(out.data_ptr()) if hasattr(out, "data_ptr") else int(out)
+            ctx.check(ctx.lib.svgp_sampler_eval(ctx.h, self.h, data.h, off, length, pmr, C.c_void_p(ptr), ldo, 1))
+            return None
+        ldo = length if ldo is None else int(ldo)
+        buf = np.zeros((self.n_samples, max(ldo, 1)), dtype=np_dtype(self.dtype))
+        ctx.check(ctx.lib.svgp_sampler_eval(ctx.h, self.h, data.h, off, length, pmr, _ptr(buf), ldo, 0))
+        return buf if ldo != length else buf[:, :length]
+
+    def state(self):
+        """(u, V) in fp64, (M, S) each: the draws u_s ~ q(u) and V_s = Kuu^-1 (u_s - mean(z) - Phi(z) w_s)."""
+        u = np.zeros((self.M, self.n_samples), order="F")
+        V = np.zeros((self.M, self.n_samples), order="F")
+        self.ctx.check(self.ctx.lib.svgp_sampler_state(self.ctx.h, self.h, _ptr(u), _ptr(V)))
+        return u, V
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.svgp_sampler_free(self.ctx.h, self.h)
             self.h = None
 
     def __del__(self):

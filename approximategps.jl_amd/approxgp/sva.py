@@ -309,6 +309,13 @@ class ApproxPosteriorGP:
         rng = rng if rng is not None else np.random.default_rng()
         return m[:, None] + L @ rng.standard_normal((c.shape[0], int(n_samples)))
 
+    def function_samples(self, n_samples, n_features=2048, rng=None):
+        """n_samples FUNCTIONS drawn from the posterior by pathwise conditioning (pathwise.py, svgp_sampler_*): -> a callable
+        fs(x) -> (n, n_samples) that can be evaluated at any x, again and again, on the device in one data pass linear in n.  The prior
+        part uses n_features random Fourier features (error O(variance / sqrt(n_features))); the update term is exact."""
+        from .pathwise import function_samples
+        return function_samples(self, n_samples, n_features, rng)
+
     def _predictive(self, x, y, lik, quadrature, want):
         """svgp_predictive on (x, y): the forward data pass, then the likelihood on the device"""
         lik = lik if lik is not None else self.lik

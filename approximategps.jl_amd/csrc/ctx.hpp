@@ -149,6 +149,7 @@ struct svgp_ctx {
   svgp::DevBuf pred_in;     // [3][n] a caller's mu | var | y (double; svgp_lik_predictive)
   svgp::DevBuf pred_gh;     // [2][pred_gh_n] Gauss-Hermite nodes | weights / sqrt(pi) of the predictive rule (double)
   int pred_gh_n = 0;
+  svgp::DevBuf smp_out;     // [S][len] samples of a host-output svgp_sampler_eval call, copied out (model dtype)
   struct GradWs* gws = nullptr;  // gradient workspace, cached by problem shape (deleted by svgp_ctx_destroy)
   struct CollapsedWs* cws = nullptr;   // fp64 M-sized tail of svgp_collapsed_*, cached by Mp (deleted by svgp_ctx_destroy)
   // data-parallel communicator (comm.hip): one RCCL rank per context; world == 1 without one
@@ -224,6 +225,17 @@ struct svgp_model {
   // host copies of the last prep's scalars
   double kl = 0, logdet_kuu = 0;
   int chol_info = 0;
+};
+
+// svgp_sampler_create's snapshot of S pathwise function samples (sample_api.hip): everything svgp_sampler_eval reads, so that the
+// model it was made from may change or go
+struct svgp_sampler {
+  int dtype = 0, d = 0, family = 0, device = 0;
+  size_t es = 8;
+  int64_t M = 0, Mp = 0, L = 0, Lp = 0, S = 0, Sp = 0;
+  double variance = 0, mean_const = 0;
+  svgp::DevBuf invl, rows, bias, panel;   // model dtype (kernels.hpp: SampleEvalArgs)
+  svgp::DevBuf u, V;                      // fp64: u [S][M], V [S][Mp] before its rounding into the panel (svgp_sampler_state)
 };
 
 // one process driving several GPUs: member contexts share one RCCL communicator (ncclCommInitAll), rank i = member i

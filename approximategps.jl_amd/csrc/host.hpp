@@ -1,5 +1,5 @@
 // host.hpp — the declarations that cross the host-only translation units of the C-ABI (api.hip, api_forward.hip, api_grad.hip,
-// api_qopt.hip, api_predictive.hip), each under the unit that defines it.  A function used by one unit only lives in that unit's
+// api_qopt.hip, api_predictive.hip, sample_api.hip), each under the unit that defines it.  A function used by one unit only lives in that unit's
 // anonymous namespace; the owning types and the handles are ctx.hpp's.  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -258,5 +258,37 @@ void launch_natgrad_rhs(hipStream_t s, const double* Bm, const double* mw, const
 void launch_natgrad_status(hipStream_t s, const double* Wm, const double* a, int64_t Mp, const int* info_b, int* info_s, const int* info_q,
                            const int* kuu_info, const double* gsums, int neg_var_is_error, double* scal);
 
+// ---- sample.hip (pathwise posterior function samples: svgp_sampler_*) ------------------------------------------------------
+// the data stage: out[s * ldo + j] = (mean_const + mux[j]) + sum_k panel[k][s] g_k(x_{off + j}), j < len, s < S, where row k < Lp is the
+// feature cos(rows[.][k] . xs + bias[k]) and row Lp + i the kernel value kappa(|xs|^2 + bias + rows[.][k] . xs) of inducing point i
+// (xs = invl o x; rows = -2 zs, bias = |zs|^2 there).  Lp and Mp are multiples of 32, Sp = S rounded up to 16; all arrays in `dtype`
+struct SampleEvalArgs {
+  const void* rows;    // [d][Lp + Mp]
+  const void* bias;    // [Lp + Mp]
+  const void* panel;   // [Lp + Mp][Sp]: {sqrt(2 variance / L) w | V}, zero on every padding row and column
+  const void* invl;    // [d]
+  const void* x;       // [d][ldx] feature-major inputs
+  const void* mux;     // nullable: [len] prior mean offsets of the window's points
+  void* out;
+  int64_t ldx, off, len, ldo;
+  int64_t Lp, Mp, S, Sp;
+  int64_t s0;          // first sample of the launch's column block (set by the launcher)
+  int family, d;
+  double variance, mean_const;
+};
+void launch_sample_eval(int dtype, hipStream_t s, const SampleEvalArgs& a);   // one launch per block of <= 64 samples
+// the M-sized stage, fp64 from the model-dtype inputs (dtype names the type of z, omega, tau, w, eps, m, Lq, muz and of rows / bias / panel)
+void launch_sample_widen_z(int dtype, hipStream_t s, const void* z, int layout, int d, int64_t M, int64_t Mp, const double* invl64, double* zs64);
+void launch_sample_rows(int dtype, hipStream_t s, const double* zs64, const void* omega, const void* tau, int d, int64_t L, int64_t Lp, int64_t Mp,
+                        void* rows, void* bias);
+// rhs[s][Mp] = u_s - mean(z) (zero padding), u[s][M] = u_s; tmp: S x Mp doubles of scratch; Lk: the fp64 factor of Kuu (ld Mp)
+void launch_sample_u(int dtype, hipStream_t s, const void* m, const void* Lq, const void* eps, const void* muz, const double* Lk, int64_t M,
+                     int64_t Mp, int64_t S, int centered, double mean_const, double* tmp, double* rhs, double* u);
+// rhs[s][i] -= (Phi(z) w_s)_i, amp = sqrt(2 variance / L)
+void launch_sample_phiz(int dtype, hipStream_t s, const double* zs64, const void* omega, const void* tau, const void* w, int d, int64_t M, int64_t L,
+                        int64_t S, int64_t Mp, double amp, double* rhs);
+void launch_sample_panel(int dtype, hipStream_t s, const void* w, const double* V, int64_t L, int64_t Lp, int64_t M, int64_t Mp, int64_t S, int64_t Sp,
+                         double amp, void* panel);
+
 
 }  // namespace svgp

@@ -716,6 +716,53 @@ int32_t svgp_lik_predictive(svgp_ctx* ctx, int32_t likelihood, double lik_param,
                             const double* var, const double* y, svgp_pred_summary* summary_out, double* lpd_out, double* ymean_out,
                             double* yvar_out);
 
+/* ---- pathwise posterior function samples (Wilson et al. 2020, Matheron's rule) ---------------------------------------------------
+ * S functions drawn from the fitted posterior, each one a FUNCTION that can be evaluated at any points, any number of times:
+ *   f_s(x) = mean(x) + sum_l phi_l(x) w_sl + sum_i k(x, z_i) V_is,        V_s = Kuu^-1 (u_s - mean(z) - Phi(z) w_s),   u_s ~ q(u)
+ *   phi_l(x) = sqrt(2 variance / L) cos(sum_k omega_lk invl_k x_k + tau_l)
+ * The library draws nothing: the caller supplies every random number (svgp_sample_basis), so a result is a deterministic function of its
+ * inputs.  omega are frequencies of the UNIT-lengthscale base kernel (SE: N(0, I); Matern-nu: g sqrt(2 nu / chi2_{2 nu}), g ~ N(0, I)); the
+ * library applies the model's inverse lengthscales (it scales the point, as it does for z).  tau ~ U[0, 2 pi), w and eps standard normal.
+ *   NonCentered: u_s - mean(z) = Lk (m + Lq eps_s);    Centered: u_s - mean(z) = (m - mean(z)) + Lq eps_s;    mean(z) = mean_const + muz.
+ * Accuracy: the Fourier part approximates the PRIOR, with a covariance error of O(variance / sqrt(L)); the update term k(., z) V is exact,
+ * so at the inducing points f_s(z) + jitter V_s = u_s holds to rounding whatever L is, and the samples' moments approach svgp_predict's as
+ * L grows.  L = 0 leaves the update term alone (with eps = 0 as well: the posterior mean).
+ *   svgp_sampler_create   the model's usual prep (SVGP_NOT_POSDEF as in svgp_elbo), then the M-sized stage in fp64 for BOTH dtypes: Kuu and
+ *                         its Cholesky factor are built again in fp64 from the widened z and parameters (an fp32 factor would lose up to
+ *                         1e-2 of the sample at cond(Kuu) ~ 5e3), then u, Phi(z) w and V.  It reads the model's device-resident q - what
+ *                         svgp_collapsed_q / svgp_natgrad_step left there counts, fetched or not - mean_const and muz
+ *                         (svgp_model_set_mean_z).  The sampler is a SNAPSHOT: it owns copies of the scaled z, the kernel parameters,
+ *                         mean_const, omega, tau, W and V (V rounded once to the model dtype); a later svgp_model_update or
+ *                         svgp_model_free neither changes nor invalidates it.  The basis arrays are host memory, read before the call returns.
+ *   svgp_sampler_eval     out[s * ldo + j] = f_s(x_{batch_off + j}), s < S, j < batch_len, in the model dtype; host memory (written before
+ *                         the call returns) or device memory of the context's GPU (out_on_device = 1).  One data pass of one kernel: the Kuf
+ *                         tiles and the cosine features are generated and multiplied by the resident (L + M) x S panel, nothing n x n and no
+ *                         tile is stored, cost linear in batch_len.  pm: the window's prior mean offsets as in svgp_marginals_with_mean, or
+ *                         NULL.  The data may have been uploaded without y.  ALWAYS LOCAL, like svgp_predictive.  The value of a point
+ *                         does not depend on the window or the call it is evaluated in, bitwise; repeated calls are bitwise equal
+ *                         (fixed-order sums, no atomics).
+ *   svgp_sampler_state    u and V in fp64 (V before its rounding), M x S column-major each: element (i, s) at [s * M + i]; either may be NULL.
+ * SVGP_INVALID_ARG, before anything is enqueued: n_samples < 1, n_features < 0, NULL eps, NULL omega / tau / w with n_features > 0; in
+ * svgp_sampler_eval a d or dtype mismatch between sampler and data, a window outside the data, ldo < batch_len, NULL out, or what
+ * svgp_marginals_with_mean rejects in pm.  Non-finite inputs give non-finite outputs with SVGP_OK.  No svgp_elbo result changes by a bit.
+ * fp32 models: the M-sized stage is fp64, the data pass fp32 (the phase accumulated by the fp32 MFMA; r^2 by differences for d <= 8,
+ * by the MFMA expansion beyond): within 5.5e-6 of the fp64 result relative to its largest entry on the test problems (cond(Kuu) <= 4.9e3,
+ * max|V| <= 50; profiles/sample/accuracy.md).  Found by symbol (no ABI version step). */
+typedef struct svgp_sample_basis {
+  int64_t n_features;  /* L >= 0; 0 = the update term alone */
+  int64_t n_samples;   /* S >= 1 */
+  const void* omega;   /* [L][d] frequencies of the UNIT-lengthscale base kernel, model dtype; the library applies inv_lengthscale */
+  const void* tau;     /* [L] phases in [0, 2 pi), model dtype */
+  const void* w;       /* [S][L] standard normal feature weights, model dtype */
+  const void* eps;     /* [S][M] standard normal draws for q(u), model dtype */
+} svgp_sample_basis;   /* 48 bytes */
+typedef struct svgp_sampler svgp_sampler;
+int32_t svgp_sampler_create(svgp_ctx* ctx, svgp_model* model, const svgp_sample_basis* basis, svgp_sampler** out);
+int32_t svgp_sampler_eval(svgp_ctx* ctx, const svgp_sampler* sampler, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                          const svgp_point_mean* pm, void* out, int64_t ldo, int32_t out_on_device);
+int32_t svgp_sampler_state(svgp_ctx* ctx, const svgp_sampler* sampler, double* u_out, double* V_out);
+int32_t svgp_sampler_free(svgp_ctx* ctx, svgp_sampler* sampler);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1042,4 +1042,58 @@ function lik_predictive(lik::Integer, param::Real, mu::Vector{Float64}, var::Vec
     return s, lpd, ymean, yvar
 end
 
+# ---------------------------------------------------------------------------------------------------------
+# Pathwise posterior function samples (svgp_sampler_*): `rand(f_post(x), S)` as S FUNCTIONS resident on the device, evaluated at any
+# points, any number of times, in one data pass linear in the number of points - f = mean + Φ w + k(·, z) V with V from u ~ q(u)
+# (Wilson et al. 2020).  The library draws nothing: Ω (unit-lengthscale frequencies, d × L), τ (L), W (L × S), E (M × S) are the
+# caller's (SE: Ω ~ N(0, I); Matern-ν: g sqrt(2ν / χ²_{2ν})).  The Fourier part approximates the prior with error O(σ² / sqrt(L)); the
+# update term is exact.
+# ---------------------------------------------------------------------------------------------------------
+struct SampleBasis                    # svgp_sample_basis (48 bytes)
+    n_features::Int64
+    n_samples::Int64
+    omega::Ptr{Cvoid}
+    tau::Ptr{Cvoid}
+    w::Ptr{Cvoid}
+    eps::Ptr{Cvoid}
+end
+
+mutable struct DeviceSampler
+    h::Ptr{Cvoid}; S::Int; M::Int
+end
+"A snapshot of S function samples of the model's posterior.  Ω is d × L, τ has L entries, W is L × S, E is M × S (Julia's column-major
+storage of these is the C-ABI's [L][d], [S][L] and [S][M]); all in the model's element type."
+function DeviceSampler(Mo::DeviceModel, Ω::Matrix{T}, τ::Vector{T}, W::Matrix{T}, E::Matrix{T}) where {T<:FT}
+    L, S, M = length(τ), size(E, 2), size(E, 1)
+    (size(Ω, 2) == L && size(W) == (L, S)) || throw(ArgumentError("Ω must be d × L, τ of length L, W L × S, E M × S"))
+    h = Ref{Ptr{Cvoid}}()
+    b = SampleBasis(L, S, L > 0 ? pointer(Ω) : C_NULL, L > 0 ? pointer(τ) : C_NULL, L > 0 ? pointer(W) : C_NULL, pointer(E))
+    GC.@preserve Ω τ W E check(ccall((:svgp_sampler_create, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{SampleBasis}, Ptr{Ptr{Cvoid}}),
+                                     ctx(), Mo.h, b, h))
+    Sm = DeviceSampler(h[], S, M)
+    finalizer(s -> (CTX[] == C_NULL || s.h == C_NULL) ||
+                   ccall((:svgp_sampler_free, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), CTX[], s.h), Sm)
+    return Sm
+end
+"The S functions at the points off+1 : off+len of resident data: a len × S matrix (column s = f_s), in the data's element type `T`.
+`mux`: the window's prior mean offsets or nothing."
+function sample_functions(Sm::DeviceSampler, D::DeviceData, ::Type{T}; off::Integer=0, len::Integer=D.n - off,
+                          mux::Union{Nothing,Vector}=nothing) where {T<:FT}
+    mux === nothing || length(mux) == len || throw(ArgumentError("one prior mean offset per point of the window"))
+    out = zeros(T, len, Sm.S)
+    pm = mux === nothing ? Ref(PointMean(C_NULL, 0, 0)) : Ref(PointMean(pointer(mux), 0, 0))
+    GC.@preserve mux pm check(ccall((:svgp_sampler_eval, lib), Int32,
+                                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{PointMean}, Ptr{Cvoid}, Int64, Int32),
+                                    ctx(), Sm.h, D.h, off, len,
+                                    mux === nothing ? Ptr{PointMean}(C_NULL) : Base.unsafe_convert(Ptr{PointMean}, pm),
+                                    out, len, Int32(0)))
+    return out
+end
+"(u, V) of the sampler in Float64, M × S each: the draws u_s ~ q(u) and V_s = Kuu \\ (u_s - mean(z) - Φ(z) w_s)."
+function sampler_state(Sm::DeviceSampler)
+    u, V = zeros(Float64, Sm.M, Sm.S), zeros(Float64, Sm.M, Sm.S)
+    check(ccall((:svgp_sampler_state, lib), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx(), Sm.h, u, V))
+    return u, V
+end
+
 end # module

@@ -20,6 +20,7 @@ ENV["SVGP_OFFLOAD_MIN_WORK"] = "0"
     @test sizeof(MI.NNDesc) == 56 && fieldoffset(MI.NNDesc, 5) == 16 && fieldoffset(MI.NNDesc, 9) == 48
     @test sizeof(MI.NNInfo) == 24 && fieldoffset(MI.NNInfo, 3) == 16
     @test sizeof(MI.CollapsedTerms) == 64 && fieldoffset(MI.CollapsedTerms, 6) == 40 && fieldoffset(MI.CollapsedTerms, 8) == 52
+    @test sizeof(MI.SampleBasis) == 48 && fieldoffset(MI.SampleBasis, 3) == 16 && fieldoffset(MI.SampleBasis, 6) == 40
     @test ccall((:svgp_version, MI.lib), Int32, ()) == 5
 end
 
