@@ -279,8 +279,9 @@ struct SampleEvalArgs {
 void launch_sample_eval(int dtype, hipStream_t s, const SampleEvalArgs& a);   // one launch per block of <= 64 samples
 // the M-sized stage, fp64 from the model-dtype inputs (dtype names the type of z, omega, tau, w, eps, m, Lq, muz and of rows / bias / panel)
 void launch_sample_widen_z(int dtype, hipStream_t s, const void* z, int layout, int d, int64_t M, int64_t Mp, const double* invl64, double* zs64);
-void launch_sample_rows(int dtype, hipStream_t s, const double* zs64, const void* omega, const void* tau, int d, int64_t L, int64_t Lp, int64_t Mp,
-                        void* rows, void* bias);
+// z, layout, M: the model's own inducing inputs, which the by-differences kernels (fp32, d <= 8) read unscaled
+void launch_sample_rows(int dtype, hipStream_t s, const double* zs64, const void* z, int layout, int64_t M, const void* omega, const void* tau, int d,
+                        int64_t L, int64_t Lp, int64_t Mp, void* rows, void* bias);
 // rhs[s][Mp] = u_s - mean(z) (zero padding), u[s][M] = u_s; tmp: S x Mp doubles of scratch; Lk: the fp64 factor of Kuu (ld Mp)
 void launch_sample_u(int dtype, hipStream_t s, const void* m, const void* Lq, const void* eps, const void* muz, const double* Lk, int64_t M,
                      int64_t Mp, int64_t S, int centered, double mean_const, double* tmp, double* rhs, double* u);

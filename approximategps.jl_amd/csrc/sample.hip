@@ -45,6 +45,9 @@ __global__ void __launch_bounds__(256) sample_eval_kernel(SampleEvalArgs a) {
   // eps32 (|xs|^2 + |zs|^2) absolutely, and a short lengthscale on a long domain (d = 1, M = 37 on [-3, 3]: |xs| <= 30) makes that 1e-4
   // of r^2, which Kuu^-1 (max|V| of tens) turns into more than the fp32 contract of the sample; 2 d instructions per entry cost less
   // than kappa at these d.  Wider inputs have scaled coordinates of order one and keep the MFMA form, as the Kuf kernels do.
+  // The difference is taken of the UNSCALED coordinates and scaled afterwards, (x_f - z_f) invl_f: x_f invl_f - z_f invl_f loses
+  // eps32 |xs| absolutely (|xs| reaches 300 at d = 1, M = 300: 1.3e-4 of the sample, tests/fuzz_pathwise.py REPLAYS), the unscaled
+  // difference only eps32 |x_f - z_f|.  The inducing rows of such a sampler hold z itself (sample_rows_kernel, raw).
   constexpr bool DIFF = sizeof(T) == 4 && DREG <= 8;
   using acc_t = typename Mfma16<T>::acc_t;
   __shared__ T zc[DREG * ZLD];   // [f][kk]  rows of the chunk (MFMA A operand of the generation)
@@ -64,14 +67,19 @@ __global__ void __launch_bounds__(256) sample_eval_kernel(SampleEvalArgs a) {
   const int64_t p0 = (int64_t(blockIdx.x) * NW + wave) * (PG * 16);
   // the wave's points: feature 4 q + kq of point c of group g, scaled (B operand of the generation), and |xs|^2 of point c
   T xb[PG][KS], xn[PG];
-  T xall[DIFF ? PG : 1][DIFF ? DREG : 1];   // DIFF: every feature of point c
+  T xall[DIFF ? PG : 1][DIFF ? DREG : 1];   // DIFF: every feature of point c, unscaled
+  T il[DIFF ? DREG : 1];
+  if constexpr (DIFF) {
+#pragma unroll
+    for (int f = 0; f < DREG; ++f) il[f] = (f < d) ? invl[f] : T(0);
+  }
 #pragma unroll
   for (int g = 0; g < PG; ++g) {
     int64_t pt = p0 + g * 16 + c;
     pt = pt < len ? pt : len - 1;
     if constexpr (DIFF) {
 #pragma unroll
-      for (int f = 0; f < DREG; ++f) xall[g][f] = (f < d) ? x[int64_t(f) * a.ldx + a.off + pt] * invl[f] : T(0);
+      for (int f = 0; f < DREG; ++f) xall[g][f] = (f < d) ? x[int64_t(f) * a.ldx + a.off + pt] : T(0);
     }
     T s2 = T(0);
 #pragma unroll
@@ -116,13 +124,13 @@ __global__ void __launch_bounds__(256) sample_eval_kernel(SampleEvalArgs a) {
 #pragma unroll
         for (int b = 0; b < NSB; ++b) pa[r][b] = pc[kk * PLD + b * 16 + c];
       }
-      T zr[DIFF ? 4 : 1][DIFF ? DREG : 1];   // DIFF: every feature of the lane's four rows (the chunk holds -2 zs: exact to undo)
+      T zr[DIFF ? 4 : 1][DIFF ? DREG : 1];   // DIFF: every feature of the lane's four rows (the chunk holds z itself)
       if constexpr (DIFF) {
         if (!feat) {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int f = 0; f < DREG; ++f) zr[r][f] = T(-0.5) * zc[f * ZLD + h * 16 + Mfma16<T>::row(lane, r)];
+            for (int f = 0; f < DREG; ++f) zr[r][f] = zc[f * ZLD + h * 16 + Mfma16<T>::row(lane, r)];
         }
       }
 #pragma unroll
@@ -136,7 +144,7 @@ __global__ void __launch_bounds__(256) sample_eval_kernel(SampleEvalArgs a) {
               T s2 = T(0);
 #pragma unroll
               for (int f = 0; f < DREG; ++f) {
-                const T df = xall[g][f] - zr[r][f];
+                const T df = (xall[g][f] - zr[r][f]) * il[f];
                 s2 = fma(df, df, s2);
               }
               t[r] = s2;
@@ -215,9 +223,11 @@ __global__ void sample_widen_z_kernel(const T* __restrict__ z, int layout, int d
 }
 
 // the generation operands of the data stage in the model's dtype: rows[f][k] = omega_k,f (k < L), 0 (L <= k < Lp), -2 zs_f,i (k = Lp + i);
-// bias[k] = tau_k, 0, |zs_i|^2 (from the ROUNDED zs, as the Kuf kernels form it)
+// bias[k] = tau_k, 0, |zs_i|^2 (from the ROUNDED zs, as the Kuf kernels form it).  raw (the by-differences kernels): the inducing rows
+// hold z_f,i itself (i < M; 0 on the padding, whose panel rows are zero) and their bias is not read
 template <typename T>
-__global__ void sample_rows_kernel(const double* __restrict__ zs64, const T* __restrict__ omega, const T* __restrict__ tau, int d, int64_t L,
+__global__ void sample_rows_kernel(const double* __restrict__ zs64, const T* __restrict__ z, int layout, int64_t M, int raw,
+                                   const T* __restrict__ omega, const T* __restrict__ tau, int d, int64_t L,
                                    int64_t Lp, int64_t Mp, T* __restrict__ rows, T* __restrict__ bias) {
   const int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   const int64_t Kp = Lp + Mp;
@@ -228,8 +238,9 @@ __global__ void sample_rows_kernel(const double* __restrict__ zs64, const T* __r
     if (k < Lp) {
       r = (k < L) ? omega[k * d + f] : T(0);
     } else {
-      const T v = T(zs64[int64_t(f) * Mp + (k - Lp)]);
-      r = T(-2) * v;
+      const int64_t i = k - Lp;
+      const T v = T(zs64[int64_t(f) * Mp + i]);
+      r = raw ? (i < M ? (layout == 1 ? z[int64_t(f) * M + i] : z[i * d + f]) : T(0)) : T(-2) * v;
       s = fma(v, v, s);
     }
     rows[int64_t(f) * Kp + k] = r;
@@ -327,11 +338,12 @@ void launch_sample_widen_z(int dtype, hipStream_t s, const void* z, int layout, 
   else hipLaunchKernelGGL(sample_widen_z_kernel<float>, grid, dim3(256), 0, s, (const float*)z, layout, d, M, Mp, invl64, zs64);
 }
 
-void launch_sample_rows(int dtype, hipStream_t s, const double* zs64, const void* omega, const void* tau, int d, int64_t L, int64_t Lp, int64_t Mp,
-                        void* rows, void* bias) {
+void launch_sample_rows(int dtype, hipStream_t s, const double* zs64, const void* z, int layout, int64_t M, const void* omega, const void* tau, int d,
+                        int64_t L, int64_t Lp, int64_t Mp, void* rows, void* bias) {
   const dim3 grid((unsigned)((Lp + Mp + 255) / 256));
-  if (dtype == 0) hipLaunchKernelGGL(sample_rows_kernel<double>, grid, dim3(256), 0, s, zs64, (const double*)omega, (const double*)tau, d, L, Lp, Mp, (double*)rows, (double*)bias);
-  else hipLaunchKernelGGL(sample_rows_kernel<float>, grid, dim3(256), 0, s, zs64, (const float*)omega, (const float*)tau, d, L, Lp, Mp, (float*)rows, (float*)bias);
+  const int raw = (dtype != 0 && d <= 8) ? 1 : 0;   // DIFF of the sample_eval_kernel this d is dispatched to (launch_eval_t)
+  if (dtype == 0) hipLaunchKernelGGL(sample_rows_kernel<double>, grid, dim3(256), 0, s, zs64, (const double*)z, layout, M, raw, (const double*)omega, (const double*)tau, d, L, Lp, Mp, (double*)rows, (double*)bias);
+  else hipLaunchKernelGGL(sample_rows_kernel<float>, grid, dim3(256), 0, s, zs64, (const float*)z, layout, M, raw, (const float*)omega, (const float*)tau, d, L, Lp, Mp, (float*)rows, (float*)bias);
 }
 
 void launch_sample_u(int dtype, hipStream_t s, const void* m, const void* Lq, const void* eps, const void* muz, const double* Lk, int64_t M,

@@ -103,7 +103,7 @@ extern "C" int32_t svgp_sampler_create(svgp_ctx* ctx, svgp_model* m, const svgp_
     launch_trsv2(SVGP_F64, s, K64.p, T64.p, Mp, 1, V + j * Mp);
   }
   KCHECK(ctx, "sampler (V)");
-  launch_sample_rows(dt, s, zs64.as<double>(), d_omega.p, d_tau.p, d, L, Lp, Mp, sp->rows.p, sp->bias.p);
+  launch_sample_rows(dt, s, zs64.as<double>(), m->z_raw.p, m->desc.layout_z, M, d_omega.p, d_tau.p, d, L, Lp, Mp, sp->rows.p, sp->bias.p);
   launch_sample_panel(dt, s, d_w.p, V, L, Lp, M, Mp, S, Sp, amp, sp->panel.p);
   KCHECK(ctx, "sampler (panel)");
   int chol = 0;
