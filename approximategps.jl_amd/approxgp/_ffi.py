@@ -194,6 +194,7 @@ SYMBOLS = {
     # pathwise posterior function samples
     "svgp_sampler_create": (C.c_int32, [_P, _P, C.POINTER(SampleBasis), C.POINTER(_P)]),
     "svgp_sampler_eval": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), _P, C.c_int64, C.c_int32]),
+    "svgp_sampler_eval_grad": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), _P, C.c_int64, _P, C.c_int64, C.c_int32]),
     "svgp_sampler_state": (C.c_int32, [_P, _P, _P, _P]),
     "svgp_sampler_free": (C.c_int32, [_P, _P]),
     # multi-GPU
@@ -895,6 +896,32 @@ class DeviceSampler:
         buf = np.zeros((self.n_samples, max(ldo, 1)), dtype=np_dtype(self.dtype))
         ctx.check(ctx.lib.svgp_sampler_eval(ctx.h, self.h, data.h, off, length, pmr, _ptr(buf), ldo, 0))
         return buf if ldo != length else buf[:, :length]
+
+    def eval_grad(self, data: DeviceData, off=0, length=None, prior_mean=None, values=True, out=None, grad_out=None, ldo=None, ldg=None):
+        """svgp_sampler_eval_grad at the points [off, off + length) of `data` -> (F (S, length) or None, G (S, d, length)) in the model
+        dtype: G[s, c, j] = d f_s / d x_c at point off + j, the gradient of f_s - mean (the caller adds the Jacobian of its own prior
+        mean offsets; they enter the values alone).  values=False: gradient only.  grad_out (and out, when values are wanted): device
+        pointers (int) or contiguous device tensors to write there instead, rows ldg (ldo) >= length apart; then nothing is returned."""
+        length = data.n - off if length is None else length
+        pm, _keep = point_mean(prior_mean, length, self.dtype) if prior_mean is not None else (None, None)
+        pmr = C.byref(pm) if pm is not None else None
+        ctx, S, d = self.ctx, self.n_samples, self.d
+        ldo = length if ldo is None else int(ldo)
+        ldg = length if ldg is None else int(ldg)
+        if grad_out is not None or out is not None:
+            if grad_out is None or (values and out is None):
+                raise ValueError("device output: grad_out is required, and out when values are wanted (both live in the same kind of memory)")
+            dev = lambda t: C.c_void_p(int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t))
+            ctx.check(ctx.lib.svgp_sampler_eval_grad(ctx.h, self.h, data.h, off, length, pmr, dev(out) if values else None, ldo,
+                                                     dev(grad_out), ldg, 1))
+            return None
+        dt = np_dtype(self.dtype)
+        F = np.zeros((S, max(ldo, 1)), dtype=dt) if values else None
+        G = np.zeros((S, d, max(ldg, 1)), dtype=dt)
+        ctx.check(ctx.lib.svgp_sampler_eval_grad(ctx.h, self.h, data.h, off, length, pmr, _ptr(F) if values else None, ldo, _ptr(G), ldg, 0))
+        if values and ldo == length:
+            F = F[:, :length]
+        return F, (G if ldg != length else G[:, :, :length])
 
     def state(self):
         """(u, V) in fp64, (M, S) each: the draws u_s ~ q(u) and V_s = Kuu^-1 (u_s - mean(z) - Phi(z) w_s)."""

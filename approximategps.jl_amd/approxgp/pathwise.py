@@ -67,6 +67,24 @@ class FunctionSamples:
         finally:
             data.free()
 
+    def _eval_grad(self, x, values):
+        post = self._post
+        data = _ffi.DeviceData(post.ctx, x, None, _ffi.np_dtype(self.sampler.dtype))
+        try:
+            F, G = self.sampler.eval_grad(data, prior_mean=post.prior.mean_offsets(x) if values else None, values=values)
+        finally:
+            data.free()
+        return (np.ascontiguousarray(F.T) if values else None), np.ascontiguousarray(G.transpose(2, 0, 1))
+
+    def grad(self, x):
+        """-> (n, S, d): [j, s, c] = d f_s / d x_c at x_j (svgp_sampler_eval_grad), the gradient of f_s minus the prior mean: a
+        non-constant mean function's own Jacobian is the caller's to add (the constant mean contributes nothing)."""
+        return self._eval_grad(x, False)[1]
+
+    def value_and_grad(self, x):
+        """-> (fs(x) (n, S), grad(x) (n, S, d)) from one call; the values are bitwise those of fs(x)."""
+        return self._eval_grad(x, True)
+
     def state(self):
         return self.sampler.state()
 

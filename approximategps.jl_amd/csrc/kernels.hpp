@@ -277,6 +277,15 @@ struct SampleEvalArgs {
   double variance, mean_const;
 };
 void launch_sample_eval(int dtype, hipStream_t s, const SampleEvalArgs& a);   // one launch per block of <= 64 samples
+// sample_grad.hip: grad[(s * d + c) * ldg + j] = d (f_s - mean) / d x_c at x_{off + j}, and, with v.out non-null, the values exactly as
+// launch_sample_eval writes them (the same chain: bitwise).  v.mux is read for the values alone
+struct SampleGradArgs {
+  SampleEvalArgs v;    // v.out nullable: gradient only
+  void* grad;
+  int64_t ldg;
+  int e0;              // first coordinate of the launch's coordinate block (set by the launcher)
+};
+void launch_sample_grad(int dtype, hipStream_t s, const SampleGradArgs& a);   // one launch per (16 samples, 8 coordinates)
 // the M-sized stage, fp64 from the model-dtype inputs (dtype names the type of z, omega, tau, w, eps, m, Lq, muz and of rows / bias / panel)
 void launch_sample_widen_z(int dtype, hipStream_t s, const void* z, int layout, int d, int64_t M, int64_t Mp, const double* invl64, double* zs64);
 // z, layout, M: the model's own inducing inputs, which the by-differences kernels (fp32, d <= 8) read unscaled

@@ -1,4 +1,4 @@
-// sample_api.hip — pathwise posterior function samples: svgp_sampler_create / _eval / _state / _free (sample.hip holds the kernels).
+// sample_api.hip — pathwise posterior function samples: svgp_sampler_create / _eval / _eval_grad / _state / _free (sample.hip, sample_grad.hip: the kernels).
 // Host orchestration only.
 //   f_s(.) = mean(.) + Phi(.) w_s + k(., z) V_s,     V_s = Kuu^-1 (u_s - mean(z) - Phi(z) w_s),     u_s ~ q(u) from the caller's eps_s
 // create: the model's usual prep (its status is svgp_elbo's), then the M-sized stage in fp64 for both dtypes - Kuu and its factor are
@@ -163,6 +163,74 @@ extern "C" int32_t svgp_sampler_eval(svgp_ctx* ctx, const svgp_sampler* sp, cons
   KCHECK(ctx, "sample_eval");
   if (!out_on_device)
     HIPC(ctx, hipMemcpy2DAsync(out, size_t(ldo) * es, ctx->smp_out.p, size_t(len) * es, size_t(len) * es, size_t(sp->S), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  float t = 0;
+  (void)elapsed_ms(ctx, &t, ctx->ev[0], ctx->ev[1]);
+  ctx->timing = svgp_timing{};
+  ctx->timing.ms_strip = t;
+  ctx->timing.ms_total = t;
+  return SVGP_OK;
+}
+
+// the values (optional) and the input gradient of the samples over a window: the launches of sample_grad.hip, one per 16 samples and
+// 8 coordinates; the values are written by the first coordinate block of each column block, through svgp_sampler_eval's own chain
+extern "C" int32_t svgp_sampler_eval_grad(svgp_ctx* ctx, const svgp_sampler* sp, const svgp_data* data, int64_t off, int64_t len,
+                                          const svgp_point_mean* pm, void* out, int64_t ldo, void* grad_out, int64_t ldg,
+                                          int32_t out_on_device) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!sp || !data) return fail(ctx, SVGP_INVALID_ARG, "null sampler or data");
+  if (!grad_out) return fail(ctx, SVGP_INVALID_ARG, "null gradient output");
+  if (sp->device != ctx->device) return fail(ctx, SVGP_INVALID_ARG, "the sampler lives on another device than the context");
+  if (data->dtype != sp->dtype) return fail(ctx, SVGP_INVALID_ARG, "data and sampler dtypes differ");
+  if (data->d != sp->d) return fail(ctx, SVGP_INVALID_ARG, "data and sampler input dimensions differ");
+  if (off < 0 || len < 1 || off + len > data->n) return fail(ctx, SVGP_INVALID_ARG, "window outside the data");
+  if (out && ldo < len) return fail(ctx, SVGP_INVALID_ARG, "ldo must be >= len");
+  if (ldg < len) return fail(ctx, SVGP_INVALID_ARG, "ldg must be >= len");
+  if (out_on_device != 0 && out_on_device != 1) return fail(ctx, SVGP_INVALID_ARG, "out_on_device must be 0 or 1");
+  int rc = check_point_mean(ctx, pm);
+  if (rc) return rc;
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t es = sp->es;
+  const size_t grows = size_t(sp->S) * size_t(sp->d);   // rows of the gradient: (s, c)
+  if (!out_on_device) {
+    if (out && (rc = ctx->smp_out.reserve(ctx, size_t(sp->S) * size_t(len) * es, "the samples")) != SVGP_OK) return rc;
+    if ((rc = ctx->smp_grad.reserve(ctx, grows * size_t(len) * es, "the samples' gradients")) != SVGP_OK) return rc;
+  }
+  const void* mux = nullptr;
+  if (out && pm && (rc = stage_point_mean(ctx, pm, size_t(len) * es, &mux)) != SVGP_OK) return rc;
+  SampleGradArgs g{};
+  SampleEvalArgs& a = g.v;
+  a.rows = sp->rows.p;
+  a.bias = sp->bias.p;
+  a.panel = sp->panel.p;
+  a.invl = sp->invl.p;
+  a.x = data->x.p;
+  a.mux = mux;
+  a.out = !out ? nullptr : out_on_device ? out : ctx->smp_out.p;
+  a.ldx = data->ldx;
+  a.off = off;
+  a.len = len;
+  a.ldo = out_on_device ? ldo : len;
+  a.Lp = sp->Lp;
+  a.Mp = sp->Mp;
+  a.S = sp->S;
+  a.Sp = sp->Sp;
+  a.family = sp->family;
+  a.d = sp->d;
+  a.variance = sp->variance;
+  a.mean_const = sp->mean_const;
+  g.grad = out_on_device ? grad_out : ctx->smp_grad.p;
+  g.ldg = out_on_device ? ldg : len;
+  TREC(ctx, ctx->ev[0], s);
+  launch_sample_grad(sp->dtype, s, g);
+  TREC(ctx, ctx->ev[1], s);
+  KCHECK(ctx, "sample_grad");
+  if (!out_on_device) {
+    if (out)
+      HIPC(ctx, hipMemcpy2DAsync(out, size_t(ldo) * es, ctx->smp_out.p, size_t(len) * es, size_t(len) * es, size_t(sp->S), hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipMemcpy2DAsync(grad_out, size_t(ldg) * es, ctx->smp_grad.p, size_t(len) * es, size_t(len) * es, grows, hipMemcpyDeviceToHost, s));
+  }
   HIPC(ctx, hipStreamSynchronize(s));
   float t = 0;
   (void)elapsed_ms(ctx, &t, ctx->ev[0], ctx->ev[1]);

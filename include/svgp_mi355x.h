@@ -763,6 +763,25 @@ int32_t svgp_sampler_eval(svgp_ctx* ctx, const svgp_sampler* sampler, const svgp
 int32_t svgp_sampler_state(svgp_ctx* ctx, const svgp_sampler* sampler, double* u_out, double* V_out);
 int32_t svgp_sampler_free(svgp_ctx* ctx, svgp_sampler* sampler);
 
+/* ---- input gradients of the function samples --------------------------------------------------------------------------------------
+ * With xs = invl o x, phase_l = omega_l . xs + tau_l, amp = sqrt(2 variance / L), r_i^2 = |xs - zs_i|^2 and g = variance dkappa / d(r^2):
+ *   d f_s / d x_c (x) = invl_c [ - sum_l sin(phase_l) omega_lc amp w_sl + 2 sum_i g(r_i^2) (xs_c - zs_ic) V_is ]
+ *   g:  SE -variance e^{-r^2 / 2} / 2;   Matern-3/2 -(3/2) variance e^{-sqrt(3) r};   Matern-5/2 -(5/6) variance (1 + sqrt(5) r) e^{-sqrt(5) r}
+ * No division by r: every family is finite at x = z_i, where that term vanishes.  What a maximiser of a sample needs (Thompson sampling);
+ * with n_features = 0 and eps = 0 it is the input gradient of the posterior mean.
+ *   grad_out[(s * d + c) * ldg + j] = d f_s / d x_c at point batch_off + j, s < S, c < d, j < batch_len, ldg >= batch_len.
+ *   out: the values exactly as svgp_sampler_eval writes them (ldo >= batch_len), or NULL: gradient only.
+ * The prior mean offsets pm are evaluated by the caller, so their Jacobian is the caller's too: grad_out is the gradient of f_s - mean,
+ * to which the caller adds d mean / d x (nothing for the constant mean); pm enters the values alone and is ignored with out = NULL.
+ * Both outputs are in the model dtype and in the same kind of memory (out_on_device).  ALWAYS LOCAL.  Works on any svgp_sampler.
+ * (a) the values are bitwise svgp_sampler_eval's on the same window; (b) a point's gradient does not depend on the window, the call or
+ * whether out was asked for, repeated calls and host / device output are bitwise equal (fixed-order sums, no atomics); (c) no svgp_elbo,
+ * svgp_sampler_eval or svgp_sampler_state result changes by a bit.  One data pass per 16 samples and 8 coordinates.
+ * SVGP_INVALID_ARG, before anything is enqueued: everything svgp_sampler_eval rejects (a NULL out excepted, and ldo then unread), NULL
+ * grad_out, ldg < batch_len.  Non-finite inputs give non-finite outputs with SVGP_OK.  Found by symbol (no ABI version step). */
+int32_t svgp_sampler_eval_grad(svgp_ctx* ctx, const svgp_sampler* sampler, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                               const svgp_point_mean* pm, void* out, int64_t ldo, void* grad_out, int64_t ldg, int32_t out_on_device);
+
 #ifdef __cplusplus
 }
 #endif

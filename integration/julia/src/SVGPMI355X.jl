@@ -1089,6 +1089,22 @@ function sample_functions(Sm::DeviceSampler, D::DeviceData, ::Type{T}; off::Inte
                                     out, len, Int32(0)))
     return out
 end
+"The S functions and their input gradients at the points off+1 : off+len of resident data: `(F, G)` with F len × S (as
+`sample_functions`, bitwise; `nothing` with `values=false`) and G len × d × S, `G[j, c, s] = ∂f_s/∂x_c` at point j.  G is the gradient of
+f_s minus the prior mean: the Jacobian of the caller's own offsets `mux` is the caller's to add."
+function sample_gradients(Sm::DeviceSampler, D::DeviceData, ::Type{T}, d::Integer; off::Integer=0, len::Integer=D.n - off,
+                          mux::Union{Nothing,Vector}=nothing, values::Bool=true) where {T<:FT}
+    mux === nothing || length(mux) == len || throw(ArgumentError("one prior mean offset per point of the window"))
+    F = zeros(T, len, values ? Sm.S : 0)
+    G = zeros(T, len, d, Sm.S)       # d: the input dimension of the data and the sampler
+    pm = mux === nothing ? Ref(PointMean(C_NULL, 0, 0)) : Ref(PointMean(pointer(mux), 0, 0))
+    GC.@preserve mux pm F G check(ccall((:svgp_sampler_eval_grad, lib), Int32,
+                                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{PointMean}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32),
+                                        ctx(), Sm.h, D.h, off, len,
+                                        mux === nothing ? Ptr{PointMean}(C_NULL) : Base.unsafe_convert(Ptr{PointMean}, pm),
+                                        values ? Ptr{Cvoid}(pointer(F)) : C_NULL, len, G, len, Int32(0)))
+    return (values ? F : nothing), G
+end
 "(u, V) of the sampler in Float64, M × S each: the draws u_s ~ q(u) and V_s = Kuu \\ (u_s - mean(z) - Φ(z) w_s)."
 function sampler_state(Sm::DeviceSampler)
     u, V = zeros(Float64, Sm.M, Sm.S), zeros(Float64, Sm.M, Sm.S)
