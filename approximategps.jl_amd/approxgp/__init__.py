@@ -10,7 +10,8 @@ from ._ffi import (Context, DeclinedError, DeviceData, DeviceModel, DomainError,
 # the predictive distribution of the observation: DeviceModel.predictive for resident data, lik_predictive for latent marginals a caller
 # holds; predict_y / log_predictive_density on the three posterior types
 from ._ffi import PredSummary, lik_predictive
-from .gp import (GP, BernoulliLikelihood, CustomMean, DefaultExpectationMethod, FiniteGP, GaussHermiteExpectation,
+from .gp import (GP, BernoulliLikelihood, CustomMean, DefaultExpectationMethod, Diagonal, FiniteGP,
+                 GaussHermiteExpectation,
                  GaussianLikelihood, LatentFiniteGP, LatentGP, MvNormal, PoissonLikelihood, ExponentialLikelihood,
                  GammaLikelihood, CallerLikelihood, LogisticLink, NormalCDFLink, ProbitLink)
 from .kernels import (ARDTransform, Matern32Kernel, Matern52Kernel, ScaledKernel, ScaleTransform, SEKernel,

@@ -57,6 +57,16 @@ class PointMeanGrad(C.Structure):
     _fields_ = [("mu_bar", C.c_void_p), ("on_device", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PointNoise(C.Structure):
+    """svgp_point_noise: the batch's per-point noise variances s, added to lik_sigma2 (data dtype; on_device 0: host, 1: device)."""
+    _fields_ = [("s", C.c_void_p), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PointNoiseGrad(C.Structure):
+    """svgp_point_noise_grad: where d bound / d sigma_j^2 goes (data dtype; on_device 0: host, 1: device)."""
+    _fields_ = [("s_bar", C.c_void_p), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_prep", C.c_double), ("ms_strip", C.c_double), ("ms_expect", C.c_double),
                 ("ms_kuf", C.c_double),
@@ -182,6 +192,13 @@ SYMBOLS = {
     "svgp_collapsed_q": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, C.POINTER(C.c_double)]),
     "svgp_collapsed_grad": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.POINTER(CollapsedTerms),
                                         C.POINTER(Grads), C.POINTER(InputGrad)]),
+    "svgp_collapsed_bound_with_noise": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), C.POINTER(PointNoise),
+                                                    C.POINTER(C.c_double), C.POINTER(CollapsedTerms)]),
+    "svgp_collapsed_q_with_noise": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), C.POINTER(PointNoise), _P, _P,
+                                                C.POINTER(C.c_double)]),
+    "svgp_collapsed_grad_with_noise": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), C.POINTER(PointNoise),
+                                                   C.POINTER(C.c_double), C.POINTER(CollapsedTerms), C.POINTER(Grads),
+                                                   C.POINTER(InputGrad), C.POINTER(PointMeanGrad), C.POINTER(PointNoiseGrad)]),
     # natural-gradient steps on q
     "svgp_natgrad_step": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(Terms),
                                       C.POINTER(Grads), _P, _P]),
@@ -317,6 +334,19 @@ def point_mean(mu, n, dtype):
     if buf.shape != (n,):
         raise ValueError("prior_mean: one entry per point of the batch")
     return PointMean(_ptr(buf), 0, 0), buf
+
+
+def point_noise(s, n, dtype):
+    """-> (PointNoise, what keeps its memory alive) for per-point noise variances of n points (added to the model's lik_sigma2): a
+    host array (converted to the data dtype) or a contiguous device tensor of the data dtype (read on the context's stream)."""
+    if _is_device_tensor(s):
+        if s.numel() != n or not s.is_contiguous() or s.element_size() != np.dtype(np_dtype(dtype)).itemsize or not s.is_floating_point():
+            raise ValueError("noise: a contiguous device tensor of the data dtype with one entry per point of the batch")
+        return PointNoise(C.c_void_p(s.data_ptr()), 1, 0), s
+    buf = np.ascontiguousarray(np.asarray(s, dtype=np_dtype(dtype)).reshape(-1))
+    if buf.shape != (n,):
+        raise ValueError("noise: one entry per point of the batch")
+    return PointNoise(_ptr(buf), 0, 0), buf
 
 
 PRED_WANTS = ("summary", "lpd", "ymean", "yvar")
@@ -709,28 +739,59 @@ class DeviceModel:
             raise PosDefException(terms.chol_info if terms.chol_info else terms.chol_info_b, msg)
         self.ctx.check(rc)
 
-    def collapsed_bound(self, data: DeviceData, off=0, length=None):
-        """-> (bound, CollapsedTerms): one data pass; the model's q is neither read nor changed."""
+    def _collapsed_ext(self, length, prior_mean, noise, mean_z):
+        """-> (pm, pn, keep-alive) of a svgp_collapsed_*_with_noise call, or None for the plain call (no offsets, no noise vector and
+        mean_z false: the two are bitwise equal there, but only the _with_noise calls accept a model that carries muz)."""
+        if prior_mean is None and noise is None and not mean_z:
+            return None
+        pm, k1 = point_mean(prior_mean, length, self.dtype) if prior_mean is not None else (None, None)
+        pn, k2 = point_noise(noise, length, self.dtype) if noise is not None else (None, None)
+        return pm, pn, (k1, k2)
+
+    def collapsed_bound(self, data: DeviceData, off=0, length=None, prior_mean=None, noise=None, mean_z=False):
+        """-> (bound, CollapsedTerms): one data pass; the model's q is neither read nor changed.
+        prior_mean = the batch's prior mean offsets mux, noise = its per-point noise variances s (sigma_j^2 = lik_sigma2 + s_j); each
+        a host array or a device tensor of the data dtype (svgp_collapsed_bound_with_noise).  mean_z = True: the model carries muz
+        (set_mean_z), which only the _with_noise calls accept; it enters the Centered m of collapsed_q, never the bound."""
         length = data.n - off if length is None else length
         out, terms = C.c_double(), CollapsedTerms()
-        self._collapsed_check(self.ctx.lib.svgp_collapsed_bound(self.ctx.h, self.h, data.h, off, length, C.byref(out), C.byref(terms)), terms)
+        ext = self._collapsed_ext(length, prior_mean, noise, mean_z)
+        if ext is None:
+            rc = self.ctx.lib.svgp_collapsed_bound(self.ctx.h, self.h, data.h, off, length, C.byref(out), C.byref(terms))
+        else:
+            pm, pn, _keep = ext
+            rc = self.ctx.lib.svgp_collapsed_bound_with_noise(self.ctx.h, self.h, data.h, off, length, C.byref(pm) if pm is not None else None,
+                                                              C.byref(pn) if pn is not None else None, C.byref(out), C.byref(terms))
+        self._collapsed_check(rc, terms)
         return out.value, terms
 
-    def collapsed_q(self, data: DeviceData, off=0, length=None, fetch=True):
+    def collapsed_q(self, data: DeviceData, off=0, length=None, fetch=True, prior_mean=None, noise=None, mean_z=False):
         """Writes the optimal q into the model's device-resident m / Lq (the model's own parametrisation) -> (bound, m, Lq); m and
-        Lq are host copies in the model's dtype (Lq lower triangular), None with fetch=False."""
+        Lq are host copies in the model's dtype (Lq lower triangular), None with fetch=False.  prior_mean, noise: as in
+        collapsed_bound (svgp_collapsed_q_with_noise)."""
         length = data.n - off if length is None else length
         dt = np_dtype(self.dtype)
         mb = np.zeros(self.M, dtype=dt) if fetch else None
         Lb = np.zeros((self.M, self.M), dtype=dt, order="F") if fetch else None
         out = C.c_double()
-        self.ctx.check(self.ctx.lib.svgp_collapsed_q(self.ctx.h, self.h, data.h, off, length, _ptr(mb), _ptr(Lb), C.byref(out)))
+        ext = self._collapsed_ext(length, prior_mean, noise, mean_z)
+        if ext is None:
+            self.ctx.check(self.ctx.lib.svgp_collapsed_q(self.ctx.h, self.h, data.h, off, length, _ptr(mb), _ptr(Lb), C.byref(out)))
+        else:
+            pm, pn, _keep = ext
+            self.ctx.check(self.ctx.lib.svgp_collapsed_q_with_noise(self.ctx.h, self.h, data.h, off, length,
+                                                                    C.byref(pm) if pm is not None else None,
+                                                                    C.byref(pn) if pn is not None else None, _ptr(mb), _ptr(Lb), C.byref(out)))
         return out.value, mb, Lb
 
-    def collapsed_grad(self, data: DeviceData, off=0, length=None, z_shape=None, inputs=None):
-        """-> (bound, CollapsedTerms, dict(variance, inv_lengthscale, z, lik_sigma2, mean_const[, x])): the bound's total derivatives
-        (svgp_collapsed_q, then the value-and-gradient at that q).  inputs = True: also d bound / d x as dict["x"] (host, the data's
-        layout); inputs = (device_ptr, ld): written to device memory as in elbo_grad."""
+    def collapsed_grad(self, data: DeviceData, off=0, length=None, z_shape=None, inputs=None, prior_mean=None, noise=None,
+                       want_mean_grad=None, want_noise_grad=None, mean_z=False):
+        """-> (bound, CollapsedTerms, dict(variance, inv_lengthscale, z, lik_sigma2, mean_const[, x][, mean_x][, noise])): the bound's
+        total derivatives (svgp_collapsed_q, then the value-and-gradient at that q).  inputs = True: also d bound / d x as dict["x"]
+        (host, the data's layout); inputs = (device_ptr, ld): written to device memory as in elbo_grad.
+        prior_mean, noise: as in collapsed_bound.  want_mean_grad / want_noise_grad = True: d bound / d mux as dict["mean_x"] and
+        d bound / d sigma_j^2 as dict["noise"] (host, data dtype); a device tensor or pointer: written there on the context's stream
+        (svgp_collapsed_grad_with_noise)."""
         length = data.n - off if length is None else length
         dt = np_dtype(self.dtype)
         gx, xb = None, None
@@ -752,12 +813,39 @@ class DeviceModel:
         zb = np.zeros(zshape, dtype=dt, order="F")
         g = Grads(0.0, 0.0, 0.0, il.ctypes.data_as(C.POINTER(C.c_double)), _ptr(zb), None, None)
         out, terms = C.c_double(), CollapsedTerms()
-        rc = self.ctx.lib.svgp_collapsed_grad(self.ctx.h, self.h, data.h, off, length, C.byref(out), C.byref(terms), C.byref(g),
-                                              C.byref(gx) if gx is not None else None)
+        wants = [w is not None and w is not False for w in (want_mean_grad, want_noise_grad)]
+        ext = self._collapsed_ext(length, prior_mean, noise, mean_z)
+        mxb = sxb = None
+        if ext is None and not any(wants):
+            rc = self.ctx.lib.svgp_collapsed_grad(self.ctx.h, self.h, data.h, off, length, C.byref(out), C.byref(terms), C.byref(g),
+                                                  C.byref(gx) if gx is not None else None)
+        else:
+            pm, pn, _keep = ext if ext is not None else (None, None, None)
+            gpm = gpn = None
+            if want_mean_grad is True:
+                mxb = np.zeros(length, dtype=dt)
+                gpm = PointMeanGrad(_ptr(mxb), 0, 0)
+            elif wants[0]:
+                gpm = PointMeanGrad(C.c_void_p(point_mean_grad_ptr(want_mean_grad, length, self.dtype)), 1, 0)
+            if want_noise_grad is True:
+                sxb = np.zeros(length, dtype=dt)
+                gpn = PointNoiseGrad(_ptr(sxb), 0, 0)
+            elif wants[1]:
+                gpn = PointNoiseGrad(C.c_void_p(point_mean_grad_ptr(want_noise_grad, length, self.dtype)), 1, 0)
+            rc = self.ctx.lib.svgp_collapsed_grad_with_noise(self.ctx.h, self.h, data.h, off, length,
+                                                             C.byref(pm) if pm is not None else None,
+                                                             C.byref(pn) if pn is not None else None, C.byref(out), C.byref(terms),
+                                                             C.byref(g), C.byref(gx) if gx is not None else None,
+                                                             C.byref(gpm) if gpm is not None else None,
+                                                             C.byref(gpn) if gpn is not None else None)
         self._collapsed_check(rc, terms)
         res = dict(variance=g.variance, inv_lengthscale=il, z=zb, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const)
         if xb is not None:
             res["x"] = xb
+        if mxb is not None:
+            res["mean_x"] = mxb
+        if sxb is not None:
+            res["noise"] = sxb
         return out.value, terms, res
 
     # ---- natural-gradient steps on q (svgp_natgrad_step / _ext) ----

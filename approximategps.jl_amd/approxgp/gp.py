@@ -23,6 +23,14 @@ class CustomMean:
     f: object
 
 
+@dataclass(frozen=True, eq=False)
+class Diagonal:
+    """LinearAlgebra.Diagonal(v) as a noise covariance: f(x, Diagonal(v)) has the per-point noise variances v (one per point, all
+    > 0).  AbstractGPs' VFE takes it (approxgp.vfe: svgp_collapsed_*_with_noise); the SVGP elbo needs a homoscedastic Σy (SVA:319-327).
+    A plain vector Σy keeps being refused by both: the non-isotropic noise is asked for by type, as in the reference."""
+    diag: object
+
+
 @dataclass(eq=False)
 class GP:
     """GP(kernel) with ZeroMean, GP(c, kernel) with ConstMean(c), or GP(CustomMean(fn), kernel).  Identity (`is`) matters:
@@ -58,7 +66,7 @@ class GP:
 
 @dataclass(eq=False)
 class FiniteGP:
-    """f(x, Σy).  Σy: a Real is Diagonal(Fill(σ², n)) (homoscedastic); a vector is heteroscedastic."""
+    """f(x, Σy).  Σy: a Real is Diagonal(Fill(σ², n)) (homoscedastic); a vector or a Diagonal is heteroscedastic."""
 
     f: GP
     x: np.ndarray
@@ -69,7 +77,7 @@ class FiniteGP:
         return _as_dn(self.x).shape[1]
 
     def is_isotropic(self):
-        return np.ndim(self.Sigma_y) == 0
+        return not isinstance(self.Sigma_y, Diagonal) and np.ndim(self.Sigma_y) == 0
 
 
 @dataclass(frozen=True)

@@ -242,7 +242,7 @@ int grad_plan(GradRun& g) {
   // inverse), so A is read by the SYRK only (round 3, f64: 0.32 -> 0.2 ms per 65 536-point chunk at M = 1024).
   // the SYRK's weights 2 g_v are uniform over the points for the built-in Gaussian likelihood (grad.hip: UW) unless a variance was
   // negative and clamped (then that point's g_v differs... it does not: dE/dv = -1 / (2 sigma^2) whatever v) - so: Gaussian, built in
-  g.uniform_w = m->desc.likelihood == SVGP_LIK_GAUSSIAN && !gc.ext_gmu && m->gh_n == 0 && ctx->kn.syrk_uniform;   // (knob: experiments build)
+  g.uniform_w = m->desc.likelihood == SVGP_LIK_GAUSSIAN && !gc.ext_gmu && m->gh_n == 0 && ctx->kn.syrk_uniform && !gc.noise;   // (knob: experiments build; per-point noise: g_v_j = -scale / (2 sigma_j^2))
   // Round 6: strips beside the factorisation + uniform weights = the SYRK needs nothing but A, which phase 1 has
   // written by the time the chain ends - so it goes on the second stream right behind the last phase-1 segment, BESIDE the M-sized prep
   // of phase 3 on the main stream (Lk^-1 by recursive doubling, R, alpha: ~230 us of small launches at M = 1024), instead of behind
@@ -379,9 +379,17 @@ int grad_chunk(GradRun& g, int64_t c0) {
     launch_strip_grad(dt, s, a, nt, grid, nstrips);
     KCHECK(ctx, "strip (value and gradient)");
   }
-  launch_point_grads(dt, s, lpc, a.mom_mu, a.mom_var, gc.ext_gmu ? nullptr : data->y.p, off + c0, clen, scale, n_global_dev, gc.num_data, w->gmu.p, w->gv,
-                     w->partial5.as<double>(), gop.on ? nullptr : a.counter, ncp,
-                     gc.mux_bar ? static_cast<char*>(gc.mux_bar) + size_t(c0) * es : nullptr);
+  if (gc.noise || gc.noise_bar) {   // svgp_collapsed_grad_with_noise (Gaussian, closed form, never collective): point j with sigma_j^2
+    launch_point_grads_noise(dt, s, lpc.sigma2, lpc.clamp_neg_var, a.mom_mu, a.mom_var, data->y.p, off + c0, clen, scale,
+                             gc.noise ? static_cast<const char*>(gc.noise) + size_t(c0) * es : nullptr, w->gmu.p, w->gv,
+                             w->partial5.as<double>(), gop.on ? nullptr : a.counter, ncp,
+                             gc.mux_bar ? static_cast<char*>(gc.mux_bar) + size_t(c0) * es : nullptr,
+                             gc.noise_bar ? static_cast<char*>(gc.noise_bar) + size_t(c0) * es : nullptr);
+  } else {
+    launch_point_grads(dt, s, lpc, a.mom_mu, a.mom_var, gc.ext_gmu ? nullptr : data->y.p, off + c0, clen, scale, n_global_dev, gc.num_data, w->gmu.p, w->gv,
+                       w->partial5.as<double>(), gop.on ? nullptr : a.counter, ncp,
+                       gc.mux_bar ? static_cast<char*>(gc.mux_bar) + size_t(c0) * es : nullptr);
+  }
   KCHECK(ctx, "point gradients");
   const int n5 = point_grad_blocks(clen);   // rows of partial5: one per 256-point block
   int64_t ksl = ((clen + w->ns_uf - 1) / w->ns_uf + 127) / 128 * 128;
@@ -758,6 +766,7 @@ int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t 
   if (ng) gc.ng_W = ng->c->Wm.as<double>();
   gc.ext_gmu = rq.ext_gmu; gc.ext_gv = rq.ext_gv; gc.ext_sum_e = rq.ext_sum_e;
   gc.gx = gx;
+  gc.noise = rq.noise; gc.noise_bar = rq.noise_bar;
   gc.collective = rq.collective && ctx && ctx->comm;
   gc.scale = rq.scale;
   gc.klw = gc.collective ? 1.0 / double(ctx->world) : rq.klw;
@@ -897,7 +906,7 @@ extern "C" int32_t svgp_elbo_grad_ext_inputs(svgp_ctx* ctx, svgp_model* m, const
   return elbo_grad_impl(ctx, m, data, off, len, rq, elbo_out, terms_out, g);
 }
 
-namespace {
+namespace svgp {
 // argument checks of the prior mean offsets' gradient output (before anything is enqueued)
 int check_point_mean_grad(svgp_ctx* ctx, const svgp_data* data, int64_t len, const svgp_input_grad* gx, const svgp_point_mean_grad* gpm) {
   if (!gpm) return SVGP_OK;
@@ -919,7 +928,7 @@ int check_point_mean_grad(svgp_ctx* ctx, const svgp_data* data, int64_t len, con
   }
   return SVGP_OK;
 }
-}  // namespace
+}  // namespace svgp
 
 // svgp_elbo_grad / _ext / _inputs / _ext_inputs with the batch's prior mean offsets (include/svgp_mi355x.h): the same launches; the
 // offsets enter the strips' moment epilogue, and their gradient is a second store of point_grad_kernel's g_mu

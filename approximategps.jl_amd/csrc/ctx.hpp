@@ -143,6 +143,11 @@ struct svgp_ctx {
   svgp::DevBuf ext_g;   // [2][n] point gradients of a host-evaluated likelihood (double)
   svgp::DevBuf pm_x;    // host-memory prior mean offsets of a call, copied in (svgp_*_with_mean)
   svgp::DevBuf pm_g;    // their gradient for a host destination, copied out (svgp_elbo_grad_with_mean)
+  // svgp_collapsed_*_with_noise (allocated by their first call)
+  svgp::DevBuf pn_x;    // host-memory per-point noise variances of a call, copied in (pm_x holds mux during the same call)
+  svgp::DevBuf pn_g;    // their gradient for a host destination, copied out (pm_g holds mux_bar during the same call)
+  svgp::DevBuf pn_w;    // w_j = 1 / sigma_j^2 of the window, model dtype, zero-padded to 128 points: the weighted SYRK's operand
+  svgp::DevBuf pn_wd;   // ... in fp64: the reductions' (then one int: the count of sigma_j^2 <= 0)
   // svgp_predictive / svgp_lik_predictive (allocated by their first call)
   svgp::DevBuf pred_part;   // [1024][3] per-block sums of predictive_kernel, then [4] their sums (double)
   svgp::DevBuf pred_out;    // [3][n] per-point lpd | ymean | yvar (double)
@@ -194,7 +199,8 @@ struct CollapsedWs {
   svgp::DevBuf Bm, TB, LinvRM, LinvCM, Ytmp, Sinv;   // B -> LB, its T panels, LB^-1 in both storage orders, scratch, B^-1 -> Lq_w (Mp x Mp doubles each)
   svgp::DevBuf cvec, mw;       // c (Mp), m_w (Mp)
   svgp::DevBuf bpart, spart;   // the split partials of b = A r and of {r'r, sum A^2}
-  svgp::DevBuf scal;           // [8] {rr, t, sum log diag LB, c'c, info_b, info_s, 0, 0}
+  svgp::DevBuf spart2;         // ... of {sum log sigma_j^2, sum w_j} (svgp_collapsed_*_with_noise)
+  svgp::DevBuf scal;           // [8] {rr, t, sum log diag LB, c'c, info_b, info_s, 0, 0} (with per-point noise: [6] sum log sigma_j^2, [7] sum w_j)
   svgp::DevBuf info_b, info_s; // cholesky info + hand-over counters of the two factorisations (int)
   svgp::DevBuf gemv_part;
   // svgp_natgrad_step* only (allocated by its first call): W = A diag(-2 scale g_v) A' and the whitened factor B of q in fp64

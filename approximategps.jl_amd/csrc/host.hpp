@@ -129,6 +129,11 @@ struct GradCall {
   // requested - point_grad_kernel writes its g_mu a second time there)
   const void* mux = nullptr;
   void* mux_bar = nullptr;
+  // svgp_collapsed_grad_with_noise: the batch's per-point noise variances s (device, data dtype; the Gaussian likelihood's variance of
+  // point j is lik_sigma2 + s[j]) and where d elbo / d sigma_j^2 goes (device; NULL: not requested).  With s the SYRK's weights 2 g_v
+  // differ from point to point: the weighted route
+  const void* noise = nullptr;
+  void* noise_bar = nullptr;
   // svgp_natgrad_step: where W = A diag(-2 scale g_v) A' goes in fp64, gathered from the SYRK's slices before the tail reuses their
   // buffer as split-K scratch (NULL: not requested, nothing more is launched)
   double* ng_W = nullptr;
@@ -151,11 +156,14 @@ struct GradRequest {
   const svgp_input_grad* gx = nullptr;
   const svgp_point_mean* pm = nullptr;
   const svgp_point_mean_grad* gpm = nullptr;
+  const void* noise = nullptr;   // GradCall's: device pointers, staged by the caller (svgp_collapsed_grad_with_noise)
+  void* noise_bar = nullptr;
   NatgradCall* ng = nullptr;   // (never collective): the natural-gradient tail behind the same launches
 };
 int elbo_grad_impl(svgp_ctx* ctx, svgp_model* m, const svgp_data* data, int64_t off, int64_t len, const GradRequest& rq,
                    double* elbo_out, svgp_terms* terms_out, svgp_grads* g);
 int check_input_grad(svgp_ctx* ctx, const svgp_data* data, int64_t len, const svgp_input_grad* gx);
+int check_point_mean_grad(svgp_ctx* ctx, const svgp_data* data, int64_t len, const svgp_input_grad* gx, const svgp_point_mean_grad* gpm);
 
 // ---- api_qopt.hip -----------------------------------------------------------------------------------------------------------
 int natgrad_enqueue(svgp_ctx* ctx, svgp_model* m, GradCall& gc, NatgradCall& ng);

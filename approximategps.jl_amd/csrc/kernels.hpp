@@ -239,7 +239,24 @@ void launch_collapsed_form_b(int dtype, hipStream_t s, const void* G, int nslice
 void launch_collapsed_scal(hipStream_t s, const double* LB, const double* c, int64_t Mp, const int* info_b, const int* info_s, double* scal);
 // the optimal q in the model's parametrisation into m_out [M] / Lq_out (M x M column-major, upper zeroed), model dtype
 void launch_collapsed_write_q(int dtype, hipStream_t s, const double* Lqw, const double* mw, const void* Lk, int64_t M, int64_t Mp, int centered,
-                              double mean_const, const double* scal, const int* info_b, const int* info_s, void* m_out, void* Lq_out);
+                              double mean_const, const double* scal, const int* info_b, const int* info_s, const void* muz, void* m_out,
+                              void* Lq_out);   // muz (nullable, [M], model dtype): added to the Centered m
+// per-point noise (svgp_collapsed_*_with_noise): w[j] = 1 / (sigma2 + sv[j]) for j < n in the model's dtype and in fp64 (wd), zeros
+// on [n, pad_to); *nbad (zeroed by the caller) += the number of sigma2 + sv[j] <= 0
+void launch_collapsed_weights(int dtype, hipStream_t s, const void* sv, double sigma2, int64_t n, int64_t pad_to, void* w, double* wd, int* nbad);
+// launch_collapsed_reduce with r_j = y[off + j] - mean_const - mux[j] and weights wd[j] (mux, sv, wd nullable, indexed by the point's
+// place in the chunk): bpart (+)= A (w r), spart (+)= {sum w r^2, sum w ssq}, spart2[kCollapsedSplit][2] (+)= {sum log(sigma2 + sv), sum w}
+void launch_collapsed_reduce_w(int dtype, hipStream_t s, const void* At, const void* y, const void* mux, const void* sv, const double* wd,
+                               const double* ssq, int64_t Mp, int64_t off, int64_t n, double mean_const, double sigma2, int first,
+                               double* bpart, double* spart, double* spart2);
+// scal[6] = sum log sigma_j^2, scal[7] = sum w_j from spart2, in split order
+void launch_collapsed_extra(hipStream_t s, const double* spart2, double* scal);
+// launch_point_grads for the Gaussian likelihood (closed form) with a per-point noise variance: point i is evaluated with
+// sigma_i^2 = sigma2 + noise[i] (noise nullable, compute dtype, [len]); the same outputs in the same layout, plus noise_bar[i] =
+// scale dE_i/dsigma_i^2 (nullable).  strip.hip stays as it is: the strips' translation unit is not rebuilt differently for this
+void launch_point_grads_noise(int dtype, hipStream_t s, double sigma2, int clamp_neg_var, const double* mom_mu, const double* mom_var,
+                              const void* y, int64_t off, int64_t len, double scale, const void* noise, void* gmu_out, void* gv_out,
+                              double* part5, unsigned* strip_queue, int64_t pad_to, void* gmu_copy, void* noise_bar);
 
 // ---- natgrad.hip (one natural-gradient step on q: svgp_natgrad_step*) -----------------------------------------------------
 // Wm (fp64, full, symmetric) = - sum(slices of G: the SYRK's lower tiles of A diag(2 scale g_v) A', model dtype), in slice order

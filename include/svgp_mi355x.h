@@ -597,8 +597,8 @@ int32_t svgp_nn_predict_local(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_
  * are bitwise repeatable call to call: fixed splits, fixed-order sums, no floating-point atomics.
  * SVGP_INVALID_ARG, before anything is enqueued: a likelihood other than SVGP_LIK_GAUSSIAN, a window outside the data, data without
  * y, a dtype / d that differs from the model's, (grad) a NULL grads_out or non-NULL grads_out->m / ->Lq or a bad gx.
- * SVGP_UNSUPPORTED: a context with a communicator attached, a model carrying muz.  Multi-GPU evaluation and prior mean offsets (the
- * calls take no mux) are out of scope.  SVGP_NOT_POSDEF: a non-positive pivot of Kuu (chol_info) or of B (chol_info_b); the model's
+ * SVGP_UNSUPPORTED: a context with a communicator attached, a model carrying muz (prior mean offsets and per-point noise variances:
+ * the svgp_collapsed_*_with_noise calls below).  Multi-GPU evaluation is out of scope.  SVGP_NOT_POSDEF: a non-positive pivot of Kuu (chol_info) or of B (chol_info_b); the model's
  * q is then left as it was.  For Kuu "non-positive" includes a pivot at or below its rounding noise, 4 eps (i + 1) (variance + jitter)
  * in the model's dtype: an exactly repeated inducing point at jitter 0 leaves +-1e-16 there, not an exact zero, and A = Lk \\ Kuf
  * built on it would be noise (the existing calls keep LAPACK's rule, pivot <= 0).  Found by symbol (no ABI version step). */
@@ -619,6 +619,50 @@ int32_t svgp_collapsed_q(svgp_ctx* ctx, svgp_model* model, const svgp_data* data
                          void* Lq_out, double* bound_out);
 int32_t svgp_collapsed_grad(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
                             double* bound_out, svgp_collapsed_terms* terms_out, svgp_grads* grads_out, const svgp_input_grad* gx);
+
+/* ---- the collapsed bound with per-point noise variances and any prior mean ----------------------------------------------------------
+ * AbstractGPs' VFE accepts f(x, Sigma_y::Diagonal) (Kuf / chol(Sigma_y).U, trace term sum_j (k_jj - q_jj) / Sigma_y_jj) and any mean
+ * function.  The caller evaluates the O(n) functions - the noise vector and the mean at x and at z - and these calls do the
+ * O(n M^2) work.  With s = pn->s and mux = pm->mu over the window (each NULL: zeros) and A = Lk \ Kuf:
+ *   sigma_j^2 = lik_sigma2 + s_j (the per-point term ADDS to the descriptor's variance, as mux adds to mean_const),  w_j = 1 / sigma_j^2,
+ *   r_j = y_j - mean_const - mux_j,  C = sum_j w_j a_j a_j',  b = sum_j w_j a_j r_j,  rr = sum_j w_j r_j^2,
+ *   t = sum_j w_j (variance - |a_j|^2),  ld = sum_j log sigma_j^2,  B = I + C = LB LB',  c = LB \ b
+ *   bound = -n/2 log 2 pi - ld / 2 - sum log diag LB - rr / 2 + c'c / 2 - t / 2
+ *         = log N(r | 0, Qff + diag sigma^2)  [fit]  - 1/2 sum_j (k_jj - q_jj) / sigma_j^2  [trace]
+ *   optimal whitened q: m_w = LB' \ c, S_w = inv(B);  Centered: m = mean_const + muz + Lk m_w, Lq = Lk chol(S_w)
+ * The bound does not depend on muz (svgp_model_set_mean_z): it enters the Centered m only, and a model carrying it is accepted here
+ * (the three calls above keep their SVGP_UNSUPPORTED).  pm, pn, gpm, gpn and gx may each be NULL; with pm = pn = NULL and no muz every
+ * output is bitwise that of the corresponding call above (the same launches).  s / s_bar: batch_len values in the data's dtype,
+ * element j belongs to point batch_off + j, in host or device memory as svgp_point_mean / _grad; nothing past batch_len is touched.
+ *   svgp_collapsed_grad_with_noise  also  s_bar_j = d bound / d sigma_j^2 = -1 / (2 sigma_j^2) + ((r_j - mu~_j)^2 + v_j) / (2 sigma_j^4)
+ *                                   into gpn and mux_bar_j = (r_j - mu~_j) / sigma_j^2 into gpm (mu~, v: the marginals of the optimal
+ *                                   q without the prior mean); grads_out->lik_sigma2 = sum_j s_bar_j keeps its meaning.
+ * With pn the data pass computes C with per-point weights (the weighted SYRK of the non-Gaussian value-and-gradient) and the
+ * gradient pass takes that route too; the M-sized tail is unchanged, fp64.  Results stay bitwise repeatable.
+ * Statuses: those of the calls above and of svgp_point_mean, before anything is enqueued; SVGP_INVALID_ARG: NULL pn->s or
+ * gpn->s_bar, on_device not 0 / 1, reserved != 0; SVGP_NOT_POSDEF with the model's q untouched: any sigma_j^2 <= 0 (the reference
+ * throws from cholesky(Sigma_y)), found before the data pass; NaN results with SVGP_OK: a NaN in s, mux, x or y; SVGP_UNSUPPORTED: a
+ * communicator attached.  terms_out keeps its struct: fit and trace take the meanings above.  Found by symbol. */
+typedef struct svgp_point_noise {        /* s: batch_len values in the data's dtype, element j belongs to point batch_off + j */
+  const void* s;
+  int32_t on_device;   /* 0: host memory, 1: device memory */
+  int32_t reserved;    /* 0 */
+} svgp_point_noise;      /* 16 bytes */
+typedef struct svgp_point_noise_grad {   /* s_bar: batch_len values in the data's dtype, element j belongs to point batch_off + j */
+  void* s_bar;
+  int32_t on_device;
+  int32_t reserved;
+} svgp_point_noise_grad; /* 16 bytes */
+int32_t svgp_collapsed_bound_with_noise(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                                        const svgp_point_mean* pm, const svgp_point_noise* pn, double* bound_out,
+                                        svgp_collapsed_terms* terms_out);
+int32_t svgp_collapsed_q_with_noise(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                                    const svgp_point_mean* pm, const svgp_point_noise* pn, void* m_out, void* Lq_out,
+                                    double* bound_out);
+int32_t svgp_collapsed_grad_with_noise(svgp_ctx* ctx, svgp_model* model, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                                       const svgp_point_mean* pm, const svgp_point_noise* pn, double* bound_out,
+                                       svgp_collapsed_terms* terms_out, svgp_grads* grads_out, const svgp_input_grad* gx,
+                                       svgp_point_mean_grad* gpm, svgp_point_noise_grad* gpn);
 
 /* ---- natural-gradient steps on q(u) -------------------------------------------------------------------------------------------------
  * The reference trains q = N(m, Lq Lq') with the optimiser that trains everything else: svgp_elbo_grad hands it the Euclidean

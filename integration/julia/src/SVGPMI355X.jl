@@ -87,6 +87,18 @@ struct PointMeanGrad                  # svgp_point_mean_grad (16 bytes): d elbo 
     reserved::Int32
 end
 
+struct PointNoise                     # svgp_point_noise (16 bytes): the batch's per-point noise variances s (added to lik_sigma2)
+    s::Ptr{Cvoid}
+    on_device::Int32
+    reserved::Int32
+end
+
+struct PointNoiseGrad                 # svgp_point_noise_grad (16 bytes): d bound / d sigma_j^2
+    s_bar::Ptr{Cvoid}
+    on_device::Int32
+    reserved::Int32
+end
+
 mutable struct PredSummary            # svgp_pred_summary (32 bytes): the sums of svgp_predictive / svgp_lik_predictive
     sum_lpd::Float64; sum_sq_err::Float64
     n_points::Int64; n_neg_var::Int64
@@ -967,6 +979,48 @@ function collapsed_bound_and_grad!(Mo::DeviceModel, D::DeviceData, M::Integer, d
                                              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{Float64}, Ref{CollapsedTerms}, Ref{Grads}, Ptr{Cvoid}),
                                              ctx(), Mo.h, D.h, off, len, out, t, g, C_NULL), t)
     return out[], t, (variance=g.variance, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const, inv_lengthscale=gl, z=gz)
+end
+
+# ... with per-point noise variances Σy = Diagonal(lik_sigma2 .+ s) and prior mean offsets mux (svgp_collapsed_*_with_noise): what
+# AbstractGPs' VFE computes for f(x, Σy::Diagonal) and any mean function.  s, mux: host vectors of the data's element type, one entry
+# per point of the window, or `nothing`; a model carrying muz (svgp_model_set_mean_z) is accepted.
+point_noise_arg(s::Nothing) = Ptr{PointNoise}(C_NULL)
+point_noise_arg(s::Vector) = Ref(PointNoise(pointer(s), 0, 0))
+point_mean_arg(mux::Nothing) = Ptr{PointMean}(C_NULL)
+point_mean_arg(mux::Vector) = Ref(PointMean(pointer(mux), 0, 0))
+"The collapsed bound over the points off+1 : off+len of D with noise variances lik_sigma2 .+ s and prior mean mean_const .+ mux."
+function collapsed_bound_with_noise(Mo::DeviceModel, D::DeviceData; s=nothing, mux=nothing, off::Integer=0, len::Integer=D.n - off)
+    out, t = Ref{Float64}(), CollapsedTerms()
+    pm, pn = point_mean_arg(mux), point_noise_arg(s)
+    GC.@preserve s mux collapsed_check(ccall((:svgp_collapsed_bound_with_noise, lib), Int32,
+                                             (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{PointMean}, Ptr{PointNoise}, Ref{Float64}, Ref{CollapsedTerms}),
+                                             ctx(), Mo.h, D.h, off, len, pm, pn, out, t), t)
+    return out[], t
+end
+"Writes that problem's optimal q into the model's device-resident m / Lq; returns (bound, m, Lq) as host arrays."
+function collapsed_q_with_noise!(Mo::DeviceModel, D::DeviceData, M::Integer, ::Type{T}; s=nothing, mux=nothing, off::Integer=0,
+                                 len::Integer=D.n - off) where {T<:FT}
+    out = Ref{Float64}()
+    m, Lq = zeros(T, M), zeros(T, M, M)
+    pm, pn = point_mean_arg(mux), point_noise_arg(s)
+    GC.@preserve s mux check(ccall((:svgp_collapsed_q_with_noise, lib), Int32,
+                                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{PointMean}, Ptr{PointNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Float64}),
+                                   ctx(), Mo.h, D.h, off, len, pm, pn, m, Lq, out))
+    return out[], m, LowerTriangular(Lq)
+end
+"The bound and its total derivatives, with s_bar = d bound / d Σy_jj and mux_bar = d bound / d mean(x_j) (host vectors of length len)."
+function collapsed_bound_and_grad_with_noise!(Mo::DeviceModel, D::DeviceData, M::Integer, d::Integer, ::Type{T}; s=nothing, mux=nothing,
+                                              off::Integer=0, len::Integer=D.n - off) where {T<:FT}
+    out, t = Ref{Float64}(), CollapsedTerms()
+    gl, gz = zeros(Float64, d), zeros(T, d, M)
+    sbar, mbar = zeros(T, len), zeros(T, len)
+    g = Grads(0.0, 0.0, 0.0, pointer(gl), pointer(gz), C_NULL, C_NULL)
+    pm, pn = point_mean_arg(mux), point_noise_arg(s)
+    gpm, gpn = Ref(PointMeanGrad(pointer(mbar), 0, 0)), Ref(PointNoiseGrad(pointer(sbar), 0, 0))
+    GC.@preserve gl gz s mux sbar mbar collapsed_check(ccall((:svgp_collapsed_grad_with_noise, lib), Int32,
+                                                             (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{PointMean}, Ptr{PointNoise}, Ref{Float64}, Ref{CollapsedTerms}, Ref{Grads}, Ptr{Cvoid}, Ptr{PointMeanGrad}, Ptr{PointNoiseGrad}),
+                                                             ctx(), Mo.h, D.h, off, len, pm, pn, out, t, g, C_NULL, gpm, gpn), t)
+    return out[], t, (variance=g.variance, lik_sigma2=g.lik_sigma2, mean_const=g.mean_const, inv_lengthscale=gl, z=gz, s=sbar, mux=mbar)
 end
 
 # ---------------------------------------------------------------------------------------------------------
