@@ -32,5 +32,9 @@ from .natgrad import natural_gradient_step
 # pathwise posterior function samples: ApproxPosteriorGP.function_samples, DeviceModel.sampler; draw_basis draws their random numbers
 from ._ffi import DeviceSampler, SampleBasis
 from .pathwise import FunctionSamples, draw_basis, function_samples
+# ConjugateGradients: the exact GP by matrix-free iterative solves; approx_lml, approx_lml_and_gradient and posterior dispatch on it too
+from ._ffi import CGDesc, CGInfo
+from .iterative import (CGPosteriorGP, ConjugateGradients, DeviceConjugateGradients, approx_lml, approx_lml_and_gradient, draw_probes,
+                        posterior)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

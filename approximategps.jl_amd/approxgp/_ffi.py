@@ -117,6 +117,20 @@ class SampleBasis(C.Structure):
                 ("w", C.c_void_p), ("eps", C.c_void_p)]
 
 
+class CGDesc(C.Structure):
+    """svgp_cg_desc: one parameter set of the exact GP by conjugate gradients (64 bytes)."""
+    _fields_ = [("dtype", C.c_int32), ("kernel", C.c_int32), ("d", C.c_int32), ("maxiter", C.c_int32), ("variance", C.c_double),
+                ("inv_lengthscale", C.POINTER(C.c_double)), ("diag", C.c_double), ("mean_const", C.c_double), ("tol", C.c_double),
+                ("reserved", C.c_int64)]
+
+
+class CGInfo(C.Structure):
+    """svgp_cg_info: what a batched solve did (64 bytes)."""
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("n_unconverged", C.c_int32), ("reserved", C.c_int32),
+                ("max_rel_residual", C.c_double), ("quad", C.c_double), ("logdet", C.c_double), ("lml", C.c_double),
+                ("ms_matvec", C.c_double), ("ms_vector", C.c_double)]
+
+
 # every symbol include/svgp_mi355x.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -214,6 +228,20 @@ SYMBOLS = {
     "svgp_sampler_eval_grad": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), _P, C.c_int64, _P, C.c_int64, C.c_int32]),
     "svgp_sampler_state": (C.c_int32, [_P, _P, _P, _P]),
     "svgp_sampler_free": (C.c_int32, [_P, _P]),
+    # the exact GP by matrix-free conjugate gradients
+    "svgp_cg_create": (C.c_int32, [_P, _P, C.POINTER(_P)]),
+    "svgp_cg_free": (C.c_int32, [_P, _P]),
+    "svgp_cg_matvec": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32]),
+    "svgp_cg_solve": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_double), C.POINTER(CGInfo)]),
+    "svgp_cg_fit": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                                C.POINTER(C.c_double), C.POINTER(CGInfo)]),
+    "svgp_cg_lml_grad": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.POINTER(CGInfo), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "svgp_cg_alpha": (C.c_int32, [_P, _P, _P]),
+    "svgp_cg_predict": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P, C.POINTER(CGInfo)]),
+    "svgp_lanczos_logdet": (C.c_int32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),
     "svgp_ctx_attach_comm": (C.c_int32, [_P, _P, C.c_int32, C.c_int32]),

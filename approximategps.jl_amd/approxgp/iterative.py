@@ -1,0 +1,339 @@
+"""The exact GP by matrix-free conjugate gradients (GPyTorch's BBMM, Gardner et al. 2018; Wang et al. 2019) over the C-ABI of
+libsvgp_mi355x.so (include/svgp_mi355x.h, svgp_cg_*): the batched solves, the stochastic Lanczos quadrature of log det, the
+gradient and the predictions all run on the device.  This file packs parameters and draws the probe vectors, which the library never
+does itself."""
+from __future__ import annotations
+
+import ctypes as C
+import warnings
+
+import numpy as np
+
+from . import _ffi
+from . import nearest_neighbors as _nn
+from . import vfe as _vfe
+from .gp import FiniteGP
+from .kernels import unpack_kernel
+
+
+def draw_probes(N: int, T: int, rng=None):
+    """(N, T) Rademacher columns (E z z' = I), float64, column-major: the probe vectors of the log det estimate."""
+    rng = np.random.default_rng(rng)
+    return np.asfortranarray(rng.integers(0, 2, size=(int(N), int(T))).astype(np.float64) * 2.0 - 1.0)
+
+
+class ConjugateGradients:
+    """ConjugateGradients(tol, maxiter, n_probes, seed, probes): logpdf(fx, y), its gradient and the posterior of the exact GP by
+    iterative solves against K(x, x) + Σy, never stored.  tol None: 1e-8, and 1e-4 for float32 data.  The log det comes from n_probes
+    Rademacher vectors drawn from default_rng(seed) - the same vectors on every call, so the objective is a deterministic function of
+    the hyperparameters (common random numbers) - or from the caller's (N, T) probes."""
+
+    def __init__(self, tol=None, maxiter: int = 1000, n_probes: int = 16, seed: int = 0, probes=None):
+        if tol is not None and not float(tol) > 0:
+            raise ValueError("ConjugateGradients needs tol > 0")
+        if int(maxiter) != maxiter or int(maxiter) < 1:
+            raise ValueError("ConjugateGradients needs maxiter >= 1")
+        if int(n_probes) != n_probes or int(n_probes) < 0:
+            raise ValueError("ConjugateGradients needs n_probes >= 0")
+        if probes is not None:
+            probes = np.asarray(probes, dtype=np.float64)
+            if probes.ndim != 2:
+                raise ValueError("probes is an (N, T) array")
+        self.tol = None if tol is None else float(tol)
+        self.maxiter, self.n_probes, self.seed, self.probes = int(maxiter), int(n_probes), seed, probes
+
+    def tol_for(self, dtype) -> float:
+        if self.tol is not None:
+            return self.tol
+        return 1e-4 if np.dtype(dtype) == np.float32 else 1e-8
+
+    def probes_for(self, N: int):
+        if self.probes is not None:
+            if self.probes.shape[0] != N:
+                raise ValueError("probes has one row per data point")
+            return np.asfortranarray(self.probes)
+        return draw_probes(N, self.n_probes, self.seed)
+
+
+class DeviceConjugateGradients:
+    """A resident svgp_cg handle over x (and y): x a plain vector (d = 1) or a (d, n) ColVecs array; with layout = ROWVECS an (n, d)
+    RowVecs array."""
+
+    def __init__(self, ctx: _ffi.Context, x, y, dtype, layout=None):
+        self.ctx = ctx
+        x = np.asarray(x)
+        if layout is None:
+            layout = _ffi.VEC if x.ndim == 1 else _ffi.COLVECS
+        self.data = _ffi.DeviceData(ctx, x, y, dtype, layout)
+        self.dtype, self.d, self.n = self.data.dtype, self.data.d, self.data.n
+        h = C.c_void_p()
+        ctx.check(ctx.lib.svgp_cg_create(ctx.h, self.data.h, C.byref(h)))
+        self.h = h
+
+    def desc(self, kernel, diag=0.0, mean_const=0.0, tol=1e-8, maxiter=1000):
+        """-> (CGDesc, the array it points into: keep it alive)"""
+        family, variance, il = unpack_kernel(kernel, self.d)
+        il = np.ascontiguousarray(il, dtype=np.float64)
+        ds = _ffi.CGDesc(dtype=self.dtype, kernel=family, d=self.d, maxiter=int(maxiter), variance=float(variance),
+                         inv_lengthscale=il.ctypes.data_as(C.POINTER(C.c_double)), diag=float(diag), mean_const=float(mean_const),
+                         tol=float(tol), reserved=0)
+        return ds, il
+
+    def _check(self, rc):
+        if rc == _ffi.NOT_POSDEF:
+            msg = (self.ctx.lib.svgp_last_error(self.ctx.h) or b"").decode()
+            raise _ffi.PosDefException(-1, msg)
+        self.ctx.check(rc)
+
+    def _cols(self, a, name):
+        """-> (pointer, ld, S, on_device, host array or None) of an (N, S) panel: a numpy array, or a torch device tensor holding it
+        column-major (shape (S, N) contiguous, or (N,))"""
+        if _ffi._is_device_tensor(a):
+            if (not a.is_contiguous() or a.element_size() != np.dtype(_ffi.np_dtype(self.dtype)).itemsize or not a.is_floating_point()
+                    or a.shape[-1] != self.n or a.dim() > 2):
+                raise ValueError(f"{name}: a contiguous (S, N) device tensor of the data dtype (its rows are the columns)")
+            S = 1 if a.dim() == 1 else a.shape[0]
+            return C.c_void_p(int(a.data_ptr())), self.n, S, 1, None
+        h = np.asarray(a, dtype=_ffi.np_dtype(self.dtype))
+        if h.ndim == 1:
+            h = h[:, None]
+        if h.ndim != 2 or h.shape[0] != self.n:
+            raise ValueError(f"{name}: an (N, S) array")
+        h = np.asfortranarray(h)
+        return _ffi._ptr(h), self.n, h.shape[1], 0, h
+
+    def matvec(self, desc, V, out=None):
+        """(K(x, x) + diag I) V for an (N, S) panel.  A torch device tensor ((S, N), contiguous) needs out of the same kind."""
+        vp, ldv, S, dev, keep = self._cols(V, "V")
+        if S < 1:
+            raise ValueError("V: an (N, S) array with S >= 1")
+        if dev:
+            if out is None or not _ffi._is_device_tensor(out):
+                raise ValueError("out: a device tensor like V")
+            op, ldo, So, _, _ = self._cols(out, "out")
+            if So != S:
+                raise ValueError("out: a device tensor like V")
+            res = out
+        else:
+            res = np.zeros((self.n, S), dtype=_ffi.np_dtype(self.dtype), order="F")
+            op, ldo = _ffi._ptr(res), self.n
+        self._check(self.ctx.lib.svgp_cg_matvec(self.ctx.h, self.h, C.byref(desc), S, vp, ldv, op, ldo, dev))
+        return res
+
+    def solve(self, desc, B, out=None):
+        """-> (X, iterations (S,), relative residuals (S,), CGInfo).  PosDefException when a curvature is not positive."""
+        bp, ldb, S, dev, keep = self._cols(B, "B")
+        if S < 1:
+            raise ValueError("B: an (N, S) array with S >= 1")
+        if dev:
+            if out is None or not _ffi._is_device_tensor(out):
+                raise ValueError("out: a device tensor like B")
+            xp, ldx, So, _, _ = self._cols(out, "out")
+            if So != S:
+                raise ValueError("out: a device tensor like B")
+            res = out
+        else:
+            res = np.zeros((self.n, S), dtype=_ffi.np_dtype(self.dtype), order="F")
+            xp, ldx = _ffi._ptr(res), self.n
+        iters, rel, info = np.zeros(S, dtype=np.int32), np.zeros(S), _ffi.CGInfo()
+        self._check(self.ctx.lib.svgp_cg_solve(self.ctx.h, self.h, C.byref(desc), S, bp, ldb, xp, ldx, dev,
+                                               iters.ctypes.data_as(C.POINTER(C.c_int32)), rel.ctypes.data_as(C.POINTER(C.c_double)),
+                                               C.byref(info)))
+        return res, iters, rel, info
+
+    @staticmethod
+    def _f64(a):
+        return None if a is None else np.asfortranarray(np.asarray(a, dtype=np.float64))
+
+    def fit(self, desc, probes=None, delta=None):
+        """-> (lml, CGInfo); caches alpha for predict.  probes: (N, T) float64 or None (T = 0: lml is NaN, info.quad valid)."""
+        z, dl = self._f64(probes), self._f64(delta)
+        T = 0 if z is None else z.shape[1]
+        lml, info = C.c_double(), _ffi.CGInfo()
+        dp = C.POINTER(C.c_double)
+        self._check(self.ctx.lib.svgp_cg_fit(self.ctx.h, self.h, C.byref(desc), None if dl is None else dl.ctypes.data_as(dp), T,
+                                             None if z is None or T == 0 else z.ctypes.data_as(dp), C.byref(lml), C.byref(info)))
+        return lml.value, info
+
+    def lml_grad(self, desc, probes, delta=None):
+        """-> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const"}, CGInfo)"""
+        z, dl = self._f64(probes), self._f64(delta)
+        T = 0 if z is None else z.shape[1]
+        lml, info = C.c_double(), _ffi.CGInfo()
+        dv, dd, dm, dil = C.c_double(), C.c_double(), C.c_double(), np.zeros(self.d)
+        dp = C.POINTER(C.c_double)
+        self._check(self.ctx.lib.svgp_cg_lml_grad(self.ctx.h, self.h, C.byref(desc), None if dl is None else dl.ctypes.data_as(dp), T,
+                                                  None if z is None or T == 0 else z.ctypes.data_as(dp), C.byref(lml), C.byref(info),
+                                                  C.byref(dv), dil.ctypes.data_as(dp), C.byref(dd), C.byref(dm)))
+        return lml.value, {"variance": dv.value, "inv_lengthscale": dil, "diag": dd.value, "mean_const": dm.value}, info
+
+    def alpha(self):
+        a = np.zeros(self.n, dtype=_ffi.np_dtype(self.dtype))
+        self.ctx.check(self.ctx.lib.svgp_cg_alpha(self.ctx.h, self.h, _ffi._ptr(a)))
+        return a
+
+    def predict(self, x, mean=True, var=True, layout=None):
+        """-> (mean, var, CGInfo of the variance's solve); x as for the handle"""
+        dt = _ffi.np_dtype(self.dtype)
+        x = np.asarray(x, dtype=dt)
+        if x.ndim == 1:
+            if self.d != 1:
+                raise ValueError("test inputs have a different dimension than the data")
+            layout, n, xb = _ffi.VEC, x.shape[0], np.ascontiguousarray(x)
+        elif layout == _ffi.ROWVECS:
+            if x.shape[1] != self.d:
+                raise ValueError("test inputs have a different dimension than the data")
+            n, xb = x.shape[0], np.asfortranarray(x)
+        else:
+            if x.shape[0] != self.d:
+                raise ValueError("test inputs have a different dimension than the data")
+            layout, n, xb = _ffi.COLVECS, x.shape[1], np.asfortranarray(x)
+        m = np.zeros(n, dtype=dt) if mean else None
+        v = np.zeros(n, dtype=dt) if var else None
+        info = _ffi.CGInfo()
+        self._check(self.ctx.lib.svgp_cg_predict(self.ctx.h, self.h, layout, n, _ffi._ptr(xb), _ffi._ptr(m), _ffi._ptr(v), C.byref(info)))
+        return m, v, info
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.svgp_cg_free(self.ctx.h, self.h)
+            self.h = None
+        if getattr(self, "data", None) is not None:
+            self.data.free()
+            self.data = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _warn(info, what):
+    if not info.converged:
+        warnings.warn(f"conjugate gradients: {info.n_unconverged} column(s) of {what} did not reach tol in {info.iterations} "
+                      f"iterations (largest relative residual {info.max_rel_residual:.3e})", RuntimeWarning, stacklevel=3)
+
+
+def _cg_kwargs(fn, kwargs):
+    extra = set(kwargs) - {"ctx", "dtype"}
+    if extra:
+        raise TypeError(f"{fn}() with ConjugateGradients got unexpected keyword arguments {sorted(extra)}")
+    return kwargs.get("ctx"), kwargs.get("dtype")
+
+
+def _check_inputs(fx: FiniteGP, y):
+    """-> (diag, mean_const, delta or None), before the GPU is touched.  A CustomMean prior is passed as delta = y - mean(x)."""
+    if not isinstance(fx, FiniteGP):
+        raise TypeError("ConjugateGradients takes fx = f(x, Σy)")
+    if not fx.is_isotropic():
+        raise _ffi.UnsupportedError("ConjugateGradients needs an isotropic fx.Σy (per-point noise is out of scope)")
+    diag = float(fx.Sigma_y)
+    if not diag >= 0:
+        raise ValueError("fx.Σy must be >= 0")
+    if np.shape(y)[0] != fx.n:
+        raise ValueError("x and y lengths differ")
+    delta = None
+    if fx.f.mean_fn is not None:
+        delta = np.asarray(y, dtype=np.float64).reshape(-1) - fx.f.mean_offsets(fx.x)
+    return diag, float(fx.f.mean_const), delta
+
+
+def _device(cg: ConjugateGradients, fx: FiniteGP, y, ctx, dtype):
+    diag, mean_const, delta = _check_inputs(fx, y)
+    dt = _nn._dtype_of(fx, dtype)
+    probes = cg.probes_for(fx.n)
+    dev = DeviceConjugateGradients(ctx or _ffi.default_context(), fx.x, y, dt)
+    desc, keep = dev.desc(fx.f.kernel, diag, mean_const, cg.tol_for(dt), cg.maxiter)
+    return dev, desc, keep, probes, delta
+
+
+def approx_lml(approx, fx, y, **kwargs):
+    """approx_lml(ConjugateGradients(), fx, y; ctx, dtype): logpdf(fx, y) of the exact GP with log det by stochastic Lanczos
+    quadrature; any other approximation: the existing methods with every keyword passed on exactly as given."""
+    if not isinstance(approx, ConjugateGradients):
+        return _vfe.approx_lml(approx, fx, y, **kwargs)
+    ctx, dtype = _cg_kwargs("approx_lml", kwargs)
+    dev, desc, keep, probes, delta = _device(approx, fx, y, ctx, dtype)
+    try:
+        lml, info = dev.fit(desc, probes, delta)
+    finally:
+        dev.free()
+    _warn(info, "the fit")
+    return lml
+
+
+def approx_lml_and_gradient(approx, fx, y, **kwargs):
+    """ConjugateGradients: -> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const"}): the gradient with respect to the
+    kernel parameters, the noise variance Σy and the constant mean.  Any other approximation: the existing methods."""
+    if not isinstance(approx, ConjugateGradients):
+        return _nn.approx_lml_and_gradient(approx, fx, y, **kwargs)
+    ctx, dtype = _cg_kwargs("approx_lml_and_gradient", kwargs)
+    dev, desc, keep, probes, delta = _device(approx, fx, y, ctx, dtype)
+    try:
+        lml, grads, info = dev.lml_grad(desc, probes, delta)
+    finally:
+        dev.free()
+    _warn(info, "the fit")
+    return lml, grads
+
+
+class CGPosteriorGP:
+    """posterior(fx, y) of the exact GP with alpha = (K + Σy)^-1 (y - mean(x)) resident on the device.  Test inputs: a plain vector
+    (d = 1) or a (d, n) ColVecs array.  The variance costs one batched solve with k(X, x*) as right-hand sides."""
+
+    def __init__(self, cg: ConjugateGradients, fx: FiniteGP, y, ctx=None, dtype=None):
+        self.approx, self.prior = cg, fx.f
+        self.dev, desc, keep, probes, delta = _device(cg, fx, y, ctx, dtype)
+        self.noise = float(fx.Sigma_y)
+        try:
+            self.lml, self.info = self.dev.fit(desc, probes, delta)
+        except Exception:
+            self.dev.free()
+            raise
+        _warn(self.info, "the fit")
+
+    @property
+    def alpha(self):
+        return self.dev.alpha()
+
+    def _offsets(self, x, m):
+        mu = self.prior.mean_offsets(np.asarray(x))
+        return m if mu is None or m is None else (m + mu).astype(m.dtype)
+
+    def mean(self, x):
+        return self._offsets(x, self.dev.predict(x, mean=True, var=False)[0])
+
+    def var(self, x):
+        _, v, info = self.dev.predict(x, mean=False, var=True)
+        _warn(info, "the predictive variance")
+        return v
+
+    def mean_and_var(self, x):
+        m, v, info = self.dev.predict(x, mean=True, var=True)
+        _warn(info, "the predictive variance")
+        return self._offsets(x, m), v
+
+    def _lik_predictive(self, x, y, want):
+        if not self.noise > 0:
+            raise ValueError("predictions of y need observation noise fx.Σy > 0")
+        m, v = self.mean_and_var(x)
+        return _ffi.lik_predictive(self.dev.ctx, _ffi.LIK_GAUSSIAN, self.noise, 0, m, v, y, want=want)
+
+    def predict_y(self, x):
+        """(E[y*], Var[y*]) = (mean, var + noise)"""
+        r = self._lik_predictive(x, None, ("ymean", "yvar"))
+        return r["ymean"], r["yvar"]
+
+    def log_predictive_density(self, x, y):
+        """log N(y*_i; mean_i, var_i + noise) per point"""
+        return self._lik_predictive(x, y, ("lpd",))["lpd"]
+
+
+def posterior(approx, *args, **kwargs):
+    """posterior(ConjugateGradients(), fx, y; ctx, dtype) -> CGPosteriorGP; any other approximation: the existing methods."""
+    if isinstance(approx, ConjugateGradients):
+        fx, y = args
+        ctx, dtype = _cg_kwargs("posterior", kwargs)
+        return CGPosteriorGP(approx, fx, y, ctx=ctx, dtype=dtype)
+    return _vfe.posterior(approx, *args, **kwargs)

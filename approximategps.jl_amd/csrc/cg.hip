@@ -1,0 +1,433 @@
+// cg.hip — the exact GP by matrix-free conjugate gradients (svgp_cg_*: cg_api.hip holds the host side).
+//   out[i, s] = sum_j prof(r^2(P_i, R_j)) V[j, s]  (+ diag addv[i, s]),     prof = kappa, or 2 g (xs_ic - xs_jc)^2 of one coordinate c
+// kmv_kernel is sample_eval_kernel (sample.hip) with the inducing rows replaced by the N data rows R and the resident panel by an
+// N x S one read from global memory chunk by chunk: every 16 x 16 tile (16 rows j, 16 points i) is generated TRANSPOSED on the MFMA in
+// the expansion form r^2 = |xs_j|^2 + |xs_i|^2 - 2 xs_j . xs_i, kappa<T> is applied in registers, and the C/D registers are the B
+// operand of the second product out'[s][i] += V'[s][j] tile[j][i].  No entry of K is ever stored.  Every sum has a fixed order (j
+// ascending in steps of 4 inside one accumulator chain), no atomics; an output column depends on its own panel column alone, so a
+// column's value does not depend on which other columns share the launch.
+// The vector stage of the solver (masked axpys, column dots) is a handful of streaming kernels; every dot is a fixed two-stage
+// reduction in fp64 for both dtypes, and the per-column CG scalars live in a small fp64 state block on the device.
+#include <hip/hip_runtime.h>
+
+#include "device_common.hpp"
+#include "kernels.hpp"
+
+namespace svgp {
+
+namespace {
+
+constexpr int kKmvKC = 32;   // rows per LDS chunk (Np is a multiple of it)
+
+// groups of 16 points a wave owns: sample_point_groups' rule (two waves per SIMD: <= 256 VGPRs + AGPRs); the lengthscale profile
+// carries the coordinate's registers as well, and its f64 form with 32 features and four column blocks measured 262 - 268 with two groups
+template <typename T, int DREG, int NSB, int PROFILE>
+constexpr int kmv_point_groups() {
+  return (sizeof(T) == 8 && NSB > 1 && (DREG > 32 || (DREG > 16 && PROFILE != 0))) ? 1 : (DREG > 16 || NSB > 1) ? 2 : 4;
+}
+
+// One workgroup = 4 waves; a wave owns PG groups of 16 points and, per launch, NSB 16-column blocks of the panel (<= 64 columns).
+// PROFILE 0: kappa.  PROFILE 1: 2 g(r^2) (xs_ic - xs_jc)^2 for the coordinate a.coord, the difference taken per ENTRY before the
+// product (sample_grad.hip's design: the expanded square cancels like |xs|^2 against the difference).
+template <typename T, int DREG, int NSB, int PROFILE>
+__global__ void __launch_bounds__(256) kmv_kernel(KmvArgs a) {
+  constexpr int KS = DREG / 4, KC = kKmvKC, NW = 4;
+  constexpr int PG = kmv_point_groups<T, DREG, NSB, PROFILE>();
+  constexpr int ZLD = KC + 16, PLD = NSB * 16 + 4;
+  // fp32, d <= 8: r^2 by differences of the UNSCALED coordinates on the VALU, scaled afterwards (sample.hip explains why: the
+  // expansion loses eps32 (|xs_i|^2 + |xs_j|^2) absolutely, and here |xs| grows with the domain while r^2 of the entries that
+  // matter stays of order one).  The rows of such a handle hold x itself (kmv_prep_kernel, raw).
+  constexpr bool DIFF = sizeof(T) == 4 && DREG <= 8;
+  using acc_t = typename Mfma16<T>::acc_t;
+  __shared__ T zc[DREG * ZLD];   // [f][kk]  rows of the chunk (MFMA A operand of the generation)
+  __shared__ T pc[KC * PLD];     // [kk][j]  panel rows of the chunk, the launch's column block
+  __shared__ T tc[KC];           // [kk]     bias |xs_j|^2
+  const T* __restrict__ rows = static_cast<const T*>(a.rows);
+  const T* __restrict__ bias = static_cast<const T*>(a.bias);
+  const T* __restrict__ V = static_cast<const T*>(a.V);
+  const T* __restrict__ invl = static_cast<const T*>(a.invl);
+  const T* __restrict__ x = static_cast<const T*>(a.px);
+  const T* __restrict__ addv = static_cast<const T*>(a.addv);
+  T* __restrict__ out = static_cast<T*>(a.out);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, kq = lane >> 4;
+  const int d = a.d, family = a.family, coord = a.coord;
+  const int64_t n = a.n, N = a.N, Np = a.Np;
+  const T variance = T(a.variance);
+  const int64_t p0 = (int64_t(blockIdx.x) * NW + wave) * (PG * 16);
+  T xb[PG][KS], xn[PG];
+  T xall[DIFF ? PG : 1][DIFF ? DREG : 1];   // DIFF: every feature of point c, unscaled
+  T il[DIFF ? DREG : 1];
+  T xc[PROFILE ? PG : 1];                   // PROFILE 1: coordinate `coord` of point c (DIFF: unscaled, otherwise scaled)
+  const T ilc = PROFILE ? invl[coord] : T(0);
+  if constexpr (DIFF) {
+#pragma unroll
+    for (int f = 0; f < DREG; ++f) il[f] = (f < d) ? invl[f] : T(0);
+  }
+#pragma unroll
+  for (int g = 0; g < PG; ++g) {
+    int64_t pt = p0 + g * 16 + c;
+    pt = pt < n ? pt : n - 1;
+    if constexpr (DIFF) {
+#pragma unroll
+      for (int f = 0; f < DREG; ++f) xall[g][f] = (f < d) ? x[int64_t(f) * a.ldp + pt] : T(0);
+    }
+    if constexpr (PROFILE != 0) {
+      const T v = x[int64_t(coord) * a.ldp + pt];
+      xc[g] = DIFF ? v : v * ilc;
+    }
+    T s2 = T(0);
+#pragma unroll
+    for (int q = 0; q < KS; ++q) {
+      const int f = 4 * q + kq;
+      const T v = (f < d) ? x[int64_t(f) * a.ldp + pt] * invl[f] : T(0);
+      xb[g][q] = v;
+      s2 = fma(v, v, s2);
+    }
+    s2 += __shfl_xor(s2, 16);
+    s2 += __shfl_xor(s2, 32);
+    xn[g] = s2;
+  }
+  acc_t acc[PG][NSB];
+#pragma unroll
+  for (int g = 0; g < PG; ++g)
+#pragma unroll
+    for (int b = 0; b < NSB; ++b) acc[g][b] = acc_t{0, 0, 0, 0};
+
+  for (int64_t k0 = 0; k0 < Np; k0 += KC) {
+    __syncthreads();   // the previous chunk has been read
+    for (int idx = tid; idx < DREG * KC; idx += 256) {
+      const int f = idx / KC, kk = idx % KC;
+      zc[f * ZLD + kk] = (f < d) ? rows[int64_t(f) * Np + k0 + kk] : T(0);
+    }
+    for (int idx = tid; idx < KC * NSB * 16; idx += 256) {   // the panel is column-major: kk runs fastest over the threads
+      const int j = idx / KC, kk = idx % KC;
+      pc[kk * PLD + j] = (a.s0 + j < a.S && k0 + kk < N) ? V[(a.s0 + j) * a.ldv + k0 + kk] : T(0);
+    }
+    if (tid < KC) tc[tid] = bias[k0 + tid];
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < KC / 16; ++h) {
+      T za[KS], pa[4][NSB], tb[4];
+#pragma unroll
+      for (int q = 0; q < KS; ++q) za[q] = zc[(4 * q + kq) * ZLD + h * 16 + c];
+      T zrc[PROFILE ? 4 : 1];   // PROFILE 1: coordinate `coord` of the lane's four rows, as the chunk holds it
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int kk = h * 16 + Mfma16<T>::row(lane, r);   // the row this lane's register r holds after the generation
+        tb[r] = tc[kk];
+        if constexpr (PROFILE != 0) zrc[r] = zc[coord * ZLD + kk];
+#pragma unroll
+        for (int b = 0; b < NSB; ++b) pa[r][b] = pc[kk * PLD + b * 16 + c];
+      }
+      T zr[DIFF ? 4 : 1][DIFF ? DREG : 1];   // DIFF: every feature of the lane's four rows (the chunk holds x itself)
+      if constexpr (DIFF) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int f = 0; f < DREG; ++f) zr[r][f] = zc[f * ZLD + h * 16 + Mfma16<T>::row(lane, r)];
+      }
+#pragma unroll
+      for (int g = 0; g < PG; ++g) {
+        if (p0 + g * 16 >= n) break;   // wave-uniform
+        acc_t t;
+        if constexpr (DIFF) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            T s2 = T(0);
+#pragma unroll
+            for (int f = 0; f < DREG; ++f) {
+              const T df = (xall[g][f] - zr[r][f]) * il[f];
+              s2 = fma(df, df, s2);
+            }
+            t[r] = s2;
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) t[r] = tb[r] + xn[g];
+#pragma unroll
+          for (int q = 0; q < KS; ++q) t = Mfma16<T>::mma(za[q], xb[g][q], t);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          T r2 = t[r] < T(0) ? T(0) : t[r];
+          // P = R: the diagonal of K is exactly the variance (the expansion leaves eps (|xs_i|^2 + |xs_j|^2) there, which the square root
+          // of the Matern families turns into sqrt(eps) |xs|)
+          if (a.self && k0 + h * 16 + Mfma16<T>::row(lane, r) == p0 + g * 16 + c) r2 = T(0);
+          const T kv = kappa<T>(family, r2, variance);
+          if constexpr (PROFILE == 0) {
+            t[r] = kv;
+          } else {
+            // scaled difference of the coordinate: the rows hold x_jc (DIFF) or -2 xs_jc
+            const T dc = DIFF ? (xc[g] - zrc[r]) * ilc : fma(T(0.5), zrc[r], xc[g]);
+            t[r] = kappa_2g<T>(family, r2, variance, kv) * (dc * dc);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int b = 0; b < NSB; ++b) acc[g][b] = Mfma16<T>::mma(pa[r][b], t[r], acc[g][b]);
+      }
+    }
+  }
+  const T dg = T(a.diag);
+#pragma unroll
+  for (int g = 0; g < PG; ++g) {
+    const int64_t pt = p0 + g * 16 + c;
+    if (pt >= n) continue;
+#pragma unroll
+    for (int b = 0; b < NSB; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t s = a.s0 + b * 16 + Mfma16<T>::row(lane, r);
+        if (s >= a.S) continue;
+        T v = acc[g][b][r];
+        if (addv) v = fma(dg, addv[s * a.lda + pt], v);
+        out[s * a.ldo + pt] = v;
+      }
+  }
+}
+
+template <typename T, int DREG, int PROFILE>
+void launch_kmv_d(hipStream_t s, const KmvArgs& a0) {
+  KmvArgs a = a0;
+  for (int64_t s0 = 0; s0 < a.S; s0 += 64) {   // column blocks of at most 64, one launch each
+    a.s0 = s0;
+    const bool one = a.S - s0 <= 16;
+    const int64_t per = 4 * 16 * (one ? kmv_point_groups<T, DREG, 1, PROFILE>() : kmv_point_groups<T, DREG, 4, PROFILE>());   // points per workgroup
+    const dim3 grid((unsigned)((a.n + per - 1) / per));
+    if (one) hipLaunchKernelGGL((kmv_kernel<T, DREG, 1, PROFILE>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((kmv_kernel<T, DREG, 4, PROFILE>), grid, dim3(256), 0, s, a);
+  }
+}
+
+template <typename T, int PROFILE>
+void launch_kmv_p(hipStream_t s, const KmvArgs& a) {
+  if (a.d <= 4) launch_kmv_d<T, 4, PROFILE>(s, a);
+  else if (a.d <= 8) launch_kmv_d<T, 8, PROFILE>(s, a);
+  else if (a.d <= 16) launch_kmv_d<T, 16, PROFILE>(s, a);
+  else if (a.d <= 32) launch_kmv_d<T, 32, PROFILE>(s, a);
+  else launch_kmv_d<T, 64, PROFILE>(s, a);
+}
+
+// rows[f][j] = -2 xs_jf (raw: x_jf itself), bias[j] = |xs_j|^2 from the ROUNDED xs = x invl, the product kmv_kernel forms for its points;
+// zero on the padding j >= N, whose panel rows kmv_kernel reads as zero
+template <typename T>
+__global__ void kmv_prep_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ invl, int d, int64_t N, int64_t Np, int raw,
+                                T* __restrict__ rows, T* __restrict__ bias) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= Np) return;
+  T s = T(0);
+  for (int f = 0; f < d; ++f) {
+    const T v = (j < N) ? x[int64_t(f) * ldx + j] : T(0);
+    const T xs = v * invl[f];
+    rows[int64_t(f) * Np + j] = raw ? v : T(-2) * xs;
+    s = fma(xs, xs, s);
+  }
+  bias[j] = s;
+}
+
+// ---- the vector stage --------------------------------------------------------------------------------------------------------------
+
+// partial[col * nblk + blk] = sum over the rows of block blk of a[i, col] b[i, col], fp64: a thread sums its rows i = r0 + tid + 256 t
+// ascending, then a fixed tree over the 256 threads.  The split depends on N alone
+template <typename T>
+__global__ void __launch_bounds__(256) cg_dot_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b, int64_t ldb, int64_t N,
+                                                     int64_t rows_per_blk, double* __restrict__ partial) {
+  __shared__ double sm[256];
+  const int64_t col = blockIdx.y, r0 = int64_t(blockIdx.x) * rows_per_blk;
+  const int64_t r1 = r0 + rows_per_blk < N ? r0 + rows_per_blk : N;
+  double s = 0.0;
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += 256) s = fma(double(a[col * lda + i]), double(b[col * ldb + i]), s);
+  sm[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (int(threadIdx.x) < w) sm[threadIdx.x] += sm[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[col * gridDim.x + blockIdx.x] = sm[0];
+}
+
+// out[col] = sum_blk partial[col * nblk + blk], blk ascending
+__global__ void cg_colsum_kernel(const double* __restrict__ partial, int nblk, int64_t ncols, double* __restrict__ out) {
+  const int64_t col = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (col >= ncols) return;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += partial[col * nblk + b];
+  out[col] = s;
+}
+
+// the per-column scalars of one column block (<= 64 columns), st = kCgStateDoubles fp64 words (kernels.hpp: CgState)
+//   mode 0 (partial = b'b):  bb = rr = b'b, active = bb > 0, iterations = 0; a NaN norm marks the block bad
+//   mode 1 (partial = p'q):  active columns: a = rr / p'q, recorded in hist_a[k]; a curvature that is not > 0 marks the block bad
+//   mode 2 (partial = r'r):  active columns: beta = r'r / rr recorded in hist_b[k], rr = r'r, iterations = k + 1, and the column stops
+//                            once r'r <= tol^2 b'b
+__global__ void cg_coef_kernel(int mode, double* __restrict__ st, const double* __restrict__ partial, int nblk, int ncols, int k, double tol2,
+                               double* __restrict__ hist_a, double* __restrict__ hist_b) {
+  const int s = threadIdx.x;
+  if (s >= 64) return;
+  if (s >= ncols) {
+    if (mode == 0) {
+      st[CgState::BB + s] = 0.0; st[CgState::RR + s] = 0.0; st[CgState::A + s] = 0.0; st[CgState::BE + s] = 0.0;
+      st[CgState::ACT + s] = 0.0; st[CgState::IT + s] = 0.0;
+    }
+    return;
+  }
+  double v = 0.0;
+  for (int b = 0; b < nblk; ++b) v += partial[s * nblk + b];
+  if (mode == 0) {
+    st[CgState::BB + s] = v;
+    st[CgState::RR + s] = v;
+    st[CgState::A + s] = 0.0;
+    st[CgState::BE + s] = 0.0;
+    st[CgState::ACT + s] = v > 0.0 ? 1.0 : 0.0;
+    st[CgState::IT + s] = 0.0;
+    if (s == 0) st[CgState::BAD] = 0.0;
+    __syncthreads();
+    if (!(v == v)) st[CgState::BAD] = 1.0;   // (every writer stores the same word)
+    return;
+  }
+  const bool act = st[CgState::ACT + s] != 0.0;
+  if (mode == 1) {
+    double al = 0.0;
+    if (act) {
+      if (v > 0.0) {
+        al = st[CgState::RR + s] / v;
+      } else {
+        st[CgState::BAD] = 1.0;
+        st[CgState::ACT + s] = 0.0;
+      }
+      if (hist_a) hist_a[int64_t(k) * 64 + s] = al;
+    }
+    st[CgState::A + s] = al;
+    return;
+  }
+  double be = 0.0;
+  if (act) {
+    const double rr = st[CgState::RR + s];
+    be = v / rr;
+    if (hist_b) hist_b[int64_t(k) * 64 + s] = be;
+    st[CgState::RR + s] = v;
+    st[CgState::IT + s] = double(k + 1);
+    if (v <= tol2 * st[CgState::BB + s]) st[CgState::ACT + s] = 0.0;
+  }
+  st[CgState::BE + s] = be;
+}
+
+// active columns: x += a p, r -= a q
+template <typename T>
+__global__ void cg_update_xr_kernel(const double* __restrict__ st, int64_t N, T* __restrict__ x, T* __restrict__ r, const T* __restrict__ p,
+                                    const T* __restrict__ q) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, col = blockIdx.y;
+  if (i >= N || st[CgState::ACT + col] == 0.0) return;
+  const T al = T(st[CgState::A + col]);
+  const int64_t o = col * N + i;
+  x[o] = fma(al, p[o], x[o]);
+  r[o] = fma(-al, q[o], r[o]);
+}
+
+// columns still active after the residual check: p = r + beta p
+template <typename T>
+__global__ void cg_update_p_kernel(const double* __restrict__ st, int64_t N, const T* __restrict__ r, T* __restrict__ p) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, col = blockIdx.y;
+  if (i >= N || st[CgState::ACT + col] == 0.0) return;
+  const T be = T(st[CgState::BE + col]);
+  const int64_t o = col * N + i;
+  p[o] = fma(be, p[o], r[o]);
+}
+
+// dst[i, col] = T(alpha src[i, col] + beta)   (src fp64 or T)
+template <typename T, typename U>
+__global__ void cg_affine_kernel(const U* __restrict__ src, int64_t lds, int64_t N, double alpha, double beta, T* __restrict__ dst, int64_t ldd) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, col = blockIdx.y;
+  if (i >= N) return;
+  dst[col * ldd + i] = T(alpha * double(src[col * lds + i]) + beta);
+}
+
+// out[i, j] = kappa(r^2(x_i, xt_j)), r^2 by differences of the scaled coordinates: the right-hand sides k(X, x*) of the predictive variance
+template <typename T>
+__global__ void cg_kcols_kernel(const T* __restrict__ x, int64_t ldx, int64_t N, const T* __restrict__ xt, int64_t ldt, const T* __restrict__ invl,
+                                int d, int family, double variance, T* __restrict__ out, int64_t ldo) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, j = blockIdx.y;
+  if (i >= N) return;
+  T s2 = T(0);
+  for (int f = 0; f < d; ++f) {
+    const T df = (x[int64_t(f) * ldx + i] - xt[int64_t(f) * ldt + j]) * invl[f];
+    s2 = fma(df, df, s2);
+  }
+  out[j * ldo + i] = kappa<T>(family, s2, T(variance));
+}
+
+inline dim3 grid2(int64_t N, int64_t cols) { return dim3((unsigned)((N + 255) / 256), (unsigned)cols); }
+
+}  // namespace
+
+void launch_kmv(int dtype, hipStream_t s, const KmvArgs& a) {
+  if (dtype == 0) {
+    if (a.profile == 0) launch_kmv_p<double, 0>(s, a); else launch_kmv_p<double, 1>(s, a);
+  } else {
+    if (a.profile == 0) launch_kmv_p<float, 0>(s, a); else launch_kmv_p<float, 1>(s, a);
+  }
+}
+
+void launch_kmv_prep(int dtype, hipStream_t s, const void* x, int64_t ldx, const void* invl, int d, int64_t N, int64_t Np, void* rows, void* bias) {
+  const dim3 grid((unsigned)((Np + 255) / 256));
+  const int raw = (dtype != 0 && d <= 8) ? 1 : 0;   // DIFF of the kmv_kernel this d is dispatched to (launch_kmv_p)
+  if (dtype == 0) hipLaunchKernelGGL(kmv_prep_kernel<double>, grid, dim3(256), 0, s, (const double*)x, ldx, (const double*)invl, d, N, Np, raw, (double*)rows, (double*)bias);
+  else hipLaunchKernelGGL(kmv_prep_kernel<float>, grid, dim3(256), 0, s, (const float*)x, ldx, (const float*)invl, d, N, Np, raw, (float*)rows, (float*)bias);
+}
+
+int cg_dot_blocks(int64_t N) {
+  const int64_t nb = (N + 4095) / 4096;
+  return int(nb < 1 ? 1 : nb > 256 ? 256 : nb);
+}
+
+void launch_cg_dot(int dtype, hipStream_t s, const void* a, int64_t lda, const void* b, int64_t ldb, int64_t N, int64_t ncols, double* partial) {
+  const int nblk = cg_dot_blocks(N);
+  const int64_t per = (N + nblk - 1) / nblk;
+  for (int64_t c0 = 0; c0 < ncols; c0 += 32768) {   // (grid.y limit)
+    const int64_t nc = ncols - c0 < 32768 ? ncols - c0 : 32768;
+    const dim3 grid((unsigned)nblk, (unsigned)nc);
+    if (dtype == 0) hipLaunchKernelGGL(cg_dot_kernel<double>, grid, dim3(256), 0, s, (const double*)a + c0 * lda, lda, (const double*)b + c0 * ldb, ldb, N, per, partial + c0 * nblk);
+    else hipLaunchKernelGGL(cg_dot_kernel<float>, grid, dim3(256), 0, s, (const float*)a + c0 * lda, lda, (const float*)b + c0 * ldb, ldb, N, per, partial + c0 * nblk);
+  }
+}
+
+void launch_cg_colsum(hipStream_t s, const double* partial, int64_t N, int64_t ncols, double* out) {
+  hipLaunchKernelGGL(cg_colsum_kernel, dim3((unsigned)((ncols + 63) / 64)), dim3(64), 0, s, partial, cg_dot_blocks(N), ncols, out);
+}
+
+void launch_cg_coef(hipStream_t s, int mode, double* st, const double* partial, int64_t N, int ncols, int k, double tol2, double* hist_a, double* hist_b) {
+  hipLaunchKernelGGL(cg_coef_kernel, dim3(1), dim3(64), 0, s, mode, st, partial, cg_dot_blocks(N), ncols, k, tol2, hist_a, hist_b);
+}
+
+void launch_cg_update_xr(int dtype, hipStream_t s, const double* st, int64_t N, int ncols, void* x, void* r, const void* p, const void* q) {
+  if (dtype == 0) hipLaunchKernelGGL(cg_update_xr_kernel<double>, grid2(N, ncols), dim3(256), 0, s, st, N, (double*)x, (double*)r, (const double*)p, (const double*)q);
+  else hipLaunchKernelGGL(cg_update_xr_kernel<float>, grid2(N, ncols), dim3(256), 0, s, st, N, (float*)x, (float*)r, (const float*)p, (const float*)q);
+}
+
+void launch_cg_update_p(int dtype, hipStream_t s, const double* st, int64_t N, int ncols, const void* r, void* p) {
+  if (dtype == 0) hipLaunchKernelGGL(cg_update_p_kernel<double>, grid2(N, ncols), dim3(256), 0, s, st, N, (const double*)r, (double*)p);
+  else hipLaunchKernelGGL(cg_update_p_kernel<float>, grid2(N, ncols), dim3(256), 0, s, st, N, (const float*)r, (float*)p);
+}
+
+void launch_cg_affine(int dtype, hipStream_t s, const void* src, int src_f64, int64_t lds, int64_t N, int64_t ncols, double alpha, double beta, void* dst, int64_t ldd) {
+  for (int64_t c0 = 0; c0 < ncols; c0 += 32768) {
+    const int64_t nc = ncols - c0 < 32768 ? ncols - c0 : 32768;
+    const dim3 g = grid2(N, nc);
+    if (dtype == 0) hipLaunchKernelGGL((cg_affine_kernel<double, double>), g, dim3(256), 0, s, (const double*)src + c0 * lds, lds, N, alpha, beta, (double*)dst + c0 * ldd, ldd);
+    else if (src_f64) hipLaunchKernelGGL((cg_affine_kernel<float, double>), g, dim3(256), 0, s, (const double*)src + c0 * lds, lds, N, alpha, beta, (float*)dst + c0 * ldd, ldd);
+    else hipLaunchKernelGGL((cg_affine_kernel<float, float>), g, dim3(256), 0, s, (const float*)src + c0 * lds, lds, N, alpha, beta, (float*)dst + c0 * ldd, ldd);
+  }
+}
+
+void launch_cg_kcols(int dtype, hipStream_t s, const void* x, int64_t ldx, int64_t N, const void* xt, int64_t ldt, int64_t nt, const void* invl, int d,
+                     int family, double variance, void* out, int64_t ldo) {
+  for (int64_t c0 = 0; c0 < nt; c0 += 32768) {
+    const int64_t nc = nt - c0 < 32768 ? nt - c0 : 32768;
+    const dim3 g = grid2(N, nc);
+    if (dtype == 0) hipLaunchKernelGGL(cg_kcols_kernel<double>, g, dim3(256), 0, s, (const double*)x, ldx, N, (const double*)xt + c0, ldt, (const double*)invl, d, family, variance, (double*)out + c0 * ldo, ldo);
+    else hipLaunchKernelGGL(cg_kcols_kernel<float>, g, dim3(256), 0, s, (const float*)x, ldx, N, (const float*)xt + c0, ldt, (const float*)invl, d, family, variance, (float*)out + c0 * ldo, ldo);
+  }
+}
+
+}  // namespace svgp

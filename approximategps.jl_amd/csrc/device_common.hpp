@@ -158,6 +158,21 @@ __device__ __forceinline__ T kappa(int family, T r2, T variance) {
   return variance * (T(1) + s + T(5.0 / 3.0) * r2) * kexp(-s);
 }
 
+// 2 g(r^2) = 2 d kappa / d(r^2) (kappa carries the variance), from the subexpressions kappa<T> forms; kval = kappa(family, r2, variance).
+// No division by r: finite at r = 0 (sample_grad.hip: the samples' input gradients; cg.hip: the lengthscale gradient of K)
+//   SE -variance e^{-r^2 / 2} = -kappa;   Matern-3/2  -3 variance e^{-sqrt(3) r};   Matern-5/2  -(5/3) variance (1 + sqrt(5) r) e^{-sqrt(5) r}
+template <typename T>
+__device__ __forceinline__ T kappa_2g(int family, T r2, T variance, T kval) {
+  if (family == KSE) return -kval;
+  T r = ksqrt(r2);
+  if (family == KM32) {
+    T s = T(1.7320508075688772935) * r;
+    return (T(-3) * variance) * kexp(-s);
+  }
+  T s = T(2.2360679774997896964) * r;
+  return (T(-5.0 / 3.0) * variance) * ((T(1) + s) * kexp(-s));
+}
+
 // ---------------------------------------------------------------------------------------------
 // TileGemm: acc(128 x NT) += P(128 x K) * Q(K x NT) on an NTHR-thread workgroup
 // ---------------------------------------------------------------------------------------------

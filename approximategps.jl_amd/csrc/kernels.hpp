@@ -317,5 +317,40 @@ void launch_sample_phiz(int dtype, hipStream_t s, const double* zs64, const void
 void launch_sample_panel(int dtype, hipStream_t s, const void* w, const double* V, int64_t L, int64_t Lp, int64_t M, int64_t Mp, int64_t S, int64_t Sp,
                          double amp, void* panel);
 
+// cg.hip: out[s * ldo + i] = sum_j prof(r^2(P_i, R_j)) V[s * ldv + j] (+ diag addv[s * lda + i]) for the n points P and the N rows R
+struct KmvArgs {
+  const void* rows;    // [d][Np] the rows R as launch_kmv_prep wrote them
+  const void* bias;    // [Np]
+  const void* invl;    // [d]
+  const void* px;      // [d][ldp] the points P, feature-major, unscaled
+  const void* V;       // N x S panel, column-major
+  const void* addv;    // nullable: n x S, column-major
+  void* out;           // n x S, column-major
+  int64_t ldp, n, N, Np, ldv, lda, ldo, S;
+  int64_t s0;          // first column of the launch's column block (set by the launcher)
+  int family, d;
+  int profile;         // 0: kappa;  1: 2 g(r^2) (xs_ic - xs_jc)^2 of the coordinate `coord`, g = d kappa / d(r^2)
+  int coord;
+  int self;            // 1: P is R itself (point i is row i): r^2 of the diagonal is exactly 0
+  double variance, diag;
+};
+void launch_kmv(int dtype, hipStream_t s, const KmvArgs& a);   // one launch per block of <= 64 columns
+void launch_kmv_prep(int dtype, hipStream_t s, const void* x, int64_t ldx, const void* invl, int d, int64_t N, int64_t Np, void* rows, void* bias);
+// the fp64 state of one column block of the solver (<= 64 columns), on the device
+struct CgState {
+  enum : int { BB = 0, RR = 64, A = 128, BE = 192, IT = 256, ACT = 320, BAD = 384, WORDS = 392 };   // the host reads [ACT, WORDS) per iteration
+};
+int cg_dot_blocks(int64_t N);   // blocks of the first stage of a column dot: a function of N alone
+// partial[col * cg_dot_blocks(N) + blk] of sum_i a[i, col] b[i, col] (fp64), then their sums blk ascending
+void launch_cg_dot(int dtype, hipStream_t s, const void* a, int64_t lda, const void* b, int64_t ldb, int64_t N, int64_t ncols, double* partial);
+void launch_cg_colsum(hipStream_t s, const double* partial, int64_t N, int64_t ncols, double* out);
+void launch_cg_coef(hipStream_t s, int mode, double* st, const double* partial, int64_t N, int ncols, int k, double tol2, double* hist_a, double* hist_b);
+void launch_cg_update_xr(int dtype, hipStream_t s, const double* st, int64_t N, int ncols, void* x, void* r, const void* p, const void* q);
+void launch_cg_update_p(int dtype, hipStream_t s, const double* st, int64_t N, int ncols, const void* r, void* p);
+// dst = alpha src + beta, column by column (src in fp64 with src_f64, otherwise in the data dtype)
+void launch_cg_affine(int dtype, hipStream_t s, const void* src, int src_f64, int64_t lds, int64_t N, int64_t ncols, double alpha, double beta, void* dst, int64_t ldd);
+void launch_cg_kcols(int dtype, hipStream_t s, const void* x, int64_t ldx, int64_t N, const void* xt, int64_t ldt, int64_t nt, const void* invl, int d,
+                     int family, double variance, void* out, int64_t ldo);
+
 
 }  // namespace svgp

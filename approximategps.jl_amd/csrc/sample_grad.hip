@@ -45,19 +45,7 @@ constexpr int grad_point_groups() {
   return (sizeof(T) == 8 || DREG == 8) ? 1 : 2;
 }
 
-// 2 g(r^2) = 2 variance dkappa / d(r^2), from the subexpressions kappa<T> forms (device_common.hpp); no division by r: finite at r = 0
-//   SE -variance e^{-r^2 / 2} = -kappa;   Matern-3/2  -3 variance e^{-sqrt(3) r};   Matern-5/2  -(5/3) variance (1 + sqrt(5) r) e^{-sqrt(5) r}
-template <typename T>
-__device__ __forceinline__ T kappa_2g(int family, T r2, T variance, T kval) {
-  if (family == KSE) return -kval;
-  T r = ksqrt(r2);
-  if (family == KM32) {
-    T s = T(1.7320508075688772935) * r;
-    return (T(-3) * variance) * kexp(-s);
-  }
-  T s = T(2.2360679774997896964) * r;
-  return (T(-5.0 / 3.0) * variance) * ((T(1) + s) * kexp(-s));
-}
+// 2 g(r^2) = 2 variance dkappa / d(r^2): kappa_2g<T> of device_common.hpp, beside kappa<T>
 
 // One workgroup = 4 waves; a wave owns PG groups of 16 points, the 16 samples s0 .. s0 + 15 and the coordinates e0 .. e0 + CB - 1.
 // The inducing rows of the chunk hold -2 zs (then zs = -rows / 2, exact) or, for fp32 with d <= 8 (DIFF), z itself: there the scaled

@@ -826,6 +826,74 @@ int32_t svgp_sampler_free(svgp_ctx* ctx, svgp_sampler* sampler);
 int32_t svgp_sampler_eval_grad(svgp_ctx* ctx, const svgp_sampler* sampler, const svgp_data* data, int64_t batch_off, int64_t batch_len,
                                const svgp_point_mean* pm, void* out, int64_t ldo, void* grad_out, int64_t ldg, int32_t out_on_device);
 
+/* ---- the exact GP by matrix-free conjugate gradients -------------------------------------------------------------------------------
+ * Khat = K(x, x) + diag I over the N points of a data handle, delta = y - mean_const (or the caller's delta):
+ *   alpha = Khat^-1 delta,   lml = -1/2 (delta' alpha + log det Khat + N log 2 pi),   the exact GP regression beyond the dense limit.
+ * No entry of K is stored: the only O(N^2) work is one kernel that generates K tile by tile on the MFMA and feeds each tile straight
+ * into the product with an N x S panel; memory is O(N S).  SE / Matern-3/2 / Matern-5/2 with ARD, d <= SVGP_MAX_D, fp64 and fp32
+ * data; vectors are held in the data dtype, every dot product, norm and CG scalar in fp64.  The handle borrows the data handle, which
+ * must outlive it.  ALWAYS LOCAL (never collective).  Found by symbol (no ABI version step).
+ *   matvec  out = Khat V for an N x S panel (column-major, ldv / ldo >= N, data dtype; on_device: both are device pointers).
+ *   solve   X = Khat^-1 B by batched conjugate gradients, any S >= 1, in column blocks of 64 (workspace: five N x 64 arrays).  A
+ *           column stops when |r|_2 <= tol |b|_2 (norms in fp64) and its iterates are frozen from then on: A COLUMN'S SOLUTION AND
+ *           ITERATION COUNT DO NOT DEPEND, BITWISE, ON WHICH OTHER COLUMNS SHARE THE CALL (an MFMA output column depends on its own
+ *           panel column alone; every sum has a fixed order, there are no floating-point atomics), and repeated calls are bitwise
+ *           equal.  b = 0 gives x = 0 in 0 iterations.  Running out of maxiter is SVGP_OK with info->converged = 0: iters_out[s],
+ *           relres_out[s] (|r| / |b| per column; both nullable) and info report it.  A curvature p' Khat p that is not > 0, NaN
+ *           included, is SVGP_NOT_POSDEF and every output is NaN.  The host reads one array of 64 flags per iteration; the CG
+ *           coefficients of every column stay on the device until the block is done.
+ *   fit     one batched solve of [delta, z_1 .. z_T]: quad = delta' alpha; logdet ~ (1 / T) sum_t |z_t|^2 e_1' log(T_t) e_1 by stochastic
+ *           Lanczos quadrature, T_t the Lanczos tridiagonal rebuilt from column t's CG coefficients (svgp_lanczos_logdet, fp64 on the
+ *           host).  probes: N x T host doubles, column-major, drawn by the caller (E z z' = I: Rademacher columns; sqrt(N) e_t for
+ *           t = 1 .. N makes the estimate exact); the library draws no random numbers.  delta: N host doubles, or NULL for
+ *           y - mean_const.  With T = 0 lml and logdet are NaN and quad is valid.  Caches alpha and the parameter set for predict.
+ *   lml_grad  fit, and with w_t = Khat^-1 z_t from the same solve  d lml / d theta = 1/2 alpha' dKhat alpha - (1 / 2T) sum_t w_t' dKhat z_t
+ *           for theta = variance, inv_lengthscale[d], diag; d_mean_const = sum alpha.  d_diag and d_mean_const may be NULL.
+ *   alpha   the N weights of the last fit, data dtype, host.
+ *   predict mean = mean_const + k(x*, X) alpha; var = k** - k*' Khat^-1 k* by a batched solve with k(X, x*) as right-hand sides at the
+ *           fit's tol and maxiter, which info reports.  mean_out / var_out: n entries of the data dtype, host, each nullable.  With
+ *           var_out, n N <= 2^28 elements; beyond it SVGP_UNSUPPORTED and the caller tiles x*.
+ * SVGP_INVALID_ARG, before anything is enqueued: a NULL required pointer; descriptor dtype or d different from the data's; an unknown
+ * kernel; data without y when delta is NULL; maxiter < 1, tol <= 0, diag < 0, variance <= 0, reserved != 0 (NaN counts as a violation);
+ * S < 1; T < 0, or T > 0 with NULL probes; ldv, ldo, ldb or ldx < N; on_device not 0 / 1; alpha or predict before a successful fit;
+ * n < 1.  Out of scope: preconditioning, per-point noise, cov / cross-cov, pathwise samples, multi-GPU, the Julia hooks. */
+typedef struct svgp_cg svgp_cg;
+typedef struct svgp_cg_desc {
+  int32_t dtype, kernel, d, maxiter; /* maxiter >= 1 */
+  double variance;
+  const double* inv_lengthscale;     /* [d] */
+  double diag;                       /* >= 0 */
+  double mean_const;
+  double tol;                        /* > 0: a column stops when |r|_2 <= tol |b|_2, norms in fp64 */
+  int64_t reserved;                  /* 0 */
+} svgp_cg_desc;                      /* 64 bytes */
+typedef struct svgp_cg_info {
+  int32_t iterations;                /* max over columns */
+  int32_t converged;                 /* 1: every column met tol */
+  int32_t n_unconverged, reserved;
+  double max_rel_residual, quad, logdet, lml; /* quad, logdet, lml: NaN from the calls that do not form them */
+  double ms_matvec, ms_vector;       /* device time of the kmv products / of the vector stage, summed over iterations */
+} svgp_cg_info;                      /* 64 bytes */
+int32_t svgp_cg_create(svgp_ctx* ctx, const svgp_data* data, svgp_cg** out);
+int32_t svgp_cg_free(svgp_ctx* ctx, svgp_cg* cg);
+int32_t svgp_cg_matvec(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int64_t S, const void* V, int64_t ldv, void* out, int64_t ldo,
+                       int32_t on_device);
+int32_t svgp_cg_solve(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int64_t S, const void* B, int64_t ldb, void* X, int64_t ldx,
+                      int32_t on_device, int32_t* iters_out, double* relres_out, svgp_cg_info* info);
+int32_t svgp_cg_fit(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                    double* lml_out, svgp_cg_info* info);
+int32_t svgp_cg_lml_grad(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                         double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale, double* d_diag,
+                         double* d_mean_const);
+int32_t svgp_cg_alpha(svgp_ctx* ctx, svgp_cg* cg, void* alpha_out);
+int32_t svgp_cg_predict(svgp_ctx* ctx, svgp_cg* cg, int32_t layout, int64_t n, const void* x_host, void* mean_out, void* var_out,
+                        svgp_cg_info* info);
+/* host only, like svgp_gausshermite: out = e_1' log(T) e_1 for the Lanczos tridiagonal of `iters` CG steps with step lengths a[j] and
+ * residual ratios b[j] = |r_{j+1}|^2 / |r_j|^2 (diagonal 1 / a_j + b_{j-1} / a_{j-1}, off-diagonal sqrt(b_j) / a_j; b[iters - 1] is not
+ * read), by an implicit-shift QL iteration in fp64.  SVGP_INVALID_ARG: NULL pointers, iters < 1; SVGP_NOT_POSDEF (out = NaN): an
+ * eigenvalue that is not > 0. */
+int32_t svgp_lanczos_logdet(const double* a, const double* b, int32_t iters, double* out);
+
 #ifdef __cplusplus
 }
 #endif
