@@ -241,6 +241,15 @@ SYMBOLS = {
                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "svgp_cg_alpha": (C.c_int32, [_P, _P, _P]),
     "svgp_cg_predict": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P, C.POINTER(CGInfo)]),
+    "svgp_cg_set_preconditioner": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.c_double]),
+    "svgp_cg_precond_cross": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32]),
+    "svgp_cg_precond_apply": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32,
+                                          C.POINTER(C.c_double)]),
+    "svgp_cg_fit_precond": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(CGInfo)]),
+    "svgp_cg_lml_grad_precond": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(CGInfo), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "svgp_lanczos_logdet": (C.c_int32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),

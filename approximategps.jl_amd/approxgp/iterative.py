@@ -22,13 +22,27 @@ def draw_probes(N: int, T: int, rng=None):
     return np.asfortranarray(rng.integers(0, 2, size=(int(N), int(T))).astype(np.float64) * 2.0 - 1.0)
 
 
+MAX_PRECOND = 2048   # svgp_cg_set_preconditioner's limit
+
+
+def _seed_int(seed):
+    if seed is None or int(seed) != seed or int(seed) < 0:
+        raise ValueError("a preconditioner needs a non-negative integer seed")
+    return int(seed)
+
+
 class ConjugateGradients:
     """ConjugateGradients(tol, maxiter, n_probes, seed, probes): logpdf(fx, y), its gradient and the posterior of the exact GP by
     iterative solves against K(x, x) + Σy, never stored.  tol None: 1e-8, and 1e-4 for float32 data.  The log det comes from n_probes
     Rademacher vectors drawn from default_rng(seed) - the same vectors on every call, so the objective is a deterministic function of
-    the hyperparameters (common random numbers) - or from the caller's (N, T) probes."""
+    the hyperparameters (common random numbers) - or from the caller's (N, T) probes.
+    precond_size = k > 0 or precond_points (a (d, k) array, e.g. a trained model's z; a plain vector for d = 1) sets the Nystrom
+    preconditioner P = Z Kuu^-1 Z' + Σy I of k points: without points, a subset of the data drawn from default_rng([seed, 2]) without
+    replacement, k clipped to N.  precond_jitter (times the kernel variance) is added to Kuu.  The k-sized part of the probes comes from
+    default_rng([seed, 1]); the (N, T) probes of a seed do not depend on the preconditioner."""
 
-    def __init__(self, tol=None, maxiter: int = 1000, n_probes: int = 16, seed: int = 0, probes=None):
+    def __init__(self, tol=None, maxiter: int = 1000, n_probes: int = 16, seed: int = 0, probes=None, precond_size: int = 0,
+                 precond_points=None, precond_jitter: float = 1e-4):
         if tol is not None and not float(tol) > 0:
             raise ValueError("ConjugateGradients needs tol > 0")
         if int(maxiter) != maxiter or int(maxiter) < 1:
@@ -39,8 +53,25 @@ class ConjugateGradients:
             probes = np.asarray(probes, dtype=np.float64)
             if probes.ndim != 2:
                 raise ValueError("probes is an (N, T) array")
+        if int(precond_size) != precond_size or int(precond_size) < 0:
+            raise ValueError("ConjugateGradients needs precond_size >= 0")
+        if not float(precond_jitter) >= 0:
+            raise ValueError("ConjugateGradients needs precond_jitter >= 0")
+        if precond_points is not None:
+            precond_points = np.asarray(precond_points, dtype=np.float64)
+            if precond_points.ndim == 1:
+                precond_points = precond_points[None, :]
+            if precond_points.ndim != 2 or precond_points.shape[1] < 1:
+                raise ValueError("precond_points is a (d, k) array with k >= 1")
+            if precond_points.shape[1] > MAX_PRECOND:
+                raise ValueError(f"at most {MAX_PRECOND} preconditioner points")
+            if precond_size not in (0, precond_points.shape[1]):
+                raise ValueError("precond_size differs from the number of precond_points")
+        elif int(precond_size) > MAX_PRECOND:
+            raise ValueError(f"at most {MAX_PRECOND} preconditioner points")
         self.tol = None if tol is None else float(tol)
         self.maxiter, self.n_probes, self.seed, self.probes = int(maxiter), int(n_probes), seed, probes
+        self.precond_size, self.precond_points, self.precond_jitter = int(precond_size), precond_points, float(precond_jitter)
 
     def tol_for(self, dtype) -> float:
         if self.tol is not None:
@@ -54,6 +85,22 @@ class ConjugateGradients:
             return np.asfortranarray(self.probes)
         return draw_probes(N, self.n_probes, self.seed)
 
+    def precond_points_for(self, x):
+        """-> the (d, k) preconditioner points for the (d, N) inputs x, or None"""
+        if self.precond_points is not None:
+            if self.precond_points.shape[0] != x.shape[0]:
+                raise ValueError("precond_points have a different dimension than the data")
+            return self.precond_points
+        if self.precond_size == 0:
+            return None
+        N = x.shape[1]
+        idx = np.random.default_rng([_seed_int(self.seed), 2]).choice(N, size=min(self.precond_size, N), replace=False)
+        return np.asarray(x, dtype=np.float64)[:, idx]
+
+    def probes_k_for(self, k: int, T: int):
+        """(k, T) Rademacher columns from default_rng([seed, 1]): the preconditioner's part of the probes"""
+        return draw_probes(k, T, np.random.default_rng([_seed_int(self.seed), 1]))
+
 
 class DeviceConjugateGradients:
     """A resident svgp_cg handle over x (and y): x a plain vector (d = 1) or a (d, n) ColVecs array; with layout = ROWVECS an (n, d)
@@ -66,6 +113,7 @@ class DeviceConjugateGradients:
             layout = _ffi.VEC if x.ndim == 1 else _ffi.COLVECS
         self.data = _ffi.DeviceData(ctx, x, y, dtype, layout)
         self.dtype, self.d, self.n = self.data.dtype, self.data.d, self.data.n
+        self.precond_k = 0   # points of the preconditioner set through set_preconditioner
         h = C.c_void_p()
         ctx.check(ctx.lib.svgp_cg_create(ctx.h, self.data.h, C.byref(h)))
         self.h = h
@@ -145,26 +193,111 @@ class DeviceConjugateGradients:
     def _f64(a):
         return None if a is None else np.asfortranarray(np.asarray(a, dtype=np.float64))
 
-    def fit(self, desc, probes=None, delta=None):
-        """-> (lml, CGInfo); caches alpha for predict.  probes: (N, T) float64 or None (T = 0: lml is NaN, info.quad valid)."""
-        z, dl = self._f64(probes), self._f64(delta)
+    def set_preconditioner(self, points=None, jitter=1e-4, layout=None):
+        """The Nystrom preconditioner's k points: x as for the handle ((d, k), a plain vector for d = 1, or (k, d) with ROWVECS);
+        None removes it."""
+        if points is None:
+            self.ctx.check(self.ctx.lib.svgp_cg_set_preconditioner(self.ctx.h, self.h, _ffi.COLVECS, 0, None, 0.0))
+            self.precond_k = 0
+            return
+        z = np.asarray(points, dtype=_ffi.np_dtype(self.dtype))
+        if z.ndim == 1:
+            if self.d != 1:
+                raise ValueError("preconditioner points have a different dimension than the data")
+            layout, k, zb = _ffi.VEC, z.shape[0], np.ascontiguousarray(z)
+        elif layout == _ffi.ROWVECS:
+            if z.ndim != 2 or z.shape[1] != self.d:
+                raise ValueError("preconditioner points have a different dimension than the data")
+            k, zb = z.shape[0], np.asfortranarray(z)
+        else:
+            if z.ndim != 2 or z.shape[0] != self.d:
+                raise ValueError("preconditioner points have a different dimension than the data")
+            layout, k, zb = _ffi.COLVECS, z.shape[1], np.asfortranarray(z)
+        if k < 1:
+            raise ValueError("at least one preconditioner point (None removes the preconditioner)")
+        self.ctx.check(self.ctx.lib.svgp_cg_set_preconditioner(self.ctx.h, self.h, layout, k, _ffi._ptr(zb), float(jitter)))
+        self.precond_k = k
+
+    def _need_precond(self):
+        if not self.precond_k:
+            raise ValueError("no preconditioner is set (set_preconditioner)")
+        return self.precond_k
+
+    def precond_cross(self, desc, V, out=None):
+        """K(z_p, x) V, (k, S), for an (N, S) panel: the row-split kernel alone.  A torch device tensor ((S, N), contiguous) needs out
+        as an (S, k) contiguous device tensor."""
+        k = self._need_precond()
+        vp, ldv, S, dev, keep = self._cols(V, "V")
+        if S < 1:
+            raise ValueError("V: an (N, S) array with S >= 1")
+        if dev:
+            shapes = ((S, k), (k,)) if V.dim() == 1 else ((S, k),)
+            if (out is None or not _ffi._is_device_tensor(out) or not out.is_contiguous() or out.dtype != V.dtype
+                    or tuple(out.shape) not in shapes):
+                raise ValueError("out: a contiguous (S, k) device tensor of the data dtype")
+            res, op = out, C.c_void_p(int(out.data_ptr()))
+        else:
+            res = np.zeros((k, S), dtype=_ffi.np_dtype(self.dtype), order="F")
+            op = _ffi._ptr(res)
+        self._check(self.ctx.lib.svgp_cg_precond_cross(self.ctx.h, self.h, C.byref(desc), S, vp, ldv, op, k, dev))
+        return res
+
+    def precond_apply(self, desc, R, out=None):
+        """-> (P^-1 R, log det P) for an (N, S) panel"""
+        self._need_precond()
+        rp, ldr, S, dev, keep = self._cols(R, "R")
+        if S < 1:
+            raise ValueError("R: an (N, S) array with S >= 1")
+        if dev:
+            if out is None or not _ffi._is_device_tensor(out):
+                raise ValueError("out: a device tensor like R")
+            op, ldo, So, _, _ = self._cols(out, "out")
+            if So != S:
+                raise ValueError("out: a device tensor like R")
+            res = out
+        else:
+            res = np.zeros((self.n, S), dtype=_ffi.np_dtype(self.dtype), order="F")
+            op, ldo = _ffi._ptr(res), self.n
+        ld = C.c_double()
+        self._check(self.ctx.lib.svgp_cg_precond_apply(self.ctx.h, self.h, C.byref(desc), S, rp, ldr, op, ldo, dev, C.byref(ld)))
+        return res, ld.value
+
+    def _probes(self, probes, probes_k):
+        z, zk = self._f64(probes), self._f64(probes_k)
         T = 0 if z is None else z.shape[1]
-        lml, info = C.c_double(), _ffi.CGInfo()
+        if zk is not None:
+            if zk.ndim != 2 or zk.shape != (self._need_precond(), T):
+                raise ValueError("probes_k: a (k, T) array beside the (N, T) probes")
         dp = C.POINTER(C.c_double)
-        self._check(self.ctx.lib.svgp_cg_fit(self.ctx.h, self.h, C.byref(desc), None if dl is None else dl.ctypes.data_as(dp), T,
-                                             None if z is None or T == 0 else z.ctypes.data_as(dp), C.byref(lml), C.byref(info)))
+        return T, (None if z is None or T == 0 else z.ctypes.data_as(dp)), (None if zk is None or T == 0 else zk.ctypes.data_as(dp)), (z, zk)
+
+    def fit(self, desc, probes=None, delta=None, probes_k=None):
+        """-> (lml, CGInfo); caches alpha for predict.  probes: (N, T) float64 or None (T = 0: lml is NaN, info.quad valid); probes_k:
+        the (k, T) part a preconditioner's probes need."""
+        T, zp, zkp, keep = self._probes(probes, probes_k)
+        dl = self._f64(delta)
+        lml, info = C.c_double(), _ffi.CGInfo()
+        dlp = None if dl is None else dl.ctypes.data_as(C.POINTER(C.c_double))
+        if probes_k is None:
+            self._check(self.ctx.lib.svgp_cg_fit(self.ctx.h, self.h, C.byref(desc), dlp, T, zp, C.byref(lml), C.byref(info)))
+        else:
+            self._check(self.ctx.lib.svgp_cg_fit_precond(self.ctx.h, self.h, C.byref(desc), dlp, T, zp, zkp, C.byref(lml), C.byref(info)))
         return lml.value, info
 
-    def lml_grad(self, desc, probes, delta=None):
+    def lml_grad(self, desc, probes, delta=None, probes_k=None):
         """-> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const"}, CGInfo)"""
-        z, dl = self._f64(probes), self._f64(delta)
-        T = 0 if z is None else z.shape[1]
+        T, zp, zkp, keep = self._probes(probes, probes_k)
+        dl = self._f64(delta)
         lml, info = C.c_double(), _ffi.CGInfo()
         dv, dd, dm, dil = C.c_double(), C.c_double(), C.c_double(), np.zeros(self.d)
         dp = C.POINTER(C.c_double)
-        self._check(self.ctx.lib.svgp_cg_lml_grad(self.ctx.h, self.h, C.byref(desc), None if dl is None else dl.ctypes.data_as(dp), T,
-                                                  None if z is None or T == 0 else z.ctypes.data_as(dp), C.byref(lml), C.byref(info),
-                                                  C.byref(dv), dil.ctypes.data_as(dp), C.byref(dd), C.byref(dm)))
+        dlp = None if dl is None else dl.ctypes.data_as(dp)
+        if probes_k is None:
+            self._check(self.ctx.lib.svgp_cg_lml_grad(self.ctx.h, self.h, C.byref(desc), dlp, T, zp, C.byref(lml), C.byref(info),
+                                                      C.byref(dv), dil.ctypes.data_as(dp), C.byref(dd), C.byref(dm)))
+        else:
+            self._check(self.ctx.lib.svgp_cg_lml_grad_precond(self.ctx.h, self.h, C.byref(desc), dlp, T, zp, zkp, C.byref(lml), C.byref(info),
+                                                              C.byref(dv), dil.ctypes.data_as(dp), C.byref(dd), C.byref(dm)))
         return lml.value, {"variance": dv.value, "inv_lengthscale": dil, "diag": dd.value, "mean_const": dm.value}, info
 
     def alpha(self):
@@ -243,9 +376,22 @@ def _device(cg: ConjugateGradients, fx: FiniteGP, y, ctx, dtype):
     diag, mean_const, delta = _check_inputs(fx, y)
     dt = _nn._dtype_of(fx, dtype)
     probes = cg.probes_for(fx.n)
+    xa = np.asarray(fx.x)
+    points = cg.precond_points_for(xa[None, :] if xa.ndim == 1 else xa)
+    probes_k = None
+    if points is not None:
+        if not diag > 0:
+            raise ValueError("the preconditioner needs observation noise fx.Σy > 0")
+        probes_k = cg.probes_k_for(points.shape[1], probes.shape[1])
     dev = DeviceConjugateGradients(ctx or _ffi.default_context(), fx.x, y, dt)
-    desc, keep = dev.desc(fx.f.kernel, diag, mean_const, cg.tol_for(dt), cg.maxiter)
-    return dev, desc, keep, probes, delta
+    try:
+        if points is not None:
+            dev.set_preconditioner(points[0] if dev.d == 1 and xa.ndim == 1 else points, cg.precond_jitter)
+        desc, keep = dev.desc(fx.f.kernel, diag, mean_const, cg.tol_for(dt), cg.maxiter)
+    except Exception:
+        dev.free()
+        raise
+    return dev, desc, keep, (probes, probes_k), delta
 
 
 def approx_lml(approx, fx, y, **kwargs):
@@ -256,7 +402,7 @@ def approx_lml(approx, fx, y, **kwargs):
     ctx, dtype = _cg_kwargs("approx_lml", kwargs)
     dev, desc, keep, probes, delta = _device(approx, fx, y, ctx, dtype)
     try:
-        lml, info = dev.fit(desc, probes, delta)
+        lml, info = dev.fit(desc, probes[0], delta, probes_k=probes[1])
     finally:
         dev.free()
     _warn(info, "the fit")
@@ -271,7 +417,7 @@ def approx_lml_and_gradient(approx, fx, y, **kwargs):
     ctx, dtype = _cg_kwargs("approx_lml_and_gradient", kwargs)
     dev, desc, keep, probes, delta = _device(approx, fx, y, ctx, dtype)
     try:
-        lml, grads, info = dev.lml_grad(desc, probes, delta)
+        lml, grads, info = dev.lml_grad(desc, probes[0], delta, probes_k=probes[1])
     finally:
         dev.free()
     _warn(info, "the fit")
@@ -287,7 +433,7 @@ class CGPosteriorGP:
         self.dev, desc, keep, probes, delta = _device(cg, fx, y, ctx, dtype)
         self.noise = float(fx.Sigma_y)
         try:
-            self.lml, self.info = self.dev.fit(desc, probes, delta)
+            self.lml, self.info = self.dev.fit(desc, probes[0], delta, probes_k=probes[1])
         except Exception:
             self.dev.free()
             raise

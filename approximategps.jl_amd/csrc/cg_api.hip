@@ -5,6 +5,8 @@
 // the per-column scalars and the CG coefficients of every column stay on the device, the host reads the block's 64 activity flags (and
 // one failure flag) per iteration.  log det Khat by stochastic Lanczos quadrature from the caller's probe vectors: the Lanczos
 // tridiagonal of a column is rebuilt from its CG coefficients, its eigen-decomposition runs in fp64 on the host.
+// svgp_cg_set_preconditioner / _precond_cross / _precond_apply / _fit_precond / _lml_grad_precond: the Nystrom preconditioner of the same
+// solves (CgPrecond below), set up on the device once per call and applied with two kernel products of N k generated entries.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,6 +29,25 @@ struct CgPar {   // one parameter set, host side
 };
 }  // namespace
 
+// The Nystrom preconditioner P = Z Kuu^-1 Z' + sigma^2 I, Z = K(X, z_p) for k points z_p, Kuu = K(z_p, z_p) + jitter variance I = Lu Lu':
+//   P^-1 r = (r - Z W Z' r) / sigma^2,  W = Lu^-T B^-1 Lu^-1 / sigma^2,  B = I + Lu^-1 (Z'Z) Lu^-T / sigma^2,  log det P = N log sigma^2 + log det B
+// Z' r is the row-split product (launch_kmv_split), Z c the existing kmv_kernel with the k points as its rows, whose epilogue adds
+// r / sigma^2.  The k-sized stage (Kuu, Lu, the Gram Z'Z, B, its factor, W) is fp64 for both data dtypes: the Gram is accumulated in
+// fp64 from fp64 entries (in float32 accumulation B is not positive definite), so an fp32 handle widens x and z_p for the setup.
+struct CgPrecond {
+  int64_t k = 0, kp = 0, Mp = 0;   // points, padded to 32 (kmv's chunk) and to 128 (the factorisations' tile)
+  double jitter = 0;
+  svgp_data* z = nullptr;          // the points, data dtype, feature-major
+  DevBuf rows, bias;               // kmv_prep of the points under the running parameter set (data dtype)
+  DevBuf part, t, v;               // the split product's partials; Z' r and -W Z' r / sigma^2 (kp x S, data dtype)
+  DevBuf x64, z64, invl64, rows64, bias64;   // fp32 handles: the fp64 operands of the Gram
+  DevBuf zblk;                     // N x 64 fp64: a column block of Z
+  DevBuf zs64, Lu, Tu, LinvRM, LinvCM, Ytmp, G, H, H2, Bm, TB, LBinvRM, LBinvCM, W, info, info_b, scal;   // fp64, Mp x Mp
+  DevBuf rho, xi;                  // the solver's r'z words; the k x T probes
+  bool x64_ready = false, z64_ready = false;   // x of a handle never changes; the points change with set_preconditioner
+  double s2 = 0, logdet_p = 0, ms_setup = 0;
+};
+
 struct svgp_cg {
   const svgp_data* data = nullptr;
   int dtype = 0, d = 0, device = 0;
@@ -39,13 +60,15 @@ struct svgp_cg {
   DevBuf f64tmp;             // fp64 staging of delta and the probes
   bool have_fit = false;
   CgPar fit;                 // the parameter set alpha belongs to
+  CgPrecond pc;              // pc.k == 0: none
+  ~svgp_cg() { delete pc.z; }
 };
 
 namespace {
 
 constexpr int64_t kCgMaxPredict = int64_t(1) << 28;   // n N elements of the predictive variance's right-hand sides in one call
 
-struct CgHist {   // per column: its CG coefficients and |b|^2
+struct CgHist {   // per column: its CG coefficients and |b|^2 (preconditioned: b' P^-1 b, the weight of its quadrature)
   std::vector<std::vector<double>> a, b;
   std::vector<double> bb;
 };
@@ -82,8 +105,197 @@ CgPar par_of(const svgp_cg_desc* ds) {
   return p;
 }
 
-// the parameter set on the device: invl in the data dtype, the scaled padded rows and their bias (once per call)
-int set_params(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p) {
+void kmv_args(const svgp_cg* cg, const CgPar& p, KmvArgs& a) {
+  a = KmvArgs{};
+  a.invl = cg->invl.p;
+  a.family = p.family;
+  a.d = cg->d;
+  a.variance = p.variance;
+}
+
+// K(z_p, X) V (k x S, ldo) by the row-split kernel, in the data dtype
+int pc_cross(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, const void* V, int64_t ldv, int64_t S, void* out, int64_t ldo) {
+  CgPrecond& pc = cg->pc;
+  int64_t seg_rows = 0;
+  const int nseg = kmv_split_segments(cg->N, pc.k, &seg_rows);
+  const int rc = pc.part.reserve(ctx, size_t(nseg) * 64 * size_t(pc.k) * cg->es, "the preconditioner's partial products");
+  if (rc) return rc;
+  KmvArgs a;
+  kmv_args(cg, p, a);
+  a.rows = cg->rows.p;
+  a.bias = cg->bias.p;
+  a.px = pc.z->x.p;
+  a.ldp = pc.z->ldx;
+  a.n = pc.k;
+  a.N = cg->N;
+  a.Np = cg->Np;
+  a.V = V;
+  a.ldv = ldv;
+  a.S = S;
+  a.out = out;
+  a.ldo = ldo;
+  launch_kmv_split(cg->dtype, ctx->stream, a, pc.part.p);
+  return SVGP_OK;
+}
+
+// out = K(X, z_p) V + diag addv: kmv_kernel with the k points as its rows (V: kp x S, zero on the padding rows)
+void pc_expand(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, const void* V, int64_t S, const void* addv, int64_t lda, double diag, void* out, int64_t ldo) {
+  const CgPrecond& pc = cg->pc;
+  KmvArgs a;
+  kmv_args(cg, p, a);
+  a.rows = pc.rows.p;
+  a.bias = pc.bias.p;
+  a.px = cg->data->x.p;
+  a.ldp = cg->data->ldx;
+  a.n = cg->N;
+  a.N = pc.k;
+  a.Np = pc.kp;
+  a.V = V;
+  a.ldv = pc.kp;
+  a.S = S;
+  a.addv = addv;
+  a.lda = lda;
+  a.out = out;
+  a.ldo = ldo;
+  a.diag = diag;
+  a.self = 0;   // the points are not the rows, even where they coincide with data points
+  launch_kmv(cg->dtype, ctx->stream, a);
+}
+
+// out = P^-1 R for S columns on the device (data dtype); out must not alias R
+int pc_apply(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, const void* R, int64_t ldr, int64_t S, void* out, int64_t ldo) {
+  CgPrecond& pc = cg->pc;
+  int rc;
+  if ((rc = pc.t.reserve(ctx, size_t(pc.kp) * size_t(S) * cg->es, "the preconditioner's products")) != SVGP_OK) return rc;
+  if ((rc = pc.v.reserve(ctx, size_t(pc.kp) * size_t(S) * cg->es, "the preconditioner's products")) != SVGP_OK) return rc;
+  if ((rc = pc_cross(ctx, cg, p, R, ldr, S, pc.t.p, pc.kp)) != SVGP_OK) return rc;
+  launch_cg_pc_mm(cg->dtype, ctx->stream, pc.W.as<double>(), pc.Mp, pc.k, pc.t.p, 0, pc.kp, S, -1.0 / (pc.s2 * pc.s2), pc.v.p, pc.kp, pc.kp);
+  pc_expand(ctx, cg, p, pc.v.p, S, R, ldr, 1.0 / pc.s2, out, ldo);
+  return SVGP_OK;
+}
+
+// the preconditioner of one parameter set: the points' rows, Kuu = Lu Lu', the Gram Z'Z, B and its factor, W, log det P
+int pc_setup(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p) {
+  CgPrecond& pc = cg->pc;
+  hipStream_t s = ctx->stream;
+  const int dt = cg->dtype, d = cg->d;
+  const int64_t N = cg->N, k = pc.k, kp = pc.kp, Mp = pc.Mp;
+  const size_t mm = size_t(Mp) * size_t(Mp) * 8;
+  int rc;
+  pc.s2 = dt == SVGP_F64 ? p.diag : double(float(p.diag));
+  pc.logdet_p = std::numeric_limits<double>::quiet_NaN();
+  pc.ms_setup = 0;
+  struct { DevBuf* b; size_t bytes; } req[] = {
+      {&pc.rows, size_t(d) * size_t(kp) * cg->es}, {&pc.bias, size_t(kp) * cg->es}, {&pc.zblk, size_t(N) * 64 * 8}, {&pc.zs64, size_t(d) * size_t(Mp) * 8},
+      {&pc.Lu, mm}, {&pc.Tu, mm}, {&pc.LinvRM, mm}, {&pc.LinvCM, mm}, {&pc.Ytmp, mm}, {&pc.G, mm}, {&pc.H, mm}, {&pc.H2, mm}, {&pc.Bm, mm}, {&pc.TB, mm},
+      {&pc.LBinvRM, mm}, {&pc.LBinvCM, mm}, {&pc.W, mm}, {&pc.info, info_bytes(Mp)}, {&pc.info_b, info_bytes(Mp)}, {&pc.scal, 64}, {&pc.rho, 128 * 8}};
+  for (auto& r : req)
+    if ((rc = r.b->reserve(ctx, r.bytes, "the preconditioner")) != SVGP_OK) return rc;
+  TREC(ctx, ctx->ev[2], s);
+  launch_kmv_prep(dt, s, pc.z->x.p, pc.z->ldx, cg->invl.p, d, k, kp, pc.rows.p, pc.bias.p);
+  // the fp64 operands of the Gram: the handle's own, or widened
+  const double *x64, *z64, *invl64;
+  const void *rows64, *bias64;
+  int64_t ldx64, ldz64;
+  if (dt == SVGP_F64) {
+    x64 = cg->data->x.as<double>(); ldx64 = cg->data->ldx;
+    z64 = pc.z->x.as<double>(); ldz64 = pc.z->ldx;
+    invl64 = cg->invl.as<double>();
+    rows64 = cg->rows.p; bias64 = cg->bias.p;
+  } else {
+    if ((rc = pc.x64.reserve(ctx, size_t(d) * size_t(N) * 8, "the preconditioner")) != SVGP_OK) return rc;
+    if ((rc = pc.z64.reserve(ctx, size_t(d) * size_t(k) * 8, "the preconditioner")) != SVGP_OK) return rc;
+    if ((rc = pc.invl64.reserve(ctx, size_t(SVGP_MAX_D) * 8, "the preconditioner")) != SVGP_OK) return rc;
+    if ((rc = pc.rows64.reserve(ctx, size_t(d) * size_t(cg->Np) * 8, "the preconditioner")) != SVGP_OK) return rc;
+    if ((rc = pc.bias64.reserve(ctx, size_t(cg->Np) * 8, "the preconditioner")) != SVGP_OK) return rc;
+    launch_cg_widen(dt, s, cg->invl.p, d, d, 1, pc.invl64.as<double>(), d);   // the rounded inverse lengthscales the data stage uses
+    if (!pc.x64_ready) launch_cg_widen(dt, s, cg->data->x.p, cg->data->ldx, N, d, pc.x64.as<double>(), N);
+    if (!pc.z64_ready) launch_cg_widen(dt, s, pc.z->x.p, pc.z->ldx, k, d, pc.z64.as<double>(), k);
+    pc.x64_ready = pc.z64_ready = true;
+    launch_kmv_prep(SVGP_F64, s, pc.x64.p, N, pc.invl64.p, d, N, cg->Np, pc.rows64.p, pc.bias64.p);
+    x64 = pc.x64.as<double>(); ldx64 = N;
+    z64 = pc.z64.as<double>(); ldz64 = k;
+    invl64 = pc.invl64.as<double>();
+    rows64 = pc.rows64.p; bias64 = pc.bias64.p;
+  }
+  // launch_potrf's contract: T zero above the diagonal; launch_linv writes the block-lower part only (the rest is read by the products)
+  for (DevBuf* b : {&pc.Tu, &pc.TB, &pc.LinvRM, &pc.LinvCM, &pc.LBinvRM, &pc.LBinvCM, &pc.G}) HIPC(ctx, hipMemsetAsync(b->p, 0, mm, s));
+  HIPC(ctx, hipMemsetAsync(pc.info.p, 0, info_bytes(Mp), s));
+  HIPC(ctx, hipMemsetAsync(pc.info_b.p, 0, info_bytes(Mp), s));
+  // Kuu + jitter variance I = Lu Lu' and Lu^-1
+  launch_cg_pc_scale(s, z64, ldz64, invl64, d, k, Mp, pc.zs64.as<double>());
+  KernelParams kp64;
+  kp64.family = p.family;
+  kp64.d = d;
+  kp64.variance = p.variance;
+  kp64.invl = invl64;
+  launch_kuu(SVGP_F64, s, kp64, pc.zs64.p, k, Mp, pc.jitter * p.variance, pc.Lu.p);
+  launch_potrf(SVGP_F64, s, pc.Lu.p, pc.Tu.p, Mp, pc.info.as<int>(), reinterpret_cast<unsigned*>(pc.info.as<int>() + 1), ctx->num_cus);
+  launch_linv(SVGP_F64, s, pc.Lu.p, pc.Tu.p, Mp, pc.LinvRM.p, pc.LinvCM.p, pc.Ytmp.p);
+  KCHECK(ctx, "cg preconditioner (Kuu, its factor)");
+  // G = Z'Z, a column block of Z at a time: the block explicitly (N x <= 64), then the row-split product with it as the panel
+  {
+    int64_t seg_rows = 0;
+    const int nseg = kmv_split_segments(N, k, &seg_rows);
+    if ((rc = pc.part.reserve(ctx, size_t(nseg) * 64 * size_t(k) * 8, "the preconditioner's partial products")) != SVGP_OK) return rc;
+    KmvArgs a{};
+    a.rows = rows64;
+    a.bias = bias64;
+    a.invl = invl64;
+    a.px = z64;
+    a.ldp = ldz64;
+    a.n = k;
+    a.N = N;
+    a.Np = cg->Np;
+    a.V = pc.zblk.p;
+    a.ldv = N;
+    a.ldo = Mp;
+    a.family = p.family;
+    a.d = d;
+    a.variance = p.variance;
+    for (int64_t j0 = 0; j0 < k; j0 += 64) {
+      const int64_t nb = k - j0 < 64 ? k - j0 : 64;
+      launch_cg_kcols(SVGP_F64, s, x64, ldx64, N, z64 + j0, ldz64, nb, invl64, d, p.family, p.variance, pc.zblk.p, N);
+      a.S = nb;
+      a.out = pc.G.as<double>() + j0 * Mp;
+      launch_kmv_split(SVGP_F64, s, a, pc.part.p);
+    }
+    KCHECK(ctx, "cg preconditioner (Gram)");
+  }
+  // B = I + Lu^-1 G Lu^-T / sigma^2 = LB LB'  (launch_gemm_pm: out = X'Y for row-major X, Y; LinvCM read row-major is Lu^-T)
+  launch_gemm_pm(SVGP_F64, s, pc.G.p, pc.LinvCM.p, nullptr, 1.0, Mp, Mp, Mp, 1, pc.H.p, 1, kMmFull);     // G Lu^-T
+  launch_gemm_pm(SVGP_F64, s, pc.H.p, pc.LinvCM.p, nullptr, 1.0, Mp, Mp, Mp, 1, pc.H2.p, 1, kMmFull);    // Lu^-1 G Lu^-T
+  launch_cg_pc_form_b(s, pc.H2.as<double>(), Mp, pc.s2, pc.Bm.as<double>());
+  launch_potrf(SVGP_F64, s, pc.Bm.p, pc.TB.p, Mp, pc.info_b.as<int>(), reinterpret_cast<unsigned*>(pc.info_b.as<int>() + 1), ctx->num_cus);
+  launch_cg_pc_logdet(s, pc.Bm.as<double>(), Mp, k, pc.scal.as<double>());
+  // W sigma^2 = Lu^-T B^-1 Lu^-1, B^-1 = LB^-T LB^-1
+  launch_linv(SVGP_F64, s, pc.Bm.p, pc.TB.p, Mp, pc.LBinvRM.p, pc.LBinvCM.p, pc.Ytmp.p);
+  launch_gemm_pm(SVGP_F64, s, pc.LBinvRM.p, pc.LBinvRM.p, nullptr, 1.0, Mp, Mp, Mp, 1, pc.H.p, 1, kMmFull);   // B^-1
+  launch_gemm_pm(SVGP_F64, s, pc.H.p, pc.LinvRM.p, nullptr, 1.0, Mp, Mp, Mp, 1, pc.H2.p, 1, kMmFull);         // B^-1 Lu^-1
+  launch_gemm_pm(SVGP_F64, s, pc.LinvRM.p, pc.H2.p, nullptr, 1.0, Mp, Mp, Mp, 1, pc.W.p, 1, kMmFull);         // Lu^-T B^-1 Lu^-1
+  KCHECK(ctx, "cg preconditioner (B, W)");
+  TREC(ctx, ctx->ev[3], s);
+  int iu = 0, ib = 0;
+  double ld = 0;
+  HIPC(ctx, hipMemcpyAsync(&iu, pc.info.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(&ib, pc.info_b.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(&ld, pc.scal.p, 8, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  float t = 0;
+  if (elapsed_ms(ctx, &t, ctx->ev[2], ctx->ev[3]) == hipSuccess) pc.ms_setup = t;
+  if (iu != 0 || ib != 0 || !(ld == ld)) {
+    char buf[200];
+    snprintf(buf, sizeof buf, "the preconditioner's %s is not positive definite: leading minor of order %d", iu ? "Kuu + jitter" : "B",
+             iu ? iu : ib);
+    return fail(ctx, SVGP_NOT_POSDEF, buf);
+  }
+  pc.logdet_p = double(N) * std::log(pc.s2) + ld;
+  return SVGP_OK;
+}
+
+// the parameter set on the device: invl in the data dtype, the scaled padded rows and their bias (once per call); precond: the
+// preconditioner's setup as well, when one is set
+int set_params(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, bool precond = true) {
   hipStream_t s = ctx->stream;
   const int d = cg->d;
   int rc;
@@ -100,6 +312,7 @@ int set_params(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p) {
   HIPC(ctx, hipStreamSynchronize(s));   // the staging arrays are this frame's
   launch_kmv_prep(cg->dtype, s, cg->data->x.p, cg->data->ldx, cg->invl.p, d, cg->N, cg->Np, cg->rows.p, cg->bias.p);
   KCHECK(ctx, "kmv_prep");
+  if (precond && cg->pc.k > 0) return pc_setup(ctx, cg, p);
   return SVGP_OK;
 }
 
@@ -134,7 +347,7 @@ void kmv(svgp_ctx* ctx, const svgp_cg* cg, const CgPar& p, const void* px, int64
 
 int ensure_solver(svgp_ctx* ctx, svgp_cg* cg, int64_t dot_cols, bool want_hist, int maxiter) {
   int rc;
-  if ((rc = cg->ws.reserve(ctx, size_t(5) * size_t(cg->N) * 64 * cg->es, "the CG workspace")) != SVGP_OK) return rc;
+  if ((rc = cg->ws.reserve(ctx, size_t(cg->pc.k > 0 ? 6 : 5) * size_t(cg->N) * 64 * cg->es, "the CG workspace")) != SVGP_OK) return rc;   // (z = P^-1 r)
   if ((rc = cg->st.reserve(ctx, size_t(CgState::WORDS) * 8, "the CG state")) != SVGP_OK) return rc;
   const int64_t cols = dot_cols < 64 ? 64 : dot_cols;
   if ((rc = cg->partial.reserve(ctx, size_t(cols) * size_t(cg_dot_blocks(cg->N)) * 8, "the CG dot partials")) != SVGP_OK) return rc;
@@ -143,7 +356,9 @@ int ensure_solver(svgp_ctx* ctx, svgp_cg* cg, int64_t dot_cols, bool want_hist, 
 }
 
 // X = Khat^-1 B for S columns on the device (data dtype), in blocks of 64.  iters_out / relres_out: per column, host, nullable.
-// SVGP_NOT_POSDEF: every column of X is NaN.  The caller has run ensure_solver and set_params.
+// SVGP_NOT_POSDEF: every column of X is NaN.  The caller has run ensure_solver and set_params.  With a preconditioner set (pc.k > 0)
+// the recurrence is the preconditioned one: z = P^-1 r, rho = r'z, a = rho / p'q, beta = rho_new / rho, p = z + beta p; the stopping
+// test stays on the true residual, and a, beta rebuild the Lanczos tridiagonal of P^-1/2 Khat P^-1/2 started at P^-1/2 b.
 int solve_core(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int64_t S, const void* B, int64_t ldb, void* X, int64_t ldx, int32_t* iters_out,
                double* relres_out, svgp_cg_info* info, CgHist* hist) {
   hipStream_t s = ctx->stream;
@@ -152,6 +367,10 @@ int solve_core(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int64_t S, const vo
   const size_t es = cg->es, col = size_t(N) * es;
   char* w = cg->ws.as<char>();
   void *x = w, *r = w + 64 * col, *p = w + 128 * col, *q = w + 192 * col;
+  const bool pc = cg->pc.k > 0;
+  void* z = pc ? w + 320 * col : nullptr;
+  double* rho = pc ? cg->pc.rho.as<double>() : nullptr;
+  int rc;
   double* st = cg->st.as<double>();
   double* partial = cg->partial.as<double>();
   double* ha = hist ? cg->hist.as<double>() : nullptr;
@@ -159,7 +378,8 @@ int solve_core(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int64_t S, const vo
   const double tol2 = par.tol * par.tol;
   svgp_cg_info out{};
   out.converged = 1;
-  double ms_mv = 0, ms_vec = 0;
+  double ms_mv = 0, ms_vec = pc ? cg->pc.ms_setup : 0;
+  if (pc) cg->pc.ms_setup = 0;   // (counted once)
   bool bad = false;
   if (hist) {
     hist->a.assign(size_t(S), {});
@@ -171,11 +391,17 @@ int solve_core(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int64_t S, const vo
     const int nc = int(S - c0 < 64 ? S - c0 : 64);
     const char* Bc = static_cast<const char*>(B) + size_t(c0) * size_t(ldb) * es;
     HIPC(ctx, hipMemcpy2DAsync(r, col, Bc, size_t(ldb) * es, col, size_t(nc), hipMemcpyDeviceToDevice, s));
-    HIPC(ctx, hipMemcpyAsync(p, r, col * nc, hipMemcpyDeviceToDevice, s));
+    if (!pc) HIPC(ctx, hipMemcpyAsync(p, r, col * nc, hipMemcpyDeviceToDevice, s));
     HIPC(ctx, hipMemsetAsync(x, 0, col * nc, s));
     HIPC(ctx, hipMemsetAsync(st, 0, size_t(CgState::WORDS) * 8, s));
     launch_cg_dot(dt, s, r, N, r, N, N, nc, partial);
     launch_cg_coef(s, 0, st, partial, N, nc, 0, tol2, nullptr, nullptr);
+    if (pc) {
+      if ((rc = pc_apply(ctx, cg, par, r, N, nc, z, N)) != SVGP_OK) return rc;
+      HIPC(ctx, hipMemcpyAsync(p, z, col * nc, hipMemcpyDeviceToDevice, s));
+      launch_cg_dot(dt, s, r, N, z, N, N, nc, partial);
+      launch_cg_coef(s, 3, st, partial, N, nc, 0, tol2, nullptr, nullptr, rho);
+    }
     KCHECK(ctx, "cg (initial norms)");
     double flags[CgState::WORDS - CgState::ACT];
     HIPC(ctx, hipMemcpyAsync(flags, st + CgState::ACT, sizeof flags, hipMemcpyDeviceToHost, s));
@@ -192,11 +418,19 @@ int solve_core(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int64_t S, const vo
       kmv(ctx, cg, par, cg->data->x.p, cg->data->ldx, N, p, N, nc, p, N, q, N);
       TREC(ctx, ctx->ev[1], s);
       launch_cg_dot(dt, s, p, N, q, N, N, nc, partial);
-      launch_cg_coef(s, 1, st, partial, N, nc, k, tol2, ha, hb);
+      launch_cg_coef(s, 1, st, partial, N, nc, k, tol2, ha, hb, rho);
       launch_cg_update_xr(dt, s, st, N, nc, x, r, p, q);
       launch_cg_dot(dt, s, r, N, r, N, N, nc, partial);
-      launch_cg_coef(s, 2, st, partial, N, nc, k, tol2, ha, hb);
-      launch_cg_update_p(dt, s, st, N, nc, r, p);
+      if (!pc) {
+        launch_cg_coef(s, 2, st, partial, N, nc, k, tol2, ha, hb);
+        launch_cg_update_p(dt, s, st, N, nc, r, p);
+      } else {
+        launch_cg_coef(s, 4, st, partial, N, nc, k, tol2, ha, hb, rho);
+        if ((rc = pc_apply(ctx, cg, par, r, N, nc, z, N)) != SVGP_OK) return rc;
+        launch_cg_dot(dt, s, r, N, z, N, N, nc, partial);
+        launch_cg_coef(s, 5, st, partial, N, nc, k, tol2, ha, hb, rho);
+        launch_cg_update_p(dt, s, st, N, nc, z, p);
+      }
       TREC(ctx, ctx->ev[2], s);
       KCHECK(ctx, "cg (iteration)");
       HIPC(ctx, hipMemcpyAsync(flags, st + CgState::ACT, sizeof flags, hipMemcpyDeviceToHost, s));
@@ -208,8 +442,9 @@ int solve_core(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int64_t S, const vo
       ++k;
     }
     if (bad) break;
-    double sth[CgState::WORDS];
+    double sth[CgState::WORDS], rho0[64] = {0};
     HIPC(ctx, hipMemcpyAsync(sth, st, sizeof sth, hipMemcpyDeviceToHost, s));
+    if (pc) HIPC(ctx, hipMemcpyAsync(rho0, rho + 64, sizeof rho0, hipMemcpyDeviceToHost, s));
     if (hist && k > 0) {
       ha_h.resize(size_t(k) * 64);
       hb_h.resize(size_t(k) * 64);
@@ -232,7 +467,7 @@ int solve_core(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int64_t S, const vo
       }
       if (rel > out.max_rel_residual || rel != rel) out.max_rel_residual = rel;
       if (hist) {
-        hist->bb[size_t(c0 + j)] = bb;
+        hist->bb[size_t(c0 + j)] = pc ? rho0[j] : bb;
         auto& va = hist->a[size_t(c0 + j)];
         auto& vb = hist->b[size_t(c0 + j)];
         va.resize(size_t(it));
@@ -258,6 +493,9 @@ int solve_core(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int64_t S, const vo
     out = svgp_cg_info{};
     out.max_rel_residual = out.quad = out.logdet = out.lml = nan;
     if (info) *info = out;
+    if (pc)
+      return fail(ctx, SVGP_NOT_POSDEF, "conjugate gradients: a curvature p' Khat p or a product r' P^-1 r is not positive (Khat or the applied "
+                                        "preconditioner is not positive definite, or holds a NaN)");
     return fail(ctx, SVGP_NOT_POSDEF, "conjugate gradients: a curvature p' Khat p is not positive (Khat is not positive definite, or holds a NaN)");
   }
   out.quad = out.logdet = out.lml = nan;
@@ -352,6 +590,11 @@ int upload_cols(svgp_ctx* ctx, const svgp_cg* cg, DevBuf& b, const void* host, i
   return SVGP_OK;
 }
 
+int check_precond_desc(svgp_ctx* ctx, const svgp_cg_desc* ds) {
+  if (!(ds->diag > 0)) return fail(ctx, SVGP_INVALID_ARG, "a preconditioner is set: diag must be > 0 (P = Z Kuu^-1 Z' + diag I)");
+  return SVGP_OK;
+}
+
 int common_checks(svgp_ctx* ctx, const svgp_cg* cg, const svgp_cg_desc* ds) {
   if (cg->device != ctx->device) return fail(ctx, SVGP_INVALID_ARG, "the CG handle lives on another device than the context");
   return check_desc(ctx, cg, ds);
@@ -359,10 +602,18 @@ int common_checks(svgp_ctx* ctx, const svgp_cg* cg, const svgp_cg_desc* ds) {
 
 // svgp_cg_fit and svgp_cg_lml_grad: g non-null asks for the gradient {d_variance, d_inv_lengthscale[d], d_diag, d_mean_const}
 struct FitGrad { double *dv, *dil, *dd, *dm; };
+// with a preconditioner: probes_k (k x T) joins the probes, z_t = sigma eps_t + Z Lu^-T xi_t (E z z' = P), log det Khat = log det P +
+// (1 / T) sum_t (z_t' P^-1 z_t) e_1' log(T_t) e_1, and the gradient's trace terms are w_t' dKhat (P^-1 z_t)
 int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* delta, int32_t T, const double* probes, double* lml_out,
-             svgp_cg_info* info, const FitGrad* g) {
+             svgp_cg_info* info, const FitGrad* g, const double* probes_k = nullptr, bool precond_call = false) {
   int rc = common_checks(ctx, cg, ds);
   if (rc) return rc;
+  const bool pc = cg->pc.k > 0;
+  if (precond_call && !pc) return fail(ctx, SVGP_INVALID_ARG, "no preconditioner is set on this handle (svgp_cg_set_preconditioner)");
+  if (pc && (rc = check_precond_desc(ctx, ds)) != SVGP_OK) return rc;
+  if (pc && T > 0 && !precond_call)
+    return fail(ctx, SVGP_INVALID_ARG, "a preconditioner is set: the probes need their k x T part (svgp_cg_fit_precond / svgp_cg_lml_grad_precond)");
+  if (pc && T > 0 && !probes_k) return fail(ctx, SVGP_INVALID_ARG, "null probes_k with T > 0");
   if (!delta && !cg->data->y.p) return fail(ctx, SVGP_INVALID_ARG, "the data handle has no y and no delta was given");
   if (T < 0) return fail(ctx, SVGP_INVALID_ARG, "the number of probes must be >= 0");
   if (T > 0 && !probes) return fail(ctx, SVGP_INVALID_ARG, "null probes with T > 0");
@@ -380,7 +631,15 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
   if ((rc = cg->f64tmp.reserve(ctx, size_t(N) * size_t(T > 0 ? T : 1) * 8, "the probes")) != SVGP_OK) return rc;
   if ((rc = cg->res.reserve(ctx, (size_t(d + 2) * size_t(S) + 8) * 8, "the CG results")) != SVGP_OK) return rc;
   if (g && (rc = cg->gout.reserve(ctx, col * size_t(S), "the gradient's products")) != SVGP_OK) return rc;
-  if ((rc = set_params(ctx, cg, par)) != SVGP_OK) return rc;
+  if ((rc = set_params(ctx, cg, par)) != SVGP_OK) {
+    if (rc == SVGP_NOT_POSDEF) {
+      svgp_cg_info bad{};
+      bad.max_rel_residual = bad.quad = bad.logdet = bad.lml = std::numeric_limits<double>::quiet_NaN();
+      if (info) *info = bad;
+      if (lml_out) *lml_out = bad.lml;
+    }
+    return rc;
+  }
   // [delta, z_1 .. z_T], each entry rounded once to the data dtype
   if (delta) {
     HIPC(ctx, hipMemcpyAsync(cg->f64tmp.p, delta, size_t(N) * 8, hipMemcpyHostToDevice, s));
@@ -388,9 +647,19 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
   } else {
     launch_cg_affine(dt, s, cg->data->y.p, 0, N, N, 1, 1.0, -par.mean_const, cg->fitB.p, N);
   }
-  if (T > 0) {
+  if (T > 0 && !pc) {
     HIPC(ctx, hipMemcpyAsync(cg->f64tmp.p, probes, size_t(N) * size_t(T) * 8, hipMemcpyHostToDevice, s));
     launch_cg_affine(dt, s, cg->f64tmp.p, 1, N, N, T, 1.0, 0.0, cg->fitB.as<char>() + col, N);
+  }
+  if (T > 0 && pc) {   // z_t = sigma eps_t + Z (Lu^-T xi_t): eps rounded into fitX (the solve overwrites it), Lu^-T xi into pc.v
+    CgPrecond& P = cg->pc;
+    if ((rc = P.xi.reserve(ctx, size_t(P.k) * size_t(T) * 8, "the probes")) != SVGP_OK) return rc;
+    if ((rc = P.v.reserve(ctx, size_t(P.kp) * size_t(T) * cg->es, "the preconditioner's products")) != SVGP_OK) return rc;
+    HIPC(ctx, hipMemcpyAsync(cg->f64tmp.p, probes, size_t(N) * size_t(T) * 8, hipMemcpyHostToDevice, s));
+    HIPC(ctx, hipMemcpyAsync(P.xi.p, probes_k, size_t(P.k) * size_t(T) * 8, hipMemcpyHostToDevice, s));
+    launch_cg_affine(dt, s, cg->f64tmp.p, 1, N, N, T, 1.0, 0.0, cg->fitX.as<char>() + col, N);
+    launch_cg_pc_mm(dt, s, P.LinvRM.as<double>(), P.Mp, P.k, P.xi.p, 1, P.k, T, 1.0, P.v.p, P.kp, P.kp);
+    pc_expand(ctx, cg, par, P.v.p, T, cg->fitX.as<char>() + col, N, std::sqrt(P.s2), cg->fitB.as<char>() + col, N);
   }
   KCHECK(ctx, "cg (right-hand sides)");
   CgHist hist;
@@ -422,6 +691,7 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
       logdet += hist.bb[size_t(t)] * qv;
     }
     logdet /= double(T);
+    if (pc) logdet += cg->pc.logdet_p;
   }
   out.quad = quad;
   out.logdet = logdet;
@@ -433,6 +703,10 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
     HIPC(ctx, hipMemcpyAsync(cg->fitB.p, cg->fitX.p, col, hipMemcpyDeviceToDevice, s));
     const void *U = cg->fitX.p, *P = cg->fitB.p;
     void* O = cg->gout.p;
+    if (pc && T > 0) {   // the panel's probe columns become P^-1 z_t
+      if ((rc = pc_apply(ctx, cg, par, cg->fitB.as<char>() + col, N, T, static_cast<char*>(O) + col, N)) != SVGP_OK) return rc;
+      HIPC(ctx, hipMemcpyAsync(cg->fitB.as<char>() + col, static_cast<char*>(O) + col, col * size_t(T), hipMemcpyDeviceToDevice, s));
+    }
     launch_cg_dot(dt, s, U, N, P, N, N, S, partial);
     launch_cg_colsum(s, partial, N, S, res);
     kmv(ctx, cg, par, cg->data->x.p, cg->data->ldx, N, P, N, S, P, N, O, N);
@@ -524,7 +798,7 @@ int32_t svgp_cg_matvec(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int
     if ((rc = upload_cols(ctx, cg, Vd, V, ldv, S, "the panel")) != SVGP_OK) return rc;
     if ((rc = upload_cols(ctx, cg, Od, nullptr, N, S, "the product")) != SVGP_OK) return rc;
   }
-  if ((rc = set_params(ctx, cg, par)) != SVGP_OK) return rc;
+  if ((rc = set_params(ctx, cg, par, false)) != SVGP_OK) return rc;
   const void* vp = on_device ? V : Vd.p;
   void* op = on_device ? out : Od.p;
   const int64_t lv = on_device ? ldv : N, lo = on_device ? ldo : N;
@@ -551,6 +825,7 @@ int32_t svgp_cg_solve(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int6
   if (S < 1) return fail(ctx, SVGP_INVALID_ARG, "S must be >= 1");
   if (ldb < cg->N || ldx < cg->N) return fail(ctx, SVGP_INVALID_ARG, "ldb and ldx must be >= N");
   if (on_device != 0 && on_device != 1) return fail(ctx, SVGP_INVALID_ARG, "on_device must be 0 or 1");
+  if (cg->pc.k > 0 && (rc = check_precond_desc(ctx, desc)) != SVGP_OK) return rc;
   HIPC(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int64_t N = cg->N;
@@ -562,7 +837,26 @@ int32_t svgp_cg_solve(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int6
     if ((rc = upload_cols(ctx, cg, Xd, nullptr, N, S, "the solutions")) != SVGP_OK) return rc;
   }
   if ((rc = ensure_solver(ctx, cg, 64, false, par.maxiter)) != SVGP_OK) return rc;
-  if ((rc = set_params(ctx, cg, par)) != SVGP_OK) return rc;
+  if ((rc = set_params(ctx, cg, par)) == SVGP_NOT_POSDEF) {   // the preconditioner did not factor: NaN outputs, as for a bad curvature
+    const std::string keep = ctx->err;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    void* Xp = on_device ? X : Xd.p;
+    launch_cg_affine(cg->dtype, s, Xp, 0, on_device ? ldx : N, N, S, 0.0, nan, Xp, on_device ? ldx : N);
+    KCHECK(ctx, "cg (NaN outputs)");
+    if (!on_device) HIPC(ctx, hipMemcpy2DAsync(X, size_t(ldx) * cg->es, Xd.p, col, col, size_t(S), hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipStreamSynchronize(s));
+    for (int64_t j = 0; j < S; ++j) {
+      if (iters_out) iters_out[j] = 0;
+      if (relres_out) relres_out[j] = nan;
+    }
+    if (info) {
+      *info = svgp_cg_info{};
+      info->max_rel_residual = info->quad = info->logdet = info->lml = nan;
+    }
+    ctx->err = keep;
+    return rc;
+  }
+  if (rc) return rc;
   rc = solve_core(ctx, cg, par, S, on_device ? B : Bd.p, on_device ? ldb : N, on_device ? X : Xd.p, on_device ? ldx : N, iters_out, relres_out,
                   info, nullptr);
   if (rc != SVGP_OK && rc != SVGP_NOT_POSDEF) return rc;
@@ -609,6 +903,7 @@ int32_t svgp_cg_predict(svgp_ctx* ctx, svgp_cg* cg, int32_t layout, int64_t n, c
   if (cg->device != ctx->device) return fail(ctx, SVGP_INVALID_ARG, "the CG handle lives on another device than the context");
   if (!cg->have_fit) return fail(ctx, SVGP_INVALID_ARG, "no successful svgp_cg_fit on this handle yet");
   if (n < 1) return fail(ctx, SVGP_INVALID_ARG, "no test points");
+  if (var_out && cg->pc.k > 0 && !(cg->fit.diag > 0)) return fail(ctx, SVGP_INVALID_ARG, "a preconditioner is set: the fit's diag must be > 0");
   if (var_out && (n > kCgMaxPredict || n * cg->N > kCgMaxPredict))
     return fail(ctx, SVGP_UNSUPPORTED, "the predictive variance of more than 2^28 / N test points in one call");
   if (n > kCgMaxPredict) return fail(ctx, SVGP_UNSUPPORTED, "more than 2^28 test points in one call");
@@ -629,7 +924,7 @@ int32_t svgp_cg_predict(svgp_ctx* ctx, svgp_cg* cg, int32_t layout, int64_t n, c
     if ((rc = vres.reserve(ctx, size_t(n) * 8, "the predictive variances")) != SVGP_OK) return rc;
     if ((rc = ensure_solver(ctx, cg, n, false, par.maxiter)) != SVGP_OK) return rc;
   }
-  if ((rc = set_params(ctx, cg, par)) != SVGP_OK) return rc;
+  if ((rc = set_params(ctx, cg, par, var_out != nullptr)) != SVGP_OK) return rc;   // (the mean needs no preconditioner)
   svgp_cg_info out{};
   out.converged = 1;
   const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -658,6 +953,132 @@ int32_t svgp_cg_predict(svgp_ctx* ctx, svgp_cg* cg, int32_t layout, int64_t n, c
   }
   if (info) *info = out;
   return status;
+}
+
+int32_t svgp_cg_set_preconditioner(svgp_ctx* ctx, svgp_cg* cg, int32_t layout, int64_t k, const void* z_host, double jitter) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!cg) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (cg->device != ctx->device) return fail(ctx, SVGP_INVALID_ARG, "the CG handle lives on another device than the context");
+  if (k < 0 || k > 2048) return fail(ctx, SVGP_INVALID_ARG, "the number of preconditioner points must be in [0, 2048]");
+  if (k > 0 && !z_host) return fail(ctx, SVGP_INVALID_ARG, "null preconditioner points");
+  if (k > 0 && layout != SVGP_COLVECS && layout != SVGP_ROWVECS && layout != SVGP_VEC) return fail(ctx, SVGP_INVALID_ARG, "bad layout");
+  if (k > 0 && layout == SVGP_VEC && cg->d != 1) return fail(ctx, SVGP_INVALID_ARG, "bad layout: a plain vector needs d = 1");
+  if (!(jitter >= 0)) return fail(ctx, SVGP_INVALID_ARG, "jitter must be >= 0");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  HIPC(ctx, hipStreamSynchronize(ctx->stream));
+  svgp_data* z = nullptr;
+  if (k > 0) {
+    const int rc = svgp_data_upload(ctx, cg->dtype, layout, cg->d, k, z_host, nullptr, &z);
+    if (rc) return rc;
+  }
+  delete cg->pc.z;
+  cg->pc.z = z;
+  cg->pc.k = k;
+  cg->pc.kp = (k + 31) / 32 * 32;
+  cg->pc.Mp = (k + 127) / 128 * 128;
+  cg->pc.jitter = jitter;
+  cg->pc.ms_setup = 0;
+  cg->pc.z64_ready = false;
+  return SVGP_OK;
+}
+
+int32_t svgp_cg_precond_cross(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int64_t S, const void* V, int64_t ldv, void* out, int64_t ldo,
+                              int32_t on_device) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!cg || !V || !out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  int rc = common_checks(ctx, cg, desc);
+  if (rc) return rc;
+  if (cg->pc.k < 1) return fail(ctx, SVGP_INVALID_ARG, "no preconditioner is set on this handle (svgp_cg_set_preconditioner)");
+  if (S < 1) return fail(ctx, SVGP_INVALID_ARG, "S must be >= 1");
+  if (ldv < cg->N || ldo < cg->pc.k) return fail(ctx, SVGP_INVALID_ARG, "ldv must be >= N and ldo >= k");
+  if (on_device != 0 && on_device != 1) return fail(ctx, SVGP_INVALID_ARG, "on_device must be 0 or 1");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int64_t k = cg->pc.k;
+  const size_t kcol = size_t(k) * cg->es;
+  const CgPar par = par_of(desc);
+  DevBuf Vd, Od;
+  if (!on_device) {
+    if ((rc = upload_cols(ctx, cg, Vd, V, ldv, S, "the panel")) != SVGP_OK) return rc;
+    if ((rc = Od.reserve(ctx, kcol * size_t(S), "the product")) != SVGP_OK) return rc;
+  }
+  if ((rc = set_params(ctx, cg, par, false)) != SVGP_OK) return rc;
+  if ((rc = pc_cross(ctx, cg, par, on_device ? V : Vd.p, on_device ? ldv : cg->N, S, on_device ? out : Od.p, on_device ? ldo : k)) != SVGP_OK) return rc;
+  KCHECK(ctx, "kmv (row-split)");
+  if (!on_device) HIPC(ctx, hipMemcpy2DAsync(out, size_t(ldo) * cg->es, Od.p, kcol, kcol, size_t(S), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  return SVGP_OK;
+}
+
+int32_t svgp_cg_precond_apply(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int64_t S, const void* R, int64_t ldr, void* out, int64_t ldo,
+                              int32_t on_device, double* logdet_p_out) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!cg || !R || !out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  int rc = common_checks(ctx, cg, desc);
+  if (rc) return rc;
+  if (cg->pc.k < 1) return fail(ctx, SVGP_INVALID_ARG, "no preconditioner is set on this handle (svgp_cg_set_preconditioner)");
+  if ((rc = check_precond_desc(ctx, desc)) != SVGP_OK) return rc;
+  if (S < 1) return fail(ctx, SVGP_INVALID_ARG, "S must be >= 1");
+  if (ldr < cg->N || ldo < cg->N) return fail(ctx, SVGP_INVALID_ARG, "ldr and ldo must be >= N");
+  if (on_device != 0 && on_device != 1) return fail(ctx, SVGP_INVALID_ARG, "on_device must be 0 or 1");
+  if (on_device && R == out) return fail(ctx, SVGP_INVALID_ARG, "out must not be R");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int64_t N = cg->N;
+  const size_t col = size_t(N) * cg->es;
+  const CgPar par = par_of(desc);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  if (logdet_p_out) *logdet_p_out = nan;
+  DevBuf Rd, Od;
+  if (!on_device) {
+    if ((rc = upload_cols(ctx, cg, Rd, R, ldr, S, "the panel")) != SVGP_OK) return rc;
+    if ((rc = upload_cols(ctx, cg, Od, nullptr, N, S, "the product")) != SVGP_OK) return rc;
+  }
+  void* op = on_device ? out : Od.p;
+  const int64_t lo = on_device ? ldo : N;
+  rc = set_params(ctx, cg, par);
+  if (rc != SVGP_OK && rc != SVGP_NOT_POSDEF) return rc;
+  const int status = rc;
+  const std::string keep = ctx->err;
+  if (status == SVGP_OK) {
+    TREC(ctx, ctx->ev[0], s);
+    if ((rc = pc_apply(ctx, cg, par, on_device ? R : Rd.p, on_device ? ldr : N, S, op, lo)) != SVGP_OK) return rc;
+    TREC(ctx, ctx->ev[1], s);
+    KCHECK(ctx, "cg preconditioner (apply)");
+  } else {
+    launch_cg_affine(cg->dtype, s, op, 0, lo, N, S, 0.0, nan, op, lo);
+    KCHECK(ctx, "cg (NaN outputs)");
+  }
+  if (!on_device) HIPC(ctx, hipMemcpy2DAsync(out, size_t(ldo) * cg->es, Od.p, col, col, size_t(S), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  if (status == SVGP_OK) {
+    float t = 0;
+    (void)elapsed_ms(ctx, &t, ctx->ev[0], ctx->ev[1]);
+    ctx->timing = svgp_timing{};
+    ctx->timing.ms_prep = cg->pc.ms_setup;
+    ctx->timing.ms_strip = t;
+    ctx->timing.ms_total = t + cg->pc.ms_setup;
+    cg->pc.ms_setup = 0;
+    if (logdet_p_out) *logdet_p_out = cg->pc.logdet_p;
+  }
+  ctx->err = keep;
+  return status;
+}
+
+int32_t svgp_cg_fit_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                            const double* probes_k, double* lml_out, svgp_cg_info* info) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!cg) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  return fit_impl(ctx, cg, desc, delta, T, probes, lml_out, info, nullptr, probes_k, true);
+}
+
+int32_t svgp_cg_lml_grad_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                                 const double* probes_k, double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale,
+                                 double* d_diag, double* d_mean_const) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!cg) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  const FitGrad g{d_variance, d_inv_lengthscale, d_diag, d_mean_const};
+  return fit_impl(ctx, cg, desc, delta, T, probes, lml_out, info, &g, probes_k, true);
 }
 
 }  // extern "C"

@@ -344,13 +344,26 @@ int cg_dot_blocks(int64_t N);   // blocks of the first stage of a column dot: a 
 // partial[col * cg_dot_blocks(N) + blk] of sum_i a[i, col] b[i, col] (fp64), then their sums blk ascending
 void launch_cg_dot(int dtype, hipStream_t s, const void* a, int64_t lda, const void* b, int64_t ldb, int64_t N, int64_t ncols, double* partial);
 void launch_cg_colsum(hipStream_t s, const double* partial, int64_t N, int64_t ncols, double* out);
-void launch_cg_coef(hipStream_t s, int mode, double* st, const double* partial, int64_t N, int ncols, int k, double tol2, double* hist_a, double* hist_b);
+// rho (the preconditioned recurrence, modes 3 - 5 and the step length of mode 1): 128 fp64 words, r'z per column and its initial value
+void launch_cg_coef(hipStream_t s, int mode, double* st, const double* partial, int64_t N, int ncols, int k, double tol2, double* hist_a, double* hist_b,
+                    double* rho = nullptr);
 void launch_cg_update_xr(int dtype, hipStream_t s, const double* st, int64_t N, int ncols, void* x, void* r, const void* p, const void* q);
 void launch_cg_update_p(int dtype, hipStream_t s, const double* st, int64_t N, int ncols, const void* r, void* p);
 // dst = alpha src + beta, column by column (src in fp64 with src_f64, otherwise in the data dtype)
 void launch_cg_affine(int dtype, hipStream_t s, const void* src, int src_f64, int64_t lds, int64_t N, int64_t ncols, double alpha, double beta, void* dst, int64_t ldd);
 void launch_cg_kcols(int dtype, hipStream_t s, const void* x, int64_t ldx, int64_t N, const void* xt, int64_t ldt, int64_t nt, const void* invl, int d,
                      int family, double variance, void* out, int64_t ldo);
-
+// the Nystrom preconditioner.  launch_kmv_split: launch_kmv (profile 0, no addv) for FEW points a.n against the N rows, the rows split
+// into kmv_split_segments(N, n) segments of *seg_rows rows (whole chunks; a function of N and n alone); part: segments x 64 x n elements
+int kmv_split_segments(int64_t N, int64_t n, int64_t* seg_rows);
+void launch_kmv_split(int dtype, hipStream_t s, const KmvArgs& a, void* part);
+// its k-sized stage, fp64 whatever the data dtype (kernels of cg.hip; the factorisations are launch_kuu / _potrf / _linv / _gemm_pm)
+void launch_cg_widen(int dtype, hipStream_t s, const void* src, int64_t lds, int64_t n, int64_t ncols, double* dst, int64_t ldd);
+void launch_cg_pc_scale(hipStream_t s, const double* z, int64_t ldz, const double* invl, int d, int64_t k, int64_t Mp, double* zs);
+void launch_cg_pc_form_b(hipStream_t s, const double* A, int64_t Mp, double sigma2, double* Bm);   // I + sym(A) / sigma2
+void launch_cg_pc_logdet(hipStream_t s, const double* L, int64_t Mp, int64_t k, double* out);       // 2 sum log L_ii
+// out (dtype's element type, ld ldo, zero on rows [k, rows_out)) = alpha Mt' v for the k x k block of Mt (ld Mp); v fp64 or dtype's type
+void launch_cg_pc_mm(int dtype, hipStream_t s, const double* Mt, int64_t Mp, int64_t k, const void* v, int v_f64, int64_t ldv, int64_t ncols, double alpha,
+                     void* out, int64_t ldo, int64_t rows_out);
 
 }  // namespace svgp

@@ -856,7 +856,7 @@ int32_t svgp_sampler_eval_grad(svgp_ctx* ctx, const svgp_sampler* sampler, const
  * SVGP_INVALID_ARG, before anything is enqueued: a NULL required pointer; descriptor dtype or d different from the data's; an unknown
  * kernel; data without y when delta is NULL; maxiter < 1, tol <= 0, diag < 0, variance <= 0, reserved != 0 (NaN counts as a violation);
  * S < 1; T < 0, or T > 0 with NULL probes; ldv, ldo, ldb or ldx < N; on_device not 0 / 1; alpha or predict before a successful fit;
- * n < 1.  Out of scope: preconditioning, per-point noise, cov / cross-cov, pathwise samples, multi-GPU, the Julia hooks. */
+ * n < 1.  Preconditioning: the next section.  Out of scope: per-point noise, cov / cross-cov, pathwise samples, multi-GPU, the Julia hooks. */
 typedef struct svgp_cg svgp_cg;
 typedef struct svgp_cg_desc {
   int32_t dtype, kernel, d, maxiter; /* maxiter >= 1 */
@@ -888,6 +888,48 @@ int32_t svgp_cg_lml_grad(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, c
 int32_t svgp_cg_alpha(svgp_ctx* ctx, svgp_cg* cg, void* alpha_out);
 int32_t svgp_cg_predict(svgp_ctx* ctx, svgp_cg* cg, int32_t layout, int64_t n, const void* x_host, void* mean_out, void* var_out,
                         svgp_cg_info* info);
+/* ---- the Nystrom preconditioner of the conjugate gradients ---------------------------------------------------------------------------
+ * With k points z_p set on a handle, Z = K(X, z_p) (N x k), Kuu = K(z_p, z_p) + jitter variance I = Lu Lu' and sigma^2 = desc.diag:
+ *   P = Z Kuu^-1 Z' + sigma^2 I,   P^-1 r = (r - Z W Z' r) / sigma^2,   W = Lu^-T B^-1 Lu^-1 / sigma^2,   B = I + Lu^-1 (Z'Z) Lu^-T / sigma^2,
+ *   log det P = N log sigma^2 + log det B.
+ * Nothing N x k is stored: Z' r is a row-split form of the kmv kernel (few points, a long reduction: the grid is point workgroups x row
+ * segments, each segment's partial sums are written in the data dtype and added in ascending order in fp64; the number of segments
+ * depends on N and k alone, so a column's value does not depend on its neighbours and repeated calls are bitwise equal), and Z c is the
+ * kmv kernel itself with the k points as its rows, whose epilogue adds r / sigma^2.  The k-sized stage (Kuu, Lu, the Gram Z'Z, B and its
+ * factor, W) runs on the device in fp64 for both data dtypes, the Gram accumulated in fp64 from fp64 entries (accumulated in float32, B
+ * is not positive definite); it is set up once per call from the call's parameter set, and its device time is added to
+ * info->ms_vector, as is the time of every application (two kernel products with N k generated entries each per iteration).
+ *   set_preconditioner  k points in `layout` (as svgp_cg_predict's x_host, data dtype, host), 1 <= k <= 2048, jitter >= 0 (times the
+ *           variance; 1e-4 is the documented default: very small values lose accuracy with an ill-conditioned Kuu even in fp64).  k = 0
+ *           removes the preconditioner: every call is then bitwise what it is on a handle that never had one.  Replaces earlier points.
+ *   precond_cross  out (k x S, ldo >= k) = K(z_p, X) V for an N x S panel (ldv >= N): the row-split kernel alone.
+ *   precond_apply  out (N x S) = P^-1 R, and log det P (nullable).  out must not be R.
+ *   With a preconditioner set, svgp_cg_solve, svgp_cg_predict's variance solve and the T = 0 forms of svgp_cg_fit / svgp_cg_lml_grad run
+ *   the preconditioned recurrence z = P^-1 r, rho = r'z, a = rho / p'Khat p, beta = rho_new / rho, p = z + beta p; the stopping test stays
+ *   |r|_2 <= tol |b|_2 on the true residual, columns freeze as before, and the column-independence guarantee holds.
+ *   fit_precond / lml_grad_precond  svgp_cg_fit / svgp_cg_lml_grad plus probes_k (k x T host doubles, column-major).  The probes need
+ *           E z z' = P: from the caller's eps (N x T, `probes`) and xi (k x T), both with identity covariance, the library forms
+ *           z_t = sigma eps_t + Z Lu^-T xi_t on the device.  log det Khat = log det P + (1 / T) sum_t (z_t' P^-1 z_t) e_1' log(T_t) e_1, T_t the
+ *           Lanczos tridiagonal of P^-1/2 Khat P^-1/2 rebuilt from column t's coefficients; d lml / d theta = 1/2 alpha' dKhat alpha -
+ *           (1 / 2T) sum_t w_t' dKhat (P^-1 z_t).  With T = N + k, eps = sqrt(T) [I_N 0] and xi = sqrt(T) [0 I_k] the estimate is exact.
+ * SVGP_INVALID_ARG, before anything is enqueued: k outside [0, 2048]; NULL points with k > 0; a bad layout; jitter < 0 or NaN;
+ * precond_cross / precond_apply / fit_precond / lml_grad_precond without a preconditioner; NULL probes_k with T > 0; svgp_cg_fit /
+ * svgp_cg_lml_grad with T > 0 while a preconditioner is set (the probes need xi); desc.diag == 0 in any call that applies the
+ * preconditioner.  SVGP_NOT_POSDEF: Kuu + jitter or B fails to factor, or, in a solve, a product r' P^-1 r of an active column is not
+ * > 0 (the applied P^-1 has lost positive definiteness to rounding; handled like a curvature that is not > 0); the outputs are NaN and
+ * the context stays healthy.  Memory: 13 fp64 arrays of ceil128(k)^2 and one of N x 64; an fp32 handle also keeps fp64 copies of x (widened
+ * once per handle), of its prepared rows and of z_p for the Gram, about three times the bytes of its x.  Found by symbol
+ * (no ABI version step). */
+int32_t svgp_cg_set_preconditioner(svgp_ctx* ctx, svgp_cg* cg, int32_t layout, int64_t k, const void* z_host, double jitter);
+int32_t svgp_cg_precond_cross(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int64_t S, const void* V, int64_t ldv, void* out, int64_t ldo,
+                              int32_t on_device);
+int32_t svgp_cg_precond_apply(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int64_t S, const void* R, int64_t ldr, void* out, int64_t ldo,
+                              int32_t on_device, double* logdet_p_out);
+int32_t svgp_cg_fit_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                            const double* probes_k, double* lml_out, svgp_cg_info* info);
+int32_t svgp_cg_lml_grad_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                                 const double* probes_k, double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale,
+                                 double* d_diag, double* d_mean_const);
 /* host only, like svgp_gausshermite: out = e_1' log(T) e_1 for the Lanczos tridiagonal of `iters` CG steps with step lengths a[j] and
  * residual ratios b[j] = |r_{j+1}|^2 / |r_j|^2 (diagonal 1 / a_j + b_{j-1} / a_{j-1}, off-diagonal sqrt(b_j) / a_j; b[iters - 1] is not
  * read), by an implicit-shift QL iteration in fp64.  SVGP_INVALID_ARG: NULL pointers, iters < 1; SVGP_NOT_POSDEF (out = NaN): an

@@ -4,6 +4,11 @@ the same run.  The sampler's kernel is the one kmv_kernel was modelled on (same 
 entries a second are the yardstick; no ratio is fixed in advance: the run reports it.
 
     python tools/cg_time.py [--reps 7] [--n 100000] [--out profiles/cg/cg_time.jsonl]
+    python tools/cg_time.py --precond 256 512 1024 --precond-out profiles/cg/cg_precond_time.jsonl
+
+--precond K ...: after the unpreconditioned fit, the same fit (17 columns, same tol and maxiter) with the Nystrom preconditioner of K
+data points (default_rng([0, 2]).choice, jitter 1e-4): iterations, final residual, wall time, the preconditioner's setup time and
+the device time of one svgp_cg_precond_apply (16 columns) beside one matvec of the same run.
 
 Times: the device time of the call's kernels from the library's own events (svgp_last_timing's ms_strip for matvec and the sampler,
 svgp_cg_info's ms_matvec / ms_vector summed over the iterations of the fit) and the wall time by the host clock around the blocking
@@ -37,6 +42,8 @@ def main():
     ap.add_argument("--n-sampler", type=int, default=1_000_000)
     ap.add_argument("--maxiter", type=int, default=500)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--precond", type=int, nargs="*", default=[], help="preconditioner sizes for the preconditioned leg")
+    ap.add_argument("--precond-out", default=None)
     a = ap.parse_args()
     import torch
 
@@ -46,7 +53,7 @@ def main():
     from approxgp.synthetic import synth_arrays
 
     ctx = _ffi.Context(0)
-    rows = []
+    rows, prows = [], []
     N, d, S, M, ns = a.n, a.d, a.cols, a.M, a.n_sampler
     for dt in (np.float64, np.float32):
         tdt = torch.float64 if dt == np.float64 else torch.float32
@@ -87,6 +94,53 @@ def main():
                "finite": bool(torch.isfinite(out).all().item())}
         print(json.dumps(row), flush=True)
         rows.append(row)
+        for k in a.precond:
+            idx = np.random.default_rng([0, 2]).choice(N, size=k, replace=False)
+            dev.set_preconditioner(np.asarray(p["x"])[:, idx], 1e-4)
+            pout = torch.empty_like(V)
+            dev.precond_apply(desc, V, out=pout)   # warm-up
+            ap_dev, setup = [], []
+            for _ in range(a.reps):
+                dev.precond_apply(desc, V, out=pout)
+                tm = ctx.timing()
+                ap_dev.append(tm.ms_strip)
+                setup.append(tm.ms_prep)
+            t0 = time.perf_counter()
+            try:
+                lml_k, info_k = dev.fit(desc, z, probes_k=draw_probes(k, 16, np.random.default_rng([0, 1])))
+            except _ffi.PosDefException as e:   # r' P^-1 r of a column not > 0: the applied preconditioner lost positive definiteness
+                wall_k = 1e3 * (time.perf_counter() - t0)
+                prow = {"dtype": np.dtype(dt).name, "N": N, "d": d, "k": k, "columns": 17, "tol": 1e-6, "maxiter": a.maxiter,
+                        "status": "SVGP_NOT_POSDEF", "message": str(e), "ms_wall": round(wall_k, 1), "ms_setup": stat(setup), "ms_apply_16": stat(ap_dev)}
+                print(json.dumps(prow), flush=True)
+                prows.append(prow)
+                dev.set_preconditioner(None)
+                del pout
+                continue
+            wall_k = 1e3 * (time.perf_counter() - t0)
+            prow = {"dtype": np.dtype(dt).name, "N": N, "d": d, "k": k, "columns": 17, "tol": 1e-6, "maxiter": a.maxiter,
+                    "iterations": info_k.iterations, "converged": info_k.converged, "n_unconverged": info_k.n_unconverged,
+                    "max_rel_residual": info_k.max_rel_residual, "lml": lml_k, "ms_wall": round(wall_k, 1),
+                    "ms_matvec": round(info_k.ms_matvec, 1), "ms_vector": round(info_k.ms_vector, 1), "ms_setup": stat(setup),
+                    "ms_apply_16": stat(ap_dev), "ms_matvec_16": stat(mv_dev),
+                    "unpreconditioned": {"iterations": info.iterations, "converged": info.converged,
+                                         "max_rel_residual": info.max_rel_residual, "ms_wall": round(fit_wall, 1), "lml": lml}}
+            if not info_k.converged:   # the end of the residual curve: the same deterministic iteration stopped earlier
+                tail = {}
+                for it in (a.maxiter - 100, a.maxiter - 50, a.maxiter - 10):
+                    if it < 1:
+                        continue
+                    dk, keep_k = dev.desc(kernel, p["sigma2"], tol=1e-6, maxiter=it)
+                    try:
+                        tail[str(it)] = dev.fit(dk, z, probes_k=draw_probes(k, 16, np.random.default_rng([0, 1])))[1].max_rel_residual
+                    except _ffi.PosDefException as e:
+                        tail[str(it)] = "not positive definite"
+                tail[str(a.maxiter)] = info_k.max_rel_residual
+                prow["residual_tail"] = tail
+            print(json.dumps(prow), flush=True)
+            prows.append(prow)
+            dev.set_preconditioner(None)
+            del pout
         smp.free()
         model.free()
         data.free()
@@ -97,6 +151,11 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             for r in rows:
+                f.write(json.dumps(r) + "\n")
+    if a.precond_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.precond_out)), exist_ok=True)
+        with open(a.precond_out, "w") as f:
+            for r in prows:
                 f.write(json.dumps(r) + "\n")
 
 
