@@ -36,5 +36,7 @@ from .pathwise import FunctionSamples, draw_basis, function_samples
 from ._ffi import CGDesc, CGInfo
 from .iterative import (CGPosteriorGP, ConjugateGradients, DeviceConjugateGradients, approx_lml, approx_lml_and_gradient, draw_probes,
                         posterior)
+# pathwise function samples of the exact GP: CGPosteriorGP.function_samples, DeviceConjugateGradients.sampler
+from .iterative import CGFunctionSamples, DeviceCGSampler, cg_sample_plan, pack_cg_basis
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -250,6 +250,13 @@ SYMBOLS = {
     "svgp_cg_lml_grad_precond": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(CGInfo), C.POINTER(C.c_double),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "svgp_cg_sampler_create": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.POINTER(C.c_double), C.POINTER(SampleBasis), C.POINTER(_P),
+                                           C.POINTER(CGInfo)]),
+    "svgp_cg_sampler_eval": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int32]),
+    "svgp_cg_sampler_eval_grad": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32]),
+    "svgp_cg_sampler_state": (C.c_int32, [_P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "svgp_cg_sampler_free": (C.c_int32, [_P, _P]),
+    "svgp_cg_sampler_plan": (C.c_int32, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "svgp_lanczos_logdet": (C.c_int32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),

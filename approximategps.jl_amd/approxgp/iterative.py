@@ -327,6 +327,17 @@ class DeviceConjugateGradients:
         self._check(self.ctx.lib.svgp_cg_predict(self.ctx.h, self.h, layout, n, _ffi._ptr(xb), _ffi._ptr(m), _ffi._ptr(v), C.byref(info)))
         return m, v, info
 
+    def sampler(self, desc, basis, delta=None):
+        """svgp_cg_sampler_create: S pathwise function samples of the exact posterior under `desc` from basis = (omega (L, d), tau (L,),
+        w (S, L), eps (S, N)) - every random number is the caller's (approxgp.pathwise.draw_basis(kernel, N, L, S, ...) draws them).
+        One batched solve of S right-hand sides; the DeviceCGSampler is a snapshot and outlives this handle.  delta: (N,) or None for
+        y - mean_const."""
+        packed = pack_cg_basis(self.n, self.d, self.dtype, basis)   # every check before the GPU is touched
+        dl = self._f64(delta)
+        if dl is not None and dl.shape != (self.n,):
+            raise ValueError("delta: an (N,) array")
+        return DeviceCGSampler(self, desc, packed, dl)
+
     def free(self):
         if getattr(self, "h", None):
             self.ctx.lib.svgp_cg_free(self.ctx.h, self.h)
@@ -340,6 +351,195 @@ class DeviceConjugateGradients:
             self.free()
         except Exception:
             pass
+
+
+def cg_sample_plan(N: int):
+    """-> (seg_rows, n_segments, round_points) of the sampler's evaluations over N data rows: the library's own svgp_cg_sampler_plan (host
+    only, no GPU needed), where the rule lives."""
+    N = int(N)
+    if N < 0:
+        raise ValueError("N >= 0")
+    seg_rows, nseg, rnd = C.c_int64(), C.c_int32(), C.c_int64()
+    rc = _ffi.load_library().svgp_cg_sampler_plan(N, C.byref(seg_rows), C.byref(nseg), C.byref(rnd))
+    if rc != _ffi.OK:
+        raise ValueError(f"svgp_cg_sampler_plan({N}) returned {rc}")
+    return seg_rows.value, nseg.value, rnd.value
+
+
+def pack_cg_basis(N: int, d: int, dtype: int, basis):
+    """(omega (L, d), tau (L,), w (S, L), eps (S, N)) checked and laid out for svgp_cg_sampler_create -> (L, S, omega, tau, w, eps)."""
+    try:
+        omega, tau, w, eps = basis
+    except (TypeError, ValueError):
+        raise ValueError("basis is (omega (L, d), tau (L,), w (S, L), eps (S, N))") from None
+    dt = _ffi.np_dtype(dtype)
+    eps = np.ascontiguousarray(np.asarray(eps, dtype=dt))
+    if eps.ndim != 2 or eps.shape[1] != N or eps.shape[0] < 1:
+        raise ValueError("eps must be (S, N) with S >= 1: one standard normal draw per sample and data point")
+    S = eps.shape[0]
+    w = np.asarray(np.zeros((S, 0)) if w is None else w, dtype=dt)
+    if w.ndim != 2 or w.shape[0] != S:
+        raise ValueError("w must be (S, L)")
+    w = np.ascontiguousarray(w)
+    L = w.shape[1]
+    omega = np.asarray(np.zeros((0, d)) if omega is None else omega, dtype=dt)
+    tau = np.asarray(np.zeros(0) if tau is None else tau, dtype=dt)
+    if omega.shape != (L, d):
+        raise ValueError("omega must be (L, d)")
+    if tau.shape != (L,):
+        raise ValueError("tau must be (L,)")
+    return L, S, np.ascontiguousarray(omega), np.ascontiguousarray(tau), w, eps
+
+
+def _check_sample_counts(n_samples, n_features):
+    if int(n_samples) != n_samples or int(n_samples) < 1:
+        raise ValueError("function_samples needs n_samples >= 1")
+    if int(n_features) != n_features or int(n_features) < 0:
+        raise ValueError("function_samples needs n_features >= 0")
+    return int(n_samples), int(n_features)
+
+
+class DeviceCGSampler:
+    """S function samples of the exact GP's posterior, resident in HBM (svgp_cg_sampler): evaluate them and their input gradients
+    anywhere, any number of times.  A point's value does not depend on the other points, the call or the other samples, bitwise."""
+
+    def __init__(self, dev: DeviceConjugateGradients, desc, packed, delta=None):
+        self.ctx = ctx = dev.ctx
+        self.n, self.d, self.dtype = dev.n, dev.d, dev.dtype
+        L, S, omega, tau, w, eps = packed
+        self.n_samples, self.n_features = S, L
+        basis = _ffi.SampleBasis(L, S, _ffi._ptr(omega) if L else None, _ffi._ptr(tau) if L else None, _ffi._ptr(w) if L else None,
+                                 _ffi._ptr(eps))
+        h, self.info = C.c_void_p(), _ffi.CGInfo()
+        dlp = None if delta is None else delta.ctypes.data_as(C.POINTER(C.c_double))
+        dev._check(ctx.lib.svgp_cg_sampler_create(ctx.h, dev.h, C.byref(desc), dlp, C.byref(basis), C.byref(h), C.byref(self.info)))
+        self.h = h
+
+    def _points(self, x):
+        """-> (DeviceData, owned): a resident DeviceData as it is, or x (a plain vector for d = 1, or (d, n) ColVecs) uploaded"""
+        if isinstance(x, _ffi.DeviceData):
+            if x.d != self.d or x.dtype != self.dtype:
+                raise ValueError("the data have a different dimension or dtype than the sampler")
+            return x, False
+        x = check_points(x, self.d)
+        return _ffi.DeviceData(self.ctx, x, None, _ffi.np_dtype(self.dtype)), True
+
+    def _dev_out(self, t, rows, n, name):
+        if (not _ffi._is_device_tensor(t) or not t.is_contiguous() or not t.is_floating_point()
+                or t.element_size() != np.dtype(_ffi.np_dtype(self.dtype)).itemsize or t.numel() != rows * n):
+            raise ValueError(f"{name}: a contiguous device tensor of the data dtype with {rows} x n elements")
+        return C.c_void_p(int(t.data_ptr()))
+
+    @staticmethod
+    def _window(data, off, length):
+        off = int(off)
+        n = data.n - off if length is None else int(length)
+        if off < 0 or n < 1 or off + n > data.n:
+            raise ValueError("window outside the data")
+        return off, n
+
+    def eval(self, x, out=None, off=0, length=None):
+        """f_s at the points x (of a DeviceData: its window [off, off + length)) -> (S, n) array of the data dtype (row s = sample s);
+        out: a contiguous (S, n) torch device tensor to write there instead (it is returned)."""
+        data, owned = self._points(x)
+        try:
+            ctx = self.ctx
+            off, n = self._window(data, off, length)
+            if out is not None:
+                ctx.check(ctx.lib.svgp_cg_sampler_eval(ctx.h, self.h, data.h, off, n, self._dev_out(out, self.n_samples, n, "out"), n, 1))
+                return out
+            buf = np.zeros((self.n_samples, n), dtype=_ffi.np_dtype(self.dtype))
+            ctx.check(ctx.lib.svgp_cg_sampler_eval(ctx.h, self.h, data.h, off, n, _ffi._ptr(buf), n, 0))
+            return buf
+        finally:
+            if owned:
+                data.free()
+
+    def eval_grad(self, x, values=True, out=None, grad_out=None, off=0, length=None):
+        """-> (F (S, n) or None, G (S, d, n)): G[s, c, j] = d f_s / d x_c at point j; the values are bitwise eval's.  grad_out (and out,
+        when values are wanted): contiguous torch device tensors of S d n (S n) elements to write there instead."""
+        data, owned = self._points(x)
+        try:
+            ctx, S, d = self.ctx, self.n_samples, self.d
+            off, n = self._window(data, off, length)
+            if grad_out is not None or out is not None:
+                if grad_out is None or (values and out is None):
+                    raise ValueError("device output: grad_out is required, and out when values are wanted (both live in the same kind of memory)")
+                gp = self._dev_out(grad_out, S * d, n, "grad_out")
+                op = self._dev_out(out, S, n, "out") if values else None
+                ctx.check(ctx.lib.svgp_cg_sampler_eval_grad(ctx.h, self.h, data.h, off, n, op, n, gp, n, 1))
+                return (out if values else None), grad_out
+            dt = _ffi.np_dtype(self.dtype)
+            F = np.zeros((S, n), dtype=dt) if values else None
+            G = np.zeros((S, d, n), dtype=dt)
+            ctx.check(ctx.lib.svgp_cg_sampler_eval_grad(ctx.h, self.h, data.h, off, n, _ffi._ptr(F), n, _ffi._ptr(G), n, 0))
+            return F, G
+        finally:
+            if owned:
+                data.free()
+
+    def state(self):
+        """-> (V (N, S) in the data dtype exactly as evaluated, iterations (S,), relative residuals (S,)) of the solve"""
+        V = np.zeros((self.n, self.n_samples), dtype=_ffi.np_dtype(self.dtype), order="F")
+        iters, rel = np.zeros(self.n_samples, dtype=np.int32), np.zeros(self.n_samples)
+        self.ctx.check(self.ctx.lib.svgp_cg_sampler_state(self.ctx.h, self.h, _ffi._ptr(V), iters.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          rel.ctypes.data_as(C.POINTER(C.c_double))))
+        return V, iters, rel
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.svgp_cg_sampler_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def check_points(x, d):
+    """test inputs as an array: a plain vector for d = 1, or a (d, n) ColVecs array with n >= 1"""
+    x = np.asarray(x)
+    if x.ndim == 1:
+        if d != 1:
+            raise ValueError("test inputs have a different dimension than the data")
+    elif x.ndim != 2 or x.shape[0] != d:
+        raise ValueError("test inputs have a different dimension than the data")
+    if x.shape[-1] < 1:
+        raise ValueError("no test points")
+    return x
+
+
+class CGFunctionSamples:
+    """S functions drawn from a CGPosteriorGP, resident on the device, with pathwise.FunctionSamples' interface: fs(x) -> (n, S),
+    fs.grad(x) -> (n, S, d), fs.value_and_grad(x), fs.state(), fs.free()."""
+
+    def __init__(self, post, sampler):
+        self._post, self.sampler, self.n_samples = post, sampler, sampler.n_samples
+
+    def _offsets(self, x, F):
+        mu = self._post.prior.mean_offsets(np.asarray(x))
+        return F if mu is None else (F + np.asarray(mu)[:, None]).astype(F.dtype)
+
+    def __call__(self, x):
+        return self._offsets(x, np.ascontiguousarray(self.sampler.eval(check_points(x, self.sampler.d)).T))
+
+    def grad(self, x):
+        """-> (n, S, d): [j, s, c] = d f_s / d x_c at x_j, the gradient of f_s minus the prior mean (a non-constant mean function's own
+        Jacobian is the caller's to add)."""
+        return np.ascontiguousarray(self.sampler.eval_grad(check_points(x, self.sampler.d), values=False)[1].transpose(2, 0, 1))
+
+    def value_and_grad(self, x):
+        """-> (fs(x) (n, S), grad(x) (n, S, d)) from one call; the values are bitwise those of fs(x)."""
+        F, G = self.sampler.eval_grad(check_points(x, self.sampler.d), values=True)
+        return self._offsets(x, np.ascontiguousarray(F.T)), np.ascontiguousarray(G.transpose(2, 0, 1))
+
+    def state(self):
+        return self.sampler.state()
+
+    def free(self):
+        self.sampler.free()
 
 
 def _warn(info, what):
@@ -431,6 +631,7 @@ class CGPosteriorGP:
     def __init__(self, cg: ConjugateGradients, fx: FiniteGP, y, ctx=None, dtype=None):
         self.approx, self.prior = cg, fx.f
         self.dev, desc, keep, probes, delta = _device(cg, fx, y, ctx, dtype)
+        self._desc, self._keep, self._delta = desc, keep, delta   # function_samples solves under the same parameter set
         self.noise = float(fx.Sigma_y)
         try:
             self.lml, self.info = self.dev.fit(desc, probes[0], delta, probes_k=probes[1])
@@ -459,6 +660,17 @@ class CGPosteriorGP:
         m, v, info = self.dev.predict(x, mean=True, var=True)
         _warn(info, "the predictive variance")
         return self._offsets(x, m), v
+
+    def function_samples(self, n_samples, n_features=2048, rng=None):
+        """n_samples pathwise function samples of the exact posterior (svgp_cg_sampler_*): one batched solve of n_samples right-hand
+        sides at the posterior's own tol, maxiter and preconditioner, then fs(x) -> (n, S), fs.grad(x) -> (n, S, d), fs.value_and_grad(x)
+        at any x, any number of times.  The random numbers come from pathwise.draw_basis(kernel, N, n_features, n_samples, rng)."""
+        from .pathwise import draw_basis
+        S, L = _check_sample_counts(n_samples, n_features)
+        basis = draw_basis(self.prior.kernel, self.dev.n, L, S, rng, _ffi.np_dtype(self.dev.dtype), d=self.dev.d)
+        smp = self.dev.sampler(self._desc, basis, self._delta)
+        _warn(smp.info, "the function samples")
+        return CGFunctionSamples(self, smp)
 
     def _lik_predictive(self, x, y, want):
         if not self.noise > 0:

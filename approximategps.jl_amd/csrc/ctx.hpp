@@ -156,6 +156,7 @@ struct svgp_ctx {
   int pred_gh_n = 0;
   svgp::DevBuf smp_out;     // [S][len] samples of a host-output svgp_sampler_eval call, copied out (model dtype)
   svgp::DevBuf smp_grad;    // [S][d][len] gradients of a host-output svgp_sampler_eval_grad call, copied out (model dtype)
+  svgp::DevBuf cgs_part;    // the row segments' partial sums of one svgp_cg_sampler_eval / _eval_grad call (kernels.hpp: CgSampleArgs::part)
   struct GradWs* gws = nullptr;  // gradient workspace, cached by problem shape (deleted by svgp_ctx_destroy)
   struct CollapsedWs* cws = nullptr;   // fp64 M-sized tail of svgp_collapsed_*, cached by Mp (deleted by svgp_ctx_destroy)
   // data-parallel communicator (comm.hip): one RCCL rank per context; world == 1 without one

@@ -366,4 +366,42 @@ void launch_cg_pc_logdet(hipStream_t s, const double* L, int64_t Mp, int64_t k, 
 void launch_cg_pc_mm(int dtype, hipStream_t s, const double* Mt, int64_t Mp, int64_t k, const void* v, int v_f64, int64_t ldv, int64_t ncols, double alpha,
                      void* out, int64_t ldo, int64_t rows_out);
 
+// ---- cg_sample.hip (pathwise function samples of the exact GP: svgp_cg_sampler_*) -----------------------------------------------
+//   out[s * ldo + j] = mean_const + sum_l cos(frows[.][l] . xs_j + fbias[l]) W[l, s] + sum_i kappa(r^2(x_j, X_i)) V[i, s],   xs = invl o x
+//   grad[(s * d + c) * ldg + j] = invl_c [ - sum_l sin(phase_l) frows[c][l] W[l, s] + 2 sum_i g(r_i^2) (xs_jc - Xs_ic) V[i, s] ]
+// for the points j < len of the window [off, off + len) of x.  The grid is (point workgroups) x (row segments): cg_sample_plan gives
+// the segments (whole chunks of 32 rows; a function of N alone) and the round, the number of points one set of launches covers
+struct CgSampleArgs {
+  const void* frows;   // [d][Lp] omega, zero on the padding
+  const void* fbias;   // [Lp] tau
+  const void* W;       // Lp x S column-major (ld Lp): amp w, zero on the padding rows
+  const void* rows;    // [d][Np] the data rows as launch_kmv_prep wrote them
+  const void* bias;    // [Np]
+  const void* V;       // N x S column-major (ld N)
+  const void* invl;    // [d]
+  const void* x;       // [d][ldx] feature-major inputs
+  void* part;          // nseg x (144 grad | 64 value) x min(round, len) elements of the data dtype
+  void* out;           // nullable in the gradient form
+  void* grad;          // NULL: the value form
+  int64_t ldx, off, len, ldo, ldg;
+  int64_t Lp, N, Np, S;     // N = Np = 0: the features alone
+  int64_t seg_rows, round;  // cg_sample_plan(N)
+  int nseg;
+  int family, d;
+  double variance, mean_const;
+  // set by the launcher: the column block, the coordinate block, the round's points [p_base, p_base + p_len), the partial slots
+  int64_t s0, p_base, p_len;
+  int e0, nq;
+};
+void cg_sample_plan(int64_t N, int64_t* seg_rows, int* nseg, int64_t* round);
+// the points of one set of launches: the plan's round, a quarter of it (at least 256) in the gradient form, whose partial sums have
+// 144 slots a point against at most 64.  It enters no value
+inline int64_t cg_sample_round(int64_t round, bool grad) { return !grad ? round : round / 4 < 256 ? 256 : round / 4; }
+void launch_cg_sample(int dtype, hipStream_t s, const CgSampleArgs& a);
+// B[s * N + i] = delta[i] - phi[s * N + i] - sigma eps[s * N + i], formed in fp64 and rounded once (phi nullable: no features)
+void launch_cg_sample_rhs(int dtype, hipStream_t s, const void* delta, const void* phi, const void* eps, double sigma, int64_t N, int64_t S, void* B);
+// W[s * Lp + l] = amp w[s * L + l] (l < L), 0 on the padding; frows[f][l] = omega[l * d + f], fbias[l] = tau[l], 0 on the padding
+void launch_cg_sample_basis(int dtype, hipStream_t s, const void* omega, const void* tau, const void* w, int d, int64_t L, int64_t Lp, int64_t S,
+                            double amp, void* frows, void* fbias, void* W);
+
 }  // namespace svgp

@@ -856,7 +856,8 @@ int32_t svgp_sampler_eval_grad(svgp_ctx* ctx, const svgp_sampler* sampler, const
  * SVGP_INVALID_ARG, before anything is enqueued: a NULL required pointer; descriptor dtype or d different from the data's; an unknown
  * kernel; data without y when delta is NULL; maxiter < 1, tol <= 0, diag < 0, variance <= 0, reserved != 0 (NaN counts as a violation);
  * S < 1; T < 0, or T > 0 with NULL probes; ldv, ldo, ldb or ldx < N; on_device not 0 / 1; alpha or predict before a successful fit;
- * n < 1.  Preconditioning: the next section.  Out of scope: per-point noise, cov / cross-cov, pathwise samples, multi-GPU, the Julia hooks. */
+ * n < 1.  Preconditioning: the next section; pathwise function samples: the one after it.  Out of scope: per-point noise, cov /
+ * cross-cov, multi-GPU, the Julia hooks. */
 typedef struct svgp_cg svgp_cg;
 typedef struct svgp_cg_desc {
   int32_t dtype, kernel, d, maxiter; /* maxiter >= 1 */
@@ -930,6 +931,55 @@ int32_t svgp_cg_fit_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc
 int32_t svgp_cg_lml_grad_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
                                  const double* probes_k, double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale,
                                  double* d_diag, double* d_mean_const);
+/* ---- pathwise function samples of the exact GP ---------------------------------------------------------------------------------------
+ * S draws from the exact posterior by pathwise conditioning (Wilson et al. 2020, 2021) with the CG solve, each one a FUNCTION that can be
+ * evaluated at any points, any number of times.  With Khat = K(X, X) + sigma^2 I (sigma^2 = desc.diag), delta = y - mean(X), phi_l as in
+ * svgp_sampler_* and eps_s ~ N(0, I_N):
+ *   f_s(x) = mean_const + sum_l phi_l(x) w_sl + sum_j k(x, X_j) V_js,      V_s = Khat^-1 (delta - Phi(X) w_s - sigma eps_s)
+ *   d f_s / d x_c = invl_c [ - sum_l sin(phase_l) omega_lc amp w_sl + 2 sum_j g(r_j^2) (xs_c - Xs_jc) V_js ]     (g as in svgp_sampler_eval_grad)
+ * With n_features = 0 and eps = 0, V_s = alpha and f_s is the posterior mean.  The Fourier part approximates the PRIOR; the update term is
+ * exact: f_s(X) + sigma eps_s + sigma^2 V_s = y to the solve's tolerance whatever L is.  The library draws nothing: the caller supplies
+ * every random number in a svgp_sample_basis whose eps is [S][N] in the data dtype (omega, tau, w as there, data dtype).
+ *   create  forms the S right-hand sides on the device (Phi(X) w through the evaluation kernel over the features alone, then one affine
+ *           pass in fp64 rounded once) and runs ONE batched solve over the S columns, preconditioned when the handle has a preconditioner;
+ *           info reports it as in svgp_cg_solve (nullable).  Running out of maxiter is SVGP_OK with info->converged = 0.
+ *           SVGP_NOT_POSDEF as there: no sampler is made.  delta: N host doubles, or NULL for y - mean_const.  The sampler is a SNAPSHOT:
+ *           it owns the prepared rows of X and their bias, the parameters, omega, tau, amp W and V in the data dtype, O(N (d + S)) memory;
+ *           later calls on the CG handle, or freeing it or the data handle, change nothing.  It needs no preceding svgp_cg_fit and leaves
+ *           the handle's cached fit as it was.  The basis arrays are host memory, read before the call returns.
+ *   eval    out[s * ldo + j] = f_s(x_{batch_off + j}), s < S, j < batch_len, data dtype; host memory, or device memory of the context's
+ *           GPU (out_on_device = 1).  A non-constant prior mean's offsets are the caller's to add.
+ *   eval_grad  grad_out[(s * d + c) * ldg + j] = d f_s / d x_c at point batch_off + j; out: the values, bitwise svgp_cg_sampler_eval's, or
+ *           NULL.  Both outputs live in the same kind of memory.
+ *   state   V (N x S column-major, data dtype, exactly as evaluated), the per-column iteration counts and relative residuals of the
+ *           solve; each output nullable.
+ * One data-sized kernel family: the feature and kernel tiles are generated on the MFMA and multiplied by amp W and by the N x S panel V
+ * read from global memory; nothing n* x N is stored.  The grid is (point workgroups) x (row segments): every segment's partial sums are
+ * written in the data dtype and added in ascending segment order in fp64, no atomics.  THE SEGMENTATION IS A FUNCTION OF N ALONE, so,
+ * bitwise: a point's value and gradient do not depend on the window, the call, the other points or the other columns (column s of an
+ * S-sample sampler is the 1-sample sampler of the same draws); host and device output agree; repeated calls agree; eval_grad's values
+ * are eval's.  Points are processed in rounds (at most 4096 points), which bounds the partial buffer; that buffer belongs to the CONTEXT, the
+ * evaluations only read the sampler, so one sampler may serve several contexts of its device (one thread per context, as everywhere).
+ * ALWAYS LOCAL.
+ * SVGP_INVALID_ARG, before anything is enqueued: everything svgp_cg_solve rejects in the descriptor; n_samples < 1, n_features < 0,
+ * NULL eps, NULL omega / tau / w with n_features > 0; data without y when delta is NULL; desc.diag == 0 with a preconditioner set; in
+ * the evaluations a d or dtype mismatch between sampler and data, a window outside the data, ldo (with out) or ldg < batch_len, NULL
+ * out (eval) or grad_out.  Non-finite inputs give non-finite outputs with SVGP_OK (a right-hand side whose norm is not finite is not
+ * solved: V is NaN, info->converged = 0), and the context stays healthy.  No other entry point's result changes by a bit.  Found by
+ * symbol (no ABI version step). */
+typedef struct svgp_cg_sampler svgp_cg_sampler;
+int32_t svgp_cg_sampler_create(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, const svgp_sample_basis* basis,
+                               svgp_cg_sampler** out, svgp_cg_info* info);
+int32_t svgp_cg_sampler_eval(svgp_ctx* ctx, const svgp_cg_sampler* sampler, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                             void* out, int64_t ldo, int32_t out_on_device);
+int32_t svgp_cg_sampler_eval_grad(svgp_ctx* ctx, const svgp_cg_sampler* sampler, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                                  void* out, int64_t ldo, void* grad_out, int64_t ldg, int32_t out_on_device);
+int32_t svgp_cg_sampler_state(svgp_ctx* ctx, const svgp_cg_sampler* sampler, void* V_out, int32_t* iters_out, double* relres_out);
+int32_t svgp_cg_sampler_free(svgp_ctx* ctx, svgp_cg_sampler* sampler);
+/* host only: the row segmentation and the round of the evaluations for N data rows - segments of seg_rows rows (512; more beyond 1024
+ * segments), round_points points per set of launches (about 2^20 / n_segments, a multiple of 256 in [256, 4096]; the gradient form
+ * takes a quarter of it, at least 256).  SVGP_INVALID_ARG: N < 0 or a NULL pointer. */
+int32_t svgp_cg_sampler_plan(int64_t N, int64_t* seg_rows, int32_t* n_segments, int64_t* round_points);
 /* host only, like svgp_gausshermite: out = e_1' log(T) e_1 for the Lanczos tridiagonal of `iters` CG steps with step lengths a[j] and
  * residual ratios b[j] = |r_{j+1}|^2 / |r_j|^2 (diagonal 1 / a_j + b_{j-1} / a_{j-1}, off-diagonal sqrt(b_j) / a_j; b[iters - 1] is not
  * read), by an implicit-shift QL iteration in fp64.  SVGP_INVALID_ARG: NULL pointers, iters < 1; SVGP_NOT_POSDEF (out = NaN): an

@@ -5,6 +5,7 @@ entries a second are the yardstick; no ratio is fixed in advance: the run report
 
     python tools/cg_time.py [--reps 7] [--n 100000] [--out profiles/cg/cg_time.jsonl]
     python tools/cg_time.py --precond 256 512 1024 --precond-out profiles/cg/cg_precond_time.jsonl
+    python tools/cg_time.py --sample --sample-out profiles/cg/cg_sample_time.jsonl      (sample_leg below)
 
 --precond K ...: after the unpreconditioned fit, the same fit (17 columns, same tol and maxiter) with the Nystrom preconditioner of K
 data points (default_rng([0, 2]).choice, jitter 1e-4): iterations, final residual, wall time, the preconditioner's setup time and
@@ -32,8 +33,108 @@ def stat(ts):
     return [round(statistics.median(ts), 3), round(min(ts), 3), round(max(ts), 3)]
 
 
+def sample_leg(a):
+    """--sample: what the pathwise function samples of the exact GP cost at N = --n, d = --d, S = --cols, L = --features, both dtypes,
+    median [min, max] of --sample-reps: svgp_cg_sampler_eval over n* = N points (the data themselves) beside svgp_cg_matvec at the same N
+    and S (generated kernel entries a second: (N + L) n* and N^2 per device time); eval and eval_grad over n* = 256 points beside
+    kmv_kernel over the same points (svgp_cg_predict, mean only; wall time of the blocking calls, upload of the 256 points included in
+    both); svgp_cg_sampler_create beside one svgp_cg_solve of the same number of columns at the same tol and --sample-maxiter."""
+    import torch
+
+    from approxgp import DeviceConjugateGradients, _ffi, cg_sample_plan
+    from approxgp.kernels import ARDTransform, ScaledKernel, SEKernel, TransformedKernel
+    from approxgp.pathwise import draw_basis
+    from approxgp.synthetic import synth_arrays
+
+    ctx = _ffi.Context(0)
+    N, d, S, L, reps = a.n, a.d, a.cols, a.features, a.sample_reps
+    rows = []
+    for dt in (np.float64, np.float32):
+        tdt = torch.float64 if dt == np.float64 else torch.float32
+        p = synth_arrays(0, N, 64, d, dtype=dt)
+        kernel = ScaledKernel(TransformedKernel(SEKernel(), ARDTransform(np.asarray(p["inv_lengthscale"], dtype=np.float64))), p["variance"])
+        x = np.asarray(p["x"])[:, :N]
+        dev = DeviceConjugateGradients(ctx, x, p["y"][:N], dt)
+        desc, keep = dev.desc(kernel, p["sigma2"], tol=1e-6, maxiter=a.sample_maxiter)
+        basis = draw_basis(_ffi.KERNEL_SE, N, L, S, np.random.default_rng(0), dt, d=d)
+        V = torch.randn((S, N), dtype=tdt, device="cuda")
+        out = torch.empty_like(V)
+        X = torch.empty_like(V)
+        x256 = np.ascontiguousarray(x[:, :256] + 0.01)
+        big = torch.empty((S, N), dtype=tdt, device="cuda")
+        f256 = torch.empty((S, 256), dtype=tdt, device="cuda")
+        g256 = torch.empty((S, d, 256), dtype=tdt, device="cuda")
+        torch.cuda.synchronize()
+        wall = lambda fn: (lambda t0: (fn(), 1e3 * (time.perf_counter() - t0))[1])(time.perf_counter())
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            smp = dev.sampler(desc, basis)   # warm-up of every shape
+            dev.fit(desc)
+            dev.matvec(desc, V, out=out)
+            smp.eval(dev.data, out=big)
+            smp.eval(x256, out=f256)
+            smp.eval_grad(x256, out=f256, grad_out=g256)
+            dev.predict(x256, var=False)
+            smp.free()
+            cr_wall, so_wall, so_mv, cr_mv, iters = [], [], [], [], []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                smp = dev.sampler(desc, basis)
+                cr_wall.append(1e3 * (time.perf_counter() - t0))
+                cr_mv.append(smp.info.ms_matvec)
+                iters.append(smp.info.iterations)
+                t0 = time.perf_counter()
+                info = dev.solve(desc, V, out=X)[3]
+                so_wall.append(1e3 * (time.perf_counter() - t0))
+                so_mv.append(info.ms_matvec)
+                if _ < reps - 1:
+                    smp.free()
+        mv, ev, e256, g256t, e256w, g256w, p256w = [], [], [], [], [], [], []
+        for _ in range(reps):
+            dev.matvec(desc, V, out=out)
+            mv.append(ctx.timing().ms_strip)
+            smp.eval(dev.data, out=big)
+            ev.append(ctx.timing().ms_strip)
+            e256w.append(wall(lambda: smp.eval(x256, out=f256)))
+            e256.append(ctx.timing().ms_strip)
+            g256w.append(wall(lambda: smp.eval_grad(x256, out=f256, grad_out=g256)))
+            g256t.append(ctx.timing().ms_strip)
+            p256w.append(wall(lambda: dev.predict(x256, var=False)))
+        m_mv, m_ev = statistics.median(mv), statistics.median(ev)
+        seg_rows, nseg, rnd = cg_sample_plan(N)
+        row = {"dtype": np.dtype(dt).name, "N": N, "d": d, "S": S, "L": L, "reps": reps, "plan": {"seg_rows": seg_rows, "segments": nseg, "round": rnd},
+               "eval_all": {"n": N, "ms": stat(ev), "generated_per_s": float(f"{(N + L) * N / (1e-3 * m_ev):.4g}") if m_ev > 0 else None},
+               "matvec": {"ms": stat(mv), "generated_per_s": float(f"{N * N / (1e-3 * m_mv):.4g}") if m_mv > 0 else None},
+               "rate_over_matvec": round(((N + L) * N / m_ev) / (N * N / m_mv), 3) if m_mv > 0 and m_ev > 0 else None,
+               "n256": {"ms_eval": stat(e256), "ms_eval_grad": stat(g256t), "ms_eval_wall": stat(e256w), "ms_eval_grad_wall": stat(g256w),
+                        "ms_predict_mean_wall": stat(p256w),
+                        "predict_over_eval_wall": round(statistics.median(p256w) / statistics.median(e256w), 2),
+                        "predict_over_eval_grad_wall": round(statistics.median(p256w) / statistics.median(g256w), 2)},
+               "create": {"tol": 1e-6, "maxiter": a.sample_maxiter, "iterations": max(iters), "ms_wall": stat(cr_wall), "ms_matvec": stat(cr_mv),
+                          "solve_ms_wall": stat(so_wall), "solve_ms_matvec": stat(so_mv),
+                          "create_over_solve_wall": round(statistics.median(cr_wall) / statistics.median(so_wall), 3)},
+               "finite": bool(torch.isfinite(big).all().item() and torch.isfinite(g256).all().item())}
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        smp.free()
+        dev.free()
+        del V, out, X, big, f256, g256
+    ctx.close()
+    if a.sample_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.sample_out)), exist_ok=True)
+        with open(a.sample_out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sample", action="store_true", help="the pathwise sampler's leg alone (svgp_cg_sampler_*)")
+    ap.add_argument("--features", type=int, default=2048)
+    ap.add_argument("--sample-reps", type=int, default=3)
+    ap.add_argument("--sample-maxiter", type=int, default=30)
+    ap.add_argument("--sample-out", default=None, help="e.g. profiles/cg/cg_sample_time.jsonl")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--n", type=int, default=100_000)
     ap.add_argument("--d", type=int, default=8)
@@ -45,6 +146,8 @@ def main():
     ap.add_argument("--precond", type=int, nargs="*", default=[], help="preconditioner sizes for the preconditioned leg")
     ap.add_argument("--precond-out", default=None)
     a = ap.parse_args()
+    if a.sample:
+        return sample_leg(a)
     import torch
 
     from approxgp import DeviceConjugateGradients, _ffi, draw_probes
