@@ -104,14 +104,26 @@ class ConjugateGradients:
 
 class DeviceConjugateGradients:
     """A resident svgp_cg handle over x (and y): x a plain vector (d = 1) or a (d, n) ColVecs array; with layout = ROWVECS an (n, d)
-    RowVecs array."""
+    RowVecs array.  data = an existing _ffi.DeviceData (x, y, dtype and layout None) borrows it instead of uploading: e.g. a
+    DeviceData.wrap of torch features, with no host round trip; the caller keeps it alive and frees it."""
 
-    def __init__(self, ctx: _ffi.Context, x, y, dtype, layout=None):
+    def __init__(self, ctx: _ffi.Context, x=None, y=None, dtype=None, layout=None, data=None):
         self.ctx = ctx
-        x = np.asarray(x)
-        if layout is None:
-            layout = _ffi.VEC if x.ndim == 1 else _ffi.COLVECS
-        self.data = _ffi.DeviceData(ctx, x, y, dtype, layout)
+        if data is not None:
+            if not isinstance(data, _ffi.DeviceData):
+                raise TypeError("data: an _ffi.DeviceData")
+            if x is not None or y is not None or dtype is not None or layout is not None:
+                raise ValueError("data replaces x, y, dtype and layout")
+            if getattr(data, "h", None) is None:
+                raise ValueError("data has been freed")
+            self.data, self._owns_data = data, False
+        else:
+            if x is None or dtype is None:
+                raise ValueError("DeviceConjugateGradients needs x and dtype, or data")
+            x = np.asarray(x)
+            if layout is None:
+                layout = _ffi.VEC if x.ndim == 1 else _ffi.COLVECS
+            self.data, self._owns_data = _ffi.DeviceData(ctx, x, y, dtype, layout), True
         self.dtype, self.d, self.n = self.data.dtype, self.data.d, self.data.n
         self.precond_k = 0   # points of the preconditioner set through set_preconditioner
         h = C.c_void_p()
@@ -284,14 +296,41 @@ class DeviceConjugateGradients:
             self._check(self.ctx.lib.svgp_cg_fit_precond(self.ctx.h, self.h, C.byref(desc), dlp, T, zp, zkp, C.byref(lml), C.byref(info)))
         return lml.value, info
 
-    def lml_grad(self, desc, probes, delta=None, probes_k=None):
-        """-> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const"}, CGInfo)"""
+    def _x_grad(self, x_grad_out):
+        """-> (InputGrad, what lml_grad returns as grads["x"]): a (d, N) array of the data dtype, or the caller's device tensor"""
+        if x_grad_out is None:
+            xg = np.zeros((self.d, self.n), dtype=_ffi.np_dtype(self.dtype))
+            return _ffi.InputGrad(_ffi._ptr(xg), self.n, 0, 0), xg
+        t = x_grad_out
+        if (not _ffi._is_device_tensor(t) or not t.is_contiguous() or not t.is_floating_point() or tuple(t.shape) != (self.d, self.n)
+                or t.element_size() != np.dtype(_ffi.np_dtype(self.dtype)).itemsize):
+            raise ValueError("x_grad_out: a contiguous (d, N) device tensor of the data dtype")
+        return _ffi.InputGrad(C.c_void_p(int(t.data_ptr())), self.n, 1, 0), t
+
+    def lml_grad(self, desc, probes, delta=None, probes_k=None, wrt_inputs=False, x_grad_out=None):
+        """-> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const"}, CGInfo).  wrt_inputs: grads["x"] as well, (d, N) in the
+        data dtype: d lml / d x_ic by the same trace estimator (svgp_cg_lml_grad_inputs), every other entry bitwise what it is without;
+        x_grad_out: a contiguous (d, N) torch device tensor to write it into (it is returned as grads["x"])."""
+        if not isinstance(wrt_inputs, (bool, np.bool_)):
+            raise ValueError("wrt_inputs is True or False")
+        if x_grad_out is not None and not wrt_inputs:
+            raise ValueError("x_grad_out needs wrt_inputs=True")
         T, zp, zkp, keep = self._probes(probes, probes_k)
         dl = self._f64(delta)
+        if wrt_inputs and dl is not None and dl.shape != (self.n,):
+            raise ValueError("delta: an (N,) array")
         lml, info = C.c_double(), _ffi.CGInfo()
         dv, dd, dm, dil = C.c_double(), C.c_double(), C.c_double(), np.zeros(self.d)
         dp = C.POINTER(C.c_double)
         dlp = None if dl is None else dl.ctypes.data_as(dp)
+        if wrt_inputs:
+            if self.precond_k and T > 0 and probes_k is None:
+                raise ValueError("a preconditioner is set: the probes need probes_k, a (k, T) array")
+            gx, xg = self._x_grad(x_grad_out)
+            self._check(self.ctx.lib.svgp_cg_lml_grad_inputs(self.ctx.h, self.h, C.byref(desc), dlp, T, zp, zkp if self.precond_k else None,
+                                                             C.byref(lml), C.byref(info), C.byref(dv), dil.ctypes.data_as(dp), C.byref(dd),
+                                                             C.byref(dm), C.byref(gx)))
+            return lml.value, {"variance": dv.value, "inv_lengthscale": dil, "diag": dd.value, "mean_const": dm.value, "x": xg}, info
         if probes_k is None:
             self._check(self.ctx.lib.svgp_cg_lml_grad(self.ctx.h, self.h, C.byref(desc), dlp, T, zp, C.byref(lml), C.byref(info),
                                                       C.byref(dv), dil.ctypes.data_as(dp), C.byref(dd), C.byref(dm)))
@@ -343,7 +382,8 @@ class DeviceConjugateGradients:
             self.ctx.lib.svgp_cg_free(self.ctx.h, self.h)
             self.h = None
         if getattr(self, "data", None) is not None:
-            self.data.free()
+            if getattr(self, "_owns_data", True):
+                self.data.free()
             self.data = None
 
     def __del__(self):
@@ -548,8 +588,8 @@ def _warn(info, what):
                       f"iterations (largest relative residual {info.max_rel_residual:.3e})", RuntimeWarning, stacklevel=3)
 
 
-def _cg_kwargs(fn, kwargs):
-    extra = set(kwargs) - {"ctx", "dtype"}
+def _cg_kwargs(fn, kwargs, also=()):
+    extra = set(kwargs) - {"ctx", "dtype"} - set(also)
     if extra:
         raise TypeError(f"{fn}() with ConjugateGradients got unexpected keyword arguments {sorted(extra)}")
     return kwargs.get("ctx"), kwargs.get("dtype")
@@ -611,16 +651,26 @@ def approx_lml(approx, fx, y, **kwargs):
 
 def approx_lml_and_gradient(approx, fx, y, **kwargs):
     """ConjugateGradients: -> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const"}): the gradient with respect to the
-    kernel parameters, the noise variance Σy and the constant mean.  Any other approximation: the existing methods."""
+    kernel parameters, the noise variance Σy and the constant mean.  wrt_inputs=True adds grads["x"] = d lml / d x shaped like fx.x (a
+    vector for a plain vector x, (d, N) ColVecs otherwise), from the same solve and the same probes: what a feature map in front of the
+    kernel, input warping or latent inputs chain through.  With a CustomMean prior it is the gradient of the kernel part alone:
+    d lml / d (y - mean(x)) is the posterior's alpha, and the mean's Jacobian is the caller's.  The estimator is unbiased for the gradient
+    but is not the derivative of the estimated value: a caller who trains a flexible map through grads["x"] passes a new seed each step.
+    Any other approximation: the existing methods."""
     if not isinstance(approx, ConjugateGradients):
         return _nn.approx_lml_and_gradient(approx, fx, y, **kwargs)
-    ctx, dtype = _cg_kwargs("approx_lml_and_gradient", kwargs)
+    ctx, dtype = _cg_kwargs("approx_lml_and_gradient", kwargs, also=("wrt_inputs",))
+    wrt_inputs = kwargs.get("wrt_inputs", False)
+    if not isinstance(wrt_inputs, (bool, np.bool_)):
+        raise ValueError("wrt_inputs is True or False")
     dev, desc, keep, probes, delta = _device(approx, fx, y, ctx, dtype)
     try:
-        lml, grads, info = dev.lml_grad(desc, probes[0], delta, probes_k=probes[1])
+        lml, grads, info = dev.lml_grad(desc, probes[0], delta, probes_k=probes[1], wrt_inputs=bool(wrt_inputs))
     finally:
         dev.free()
     _warn(info, "the fit")
+    if wrt_inputs and np.ndim(fx.x) == 1:
+        grads["x"] = grads["x"][0]
     return lml, grads
 
 

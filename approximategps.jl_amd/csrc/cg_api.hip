@@ -1,5 +1,5 @@
 // cg_api.hip — the exact GP by matrix-free conjugate gradients: svgp_cg_create / _matvec / _solve / _fit / _lml_grad / _alpha / _predict /
-// _free and the host-only svgp_lanczos_logdet (cg.hip: the kernels).  Host orchestration only.
+// _free and the host-only svgp_lanczos_logdet (cg.hip: the kernels); svgp_cg_lml_grad_inputs (cg_xgrad.hip: its kernel).  Host orchestration only.
 //   Khat = K(x, x) + diag I,  alpha = Khat^-1 delta,  lml = -1/2 (delta' alpha + log det Khat + N log 2 pi)
 // Batched CG over column blocks of 64: per iteration one kmv product (the only O(N^2) work), two column dots, two masked axpy passes;
 // the per-column scalars and the CG coefficients of every column stay on the device, the host reads the block's 64 activity flags (and
@@ -60,6 +60,7 @@ struct svgp_cg {
   DevBuf st, partial, hist, res;   // fp64: the block's state, dot partials, CG coefficient histories [2][maxiter][64], small results
   DevBuf fitB, fitX, gout;   // N x (T + 1): [delta, z_1 .. z_T], [alpha, w_1 .. w_T] of the last fit; the gradient's products
   DevBuf f64tmp;             // fp64 staging of delta and the probes
+  DevBuf xL, xR, xpart, xout;   // d lml / d x: the N x (2T + 1) panels, the column blocks' partial sums (fp64), a host output's staging
   bool have_fit = false;
   CgPar fit;                 // the parameter set alpha belongs to
   CgPrecond pc;              // pc.k == 0: none
@@ -618,10 +619,72 @@ int common_checks(svgp_ctx* ctx, const svgp_cg* cg, const svgp_cg_desc* ds) {
 
 // svgp_cg_fit and svgp_cg_lml_grad: g non-null asks for the gradient {d_variance, d_inv_lengthscale[d], d_diag, d_mean_const}
 struct FitGrad { double *dv, *dil, *dd, *dm; };
+
+// NaN into every entry of the input gradient's output (T = 0, SVGP_NOT_POSDEF); the context's message is the caller's to keep
+int xgrad_fill_nan(svgp_ctx* ctx, const svgp_cg* cg, const svgp_input_grad* gx) {
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  if (gx->on_device) {
+    launch_cg_affine(cg->dtype, ctx->stream, gx->x, 0, gx->ld, cg->N, cg->d, 0.0, nan, gx->x, gx->ld);
+    KCHECK(ctx, "cg (NaN outputs)");
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    return SVGP_OK;
+  }
+  for (int f = 0; f < cg->d; ++f)
+    for (int64_t i = 0; i < cg->N; ++i) {
+      if (cg->dtype == SVGP_F64) static_cast<double*>(gx->x)[int64_t(f) * gx->ld + i] = nan;
+      else static_cast<float*>(gx->x)[int64_t(f) * gx->ld + i] = std::numeric_limits<float>::quiet_NaN();
+    }
+  return SVGP_OK;
+}
+
+// d lml / d x after the gradient block of fit_impl: U = fitX = [alpha, w_t], P = fitB = [alpha, p_t] on the device.
+//   Lp = [alpha, w_t .., p_t ..],  Rp = [alpha, -p_t / 2T .., -w_t / 2T ..]  (each entry of Rp rounded once to the data dtype)
+int xgrad_enqueue(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int32_t T, const svgp_input_grad* gx) {
+  hipStream_t s = ctx->stream;
+  const int dt = cg->dtype;
+  const int64_t N = cg->N, S2 = 2 * int64_t(T) + 1;
+  const size_t col = size_t(N) * cg->es;
+  char *L = cg->xL.as<char>(), *R = cg->xR.as<char>();
+  const char *U = cg->fitX.as<char>(), *P = cg->fitB.as<char>();
+  const double w = -1.0 / (2.0 * double(T));
+  HIPC(ctx, hipMemcpyAsync(L, U, col * size_t(T + 1), hipMemcpyDeviceToDevice, s));
+  HIPC(ctx, hipMemcpyAsync(L + col * size_t(T + 1), P + col, col * size_t(T), hipMemcpyDeviceToDevice, s));
+  HIPC(ctx, hipMemcpyAsync(R, U, col, hipMemcpyDeviceToDevice, s));
+  launch_cg_affine(dt, s, P + col, 0, N, N, T, w, 0.0, R + col, N);
+  launch_cg_affine(dt, s, U + col, 0, N, N, T, w, 0.0, R + col * size_t(T + 1), N);
+  CgXgradArgs a{};
+  a.rows = cg->rows.p;
+  a.bias = cg->bias.p;
+  a.invl = cg->invl.p;
+  a.x = cg->data->x.p;
+  a.Lp = L;
+  a.Rp = R;
+  a.part = cg->xpart.p;
+  a.ldx = cg->data->ldx;
+  a.N = N;
+  a.Np = cg->Np;
+  a.S = S2;
+  a.family = par.family;
+  a.d = cg->d;
+  a.variance = par.variance;
+  TREC(ctx, ctx->ev[0], s);
+  launch_cg_xgrad(dt, s, a, gx->on_device ? gx->x : cg->xout.p, gx->on_device ? gx->ld : N);
+  TREC(ctx, ctx->ev[1], s);
+  KCHECK(ctx, "cg (input gradient)");
+  if (!gx->on_device) HIPC(ctx, hipMemcpy2DAsync(gx->x, size_t(gx->ld) * cg->es, cg->xout.p, col, col, size_t(cg->d), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  float t = 0;
+  (void)elapsed_ms(ctx, &t, ctx->ev[0], ctx->ev[1]);
+  ctx->timing = svgp_timing{};
+  ctx->timing.ms_strip = t;   // the data-sized kernels of the input gradient alone
+  ctx->timing.ms_total = t;
+  return SVGP_OK;
+}
 // with a preconditioner: probes_k (k x T) joins the probes, z_t = sigma eps_t + Z Lu^-T xi_t (E z z' = P), log det Khat = log det P +
 // (1 / T) sum_t (z_t' P^-1 z_t) e_1' log(T_t) e_1, and the gradient's trace terms are w_t' dKhat (P^-1 z_t)
 int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* delta, int32_t T, const double* probes, double* lml_out,
-             svgp_cg_info* info, const FitGrad* g, const double* probes_k = nullptr, bool precond_call = false) {
+             svgp_cg_info* info, const FitGrad* g, const double* probes_k = nullptr, bool precond_call = false,
+             const svgp_input_grad* gx = nullptr) {
   int rc = common_checks(ctx, cg, ds);
   if (rc) return rc;
   const bool pc = cg->pc.k > 0;
@@ -634,6 +697,7 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
   if (T < 0) return fail(ctx, SVGP_INVALID_ARG, "the number of probes must be >= 0");
   if (T > 0 && !probes) return fail(ctx, SVGP_INVALID_ARG, "null probes with T > 0");
   if (g && (!g->dv || !g->dil)) return fail(ctx, SVGP_INVALID_ARG, "null gradient output");
+  if (gx && (rc = check_input_grad(ctx, cg->data, cg->N, gx)) != SVGP_OK) return rc;
   HIPC(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int dt = cg->dtype, d = cg->d;
@@ -647,6 +711,22 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
   if ((rc = cg->f64tmp.reserve(ctx, size_t(N) * size_t(T > 0 ? T : 1) * 8, "the probes")) != SVGP_OK) return rc;
   if ((rc = cg->res.reserve(ctx, (size_t(d + 2) * size_t(S) + 8) * 8, "the CG results")) != SVGP_OK) return rc;
   if (g && (rc = cg->gout.reserve(ctx, col * size_t(S), "the gradient's products")) != SVGP_OK) return rc;
+  if (gx && T > 0) {
+    const size_t S2 = 2 * size_t(T) + 1;
+    if ((rc = cg->xL.reserve(ctx, col * S2, "the input gradient's panels")) != SVGP_OK) return rc;
+    if ((rc = cg->xR.reserve(ctx, col * S2, "the input gradient's panels")) != SVGP_OK) return rc;
+    if ((rc = cg->xpart.reserve(ctx, ((S2 + 15) / 16) * size_t(d) * size_t(N) * 8, "the input gradient's partial sums")) != SVGP_OK) return rc;
+    if (!gx->on_device && (rc = cg->xout.reserve(ctx, col * size_t(d), "the input gradient")) != SVGP_OK) return rc;
+  }
+  // SVGP_NOT_POSDEF: NaN in the input gradient as well, the status and its message kept
+  auto nan_inputs = [&](int status) {
+    if (gx && status == SVGP_NOT_POSDEF) {
+      const std::string keep = ctx->err;
+      (void)xgrad_fill_nan(ctx, cg, gx);
+      ctx->err = keep;
+    }
+    return status;
+  };
   if ((rc = set_params(ctx, cg, par)) != SVGP_OK) {
     if (rc == SVGP_NOT_POSDEF) {
       svgp_cg_info bad{};
@@ -654,7 +734,7 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
       if (info) *info = bad;
       if (lml_out) *lml_out = bad.lml;
     }
-    return rc;
+    return nan_inputs(rc);
   }
   // [delta, z_1 .. z_T], each entry rounded once to the data dtype
   if (delta) {
@@ -684,7 +764,7 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
   if (rc) {
     if (info) *info = out;
     if (lml_out) *lml_out = out.lml;
-    return rc;
+    return nan_inputs(rc);
   }
   double* partial = cg->partial.as<double>();
   double* res = cg->res.as<double>();
@@ -751,6 +831,7 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
     *g->dv = combine(h.data() + S, h.data(), par.diag) / par.variance;   // K v = Khat v - diag v
     for (int f = 0; f < d; ++f) g->dil[f] = combine(h.data() + size_t(2 + f) * size_t(S), nullptr, 0.0) / par.invl[f];
     if (g->dm) *g->dm = h[size_t(d + 2) * size_t(S)];
+    if (gx && (rc = T > 0 ? xgrad_enqueue(ctx, cg, par, T, gx) : xgrad_fill_nan(ctx, cg, gx)) != SVGP_OK) return rc;
   }
   if (info) *info = out;
   if (lml_out) *lml_out = out.lml;
@@ -1095,6 +1176,18 @@ int32_t svgp_cg_lml_grad_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc*
   if (!cg) return fail(ctx, SVGP_INVALID_ARG, "null argument");
   const FitGrad g{d_variance, d_inv_lengthscale, d_diag, d_mean_const};
   return fit_impl(ctx, cg, desc, delta, T, probes, lml_out, info, &g, probes_k, true);
+}
+
+int32_t svgp_cg_lml_grad_inputs(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                                const double* probes_k, double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale,
+                                double* d_diag, double* d_mean_const, const svgp_input_grad* gx) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!cg) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (!gx || !gx->x) return fail(ctx, SVGP_INVALID_ARG, "null input-gradient output");
+  const bool pc = cg->pc.k > 0;
+  if (!pc && probes_k) return fail(ctx, SVGP_INVALID_ARG, "probes_k without a preconditioner on this handle (svgp_cg_set_preconditioner)");
+  const FitGrad g{d_variance, d_inv_lengthscale, d_diag, d_mean_const};
+  return fit_impl(ctx, cg, desc, delta, T, probes, lml_out, info, &g, probes_k, pc, gx);
 }
 
 }  // extern "C"

@@ -404,4 +404,25 @@ void launch_cg_sample_rhs(int dtype, hipStream_t s, const void* delta, const voi
 void launch_cg_sample_basis(int dtype, hipStream_t s, const void* omega, const void* tau, const void* w, int d, int64_t L, int64_t Lp, int64_t S,
                             double amp, void* frows, void* fbias, void* W);
 
+// ---- cg_xgrad.hip (d lml / d x of the exact GP: svgp_cg_lml_grad_inputs) -----------------------------------------------------------
+//   out[c * ldo + i] = invl_c sum_s Lp[i, s] sum_j 2 g(r^2(x_i, x_j)) (xs_ic - xs_jc) Rp[j, s],   g = d kappa / d(r^2), xs = invl o x
+// over the N data points against themselves (r^2 of the diagonal is exactly 0).  One launch per (16 columns, coordinate block); the
+// column blocks' partial sums part[block][c][i] (fp64) are added in ascending order, scaled and rounded once to the data dtype
+struct CgXgradArgs {
+  const void* rows;    // [d][Np] the data rows as launch_kmv_prep wrote them
+  const void* bias;    // [Np]
+  const void* invl;    // [d]
+  const void* x;       // [d][ldx] the data, feature-major, unscaled
+  const void* Lp;      // N x S column-major (ld N): the left panel
+  const void* Rp;      // N x S column-major (ld N): the right panel
+  void* part;          // ceil(S / 16) x d x N doubles
+  int64_t ldx, N, Np, S;
+  int family, d;
+  double variance;
+  // set by the launcher: the column block and the coordinate block
+  int64_t s0;
+  int blk, e0;
+};
+void launch_cg_xgrad(int dtype, hipStream_t s, const CgXgradArgs& a, void* out, int64_t ldo);
+
 }  // namespace svgp

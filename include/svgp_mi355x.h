@@ -931,6 +931,33 @@ int32_t svgp_cg_fit_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc
 int32_t svgp_cg_lml_grad_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
                                  const double* probes_k, double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale,
                                  double* d_diag, double* d_mean_const);
+/* ---- the gradient of the exact GP's log marginal likelihood with respect to the data inputs --------------------------------------------
+ * svgp_cg_lml_grad / svgp_cg_lml_grad_precond, and from the same solve, with p_t = z_t (no preconditioner) or P^-1 z_t, g = d kappa / d(r^2)
+ * as in svgp_sampler_eval_grad and il = inv_lengthscale:
+ *   x_bar[c, i] = d lml / d x_ic = il_c^2 sum_j 2 g(r_ij^2) (x_ic - x_jc) [ alpha_i alpha_j - (1 / 2T) sum_t (w_it p_jt + w_jt p_it) ]
+ * the same trace estimator as the other gradient blocks (unbiased for the exact gradient, exact with unit probes; it is NOT the derivative
+ * of the stochastic Lanczos value).  What a learned feature map in front of the kernel (deep kernel learning), input warping or latent
+ * inputs need.  With a preconditioner whose points are a subset of the data, the dependence of P on x is ignored: P changes the
+ * estimator's variance, not its expectation.  Two identities hold term by term, for any probes: sum_i x_bar[c, i] = 0 (translation) and
+ * sum_i x_ic x_bar[c, i] = il_c d_inv_lengthscale[c] (scaling).
+ *   gx: svgp_input_grad as in svgp_elbo_grad_inputs over the handle's N points: feature-major gx->x[c * ld + i], ld >= N, host or device
+ *       (on_device), data dtype, reserved == 0.
+ *   probes_k: NULL exactly when no preconditioner is set on the handle; with one, as in svgp_cg_lml_grad_precond.
+ * One data-sized kernel family: with the left panel [alpha, w_t .., p_t ..] and the right panel [alpha, -p_t / 2T .., -w_t / 2T ..] of
+ * 2T + 1 columns, every 16 x 16 tile of K(X, X) is generated once per (16 columns, coordinate block) on the MFMA, multiplied into the
+ * right panel per coordinate (the coordinate difference per entry, before the product; no division by r; fp32 with d <= 8 by
+ * differences), and the accumulators are contracted with the left panel in registers: nothing of size S x d x N is written.  Memory:
+ * two N x (2T + 1) panels and ceil((2T + 1) / 16) d N doubles.  ceil((2T + 1) / 16) ceil(d / 8) passes over K (coordinate blocks of 4
+ * for fp64 with d > 32).  The diagonal entry has r^2 = 0 exactly and contributes exactly nothing; duplicated points are finite.
+ * (a) every other output is bitwise what svgp_cg_lml_grad / svgp_cg_lml_grad_precond returns on the same handle and inputs, and those
+ * calls are unchanged by a bit; (b) no atomics, every sum has a fixed order: repeated calls are bitwise equal, and x_bar does not depend
+ * on on_device.  T = 0: x_bar is NaN, like the other trace blocks.  SVGP_NOT_POSDEF: x_bar is NaN and the context stays healthy.
+ * SVGP_INVALID_ARG, before anything is enqueued: what svgp_cg_lml_grad(_precond) rejects; NULL gx or gx->x; gx->ld < N; on_device not
+ * 0 / 1 or reserved != 0; a device gx->x overlapping the data's x; probes_k without a preconditioner.  Found by symbol (no ABI version
+ * step). */
+int32_t svgp_cg_lml_grad_inputs(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                                const double* probes_k, double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale,
+                                double* d_diag, double* d_mean_const, const svgp_input_grad* gx);
 /* ---- pathwise function samples of the exact GP ---------------------------------------------------------------------------------------
  * S draws from the exact posterior by pathwise conditioning (Wilson et al. 2020, 2021) with the CG solve, each one a FUNCTION that can be
  * evaluated at any points, any number of times.  With Khat = K(X, X) + sigma^2 I (sigma^2 = desc.diag), delta = y - mean(X), phi_l as in

@@ -6,6 +6,7 @@ entries a second are the yardstick; no ratio is fixed in advance: the run report
     python tools/cg_time.py [--reps 7] [--n 100000] [--out profiles/cg/cg_time.jsonl]
     python tools/cg_time.py --precond 256 512 1024 --precond-out profiles/cg/cg_precond_time.jsonl
     python tools/cg_time.py --sample --sample-out profiles/cg/cg_sample_time.jsonl      (sample_leg below)
+    python tools/cg_time.py --xgrad --xgrad-out profiles/cg/cg_xgrad_time.jsonl         (xgrad_leg below; after tools/build_prev.sh)
 
 --precond K ...: after the unpreconditioned fit, the same fit (17 columns, same tol and maxiter) with the Nystrom preconditioner of K
 data points (default_rng([0, 2]).choice, jitter 1e-4): iterations, final residual, wall time, the preconditioner's setup time and
@@ -128,8 +129,128 @@ def sample_leg(a):
                 f.write(json.dumps(r) + "\n")
 
 
+def xgrad_child(a):
+    """one leg of --xgrad in a process of its own (the library is chosen by SVGP_MI355X_LIB before the import): per dtype, after a warm-up,
+    the wall time of one blocking gradient call at N = --n, d = --d, 16 Rademacher probes, tol 1e-6 and --xgrad-maxiter iterations.
+    leg `new`: svgp_cg_lml_grad_inputs into device memory, the device time of its data-sized kernels alone (svgp_last_timing) and, with
+    --xgrad-kernel, svgp_cg_sampler_eval_grad (16 samples, no features) over the same N points in the same run.  leg `prev`: svgp_cg_lml_grad
+    of a library that lacks the new symbol.  Both print the outputs of svgp_cg_lml_grad in hex, for the bitwise comparison."""
+    import torch
+
+    from approxgp import _ffi
+    if a.xgrad_child == "prev":
+        _ffi.SYMBOLS.pop("svgp_cg_lml_grad_inputs", None)
+    from approxgp import DeviceConjugateGradients, draw_probes
+    from approxgp.kernels import ARDTransform, ScaledKernel, SEKernel, TransformedKernel
+    from approxgp.pathwise import draw_basis
+    from approxgp.synthetic import synth_arrays
+
+    ctx = _ffi.Context(0)
+    N, d, T = a.n, a.d, 16
+    for dt in (np.float64, np.float32):
+        tdt = torch.float64 if dt == np.float64 else torch.float32
+        p = synth_arrays(0, N, 64, d, dtype=dt)
+        kernel = ScaledKernel(TransformedKernel(SEKernel(), ARDTransform(np.asarray(p["inv_lengthscale"], dtype=np.float64))), p["variance"])
+        x = np.asarray(p["x"])[:, :N]
+        dev = DeviceConjugateGradients(ctx, x, p["y"][:N], dt)
+        desc, keep = dev.desc(kernel, p["sigma2"], tol=1e-6, maxiter=a.xgrad_maxiter)
+        z = draw_probes(N, T, 0)
+        new = a.xgrad_child == "new"
+        xt = torch.zeros((d, N), dtype=tdt, device="cuda") if new else None
+        torch.cuda.synchronize()
+        call = (lambda: dev.lml_grad(desc, z, wrt_inputs=True, x_grad_out=xt)) if new else (lambda: dev.lml_grad(desc, z))
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            lml0, g0, _ = dev.lml_grad(desc, z)   # the existing call (and the warm-up of the solve's shapes)
+            call()
+            t0 = time.perf_counter()
+            lml, g, info = call()
+            wall = 1e3 * (time.perf_counter() - t0)
+        row = {"leg": a.xgrad_child, "dtype": np.dtype(dt).name, "N": N, "d": d, "T": T, "maxiter": a.xgrad_maxiter, "iterations": info.iterations,
+               "ms_wall": round(wall, 2), "lml_grad_hex": [float(v).hex() for v in (lml0, g0["variance"], g0["diag"], g0["mean_const"], *g0["inv_lengthscale"])]}
+        if new:
+            row["ms_xgrad_kernels"] = round(ctx.timing().ms_strip, 3)
+            row["same_as_lml_grad"] = bool(lml == lml0 and all(g[k] == g0[k] for k in ("variance", "diag", "mean_const"))
+                                           and np.array_equal(g["inv_lengthscale"], g0["inv_lengthscale"]))
+            row["finite"] = bool(torch.isfinite(xt).all().item())
+            if a.xgrad_kernel:
+                passes = ((2 * T + 1 + 15) // 16) * ((d + 7) // 8)
+                basis = draw_basis(_ffi.KERNEL_SE, N, 0, 16, np.random.default_rng(0), dt, d=d)
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    smp = dev.sampler(desc, basis)
+                G = torch.empty((16, d, N), dtype=tdt, device="cuda")
+                torch.cuda.synchronize()
+                smp.eval_grad(dev.data, values=False, grad_out=G)
+                xs, eg = [], []
+                for _ in range(3):
+                    with warnings.catch_warnings():
+                        warnings.simplefilter("ignore")
+                        call()
+                    xs.append(ctx.timing().ms_strip)
+                    smp.eval_grad(dev.data, values=False, grad_out=G)
+                    eg.append(ctx.timing().ms_strip)
+                mx, me = statistics.median(xs), statistics.median(eg)
+                row["kernel"] = {"passes": passes, "ms_xgrad": stat(xs), "ms_eval_grad_16x8": stat(eg),
+                                 "ns_per_generated_entry": {"xgrad": float(f"{1e6 * mx / (passes * N * N):.4g}"), "eval_grad": float(f"{1e6 * me / (N * N):.4g}")},
+                                 "xgrad_over_eval_grad_per_entry": round((mx / passes) / me, 3)}
+                smp.free()
+                del G
+        print("XGRAD " + json.dumps(row), flush=True)
+        dev.free()
+    ctx.close()
+
+
+def xgrad_leg(a):
+    """--xgrad: what the input gradient of the exact GP costs.  svgp_cg_lml_grad_inputs of this tree against svgp_cg_lml_grad of the
+    library --prev-lib (tools/build_prev.sh builds the parent commit's), one process per call, interleaved new / prev, median of
+    --xgrad-reps wall times; the new kernel family alone against svgp_cg_sampler_eval_grad's gradient form per generated kernel entry;
+    and whether svgp_cg_lml_grad's outputs are bitwise the parent's."""
+    import subprocess
+
+    if not os.path.exists(a.prev_lib):
+        raise SystemExit(f"{a.prev_lib} is missing: tools/build_prev.sh builds the parent commit's library")
+    runs = {"new": [], "prev": []}
+    for rep in range(a.xgrad_reps):
+        for leg in ("new", "prev"):
+            env = dict(os.environ)
+            if leg == "prev":
+                env["SVGP_MI355X_LIB"] = os.path.abspath(a.prev_lib)
+            cmd = [sys.executable, os.path.abspath(__file__), "--xgrad-child", leg, "--n", str(a.n), "--d", str(a.d), "--xgrad-maxiter", str(a.xgrad_maxiter)]
+            if leg == "new" and rep == 0:
+                cmd.append("--xgrad-kernel")
+            r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                raise SystemExit(f"the {leg} leg failed with status {r.returncode}; nothing more is started\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+            runs[leg].append([json.loads(ln[6:]) for ln in r.stdout.splitlines() if ln.startswith("XGRAD ")])
+    rows = []
+    for i, name in enumerate(("float64", "float32")):
+        new, prev = [r[i] for r in runs["new"]], [r[i] for r in runs["prev"]]
+        mn, mp = statistics.median(r["ms_wall"] for r in new), statistics.median(r["ms_wall"] for r in prev)
+        row = {"dtype": name, "N": a.n, "d": a.d, "T": 16, "tol": 1e-6, "maxiter": a.xgrad_maxiter, "iterations": new[0]["iterations"], "reps": a.xgrad_reps,
+               "ms_lml_grad_inputs_wall": stat([r["ms_wall"] for r in new]), "ms_parent_lml_grad_wall": stat([r["ms_wall"] for r in prev]),
+               "inputs_over_parent": round(mn / mp, 3), "ms_xgrad_kernels": stat([r["ms_xgrad_kernels"] for r in new]), "kernel": new[0].get("kernel"),
+               "other_outputs_bitwise_lml_grad": all(r["same_as_lml_grad"] for r in new),
+               "lml_grad_bitwise_parent": all(r["lml_grad_hex"] == prev[0]["lml_grad_hex"] for r in new + prev), "finite": all(r["finite"] for r in new)}
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if a.xgrad_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.xgrad_out)), exist_ok=True)
+        with open(a.xgrad_out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--xgrad", action="store_true", help="the input gradient's leg alone (svgp_cg_lml_grad_inputs)")
+    ap.add_argument("--xgrad-child", choices=("new", "prev"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--xgrad-kernel", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--xgrad-reps", type=int, default=3)
+    ap.add_argument("--xgrad-maxiter", type=int, default=20)
+    ap.add_argument("--xgrad-out", default=None, help="e.g. profiles/cg/cg_xgrad_time.jsonl")
+    ap.add_argument("--prev-lib", default=os.path.join(ROOT, "approximategps.jl_amd", "csrc", "ablate", "libsvgp_prev.so"))
     ap.add_argument("--sample", action="store_true", help="the pathwise sampler's leg alone (svgp_cg_sampler_*)")
     ap.add_argument("--features", type=int, default=2048)
     ap.add_argument("--sample-reps", type=int, default=3)
@@ -146,6 +267,10 @@ def main():
     ap.add_argument("--precond", type=int, nargs="*", default=[], help="preconditioner sizes for the preconditioned leg")
     ap.add_argument("--precond-out", default=None)
     a = ap.parse_args()
+    if a.xgrad_child:
+        return xgrad_child(a)
+    if a.xgrad:
+        return xgrad_leg(a)
     if a.sample:
         return sample_leg(a)
     import torch
