@@ -253,6 +253,11 @@ SYMBOLS = {
     "svgp_cg_lml_grad_inputs": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(CGInfo), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(InputGrad)]),
+    "svgp_cg_set_noise": (C.c_int32, [_P, _P, C.POINTER(PointNoise)]),
+    "svgp_cg_lml_grad_noise": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(CGInfo), C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(InputGrad),
+                                           C.POINTER(PointNoiseGrad)]),
     "svgp_cg_sampler_create": (C.c_int32, [_P, _P, C.POINTER(CGDesc), C.POINTER(C.c_double), C.POINTER(SampleBasis), C.POINTER(_P),
                                            C.POINTER(CGInfo)]),
     "svgp_cg_sampler_eval": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int32]),

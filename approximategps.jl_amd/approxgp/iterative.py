@@ -12,7 +12,7 @@ import numpy as np
 from . import _ffi
 from . import nearest_neighbors as _nn
 from . import vfe as _vfe
-from .gp import FiniteGP
+from .gp import Diagonal, FiniteGP
 from .kernels import unpack_kernel
 
 
@@ -126,6 +126,7 @@ class DeviceConjugateGradients:
             self.data, self._owns_data = _ffi.DeviceData(ctx, x, y, dtype, layout), True
         self.dtype, self.d, self.n = self.data.dtype, self.data.d, self.data.n
         self.precond_k = 0   # points of the preconditioner set through set_preconditioner
+        self.has_noise = False   # a per-point noise vector set through set_noise
         h = C.c_void_p()
         ctx.check(ctx.lib.svgp_cg_create(ctx.h, self.data.h, C.byref(h)))
         self.h = h
@@ -230,6 +231,30 @@ class DeviceConjugateGradients:
         self.ctx.check(self.ctx.lib.svgp_cg_set_preconditioner(self.ctx.h, self.h, layout, k, _ffi._ptr(zb), float(jitter)))
         self.precond_k = k
 
+    def set_noise(self, s=None):
+        """Per-point noise variances (svgp_cg_set_noise): sigma_i^2 = diag + s_i, Khat = K + diag(sigma^2) in every later call.  s: an
+        (N,) numpy array (converted to the data dtype) or a contiguous torch device tensor of the data dtype; the handle keeps a copy.
+        None removes the vector.  The cached fit is dropped either way."""
+        if s is None:
+            self.ctx.check(self.ctx.lib.svgp_cg_set_noise(self.ctx.h, self.h, None))
+            self.has_noise = False
+            return
+        pn, keep = _ffi.point_noise(s, self.n, self.dtype)
+        self.has_noise = False
+        self.ctx.check(self.ctx.lib.svgp_cg_set_noise(self.ctx.h, self.h, C.byref(pn)))
+        self.has_noise = True
+
+    def _noise_grad(self, noise_grad_out):
+        """-> (PointNoiseGrad, what lml_grad returns as grads["noise"]): an (N,) array of the data dtype, or the caller's device tensor"""
+        if noise_grad_out is None:
+            sg = np.zeros(self.n, dtype=_ffi.np_dtype(self.dtype))
+            return _ffi.PointNoiseGrad(_ffi._ptr(sg), 0, 0), sg
+        t = noise_grad_out
+        if (not _ffi._is_device_tensor(t) or not t.is_contiguous() or not t.is_floating_point() or t.numel() != self.n
+                or t.element_size() != np.dtype(_ffi.np_dtype(self.dtype)).itemsize):
+            raise ValueError("noise_grad_out: a contiguous (N,) device tensor of the data dtype")
+        return _ffi.PointNoiseGrad(C.c_void_p(int(t.data_ptr())), 1, 0), t
+
     def _need_precond(self):
         if not self.precond_k:
             raise ValueError("no preconditioner is set (set_preconditioner)")
@@ -307,22 +332,40 @@ class DeviceConjugateGradients:
             raise ValueError("x_grad_out: a contiguous (d, N) device tensor of the data dtype")
         return _ffi.InputGrad(C.c_void_p(int(t.data_ptr())), self.n, 1, 0), t
 
-    def lml_grad(self, desc, probes, delta=None, probes_k=None, wrt_inputs=False, x_grad_out=None):
+    def lml_grad(self, desc, probes, delta=None, probes_k=None, wrt_inputs=False, x_grad_out=None, wrt_noise=False, noise_grad_out=None):
         """-> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const"}, CGInfo).  wrt_inputs: grads["x"] as well, (d, N) in the
         data dtype: d lml / d x_ic by the same trace estimator (svgp_cg_lml_grad_inputs), every other entry bitwise what it is without;
-        x_grad_out: a contiguous (d, N) torch device tensor to write it into (it is returned as grads["x"])."""
+        x_grad_out: a contiguous (d, N) torch device tensor to write it into (it is returned as grads["x"]).  wrt_noise: grads["noise"]
+        as well, (N,) in the data dtype: d lml / d sigma_i^2 (svgp_cg_lml_grad_noise), with or without a vector set; its sum is
+        grads["diag"]; noise_grad_out: a contiguous (N,) torch device tensor to write it into."""
         if not isinstance(wrt_inputs, (bool, np.bool_)):
             raise ValueError("wrt_inputs is True or False")
+        if not isinstance(wrt_noise, (bool, np.bool_)):
+            raise ValueError("wrt_noise is True or False")
         if x_grad_out is not None and not wrt_inputs:
             raise ValueError("x_grad_out needs wrt_inputs=True")
+        if noise_grad_out is not None and not wrt_noise:
+            raise ValueError("noise_grad_out needs wrt_noise=True")
         T, zp, zkp, keep = self._probes(probes, probes_k)
         dl = self._f64(delta)
-        if wrt_inputs and dl is not None and dl.shape != (self.n,):
+        if (wrt_inputs or wrt_noise) and dl is not None and dl.shape != (self.n,):
             raise ValueError("delta: an (N,) array")
         lml, info = C.c_double(), _ffi.CGInfo()
         dv, dd, dm, dil = C.c_double(), C.c_double(), C.c_double(), np.zeros(self.d)
         dp = C.POINTER(C.c_double)
         dlp = None if dl is None else dl.ctypes.data_as(dp)
+        if wrt_noise:
+            if self.precond_k and T > 0 and probes_k is None:
+                raise ValueError("a preconditioner is set: the probes need probes_k, a (k, T) array")
+            gx, xg = self._x_grad(x_grad_out) if wrt_inputs else (None, None)
+            gpn, sg = self._noise_grad(noise_grad_out)
+            self._check(self.ctx.lib.svgp_cg_lml_grad_noise(self.ctx.h, self.h, C.byref(desc), dlp, T, zp, zkp if self.precond_k else None,
+                                                            C.byref(lml), C.byref(info), C.byref(dv), dil.ctypes.data_as(dp), C.byref(dd),
+                                                            C.byref(dm), None if gx is None else C.byref(gx), C.byref(gpn)))
+            grads = {"variance": dv.value, "inv_lengthscale": dil, "diag": dd.value, "mean_const": dm.value, "noise": sg}
+            if wrt_inputs:
+                grads["x"] = xg
+            return lml.value, grads, info
         if wrt_inputs:
             if self.precond_k and T > 0 and probes_k is None:
                 raise ValueError("a preconditioner is set: the probes need probes_k, a (k, T) array")
@@ -596,24 +639,36 @@ def _cg_kwargs(fn, kwargs, also=()):
 
 
 def _check_inputs(fx: FiniteGP, y):
-    """-> (diag, mean_const, delta or None), before the GPU is touched.  A CustomMean prior is passed as delta = y - mean(x)."""
+    """-> (diag, mean_const, delta or None, s or None), before the GPU is touched.  A CustomMean prior is passed as delta = y - mean(x);
+    Σy = Diagonal(v) as diag = min(v) and the per-point variances s = v - min(v) above it (vfe.py's mapping)."""
     if not isinstance(fx, FiniteGP):
         raise TypeError("ConjugateGradients takes fx = f(x, Σy)")
-    if not fx.is_isotropic():
-        raise _ffi.UnsupportedError("ConjugateGradients needs an isotropic fx.Σy (per-point noise is out of scope)")
-    diag = float(fx.Sigma_y)
-    if not diag >= 0:
-        raise ValueError("fx.Σy must be >= 0")
+    s = None
+    if isinstance(fx.Sigma_y, Diagonal):
+        sy = np.asarray(fx.Sigma_y.diag, dtype=np.float64)
+        if sy.ndim != 1 or sy.shape[0] != fx.n:
+            raise ValueError(f"fx.Σy = Diagonal(v) needs a vector with one variance per point ({fx.n}); got shape {sy.shape}")
+        if not np.all(sy > 0.0):   # (NaN included)
+            raise ValueError("fx.Σy must be positive: every per-point noise variance must be > 0")
+        diag = float(sy.min())
+        s = sy - diag
+    elif not fx.is_isotropic():
+        raise _ffi.UnsupportedError("ConjugateGradients needs an isotropic fx.Σy, or per-point noise variances v as fx = f(x, Diagonal(v)) "
+                                    "(a full noise covariance is out of scope)")
+    else:
+        diag = float(fx.Sigma_y)
+        if not diag >= 0:
+            raise ValueError("fx.Σy must be >= 0")
     if np.shape(y)[0] != fx.n:
         raise ValueError("x and y lengths differ")
     delta = None
     if fx.f.mean_fn is not None:
         delta = np.asarray(y, dtype=np.float64).reshape(-1) - fx.f.mean_offsets(fx.x)
-    return diag, float(fx.f.mean_const), delta
+    return diag, float(fx.f.mean_const), delta, s
 
 
 def _device(cg: ConjugateGradients, fx: FiniteGP, y, ctx, dtype):
-    diag, mean_const, delta = _check_inputs(fx, y)
+    diag, mean_const, delta, s = _check_inputs(fx, y)
     dt = _nn._dtype_of(fx, dtype)
     probes = cg.probes_for(fx.n)
     xa = np.asarray(fx.x)
@@ -627,6 +682,8 @@ def _device(cg: ConjugateGradients, fx: FiniteGP, y, ctx, dtype):
     try:
         if points is not None:
             dev.set_preconditioner(points[0] if dev.d == 1 and xa.ndim == 1 else points, cg.precond_jitter)
+        if s is not None:
+            dev.set_noise(s)
         desc, keep = dev.desc(fx.f.kernel, diag, mean_const, cg.tol_for(dt), cg.maxiter)
     except Exception:
         dev.free()
@@ -651,7 +708,8 @@ def approx_lml(approx, fx, y, **kwargs):
 
 def approx_lml_and_gradient(approx, fx, y, **kwargs):
     """ConjugateGradients: -> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const"}): the gradient with respect to the
-    kernel parameters, the noise variance Σy and the constant mean.  wrt_inputs=True adds grads["x"] = d lml / d x shaped like fx.x (a
+    kernel parameters, the noise variance Σy and the constant mean.  wrt_noise=True adds grads["Sigma_y"], (N,): d lml / d σ_i² per point, for fx.Σy a
+    scalar or a Diagonal(v) alike (grads["diag"] is its sum).  wrt_inputs=True adds grads["x"] = d lml / d x shaped like fx.x (a
     vector for a plain vector x, (d, N) ColVecs otherwise), from the same solve and the same probes: what a feature map in front of the
     kernel, input warping or latent inputs chain through.  With a CustomMean prior it is the gradient of the kernel part alone:
     d lml / d (y - mean(x)) is the posterior's alpha, and the mean's Jacobian is the caller's.  The estimator is unbiased for the gradient
@@ -659,16 +717,20 @@ def approx_lml_and_gradient(approx, fx, y, **kwargs):
     Any other approximation: the existing methods."""
     if not isinstance(approx, ConjugateGradients):
         return _nn.approx_lml_and_gradient(approx, fx, y, **kwargs)
-    ctx, dtype = _cg_kwargs("approx_lml_and_gradient", kwargs, also=("wrt_inputs",))
-    wrt_inputs = kwargs.get("wrt_inputs", False)
+    ctx, dtype = _cg_kwargs("approx_lml_and_gradient", kwargs, also=("wrt_inputs", "wrt_noise"))
+    wrt_inputs, wrt_noise = kwargs.get("wrt_inputs", False), kwargs.get("wrt_noise", False)
     if not isinstance(wrt_inputs, (bool, np.bool_)):
         raise ValueError("wrt_inputs is True or False")
+    if not isinstance(wrt_noise, (bool, np.bool_)):
+        raise ValueError("wrt_noise is True or False")
     dev, desc, keep, probes, delta = _device(approx, fx, y, ctx, dtype)
     try:
-        lml, grads, info = dev.lml_grad(desc, probes[0], delta, probes_k=probes[1], wrt_inputs=bool(wrt_inputs))
+        lml, grads, info = dev.lml_grad(desc, probes[0], delta, probes_k=probes[1], wrt_inputs=bool(wrt_inputs), wrt_noise=bool(wrt_noise))
     finally:
         dev.free()
     _warn(info, "the fit")
+    if wrt_noise:
+        grads["Sigma_y"] = grads.pop("noise")
     if wrt_inputs and np.ndim(fx.x) == 1:
         grads["x"] = grads["x"][0]
     return lml, grads
@@ -676,13 +738,14 @@ def approx_lml_and_gradient(approx, fx, y, **kwargs):
 
 class CGPosteriorGP:
     """posterior(fx, y) of the exact GP with alpha = (K + Σy)^-1 (y - mean(x)) resident on the device.  Test inputs: a plain vector
-    (d = 1) or a (d, n) ColVecs array.  The variance costs one batched solve with k(X, x*) as right-hand sides."""
+    (d = 1) or a (d, n) ColVecs array.  The variance costs one batched solve with k(X, x*) as right-hand sides.  fx = f(x, Diagonal(v)):
+    per-point noise variances (svgp_cg_set_noise); predict_y and log_predictive_density then need noise= for the test points."""
 
     def __init__(self, cg: ConjugateGradients, fx: FiniteGP, y, ctx=None, dtype=None):
         self.approx, self.prior = cg, fx.f
         self.dev, desc, keep, probes, delta = _device(cg, fx, y, ctx, dtype)
         self._desc, self._keep, self._delta = desc, keep, delta   # function_samples solves under the same parameter set
-        self.noise = float(fx.Sigma_y)
+        self.noise = None if isinstance(fx.Sigma_y, Diagonal) else float(fx.Sigma_y)   # None: per-point noise, no single value for y*
         try:
             self.lml, self.info = self.dev.fit(desc, probes[0], delta, probes_k=probes[1])
         except Exception:
@@ -722,26 +785,54 @@ class CGPosteriorGP:
         _warn(smp.info, "the function samples")
         return CGFunctionSamples(self, smp)
 
-    def _lik_predictive(self, x, y, want):
-        if not self.noise > 0:
-            raise ValueError("predictions of y need observation noise fx.Σy > 0")
+    def _lik_predictive(self, x, y, want, noise=None):
+        if noise is None:
+            if self.noise is None:
+                raise ValueError("the posterior has per-point noise fx.Σy = Diagonal(v): pass noise=, the observation noise variance of "
+                                 "the test points (a scalar or an (n,) array)")
+            if not self.noise > 0:
+                raise ValueError("predictions of y need observation noise fx.Σy > 0")
+            noise = self.noise
+        nv = np.asarray(noise, dtype=np.float64)
+        xa = np.asarray(x)
+        n = xa.shape[0] if xa.ndim == 1 else xa.shape[-1]
+        if nv.ndim > 1 or (nv.ndim == 1 and nv.shape[0] != n):
+            raise ValueError("noise: a scalar or one variance per test point")
+        if not np.all(nv > 0):
+            raise ValueError("predictions of y need observation noise > 0")
         m, v = self.mean_and_var(x)
-        return _ffi.lik_predictive(self.dev.ctx, _ffi.LIK_GAUSSIAN, self.noise, 0, m, v, y, want=want)
+        if nv.ndim == 0:
+            return _ffi.lik_predictive(self.dev.ctx, _ffi.LIK_GAUSSIAN, float(nv), 0, m, v, y, want=want)
+        # one variance per test point: the Gaussian closed forms, O(n) on the host in fp64
+        m64, yv = np.asarray(m, dtype=np.float64), np.asarray(v, dtype=np.float64) + nv
+        out = {"ymean": m64, "yvar": yv}
+        if y is not None:
+            yy = np.asarray(y, dtype=np.float64).reshape(-1)
+            if yy.shape != (n,):
+                raise ValueError("y: one observation per test point")
+            out["lpd"] = -0.5 * (np.log(2.0 * np.pi * yv) + (yy - m64) ** 2 / yv)
+        return {k: out[k] for k in want}
 
-    def predict_y(self, x):
-        """(E[y*], Var[y*]) = (mean, var + noise)"""
-        r = self._lik_predictive(x, None, ("ymean", "yvar"))
+    def predict_y(self, x, noise=None):
+        """(E[y*], Var[y*]) = (mean, var + noise).  noise: the test points' observation noise variance, a scalar or (n,); the
+        posterior's own fx.Σy by default, which a per-point-noise posterior does not have."""
+        r = self._lik_predictive(x, None, ("ymean", "yvar"), noise)
         return r["ymean"], r["yvar"]
 
-    def log_predictive_density(self, x, y):
-        """log N(y*_i; mean_i, var_i + noise) per point"""
-        return self._lik_predictive(x, y, ("lpd",))["lpd"]
+    def log_predictive_density(self, x, y, noise=None):
+        """log N(y*_i; mean_i, var_i + noise_i) per point (noise as in predict_y)"""
+        return self._lik_predictive(x, y, ("lpd",), noise)["lpd"]
 
 
 def posterior(approx, *args, **kwargs):
-    """posterior(ConjugateGradients(), fx, y; ctx, dtype) -> CGPosteriorGP; any other approximation: the existing methods."""
+    """posterior(ConjugateGradients(), fx, y; ctx, dtype) -> CGPosteriorGP; any other approximation: the existing methods.  A Diagonal Σy
+    keeps raising UnsupportedError here (existing behaviour): CGPosteriorGP(approx, f(x, Diagonal(v)), y, ctx=, dtype=) is its posterior."""
     if isinstance(approx, ConjugateGradients):
         fx, y = args
         ctx, dtype = _cg_kwargs("posterior", kwargs)
+        if isinstance(fx, FiniteGP) and isinstance(fx.Sigma_y, Diagonal):
+            # this dispatch has always refused a Diagonal Σy, and callers rely on it: the per-point-noise posterior is asked for by name
+            raise _ffi.UnsupportedError("posterior(ConjugateGradients(), f(x, Diagonal(v)), y) is not dispatched: construct "
+                                        "CGPosteriorGP(approx, f(x, Diagonal(v)), y) for the exact posterior with per-point noise")
         return CGPosteriorGP(approx, fx, y, ctx=ctx, dtype=dtype)
     return _vfe.posterior(approx, *args, **kwargs)

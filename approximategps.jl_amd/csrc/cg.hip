@@ -172,10 +172,12 @@ __global__ void __launch_bounds__(256) kmv_kernel(KmvArgs a) {
     }
   }
   const T dg = T(a.diag);
+  const T* __restrict__ dvec = addv ? static_cast<const T*>(a.dvec) : nullptr;   // per-point noise: the factor of addv, per output point
 #pragma unroll
   for (int g = 0; g < PG; ++g) {
     const int64_t pt = p0 + g * 16 + c;
     if (pt >= n) continue;
+    const T dgp = dvec ? dvec[pt] : dg;   // once per point group, after the row loop: no register lives across it
 #pragma unroll
     for (int b = 0; b < NSB; ++b)
 #pragma unroll
@@ -183,7 +185,7 @@ __global__ void __launch_bounds__(256) kmv_kernel(KmvArgs a) {
         const int64_t s = a.s0 + b * 16 + Mfma16<T>::row(lane, r);
         if (s >= a.S) continue;
         T v = acc[g][b][r];
-        if (addv) v = fma(dg, addv[s * a.lda + pt], v);
+        if (addv) v = fma(dgp, addv[s * a.lda + pt], v);
         out[s * a.ldo + pt] = v;
       }
   }
@@ -615,9 +617,114 @@ __global__ void cg_pc_mm_kernel(const double* __restrict__ Mt, int64_t Mp, int64
   out[s * ldo + i] = TO(alpha * acc);
 }
 
+// ---- per-point noise variances (svgp_cg_set_noise) -----------------------------------------------------------------------------------
+
+// out[0] = min_i s[i] in fp64, NaN once any s[i] is NaN: one workgroup, a thread takes i = tid + 256 t ascending, then a fixed tree
+template <typename T>
+__global__ void __launch_bounds__(256) cg_noise_min_kernel(const T* __restrict__ sv, int64_t N, double* __restrict__ out) {
+  __shared__ double sm[256];
+  auto nmin = [](double a, double b) { return (a != a) ? a : (b != b) ? b : (b < a ? b : a); };
+  double m = INFINITY;
+  for (int64_t i = threadIdx.x; i < N; i += 256) m = nmin(m, double(sv[i]));
+  sm[threadIdx.x] = m;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (int(threadIdx.x) < w) sm[threadIdx.x] = nmin(sm[threadIdx.x], sm[threadIdx.x + w]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = sm[0];
+}
+
+// sig2 = T(diag) + s (one rounding in T), and what the preconditioner, its probes and the Gram read of it
+template <typename T>
+__global__ void cg_noise_prep_kernel(const T* __restrict__ sv, int64_t N, T dg, T* __restrict__ sig2, T* __restrict__ isig2, T* __restrict__ ssig2,
+                                     double* __restrict__ isig64) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const T v = dg + sv[i];
+  const double v64 = double(v);
+  sig2[i] = v;
+  isig2[i] = T(1.0 / v64);
+  ssig2[i] = T(sqrt(v64));
+  isig64[i] = 1.0 / v64;
+}
+
+// dst[i, col] = src[i, col] vec[i]
+template <typename T>
+__global__ void cg_rowscale_kernel(const T* __restrict__ src, int64_t lds, const T* __restrict__ vec, int64_t N, T* __restrict__ dst, int64_t ldd) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, col = blockIdx.y;
+  if (i >= N) return;
+  dst[col * ldd + i] = src[col * lds + i] * vec[i];
+}
+
+// d lml / d sigma_i^2 from the panels U = [alpha, w_t] and P = [alpha, p_t]: t ascending in fp64, rounded once
+template <typename T>
+__global__ void cg_sbar_kernel(const T* __restrict__ U, const T* __restrict__ P, int64_t N, int Tn, T* __restrict__ sbar) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  if (Tn < 1) {
+    sbar[i] = T(NAN);
+    return;
+  }
+  double tr = 0.0;
+  for (int t = 1; t <= Tn; ++t) tr = fma(double(U[int64_t(t) * N + i]), double(P[int64_t(t) * N + i]), tr);
+  sbar[i] = T(0.5 * (double(U[i]) * double(P[i])) - tr / (2.0 * double(Tn)));
+}
+
+// cg_dot_kernel's first stage for sum_i log sig2[i] (b NULL) or sum_i sig2[i] b[i]
+template <typename T>
+__global__ void __launch_bounds__(256) cg_noise_sum_kernel(const T* __restrict__ sig2, const T* __restrict__ b, int64_t N, int64_t rows_per_blk,
+                                                           double* __restrict__ partial) {
+  __shared__ double sm[256];
+  const int64_t r0 = int64_t(blockIdx.x) * rows_per_blk;
+  const int64_t r1 = r0 + rows_per_blk < N ? r0 + rows_per_blk : N;
+  double s = 0.0;
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += 256) s = b ? fma(double(sig2[i]), double(b[i]), s) : s + log(double(sig2[i]));
+  sm[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (int(threadIdx.x) < w) sm[threadIdx.x] += sm[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = sm[0];
+}
+
 inline dim3 grid2(int64_t N, int64_t cols) { return dim3((unsigned)((N + 255) / 256), (unsigned)cols); }
 
 }  // namespace
+
+void launch_cg_noise_min(int dtype, hipStream_t s, const void* sv, int64_t N, double* out) {
+  if (dtype == 0) hipLaunchKernelGGL(cg_noise_min_kernel<double>, dim3(1), dim3(256), 0, s, (const double*)sv, N, out);
+  else hipLaunchKernelGGL(cg_noise_min_kernel<float>, dim3(1), dim3(256), 0, s, (const float*)sv, N, out);
+}
+
+void launch_cg_noise_prep(int dtype, hipStream_t s, const void* sv, int64_t N, double diag, void* sig2, void* isig2, void* ssig2, double* isig64) {
+  const dim3 g((unsigned)((N + 255) / 256));
+  if (dtype == 0) hipLaunchKernelGGL(cg_noise_prep_kernel<double>, g, dim3(256), 0, s, (const double*)sv, N, diag, (double*)sig2, (double*)isig2, (double*)ssig2, isig64);
+  else hipLaunchKernelGGL(cg_noise_prep_kernel<float>, g, dim3(256), 0, s, (const float*)sv, N, float(diag), (float*)sig2, (float*)isig2, (float*)ssig2, isig64);
+}
+
+void launch_cg_rowscale(int dtype, hipStream_t s, const void* src, int64_t lds, const void* vec, int64_t N, int64_t ncols, void* dst, int64_t ldd) {
+  for (int64_t c0 = 0; c0 < ncols; c0 += 32768) {   // (grid.y limit)
+    const int64_t nc = ncols - c0 < 32768 ? ncols - c0 : 32768;
+    const dim3 g = grid2(N, nc);
+    if (dtype != 1) hipLaunchKernelGGL(cg_rowscale_kernel<double>, g, dim3(256), 0, s, (const double*)src + c0 * lds, lds, (const double*)vec, N, (double*)dst + c0 * ldd, ldd);
+    else hipLaunchKernelGGL(cg_rowscale_kernel<float>, g, dim3(256), 0, s, (const float*)src + c0 * lds, lds, (const float*)vec, N, (float*)dst + c0 * ldd, ldd);
+  }
+}
+
+void launch_cg_sbar(int dtype, hipStream_t s, const void* U, const void* P, int64_t N, int T, void* sbar) {
+  const dim3 g((unsigned)((N + 255) / 256));
+  if (dtype == 0) hipLaunchKernelGGL(cg_sbar_kernel<double>, g, dim3(256), 0, s, (const double*)U, (const double*)P, N, T, (double*)sbar);
+  else hipLaunchKernelGGL(cg_sbar_kernel<float>, g, dim3(256), 0, s, (const float*)U, (const float*)P, N, T, (float*)sbar);
+}
+
+void launch_cg_noise_sum(int dtype, hipStream_t s, const void* sig2, const void* b, int64_t N, double* partial) {
+  const int nblk = cg_dot_blocks(N);
+  const int64_t per = (N + nblk - 1) / nblk;
+  if (dtype == 0) hipLaunchKernelGGL(cg_noise_sum_kernel<double>, dim3((unsigned)nblk), dim3(256), 0, s, (const double*)sig2, (const double*)b, N, per, partial);
+  else hipLaunchKernelGGL(cg_noise_sum_kernel<float>, dim3((unsigned)nblk), dim3(256), 0, s, (const float*)sig2, (const float*)b, N, per, partial);
+}
 
 void launch_kmv(int dtype, hipStream_t s, const KmvArgs& a) {
   if (dtype == 0) {

@@ -9,6 +9,9 @@
 // solves (CgPrecond below), set up on the device once per call and applied with two kernel products of N k generated entries.
 // svgp_cg_sampler_create / _eval / _eval_grad / _state / _free: pathwise function samples of the exact GP (cg_sample.hip: the kernels) -
 // one batched solve of the S right-hand sides delta - Phi(X) w_s - sigma eps_s, then every evaluation is one data-sized pass.
+// svgp_cg_set_noise / _lml_grad_noise: per-point noise variances, Khat = K + diag(sigma^2) with sigma_i^2 = T(diag) + s_i - the vector is
+// handle state, its minimum is reduced on the device at set time and every call tests it on the host before its data pass; kmv's epilogue
+// reads sigma^2 per output point, the preconditioner's D^-1 scalings are streaming passes around its two products.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -63,6 +66,12 @@ struct svgp_cg {
   DevBuf xL, xR, xpart, xout;   // d lml / d x: the N x (2T + 1) panels, the column blocks' partial sums (fp64), a host output's staging
   bool have_fit = false;
   CgPar fit;                 // the parameter set alpha belongs to
+  // per-point noise (svgp_cg_set_noise): the snapshot s and its min (NaN-propagating, reduced on the device at set time); per call
+  // sig2 = T(diag) + s, 1 / sig2, sqrt(sig2) in the data dtype, 1 / sig2 in fp64 (the Gram's weights); d lml / d sigma_i^2
+  bool have_noise = false;
+  double noise_min = 0;
+  DevBuf noise_s, sig2, isig2, ssig2, isig64, sbar;
+  DevBuf noise_lo;           // one fp64 word: the min-reduction's result (kept, so that setting a vector every step allocates nothing)
   CgPrecond pc;              // pc.k == 0: none
   ~svgp_cg() { delete pc.z; }
 };
@@ -95,6 +104,17 @@ struct DataHold {   // test inputs uploaded for one call
   svgp_data* D = nullptr;
   ~DataHold() { if (D) svgp_data_free(ctx, D); }
 };
+
+// a noise vector is set: the smallest variance T(diag) + min s of the call's descriptor, before any data pass.  SVGP_NOT_POSDEF when it
+// is < 0 (<= 0 where the preconditioner divides by it) or NaN
+int noise_check(svgp_ctx* ctx, const svgp_cg* cg, const svgp_cg_desc* ds, bool precond) {
+  if (!cg->have_noise) return SVGP_OK;
+  const double lo = cg->dtype == SVGP_F64 ? ds->diag + cg->noise_min : double(float(ds->diag) + float(cg->noise_min));
+  if (lo != lo) return fail(ctx, SVGP_NOT_POSDEF, "per-point noise: a variance diag + s_i is NaN");
+  if (lo < 0) return fail(ctx, SVGP_NOT_POSDEF, "per-point noise: a variance diag + s_i is negative");
+  if (precond && !(lo > 0)) return fail(ctx, SVGP_NOT_POSDEF, "per-point noise: a variance diag + s_i is zero with a preconditioner set (P = Z Kuu^-1 Z' + D)");
+  return SVGP_OK;
+}
 
 int check_desc(svgp_ctx* ctx, const svgp_cg* cg, const svgp_cg_desc* ds) {
   if (!ds) return fail(ctx, SVGP_INVALID_ARG, "null descriptor");
@@ -156,7 +176,8 @@ int pc_cross(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, const void* V, int64_t 
 }
 
 // out = K(X, z_p) V + diag addv: kmv_kernel with the k points as its rows (V: kp x S, zero on the padding rows)
-void pc_expand(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, const void* V, int64_t S, const void* addv, int64_t lda, double diag, void* out, int64_t ldo) {
+void pc_expand(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, const void* V, int64_t S, const void* addv, int64_t lda, double diag, void* out, int64_t ldo,
+               const void* dvec = nullptr) {
   const CgPrecond& pc = cg->pc;
   KmvArgs a;
   kmv_args(cg, p, a);
@@ -171,6 +192,7 @@ void pc_expand(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, const void* V, int64_
   a.ldv = pc.kp;
   a.S = S;
   a.addv = addv;
+  a.dvec = dvec;
   a.lda = lda;
   a.out = out;
   a.ldo = ldo;
@@ -185,6 +207,14 @@ int pc_apply(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, const void* R, int64_t 
   int rc;
   if ((rc = pc.t.reserve(ctx, size_t(pc.kp) * size_t(S) * cg->es, "the preconditioner's products")) != SVGP_OK) return rc;
   if ((rc = pc.v.reserve(ctx, size_t(pc.kp) * size_t(S) * cg->es, "the preconditioner's products")) != SVGP_OK) return rc;
+  if (cg->have_noise) {   // D = diag(sig2): P^-1 r = D^-1 (r - Z W Z' D^-1 r), W = Lu^-T B^-1 Lu^-1; out holds D^-1 r, then r + Z v, then the result
+    launch_cg_rowscale(cg->dtype, ctx->stream, R, ldr, cg->isig2.p, cg->N, S, out, ldo);
+    if ((rc = pc_cross(ctx, cg, p, out, ldo, S, pc.t.p, pc.kp)) != SVGP_OK) return rc;
+    launch_cg_pc_mm(cg->dtype, ctx->stream, pc.W.as<double>(), pc.Mp, pc.k, pc.t.p, 0, pc.kp, S, -1.0, pc.v.p, pc.kp, pc.kp);
+    pc_expand(ctx, cg, p, pc.v.p, S, R, ldr, 1.0, out, ldo);
+    launch_cg_rowscale(cg->dtype, ctx->stream, out, ldo, cg->isig2.p, cg->N, S, out, ldo);
+    return SVGP_OK;
+  }
   if ((rc = pc_cross(ctx, cg, p, R, ldr, S, pc.t.p, pc.kp)) != SVGP_OK) return rc;
   launch_cg_pc_mm(cg->dtype, ctx->stream, pc.W.as<double>(), pc.Mp, pc.k, pc.t.p, 0, pc.kp, S, -1.0 / (pc.s2 * pc.s2), pc.v.p, pc.kp, pc.kp);
   pc_expand(ctx, cg, p, pc.v.p, S, R, ldr, 1.0 / pc.s2, out, ldo);
@@ -205,7 +235,8 @@ int pc_setup(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p) {
   struct { DevBuf* b; size_t bytes; } req[] = {
       {&pc.rows, size_t(d) * size_t(kp) * cg->es}, {&pc.bias, size_t(kp) * cg->es}, {&pc.zblk, size_t(N) * 64 * 8}, {&pc.zs64, size_t(d) * size_t(Mp) * 8},
       {&pc.Lu, mm}, {&pc.Tu, mm}, {&pc.LinvRM, mm}, {&pc.LinvCM, mm}, {&pc.Ytmp, mm}, {&pc.G, mm}, {&pc.H, mm}, {&pc.H2, mm}, {&pc.Bm, mm}, {&pc.TB, mm},
-      {&pc.LBinvRM, mm}, {&pc.LBinvCM, mm}, {&pc.W, mm}, {&pc.info, info_bytes(Mp)}, {&pc.info_b, info_bytes(Mp)}, {&pc.scal, 64}, {&pc.rho, 128 * 8}};
+      {&pc.LBinvRM, mm}, {&pc.LBinvCM, mm}, {&pc.W, mm}, {&pc.info, info_bytes(Mp)}, {&pc.info_b, info_bytes(Mp)}, {&pc.scal, 64}, {&pc.rho, 128 * 8},
+      {&cg->partial, cg->have_noise ? size_t(64) * size_t(cg_dot_blocks(N)) * 8 : 0}};   // (sum_i log sigma_i^2: ensure_solver's own minimum)
   for (auto& r : req)
     if ((rc = r.b->reserve(ctx, r.bytes, "the preconditioner")) != SVGP_OK) return rc;
   TREC(ctx, ctx->ev[2], s);
@@ -273,6 +304,7 @@ int pc_setup(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p) {
     for (int64_t j0 = 0; j0 < k; j0 += 64) {
       const int64_t nb = k - j0 < 64 ? k - j0 : 64;
       launch_cg_kcols(SVGP_F64, s, x64, ldx64, N, z64 + j0, ldz64, nb, invl64, d, p.family, p.variance, pc.zblk.p, N);
+      if (cg->have_noise) launch_cg_rowscale(2, s, pc.zblk.p, N, cg->isig64.p, N, nb, pc.zblk.p, N);   // Z' D^-1 Z: the weights on the explicit block
       a.S = nb;
       a.out = pc.G.as<double>() + j0 * Mp;
       launch_kmv_split(SVGP_F64, s, a, pc.part.p);
@@ -282,9 +314,13 @@ int pc_setup(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p) {
   // B = I + Lu^-1 G Lu^-T / sigma^2 = LB LB'  (launch_gemm_pm: out = X'Y for row-major X, Y; LinvCM read row-major is Lu^-T)
   launch_gemm_pm(SVGP_F64, s, pc.G.p, pc.LinvCM.p, nullptr, 1.0, Mp, Mp, Mp, 1, pc.H.p, 1, kMmFull);     // G Lu^-T
   launch_gemm_pm(SVGP_F64, s, pc.H.p, pc.LinvCM.p, nullptr, 1.0, Mp, Mp, Mp, 1, pc.H2.p, 1, kMmFull);    // Lu^-1 G Lu^-T
-  launch_cg_pc_form_b(s, pc.H2.as<double>(), Mp, pc.s2, pc.Bm.as<double>());
+  launch_cg_pc_form_b(s, pc.H2.as<double>(), Mp, cg->have_noise ? 1.0 : pc.s2, pc.Bm.as<double>());   // (the Gram carries D^-1 already)
   launch_potrf(SVGP_F64, s, pc.Bm.p, pc.TB.p, Mp, pc.info_b.as<int>(), reinterpret_cast<unsigned*>(pc.info_b.as<int>() + 1), ctx->num_cus);
   launch_cg_pc_logdet(s, pc.Bm.as<double>(), Mp, k, pc.scal.as<double>());
+  if (cg->have_noise) {   // sum_i log sigma_i^2: the fixed two-stage reduction
+    launch_cg_noise_sum(dt, s, cg->sig2.p, nullptr, N, cg->partial.as<double>());
+    launch_cg_colsum(s, cg->partial.as<double>(), N, 1, pc.scal.as<double>() + 1);
+  }
   // W sigma^2 = Lu^-T B^-1 Lu^-1, B^-1 = LB^-T LB^-1
   launch_linv(SVGP_F64, s, pc.Bm.p, pc.TB.p, Mp, pc.LBinvRM.p, pc.LBinvCM.p, pc.Ytmp.p);
   launch_gemm_pm(SVGP_F64, s, pc.LBinvRM.p, pc.LBinvRM.p, nullptr, 1.0, Mp, Mp, Mp, 1, pc.H.p, 1, kMmFull);   // B^-1
@@ -293,7 +329,8 @@ int pc_setup(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p) {
   KCHECK(ctx, "cg preconditioner (B, W)");
   TREC(ctx, ctx->ev[3], s);
   int iu = 0, ib = 0;
-  double ld = 0;
+  double ld = 0, ldd = 0;
+  if (cg->have_noise) HIPC(ctx, hipMemcpyAsync(&ldd, pc.scal.as<double>() + 1, 8, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipMemcpyAsync(&iu, pc.info.p, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipMemcpyAsync(&ib, pc.info_b.p, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipMemcpyAsync(&ld, pc.scal.p, 8, hipMemcpyDeviceToHost, s));
@@ -306,7 +343,7 @@ int pc_setup(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p) {
              iu ? iu : ib);
     return fail(ctx, SVGP_NOT_POSDEF, buf);
   }
-  pc.logdet_p = double(N) * std::log(pc.s2) + ld;
+  pc.logdet_p = (cg->have_noise ? ldd : double(N) * std::log(pc.s2)) + ld;
   return SVGP_OK;
 }
 
@@ -329,6 +366,15 @@ int set_params(svgp_ctx* ctx, svgp_cg* cg, const CgPar& p, bool precond = true) 
   HIPC(ctx, hipStreamSynchronize(s));   // the staging arrays are this frame's
   launch_kmv_prep(cg->dtype, s, cg->data->x.p, cg->data->ldx, cg->invl.p, d, cg->N, cg->Np, cg->rows.p, cg->bias.p);
   KCHECK(ctx, "kmv_prep");
+  if (cg->have_noise) {
+    const size_t nb = size_t(cg->N) * cg->es;
+    if ((rc = cg->sig2.reserve(ctx, nb, "the noise variances")) != SVGP_OK) return rc;
+    if ((rc = cg->isig2.reserve(ctx, nb, "the noise variances")) != SVGP_OK) return rc;
+    if ((rc = cg->ssig2.reserve(ctx, nb, "the noise variances")) != SVGP_OK) return rc;
+    if ((rc = cg->isig64.reserve(ctx, size_t(cg->N) * 8, "the noise variances")) != SVGP_OK) return rc;
+    launch_cg_noise_prep(cg->dtype, s, cg->noise_s.p, cg->N, p.diag, cg->sig2.p, cg->isig2.p, cg->ssig2.p, cg->isig64.as<double>());
+    KCHECK(ctx, "cg (noise variances)");
+  }
   if (precond && cg->pc.k > 0) return pc_setup(ctx, cg, p);
   return SVGP_OK;
 }
@@ -343,6 +389,7 @@ void kmv(svgp_ctx* ctx, const svgp_cg* cg, const CgPar& p, const void* px, int64
   a.px = px;
   a.V = V;
   a.addv = addv;
+  a.dvec = (addv && cg->have_noise) ? cg->sig2.p : nullptr;   // Khat = K + diag(sig2); addv is only ever passed with the data as the points
   a.out = out;
   a.ldp = ldp;
   a.n = n;
@@ -607,7 +654,8 @@ int upload_cols(svgp_ctx* ctx, const svgp_cg* cg, DevBuf& b, const void* host, i
   return SVGP_OK;
 }
 
-int check_precond_desc(svgp_ctx* ctx, const svgp_cg_desc* ds) {
+int check_precond_desc(svgp_ctx* ctx, const svgp_cg* cg, const svgp_cg_desc* ds) {
+  if (cg->have_noise) return SVGP_OK;   // the variances are diag + s_i: noise_check answers for them (SVGP_NOT_POSDEF)
   if (!(ds->diag > 0)) return fail(ctx, SVGP_INVALID_ARG, "a preconditioner is set: diag must be > 0 (P = Z Kuu^-1 Z' + diag I)");
   return SVGP_OK;
 }
@@ -634,6 +682,22 @@ int xgrad_fill_nan(svgp_ctx* ctx, const svgp_cg* cg, const svgp_input_grad* gx) 
       if (cg->dtype == SVGP_F64) static_cast<double*>(gx->x)[int64_t(f) * gx->ld + i] = nan;
       else static_cast<float*>(gx->x)[int64_t(f) * gx->ld + i] = std::numeric_limits<float>::quiet_NaN();
     }
+  return SVGP_OK;
+}
+
+// NaN into the noise gradient's output (SVGP_NOT_POSDEF)
+int sbar_fill_nan(svgp_ctx* ctx, const svgp_cg* cg, const svgp_point_noise_grad* gpn) {
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  if (gpn->on_device) {
+    launch_cg_affine(cg->dtype, ctx->stream, gpn->s_bar, 0, cg->N, cg->N, 1, 0.0, nan, gpn->s_bar, cg->N);
+    KCHECK(ctx, "cg (NaN outputs)");
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    return SVGP_OK;
+  }
+  for (int64_t i = 0; i < cg->N; ++i) {
+    if (cg->dtype == SVGP_F64) static_cast<double*>(gpn->s_bar)[i] = nan;
+    else static_cast<float*>(gpn->s_bar)[i] = std::numeric_limits<float>::quiet_NaN();
+  }
   return SVGP_OK;
 }
 
@@ -684,12 +748,12 @@ int xgrad_enqueue(svgp_ctx* ctx, svgp_cg* cg, const CgPar& par, int32_t T, const
 // (1 / T) sum_t (z_t' P^-1 z_t) e_1' log(T_t) e_1, and the gradient's trace terms are w_t' dKhat (P^-1 z_t)
 int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* delta, int32_t T, const double* probes, double* lml_out,
              svgp_cg_info* info, const FitGrad* g, const double* probes_k = nullptr, bool precond_call = false,
-             const svgp_input_grad* gx = nullptr) {
+             const svgp_input_grad* gx = nullptr, const svgp_point_noise_grad* gpn = nullptr) {
   int rc = common_checks(ctx, cg, ds);
   if (rc) return rc;
   const bool pc = cg->pc.k > 0;
   if (precond_call && !pc) return fail(ctx, SVGP_INVALID_ARG, "no preconditioner is set on this handle (svgp_cg_set_preconditioner)");
-  if (pc && (rc = check_precond_desc(ctx, ds)) != SVGP_OK) return rc;
+  if (pc && (rc = check_precond_desc(ctx, cg, ds)) != SVGP_OK) return rc;
   if (pc && T > 0 && !precond_call)
     return fail(ctx, SVGP_INVALID_ARG, "a preconditioner is set: the probes need their k x T part (svgp_cg_fit_precond / svgp_cg_lml_grad_precond)");
   if (pc && T > 0 && !probes_k) return fail(ctx, SVGP_INVALID_ARG, "null probes_k with T > 0");
@@ -698,9 +762,13 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
   if (T > 0 && !probes) return fail(ctx, SVGP_INVALID_ARG, "null probes with T > 0");
   if (g && (!g->dv || !g->dil)) return fail(ctx, SVGP_INVALID_ARG, "null gradient output");
   if (gx && (rc = check_input_grad(ctx, cg->data, cg->N, gx)) != SVGP_OK) return rc;
+  if (gpn && !gpn->s_bar) return fail(ctx, SVGP_INVALID_ARG, "null noise-gradient output");
+  if (gpn && gpn->on_device != 0 && gpn->on_device != 1) return fail(ctx, SVGP_INVALID_ARG, "on_device must be 0 or 1");
+  if (gpn && gpn->reserved != 0) return fail(ctx, SVGP_INVALID_ARG, "reserved must be 0");
   HIPC(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int dt = cg->dtype, d = cg->d;
+  const bool want_sbar = g && (gpn || cg->have_noise);   // with a vector set d_variance needs sum_i sigma_i^2 s_bar_i
   const int64_t N = cg->N, S = int64_t(T) + 1;
   const size_t col = size_t(N) * cg->es;
   const CgPar par = par_of(ds);
@@ -711,6 +779,7 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
   if ((rc = cg->f64tmp.reserve(ctx, size_t(N) * size_t(T > 0 ? T : 1) * 8, "the probes")) != SVGP_OK) return rc;
   if ((rc = cg->res.reserve(ctx, (size_t(d + 2) * size_t(S) + 8) * 8, "the CG results")) != SVGP_OK) return rc;
   if (g && (rc = cg->gout.reserve(ctx, col * size_t(S), "the gradient's products")) != SVGP_OK) return rc;
+  if (want_sbar && (rc = cg->sbar.reserve(ctx, col, "the noise gradient")) != SVGP_OK) return rc;
   if (gx && T > 0) {
     const size_t S2 = 2 * size_t(T) + 1;
     if ((rc = cg->xL.reserve(ctx, col * S2, "the input gradient's panels")) != SVGP_OK) return rc;
@@ -720,14 +789,16 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
   }
   // SVGP_NOT_POSDEF: NaN in the input gradient as well, the status and its message kept
   auto nan_inputs = [&](int status) {
-    if (gx && status == SVGP_NOT_POSDEF) {
+    if ((gx || gpn) && status == SVGP_NOT_POSDEF) {
       const std::string keep = ctx->err;
-      (void)xgrad_fill_nan(ctx, cg, gx);
+      if (gx) (void)xgrad_fill_nan(ctx, cg, gx);
+      if (gpn) (void)sbar_fill_nan(ctx, cg, gpn);
       ctx->err = keep;
     }
     return status;
   };
-  if ((rc = set_params(ctx, cg, par)) != SVGP_OK) {
+  if ((rc = noise_check(ctx, cg, ds, pc)) == SVGP_OK) rc = set_params(ctx, cg, par);
+  if (rc != SVGP_OK) {
     if (rc == SVGP_NOT_POSDEF) {
       svgp_cg_info bad{};
       bad.max_rel_residual = bad.quad = bad.logdet = bad.lml = std::numeric_limits<double>::quiet_NaN();
@@ -755,7 +826,8 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
     HIPC(ctx, hipMemcpyAsync(P.xi.p, probes_k, size_t(P.k) * size_t(T) * 8, hipMemcpyHostToDevice, s));
     launch_cg_affine(dt, s, cg->f64tmp.p, 1, N, N, T, 1.0, 0.0, cg->fitX.as<char>() + col, N);
     launch_cg_pc_mm(dt, s, P.LinvRM.as<double>(), P.Mp, P.k, P.xi.p, 1, P.k, T, 1.0, P.v.p, P.kp, P.kp);
-    pc_expand(ctx, cg, par, P.v.p, T, cg->fitX.as<char>() + col, N, std::sqrt(P.s2), cg->fitB.as<char>() + col, N);
+    pc_expand(ctx, cg, par, P.v.p, T, cg->fitX.as<char>() + col, N, std::sqrt(P.s2), cg->fitB.as<char>() + col, N,
+              cg->have_noise ? cg->ssig2.p : nullptr);   // per-point noise: z_t = D^1/2 eps_t + Z Lu^-T xi_t
   }
   KCHECK(ctx, "cg (right-hand sides)");
   CgHist hist;
@@ -816,8 +888,15 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
     launch_cg_affine(dt, s, O, 0, N, N, 1, 0.0, 1.0, O, N);   // ones
     launch_cg_dot(dt, s, U, N, O, N, N, 1, partial);
     launch_cg_colsum(s, partial, N, 1, res + int64_t(2 + d) * S);
+    if (want_sbar) {   // s_bar from the panels, and sum_i sigma_i^2 s_bar_i behind the other results
+      launch_cg_sbar(dt, s, U, P, N, T, cg->sbar.p);
+      if (cg->have_noise) {
+        launch_cg_noise_sum(dt, s, cg->sig2.p, cg->sbar.p, N, partial);
+        launch_cg_colsum(s, partial, N, 1, res + int64_t(2 + d) * S + 1);
+      }
+    }
     KCHECK(ctx, "cg (gradient)");
-    std::vector<double> h(size_t(d + 2) * size_t(S) + 1);
+    std::vector<double> h(size_t(d + 2) * size_t(S) + (cg->have_noise ? 2 : 1));
     HIPC(ctx, hipMemcpyAsync(h.data(), res, h.size() * 8, hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipStreamSynchronize(s));
     auto combine = [&](const double* v, const double* sub, double subw) {   //  1/2 v_0 - 1/(2T) sum_t v_t, t ascending
@@ -828,9 +907,14 @@ int fit_impl(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* ds, const double* d
     };
     const double dd = combine(h.data(), nullptr, 0.0);
     if (g->dd) *g->dd = dd;
-    *g->dv = combine(h.data() + S, h.data(), par.diag) / par.variance;   // K v = Khat v - diag v
+    if (!cg->have_noise) *g->dv = combine(h.data() + S, h.data(), par.diag) / par.variance;   // K v = Khat v - diag v
+    else *g->dv = (combine(h.data() + S, nullptr, 0.0) - h[size_t(d + 2) * size_t(S) + 1]) / par.variance;   // K v = Khat v - D v
     for (int f = 0; f < d; ++f) g->dil[f] = combine(h.data() + size_t(2 + f) * size_t(S), nullptr, 0.0) / par.invl[f];
     if (g->dm) *g->dm = h[size_t(d + 2) * size_t(S)];
+    if (gpn) {
+      HIPC(ctx, hipMemcpyAsync(gpn->s_bar, cg->sbar.p, col, gpn->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+      HIPC(ctx, hipStreamSynchronize(s));
+    }
     if (gx && (rc = T > 0 ? xgrad_enqueue(ctx, cg, par, T, gx) : xgrad_fill_nan(ctx, cg, gx)) != SVGP_OK) return rc;
   }
   if (info) *info = out;
@@ -895,10 +979,19 @@ int32_t svgp_cg_matvec(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int
     if ((rc = upload_cols(ctx, cg, Vd, V, ldv, S, "the panel")) != SVGP_OK) return rc;
     if ((rc = upload_cols(ctx, cg, Od, nullptr, N, S, "the product")) != SVGP_OK) return rc;
   }
-  if ((rc = set_params(ctx, cg, par, false)) != SVGP_OK) return rc;
   const void* vp = on_device ? V : Vd.p;
   void* op = on_device ? out : Od.p;
   const int64_t lv = on_device ? ldv : N, lo = on_device ? ldo : N;
+  if ((rc = noise_check(ctx, cg, desc, false)) != SVGP_OK) {   // a bad variance: NaN outputs, the status and its message kept
+    const std::string keep = ctx->err;
+    launch_cg_affine(cg->dtype, s, op, 0, lo, N, S, 0.0, std::numeric_limits<double>::quiet_NaN(), op, lo);
+    KCHECK(ctx, "cg (NaN outputs)");
+    if (!on_device) HIPC(ctx, hipMemcpy2DAsync(out, size_t(ldo) * cg->es, Od.p, col, col, size_t(S), hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipStreamSynchronize(s));
+    ctx->err = keep;
+    return rc;
+  }
+  if ((rc = set_params(ctx, cg, par, false)) != SVGP_OK) return rc;
   TREC(ctx, ctx->ev[0], s);
   kmv(ctx, cg, par, cg->data->x.p, cg->data->ldx, N, vp, lv, S, vp, lv, op, lo);
   TREC(ctx, ctx->ev[1], s);
@@ -922,7 +1015,7 @@ int32_t svgp_cg_solve(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int6
   if (S < 1) return fail(ctx, SVGP_INVALID_ARG, "S must be >= 1");
   if (ldb < cg->N || ldx < cg->N) return fail(ctx, SVGP_INVALID_ARG, "ldb and ldx must be >= N");
   if (on_device != 0 && on_device != 1) return fail(ctx, SVGP_INVALID_ARG, "on_device must be 0 or 1");
-  if (cg->pc.k > 0 && (rc = check_precond_desc(ctx, desc)) != SVGP_OK) return rc;
+  if (cg->pc.k > 0 && (rc = check_precond_desc(ctx, cg, desc)) != SVGP_OK) return rc;
   HIPC(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int64_t N = cg->N;
@@ -934,7 +1027,8 @@ int32_t svgp_cg_solve(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, int6
     if ((rc = upload_cols(ctx, cg, Xd, nullptr, N, S, "the solutions")) != SVGP_OK) return rc;
   }
   if ((rc = ensure_solver(ctx, cg, 64, false, par.maxiter)) != SVGP_OK) return rc;
-  if ((rc = set_params(ctx, cg, par)) == SVGP_NOT_POSDEF) {   // the preconditioner did not factor: NaN outputs, as for a bad curvature
+  if ((rc = noise_check(ctx, cg, desc, cg->pc.k > 0)) == SVGP_OK) rc = set_params(ctx, cg, par);
+  if (rc == SVGP_NOT_POSDEF) {   // the preconditioner did not factor, or a bad noise variance: NaN outputs, as for a bad curvature
     const std::string keep = ctx->err;
     const double nan = std::numeric_limits<double>::quiet_NaN();
     void* Xp = on_device ? X : Xd.p;
@@ -1000,7 +1094,7 @@ int32_t svgp_cg_predict(svgp_ctx* ctx, svgp_cg* cg, int32_t layout, int64_t n, c
   if (cg->device != ctx->device) return fail(ctx, SVGP_INVALID_ARG, "the CG handle lives on another device than the context");
   if (!cg->have_fit) return fail(ctx, SVGP_INVALID_ARG, "no successful svgp_cg_fit on this handle yet");
   if (n < 1) return fail(ctx, SVGP_INVALID_ARG, "no test points");
-  if (var_out && cg->pc.k > 0 && !(cg->fit.diag > 0)) return fail(ctx, SVGP_INVALID_ARG, "a preconditioner is set: the fit's diag must be > 0");
+  if (var_out && cg->pc.k > 0 && !cg->have_noise && !(cg->fit.diag > 0)) return fail(ctx, SVGP_INVALID_ARG, "a preconditioner is set: the fit's diag must be > 0");
   if (var_out && (n > kCgMaxPredict || n * cg->N > kCgMaxPredict))
     return fail(ctx, SVGP_UNSUPPORTED, "the predictive variance of more than 2^28 / N test points in one call");
   if (n > kCgMaxPredict) return fail(ctx, SVGP_UNSUPPORTED, "more than 2^28 test points in one call");
@@ -1114,7 +1208,7 @@ int32_t svgp_cg_precond_apply(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* de
   int rc = common_checks(ctx, cg, desc);
   if (rc) return rc;
   if (cg->pc.k < 1) return fail(ctx, SVGP_INVALID_ARG, "no preconditioner is set on this handle (svgp_cg_set_preconditioner)");
-  if ((rc = check_precond_desc(ctx, desc)) != SVGP_OK) return rc;
+  if ((rc = check_precond_desc(ctx, cg, desc)) != SVGP_OK) return rc;
   if (S < 1) return fail(ctx, SVGP_INVALID_ARG, "S must be >= 1");
   if (ldr < cg->N || ldo < cg->N) return fail(ctx, SVGP_INVALID_ARG, "ldr and ldo must be >= N");
   if (on_device != 0 && on_device != 1) return fail(ctx, SVGP_INVALID_ARG, "on_device must be 0 or 1");
@@ -1133,7 +1227,7 @@ int32_t svgp_cg_precond_apply(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* de
   }
   void* op = on_device ? out : Od.p;
   const int64_t lo = on_device ? ldo : N;
-  rc = set_params(ctx, cg, par);
+  if ((rc = noise_check(ctx, cg, desc, true)) == SVGP_OK) rc = set_params(ctx, cg, par);
   if (rc != SVGP_OK && rc != SVGP_NOT_POSDEF) return rc;
   const int status = rc;
   const std::string keep = ctx->err;
@@ -1188,6 +1282,50 @@ int32_t svgp_cg_lml_grad_inputs(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* 
   if (!pc && probes_k) return fail(ctx, SVGP_INVALID_ARG, "probes_k without a preconditioner on this handle (svgp_cg_set_preconditioner)");
   const FitGrad g{d_variance, d_inv_lengthscale, d_diag, d_mean_const};
   return fit_impl(ctx, cg, desc, delta, T, probes, lml_out, info, &g, probes_k, pc, gx);
+}
+
+int32_t svgp_cg_set_noise(svgp_ctx* ctx, svgp_cg* cg, const svgp_point_noise* pn) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!cg) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (cg->device != ctx->device) return fail(ctx, SVGP_INVALID_ARG, "the CG handle lives on another device than the context");
+  if (pn && !pn->s) return fail(ctx, SVGP_INVALID_ARG, "null noise vector");
+  if (pn && pn->on_device != 0 && pn->on_device != 1) return fail(ctx, SVGP_INVALID_ARG, "on_device must be 0 or 1");
+  if (pn && pn->reserved != 0) return fail(ctx, SVGP_INVALID_ARG, "reserved must be 0");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  HIPC(ctx, hipStreamSynchronize(s));
+  cg->have_fit = false;   // alpha belonged to the earlier Khat
+  if (!pn) {
+    cg->have_noise = false;
+    return SVGP_OK;
+  }
+  cg->have_noise = false;   // (a failure below leaves the handle without a vector)
+  const size_t nb = size_t(cg->N) * cg->es;
+  int rc;
+  if ((rc = cg->noise_s.reserve(ctx, nb, "the noise vector")) != SVGP_OK) return rc;
+  if ((rc = cg->noise_lo.reserve(ctx, 8, "the noise vector's minimum")) != SVGP_OK) return rc;
+  HIPC(ctx, hipMemcpyAsync(cg->noise_s.p, pn->s, nb, pn->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  launch_cg_noise_min(cg->dtype, s, cg->noise_s.p, cg->N, cg->noise_lo.as<double>());
+  KCHECK(ctx, "cg (noise minimum)");
+  double lo = 0;
+  HIPC(ctx, hipMemcpyAsync(&lo, cg->noise_lo.p, 8, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  cg->noise_min = lo;
+  cg->have_noise = true;
+  return SVGP_OK;
+}
+
+int32_t svgp_cg_lml_grad_noise(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                               const double* probes_k, double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale,
+                               double* d_diag, double* d_mean_const, const svgp_input_grad* gx, svgp_point_noise_grad* gpn) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!cg) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (gx && !gx->x) return fail(ctx, SVGP_INVALID_ARG, "null input-gradient output");
+  if (!gpn || !gpn->s_bar) return fail(ctx, SVGP_INVALID_ARG, "null noise-gradient output");
+  const bool pc = cg->pc.k > 0;
+  if (!pc && probes_k) return fail(ctx, SVGP_INVALID_ARG, "probes_k without a preconditioner on this handle (svgp_cg_set_preconditioner)");
+  const FitGrad g{d_variance, d_inv_lengthscale, d_diag, d_mean_const};
+  return fit_impl(ctx, cg, desc, delta, T, probes, lml_out, info, &g, probes_k, pc, gx, gpn);
 }
 
 }  // extern "C"
@@ -1275,7 +1413,7 @@ int32_t svgp_cg_sampler_create(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* d
   if (!basis->eps) return fail(ctx, SVGP_INVALID_ARG, "null eps");
   if (L > 0 && (!basis->omega || !basis->tau || !basis->w)) return fail(ctx, SVGP_INVALID_ARG, "null omega, tau or w with n_features > 0");
   if (!delta && !cg->data->y.p) return fail(ctx, SVGP_INVALID_ARG, "the data handle has no y and no delta was given");
-  if (cg->pc.k > 0 && (rc = check_precond_desc(ctx, desc)) != SVGP_OK) return rc;
+  if (cg->pc.k > 0 && (rc = check_precond_desc(ctx, cg, desc)) != SVGP_OK) return rc;
   HIPC(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int dt = cg->dtype, d = cg->d;
@@ -1308,7 +1446,8 @@ int32_t svgp_cg_sampler_create(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* d
   for (auto& r : req)
     if (r.bytes > 0 && (rc = r.b->reserve(ctx, r.bytes, "the sampler")) != SVGP_OK) return rc;
   if ((rc = ensure_solver(ctx, cg, S, false, par.maxiter)) != SVGP_OK) return rc;
-  if ((rc = set_params(ctx, cg, par)) != SVGP_OK) {   // SVGP_NOT_POSDEF: the preconditioner did not factor - no sampler
+  if ((rc = noise_check(ctx, cg, desc, cg->pc.k > 0)) == SVGP_OK) rc = set_params(ctx, cg, par);
+  if (rc != SVGP_OK) {   // SVGP_NOT_POSDEF: the preconditioner did not factor, or a bad noise variance - no sampler
     if (rc == SVGP_NOT_POSDEF && info) {
       *info = svgp_cg_info{};
       info->max_rel_residual = info->quad = info->logdet = info->lml = nan;
@@ -1337,7 +1476,7 @@ int32_t svgp_cg_sampler_create(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* d
   // Phi(X) w through the evaluation kernel over the features alone, then one affine pass: B_s = delta - Phi(X) w_s - sigma eps_s
   if (L > 0 && (rc = cgs_launch(ctx, sp.get(), cg->data->x.p, cg->data->ldx, 0, N, phi.p, N, nullptr, 0, true)) != SVGP_OK) return rc;
   const double sigma = std::sqrt(dt == SVGP_F64 ? par.diag : double(float(par.diag)));
-  launch_cg_sample_rhs(dt, s, dvec.p, L > 0 ? phi.p : nullptr, d_eps.p, sigma, N, S, B.p);
+  launch_cg_sample_rhs(dt, s, dvec.p, L > 0 ? phi.p : nullptr, d_eps.p, sigma, N, S, B.p, cg->have_noise ? cg->sig2.p : nullptr);
   launch_cg_dot(dt, s, B.p, N, B.p, N, N, S, cg->partial.as<double>());
   launch_cg_colsum(s, cg->partial.as<double>(), N, S, cg->res.as<double>());
   KCHECK(ctx, "cg sampler (right-hand sides)");

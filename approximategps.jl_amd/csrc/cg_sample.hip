@@ -329,10 +329,11 @@ void launch_cgs_t(hipStream_t s, const CgSampleArgs& a) {   // the DREG of launc
 
 template <typename T>
 __global__ void cg_sample_rhs_kernel(const T* __restrict__ delta, const T* __restrict__ phi, const T* __restrict__ eps, double sigma, int64_t N,
-                                     T* __restrict__ B) {
+                                     T* __restrict__ B, const T* __restrict__ sig2) {
   const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, col = blockIdx.y;
   if (i >= N) return;
   const int64_t o = col * N + i;
+  if (sig2) sigma = sqrt(double(sig2[i]));   // per-point noise
   B[o] = T((double(delta[i]) - (phi ? double(phi[o]) : 0.0)) - sigma * double(eps[o]));
 }
 
@@ -368,12 +369,13 @@ void launch_cg_sample(int dtype, hipStream_t s, const CgSampleArgs& a) {
   if (dtype == 0) launch_cgs_t<double>(s, a); else launch_cgs_t<float>(s, a);
 }
 
-void launch_cg_sample_rhs(int dtype, hipStream_t s, const void* delta, const void* phi, const void* eps, double sigma, int64_t N, int64_t S, void* B) {
+void launch_cg_sample_rhs(int dtype, hipStream_t s, const void* delta, const void* phi, const void* eps, double sigma, int64_t N, int64_t S, void* B,
+                          const void* sig2) {
   for (int64_t c0 = 0; c0 < S; c0 += 32768) {   // (grid.y limit)
     const int64_t nc = S - c0 < 32768 ? S - c0 : 32768;
     const dim3 g((unsigned)((N + 255) / 256), (unsigned)nc);
-    if (dtype == 0) hipLaunchKernelGGL(cg_sample_rhs_kernel<double>, g, dim3(256), 0, s, (const double*)delta, phi ? (const double*)phi + c0 * N : nullptr, (const double*)eps + c0 * N, sigma, N, (double*)B + c0 * N);
-    else hipLaunchKernelGGL(cg_sample_rhs_kernel<float>, g, dim3(256), 0, s, (const float*)delta, phi ? (const float*)phi + c0 * N : nullptr, (const float*)eps + c0 * N, sigma, N, (float*)B + c0 * N);
+    if (dtype == 0) hipLaunchKernelGGL(cg_sample_rhs_kernel<double>, g, dim3(256), 0, s, (const double*)delta, phi ? (const double*)phi + c0 * N : nullptr, (const double*)eps + c0 * N, sigma, N, (double*)B + c0 * N, (const double*)sig2);
+    else hipLaunchKernelGGL(cg_sample_rhs_kernel<float>, g, dim3(256), 0, s, (const float*)delta, phi ? (const float*)phi + c0 * N : nullptr, (const float*)eps + c0 * N, sigma, N, (float*)B + c0 * N, (const float*)sig2);
   }
 }
 

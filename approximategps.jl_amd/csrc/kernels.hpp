@@ -317,7 +317,8 @@ void launch_sample_phiz(int dtype, hipStream_t s, const double* zs64, const void
 void launch_sample_panel(int dtype, hipStream_t s, const void* w, const double* V, int64_t L, int64_t Lp, int64_t M, int64_t Mp, int64_t S, int64_t Sp,
                          double amp, void* panel);
 
-// cg.hip: out[s * ldo + i] = sum_j prof(r^2(P_i, R_j)) V[s * ldv + j] (+ diag addv[s * lda + i]) for the n points P and the N rows R
+// cg.hip: out[s * ldo + i] = sum_j prof(r^2(P_i, R_j)) V[s * ldv + j] (+ diag addv[s * lda + i]) for the n points P and the N rows R;
+// with dvec the added term's factor is per point: + dvec[i] addv[s * lda + i]
 struct KmvArgs {
   const void* rows;    // [d][Np] the rows R as launch_kmv_prep wrote them
   const void* bias;    // [Np]
@@ -325,6 +326,7 @@ struct KmvArgs {
   const void* px;      // [d][ldp] the points P, feature-major, unscaled
   const void* V;       // N x S panel, column-major
   const void* addv;    // nullable: n x S, column-major
+  const void* dvec;    // nullable: [n] the per-point factor of addv (per-point noise), read only with addv; NULL: diag for every point
   void* out;           // n x S, column-major
   int64_t ldp, n, N, Np, ldv, lda, ldo, S;
   int64_t s0;          // first column of the launch's column block (set by the launcher)
@@ -365,6 +367,18 @@ void launch_cg_pc_logdet(hipStream_t s, const double* L, int64_t Mp, int64_t k, 
 // out (dtype's element type, ld ldo, zero on rows [k, rows_out)) = alpha Mt' v for the k x k block of Mt (ld Mp); v fp64 or dtype's type
 void launch_cg_pc_mm(int dtype, hipStream_t s, const double* Mt, int64_t Mp, int64_t k, const void* v, int v_f64, int64_t ldv, int64_t ncols, double alpha,
                      void* out, int64_t ldo, int64_t rows_out);
+// per-point noise variances (svgp_cg_set_noise): sigma_i^2 = T(diag) + s_i in the data dtype T with one rounding.
+// launch_cg_noise_min: out[0] = min_i s_i in fp64, NaN if any s_i is NaN (one workgroup, a fixed tree)
+void launch_cg_noise_min(int dtype, hipStream_t s, const void* sv, int64_t N, double* out);
+// sig2[i] = T(diag) + s[i]; isig2 = T(1 / sig2), ssig2 = T(sqrt(sig2)) (formed in fp64, rounded once); isig64 = 1 / double(sig2)
+void launch_cg_noise_prep(int dtype, hipStream_t s, const void* sv, int64_t N, double diag, void* sig2, void* isig2, void* ssig2, double* isig64);
+// dst[col * ldd + i] = src[col * lds + i] vec[i] (in place allowed); dtype 0 / 1: the data dtype, 2: fp64 arrays whatever the data dtype
+void launch_cg_rowscale(int dtype, hipStream_t s, const void* src, int64_t lds, const void* vec, int64_t N, int64_t ncols, void* dst, int64_t ldd);
+// sbar[i] = T( 1/2 U[i, 0] P[i, 0] - (1 / 2T) sum_{t = 1..T} U[i, t] P[i, t] ), t ascending in fp64, rounded once; NaN with T = 0
+// (U = [alpha, w_t], P = [alpha, p_t], N x (T + 1), ld N)
+void launch_cg_sbar(int dtype, hipStream_t s, const void* U, const void* P, int64_t N, int T, void* sbar);
+// the first stage (cg_dot_blocks(N) partials, fp64) of sum_i log sig2[i] (b NULL) or sum_i sig2[i] b[i]; launch_cg_colsum adds them
+void launch_cg_noise_sum(int dtype, hipStream_t s, const void* sig2, const void* b, int64_t N, double* partial);
 
 // ---- cg_sample.hip (pathwise function samples of the exact GP: svgp_cg_sampler_*) -----------------------------------------------
 //   out[s * ldo + j] = mean_const + sum_l cos(frows[.][l] . xs_j + fbias[l]) W[l, s] + sum_i kappa(r^2(x_j, X_i)) V[i, s],   xs = invl o x
@@ -399,7 +413,9 @@ void cg_sample_plan(int64_t N, int64_t* seg_rows, int* nseg, int64_t* round);
 inline int64_t cg_sample_round(int64_t round, bool grad) { return !grad ? round : round / 4 < 256 ? 256 : round / 4; }
 void launch_cg_sample(int dtype, hipStream_t s, const CgSampleArgs& a);
 // B[s * N + i] = delta[i] - phi[s * N + i] - sigma eps[s * N + i], formed in fp64 and rounded once (phi nullable: no features)
-void launch_cg_sample_rhs(int dtype, hipStream_t s, const void* delta, const void* phi, const void* eps, double sigma, int64_t N, int64_t S, void* B);
+// sig2 non-null (per-point noise): sigma_i = sqrt(double(sig2[i])) takes the place of sigma
+void launch_cg_sample_rhs(int dtype, hipStream_t s, const void* delta, const void* phi, const void* eps, double sigma, int64_t N, int64_t S, void* B,
+                          const void* sig2 = nullptr);
 // W[s * Lp + l] = amp w[s * L + l] (l < L), 0 on the padding; frows[f][l] = omega[l * d + f], fbias[l] = tau[l], 0 on the padding
 void launch_cg_sample_basis(int dtype, hipStream_t s, const void* omega, const void* tau, const void* w, int d, int64_t L, int64_t Lp, int64_t S,
                             double amp, void* frows, void* fbias, void* W);

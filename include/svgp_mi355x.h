@@ -856,8 +856,9 @@ int32_t svgp_sampler_eval_grad(svgp_ctx* ctx, const svgp_sampler* sampler, const
  * SVGP_INVALID_ARG, before anything is enqueued: a NULL required pointer; descriptor dtype or d different from the data's; an unknown
  * kernel; data without y when delta is NULL; maxiter < 1, tol <= 0, diag < 0, variance <= 0, reserved != 0 (NaN counts as a violation);
  * S < 1; T < 0, or T > 0 with NULL probes; ldv, ldo, ldb or ldx < N; on_device not 0 / 1; alpha or predict before a successful fit;
- * n < 1.  Preconditioning: the next section; pathwise function samples: the one after it.  Out of scope: per-point noise, cov /
- * cross-cov, multi-GPU, the Julia hooks. */
+ * n < 1.  Preconditioning: the next section; pathwise function samples: the one after it; per-point noise variances
+ * (Khat = K + diag(sigma^2)): svgp_cg_set_noise below.  Out of scope: a full (non-diagonal) noise covariance, cov / cross-cov,
+ * multi-GPU, the Julia hooks. */
 typedef struct svgp_cg svgp_cg;
 typedef struct svgp_cg_desc {
   int32_t dtype, kernel, d, maxiter; /* maxiter >= 1 */
@@ -958,6 +959,41 @@ int32_t svgp_cg_lml_grad_precond(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc*
 int32_t svgp_cg_lml_grad_inputs(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
                                 const double* probes_k, double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale,
                                 double* d_diag, double* d_mean_const, const svgp_input_grad* gx);
+/* ---- per-point noise variances of the exact GP by conjugate gradients ------------------------------------------------------------------
+ * The collapsed bound's convention (svgp_point_noise): the per-point term adds to the descriptor's variance,
+ *   sigma_i^2 = T(desc.diag) + s_i   in the data dtype T with one rounding,      Khat = K(x, x) + diag(sigma^2)
+ * in every call on the handle once a vector is set: svgp_cg_matvec, _solve, _fit(_precond), _lml_grad(_precond / _inputs), _predict (the
+ * latent variance), _precond_apply and svgp_cg_sampler_create (right-hand sides delta - Phi(X) w_s - sigma_i eps_si; the sampler stays a
+ * snapshot).  svgp_cg_precond_cross is the kernel product alone and does not change.  Known measurement errors, a fixed-noise model or
+ * a learned noise function (GPyTorch's FixedNoiseGaussianLikelihood, AbstractGPs' Diagonal Sigma_y).
+ *   set_noise  N values of the data dtype, host or device memory (pn->on_device), copied into the handle: a snapshot, handle state like
+ *           the preconditioner's points.  pn = NULL removes the vector: every call is then bitwise what it is on a handle that never
+ *           had one.  Clears the cached fit: svgp_cg_alpha and svgp_cg_predict need a new one.  One NaN-propagating min-reduction of s
+ *           runs on the device at set time and its result is kept on the host: a later call fails BEFORE its data pass with
+ *           SVGP_NOT_POSDEF when T(desc.diag) + min s is < 0, or <= 0 with a preconditioner set, or NaN; its outputs are NaN and the
+ *           context stays healthy.
+ *   The kmv kernel's epilogue reads sigma_i^2 once per output point in place of the scalar.  The preconditioner becomes
+ *           P = Z Kuu^-1 Z' + D, D = diag(sigma^2):  P^-1 r = D^-1 r - D^-1 Z W Z' D^-1 r,  W = Lu^-T B^-1 Lu^-1,
+ *           B = I + Lu^-1 (Z' D^-1 Z) Lu^-T,  log det P = sum_i log sigma_i^2 + log det B (the sum a fixed two-stage fp64 reduction), the
+ *           Gram's weights applied in fp64 to the explicit N x <= 64 block of Z; the two scalings by D^-1 of an application are
+ *           streaming passes around the two kernel products.  The probes are z_t = D^1/2 eps_t + Z Lu^-T xi_t.
+ *   lml_grad_noise  the superset gradient call: svgp_cg_lml_grad_inputs' arguments with gx nullable, and
+ *           s_bar_i = d lml / d sigma_i^2 = 1/2 alpha_i^2 - (1 / 2T) sum_t w_it p_it     (p_t = z_t, or P^-1 z_t with a preconditioner)
+ *           the trace estimator of every other block: t ascending in fp64, rounded once to the data dtype; N values, host or device
+ *           (gpn->on_device).  Works with or without a vector set.  d_diag keeps its meaning, the derivative with respect to the
+ *           common term, = sum_i s_bar_i.  With a vector set d_variance = [1/2 alpha' Khat alpha - (1 / 2T) sum_t w_t' Khat p_t -
+ *           sum_i sigma_i^2 s_bar_i] / variance (a fixed two-stage fp64 reduction).  Every other output is bitwise what
+ *           svgp_cg_lml_grad(_precond / _inputs) returns on the same handle and inputs.  No atomics, every sum has a fixed order:
+ *           repeated calls and host / device output are bitwise equal.  T = 0: s_bar is NaN, like the other trace blocks;
+ *           SVGP_NOT_POSDEF: s_bar is NaN.
+ * SVGP_INVALID_ARG, before anything is enqueued: NULL pn->s, gpn or gpn->s_bar; on_device not 0 / 1; reserved != 0; a handle on another
+ * device than the context; what svgp_cg_lml_grad_inputs rejects (a NULL gx excepted).  With a vector set desc.diag == 0 is allowed with
+ * a preconditioner (the variances are diag + s_i).  Memory: six N-vectors on the handle (s, sigma^2, 1 / sigma^2, sqrt(sigma^2)
+ * and s_bar in the data dtype, 1 / sigma^2 in fp64).  Found by symbol (no ABI version step). */
+int32_t svgp_cg_set_noise(svgp_ctx* ctx, svgp_cg* cg, const svgp_point_noise* pn);
+int32_t svgp_cg_lml_grad_noise(svgp_ctx* ctx, svgp_cg* cg, const svgp_cg_desc* desc, const double* delta, int32_t T, const double* probes,
+                               const double* probes_k, double* lml_out, svgp_cg_info* info, double* d_variance, double* d_inv_lengthscale,
+                               double* d_diag, double* d_mean_const, const svgp_input_grad* gx, svgp_point_noise_grad* gpn);
 /* ---- pathwise function samples of the exact GP ---------------------------------------------------------------------------------------
  * S draws from the exact posterior by pathwise conditioning (Wilson et al. 2020, 2021) with the CG solve, each one a FUNCTION that can be
  * evaluated at any points, any number of times.  With Khat = K(X, X) + sigma^2 I (sigma^2 = desc.diag), delta = y - mean(X), phi_l as in

@@ -7,6 +7,7 @@ entries a second are the yardstick; no ratio is fixed in advance: the run report
     python tools/cg_time.py --precond 256 512 1024 --precond-out profiles/cg/cg_precond_time.jsonl
     python tools/cg_time.py --sample --sample-out profiles/cg/cg_sample_time.jsonl      (sample_leg below)
     python tools/cg_time.py --xgrad --xgrad-out profiles/cg/cg_xgrad_time.jsonl         (xgrad_leg below; after tools/build_prev.sh)
+    python tools/cg_time.py --noise --noise-out profiles/cg/cg_noise_time.jsonl         (noise_leg below; after tools/build_prev.sh)
 
 --precond K ...: after the unpreconditioned fit, the same fit (17 columns, same tol and maxiter) with the Nystrom preconditioner of K
 data points (default_rng([0, 2]).choice, jitter 1e-4): iterations, final residual, wall time, the preconditioner's setup time and
@@ -242,8 +243,150 @@ def xgrad_leg(a):
                 f.write(json.dumps(r) + "\n")
 
 
+def noise_child(a):
+    """one leg of --noise in a process of its own (the library is chosen by SVGP_MI355X_LIB before the import): per dtype at N = --n, d = --d,
+    S = --cols, after a warm-up of every shape: the device time of svgp_cg_matvec (median of 5) and the wall time of one blocking
+    svgp_cg_lml_grad (16 Rademacher probes, tol 1e-6, --noise-maxiter iterations) WITHOUT a noise vector - the calls the parent has too,
+    their outputs in hex for the bitwise comparison.  leg `new` adds: the same two WITH a vector (s = exp(U[log 0.02, log 0.5]),
+    default_rng(11)), svgp_cg_lml_grad_noise with it, and one svgp_cg_precond_apply at k = --noise-k with and without it."""
+    import warnings
+
+    import torch
+
+    from approxgp import DeviceConjugateGradients, _ffi, draw_probes
+    from approxgp.kernels import ARDTransform, ScaledKernel, SEKernel, TransformedKernel
+    from approxgp.synthetic import synth_arrays
+
+    new = a.noise_child == "new"
+    if not new:   # the parent's library lacks the new symbols
+        _ffi.SYMBOLS.pop("svgp_cg_set_noise", None)
+        _ffi.SYMBOLS.pop("svgp_cg_lml_grad_noise", None)
+    ctx = _ffi.Context(0)
+    N, d, S, T = a.n, a.d, a.cols, 16
+    wall = lambda fn: (lambda t0: (fn(), 1e3 * (time.perf_counter() - t0))[1])(time.perf_counter())
+    for dt in (np.float64, np.float32):
+        tdt = torch.float64 if dt == np.float64 else torch.float32
+        p = synth_arrays(0, N, 64, d, dtype=dt)
+        kernel = ScaledKernel(TransformedKernel(SEKernel(), ARDTransform(np.asarray(p["inv_lengthscale"], dtype=np.float64))), p["variance"])
+        x = np.asarray(p["x"])[:, :N]
+        dev = DeviceConjugateGradients(ctx, x, p["y"][:N], dt)
+        desc, keep = dev.desc(kernel, p["sigma2"], tol=1e-6, maxiter=a.noise_maxiter)
+        z = draw_probes(N, T, 0)
+        V = torch.randn((S, N), dtype=tdt, device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
+        out = torch.empty_like(V)
+        torch.cuda.synchronize()
+
+        def matvec_ms():
+            dev.matvec(desc, V, out=out)
+            ts = []
+            for _ in range(5):
+                dev.matvec(desc, V, out=out)
+                ts.append(ctx.timing().ms_strip)
+            return round(statistics.median(ts), 3)
+
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            row = {"leg": a.noise_child, "dtype": np.dtype(dt).name, "N": N, "d": d, "S": S, "T": T, "maxiter": a.noise_maxiter}
+            row["ms_matvec"] = matvec_ms()
+            row["matvec_hex"] = [float(v).hex() for v in out[0, :4].cpu().numpy()]
+            lml0, g0, info = dev.lml_grad(desc, z)
+            row["ms_lml_grad_wall"] = round(wall(lambda: dev.lml_grad(desc, z)), 2)
+            row["iterations"] = info.iterations
+            row["lml_grad_hex"] = [float(v).hex() for v in (lml0, g0["variance"], g0["diag"], g0["mean_const"], *g0["inv_lengthscale"])]
+            if new:
+                s = np.exp(np.random.default_rng(11).uniform(np.log(0.02), np.log(0.5), size=N)).astype(dt)
+                sb = torch.zeros(N, dtype=tdt, device="cuda")
+                torch.cuda.synchronize()
+                dev.lml_grad(desc, z, wrt_noise=True, noise_grad_out=sb)
+                row["ms_lml_grad_noise_wall_no_vector"] = round(wall(lambda: dev.lml_grad(desc, z, wrt_noise=True, noise_grad_out=sb)), 2)
+                k = a.noise_k
+                dev.set_preconditioner(x[:, np.random.default_rng([0, 2]).choice(N, size=k, replace=False)], 1e-4)
+                pout = torch.empty_like(V)
+
+                def apply_ms():
+                    dev.precond_apply(desc, V, out=pout)
+                    ts, st = [], []
+                    for _ in range(5):
+                        dev.precond_apply(desc, V, out=pout)
+                        ts.append(ctx.timing().ms_strip)
+                        st.append(ctx.timing().ms_prep)
+                    return round(statistics.median(ts), 3), round(statistics.median(st), 3)
+
+                row["ms_precond_apply"], row["ms_precond_setup"] = apply_ms()
+                dev.set_noise(s)
+                row["ms_precond_apply_vector"], row["ms_precond_setup_vector"] = apply_ms()
+                dev.set_preconditioner(None)
+                row["ms_matvec_vector"] = matvec_ms()
+                dev.lml_grad(desc, z)
+                row["ms_lml_grad_wall_vector"] = round(wall(lambda: dev.lml_grad(desc, z)), 2)
+                dev.lml_grad(desc, z, wrt_noise=True, noise_grad_out=sb)
+                row["ms_lml_grad_noise_wall_vector"] = round(wall(lambda: dev.lml_grad(desc, z, wrt_noise=True, noise_grad_out=sb)), 2)
+                row["finite"] = bool(torch.isfinite(sb).all().item() and torch.isfinite(pout).all().item())
+                del pout, sb
+        print("NOISE " + json.dumps(row), flush=True)
+        dev.free()
+        del V, out
+    ctx.close()
+
+
+def noise_leg(a):
+    """--noise: what per-point noise variances cost.  This tree against the library --prev-lib (tools/build_prev.sh builds the parent
+    commit's), one process per leg, interleaved new / prev, medians of --noise-reps: svgp_cg_matvec and a --noise-maxiter-iteration
+    svgp_cg_lml_grad without a vector on both, whether their outputs are bitwise the parent's, and on this tree the same calls with a
+    vector, svgp_cg_lml_grad_noise and one preconditioner application at k = --noise-k.  `spread` is (max - min) / median of the
+    parent's own repeats: a difference between the legs below it is not resolved by this run."""
+    import subprocess
+
+    if not os.path.exists(a.prev_lib):
+        raise SystemExit(f"{a.prev_lib} is missing: tools/build_prev.sh builds the parent commit's library")
+    runs = {"new": [], "prev": []}
+    for rep_ in range(a.noise_reps):
+        for leg in ("new", "prev"):
+            env = dict(os.environ)
+            if leg == "prev":
+                env["SVGP_MI355X_LIB"] = os.path.abspath(a.prev_lib)
+            cmd = [sys.executable, os.path.abspath(__file__), "--noise-child", leg, "--n", str(a.n), "--d", str(a.d), "--cols", str(a.cols),
+                   "--noise-maxiter", str(a.noise_maxiter), "--noise-k", str(a.noise_k)]
+            r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                raise SystemExit(f"the {leg} leg failed with status {r.returncode}; nothing more is started\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+            runs[leg].append([json.loads(ln[6:]) for ln in r.stdout.splitlines() if ln.startswith("NOISE ")])
+    rows = []
+    med = lambda rs, k: stat([r[k] for r in rs])
+    spread = lambda v: round((v[2] - v[1]) / v[0], 4) if v[0] > 0 else None
+    for i, name in enumerate(("float64", "float32")):
+        new, prev = [r[i] for r in runs["new"]], [r[i] for r in runs["prev"]]
+        mvn, mvp, lgn, lgp = med(new, "ms_matvec"), med(prev, "ms_matvec"), med(new, "ms_lml_grad_wall"), med(prev, "ms_lml_grad_wall")
+        row = {"dtype": name, "N": a.n, "d": a.d, "S": a.cols, "T": 16, "maxiter": a.noise_maxiter, "iterations": new[0]["iterations"], "reps": a.noise_reps,
+               "matvec": {"ms_parent": mvp, "ms_no_vector": mvn, "ms_vector": med(new, "ms_matvec_vector"), "no_vector_over_parent": round(mvn[0] / mvp[0], 4),
+                          "vector_over_parent": round(med(new, "ms_matvec_vector")[0] / mvp[0], 4), "spread_parent": spread(mvp), "spread_new": spread(mvn)},
+               "lml_grad": {"ms_parent_wall": lgp, "ms_no_vector_wall": lgn, "ms_vector_wall": med(new, "ms_lml_grad_wall_vector"),
+                            "no_vector_over_parent": round(lgn[0] / lgp[0], 4), "vector_over_parent": round(med(new, "ms_lml_grad_wall_vector")[0] / lgp[0], 4),
+                            "spread_parent": spread(lgp), "spread_new": spread(lgn)},
+               "lml_grad_noise": {"ms_no_vector_wall": med(new, "ms_lml_grad_noise_wall_no_vector"), "ms_vector_wall": med(new, "ms_lml_grad_noise_wall_vector"),
+                                  "over_lml_grad_no_vector": round(med(new, "ms_lml_grad_noise_wall_no_vector")[0] / lgn[0], 4),
+                                  "over_lml_grad_vector": round(med(new, "ms_lml_grad_noise_wall_vector")[0] / med(new, "ms_lml_grad_wall_vector")[0], 4)},
+               "precond_apply": {"k": a.noise_k, "ms_no_vector": med(new, "ms_precond_apply"), "ms_vector": med(new, "ms_precond_apply_vector"),
+                                 "ms_setup_no_vector": med(new, "ms_precond_setup"), "ms_setup_vector": med(new, "ms_precond_setup_vector")},
+               "bitwise_parent": all(r["lml_grad_hex"] == prev[0]["lml_grad_hex"] and r["matvec_hex"] == prev[0]["matvec_hex"] for r in new + prev),
+               "finite": all(r["finite"] for r in new)}
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if a.noise_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.noise_out)), exist_ok=True)
+        with open(a.noise_out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--noise", action="store_true", help="the per-point-noise leg alone (svgp_cg_set_noise, svgp_cg_lml_grad_noise)")
+    ap.add_argument("--noise-child", choices=("new", "prev"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--noise-reps", type=int, default=3)
+    ap.add_argument("--noise-maxiter", type=int, default=20)
+    ap.add_argument("--noise-k", type=int, default=256)
+    ap.add_argument("--noise-out", default=None, help="e.g. profiles/cg/cg_noise_time.jsonl")
     ap.add_argument("--xgrad", action="store_true", help="the input gradient's leg alone (svgp_cg_lml_grad_inputs)")
     ap.add_argument("--xgrad-child", choices=("new", "prev"), default=None, help=argparse.SUPPRESS)
     ap.add_argument("--xgrad-kernel", action="store_true", help=argparse.SUPPRESS)
@@ -267,6 +410,10 @@ def main():
     ap.add_argument("--precond", type=int, nargs="*", default=[], help="preconditioner sizes for the preconditioned leg")
     ap.add_argument("--precond-out", default=None)
     a = ap.parse_args()
+    if a.noise_child:
+        return noise_child(a)
+    if a.noise:
+        return noise_leg(a)
     if a.xgrad_child:
         return xgrad_child(a)
     if a.xgrad:
