@@ -129,18 +129,42 @@ __device__ __forceinline__ float kexp(float v) {
 // instructions and one LDS read against kexp's ~20 - the pre-generation is VALU-bound and f64 VALU blocks the MFMA pipe of the
 // partner workgroup too (s_memtime stamps: 140-158k of a forward strip's 2230k ticks).  Same box, three repetitions, H strip ms:
 // 33.44 / 33.41 / 33.57 with kexp, 33.35 / 33.33 / 33.27 with the table (C2 1.13 vs 1.13): -0.5 %, parity tests unchanged; 212 VGPRs either way
-__device__ __forceinline__ double kexp_tab(double v, const double* __restrict__ tab) {
-  const double nd = rint(v * 92.332482616893658);               // 64 / ln2
-  const int n = int(nd);
-  double r = fma(nd, -1.08304246932675596327e-02, v);           // ln2_hi / 64 (kexp's split, exact in binary)
-  r = fma(nd, -2.98158582698529328128e-12, r);                  // ln2_lo / 64
-  const double t = tab[n & 63];
-  double p = fma(r, 8.333333333333333e-03, 4.1666666666666664e-02);
-  p = fma(p, r, 1.6666666666666666e-01);
-  p = fma(p, r, 0.5);
-  p = fma(p, r, 1.0);
-  p *= r;                                                       // exp(r) - 1
-  return ldexp(fma(t, p, t), n >> 6);
+// kexp_tab of N independent arguments, stage by stage across the elements (all reductions, then all table reads, then the polynomial)
+// instead of one ~13-deep dependent chain after the other: the same operations on every element, so the same bits, with N results in
+// flight under every f64 latency and one wait for the N table reads
+template <int N>
+__device__ __forceinline__ void kexp_tab_n(const double (&v)[N], double (&out)[N], const double* __restrict__ tab) {
+  double nd[N], r[N], t[N], p[N];
+  int n[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) nd[e] = rint(v[e] * 92.332482616893658);                    // 64 / ln2
+#pragma unroll
+  for (int e = 0; e < N; ++e) n[e] = int(nd[e]);
+#pragma unroll
+  for (int e = 0; e < N; ++e) r[e] = fma(nd[e], -1.08304246932675596327e-02, v[e]);       // ln2_hi / 64 (kexp's split, exact in binary)
+#pragma unroll
+  for (int e = 0; e < N; ++e) r[e] = fma(nd[e], -2.98158582698529328128e-12, r[e]);       // ln2_lo / 64
+#pragma unroll
+  for (int e = 0; e < N; ++e) t[e] = tab[n[e] & 63];
+#pragma unroll
+  for (int e = 0; e < N; ++e) p[e] = fma(r[e], 8.333333333333333e-03, 4.1666666666666664e-02);
+#pragma unroll
+  for (int e = 0; e < N; ++e) p[e] = fma(p[e], r[e], 1.6666666666666666e-01);
+#pragma unroll
+  for (int e = 0; e < N; ++e) p[e] = fma(p[e], r[e], 0.5);
+#pragma unroll
+  for (int e = 0; e < N; ++e) p[e] = fma(p[e], r[e], 1.0);
+#pragma unroll
+  for (int e = 0; e < N; ++e) p[e] *= r[e];                                               // exp(r) - 1
+#pragma unroll
+  for (int e = 0; e < N; ++e) out[e] = ldexp(fma(t[e], p[e], t[e]), n[e] >> 6);
+}
+
+__device__ __forceinline__ double kexp_tab(double v, const double* __restrict__ tab) {   // one definition of the operations: kexp_tab_n
+  const double a[1] = {v};
+  double o[1];
+  kexp_tab_n<1>(a, o, tab);
+  return o[0];
 }
 
 __device__ __forceinline__ double ksqrt(double v) { return sqrt(v); }
@@ -375,6 +399,10 @@ struct TileGemm {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     return (wave % WC) * (NJ * 16) + j * 16 + (lane & 15);
   }
+  // acc_row(i, r) - acc_row(0, 0) and acc_col(j) - acc_col(0): the same for every lane, so an epilogue can address all of a thread's
+  // elements as one per-lane offset plus compile-time displacements (Mfma16<T>::row: 4 r for f64, r for f32)
+  static constexpr int acc_row_rel(int i, int r) { return 32 * i + (sizeof(T) == 8 ? 4 * r : r); }
+  static constexpr int acc_col_rel(int j) { return 16 * j; }
 
   // Workgroup barriers a thread executes inside one call of the loops below - for kernels that keep PASSENGER waves at the loops'
   // barriers (prep.hip: the 512-thread fused factorisation kernels, whose waves 4-7 only join the block factorisation afterwards):

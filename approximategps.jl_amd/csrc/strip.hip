@@ -40,8 +40,11 @@ namespace {
 #ifndef SVGP_PREGEN_EXPTAB
 #define SVGP_PREGEN_EXPTAB 1   // the f64 SE pre-generation takes exp from a 64-entry table of 2^(j/64) in LDS + a degree-5 polynomial (0: kexp; A/B builds)
 #endif
-// (kexp_tab: device_common.hpp)
-template <typename T, int NT, int NTHR, int F, int DL>
+#ifndef SVGP_PREGEN_PIPE
+#define SVGP_PREGEN_PIPE 1   // forward one-launch strips, f64 SE, d <= 16: the pre-generation software-pipelined (0: block by block; A/B builds)
+#endif
+// (kexp_tab, kexp_tab_n: device_common.hpp)
+template <typename T, int NT, int NTHR, int F, int DL, bool PIPE = false>
 __device__ __forceinline__ void pregen_mfma(const T* __restrict__ xs, const T* __restrict__ zs, int d, int64_t Mp, int64_t M,
                                             double variance_d, T* __restrict__ work, const double* __restrict__ exptab = nullptr) {
   // DL <= 16: the strip's x fragments stay in registers for the whole pass (JT x KS values).  DL = 32 / 64 (round 4: d in (16, 64]
@@ -72,6 +75,100 @@ __device__ __forceinline__ void pregen_mfma(const T* __restrict__ xs, const T* _
     s += __shfl_xor(s, 16);
     s += __shfl_xor(s, 32);
     xn[jt] = fma(c1, s, c0);
+  }
+  if constexpr (XREG && PIPE && F == KSE && sizeof(T) == 8 && SVGP_PREGEN_EXPTAB != 0 && SVGP_PREGEN_PIPE != 0) {
+    // The f64 SE register body of the forward strips, software-pipelined (round 8).  The block-at-a-time body below fetches a block's
+    // z rows and uses them on the spot, follows each tile's two dependent MFMAs with the wait for their result, and runs a tile's four
+    // exponentials one dependent chain after the other.  Here the z rows of the wave's NEXT block travel under this block's
+    // arithmetic, the distance MFMAs of all JT tiles are issued together (KS rounds over JT independent accumulators) ahead of every
+    // exponential, and the exponentials proceed stage by stage across the 8 elements of two tiles (kexp_tab_n; all 4 JT at once
+    // spilled).  Every element sees the operations it saw before, in the same order: the bits are the same.
+    // Measured (profiles/round8/strip_outside_loops_ab.md): on its own this body makes the launch SLOWER (+0.33 ms at H); it pays only
+    // together with the lean panel epilogues (SVGP_EPI_LEAN) - do not keep the one without the other.
+    constexpr int EG = JT >= 2 ? 2 : 1;   // tiles per group of staged exponentials
+    static_assert(JT % EG == 0, "whole groups");
+    const int nblk = int(Mp / 16);
+    // unconditional loads (a feature row past d reads row 0 and is zeroed where it is USED): under a per-lane test the loads sit
+    // behind exec masks, and the wait for them lands right behind them
+    auto zfetch = [&](int kb, T (&zv)[KS]) {
+#pragma unroll
+      for (int q = 0; q < KS; ++q) {
+        const int f = 4 * q + g;
+        zv[q] = zs[int64_t(f < d ? f : 0) * Mp + int64_t(kb) * 16 + l15];
+      }
+    };
+    // distance MFMAs of one block from its z rows: all JT tiles together, KS rounds over JT independent accumulators
+    acc_t acc[JT];
+    auto distances = [&](const T (&zv)[KS]) {
+      T za[KS];
+      T s = T(0);
+#pragma unroll
+      for (int q = 0; q < KS; ++q) {
+        const T v = (4 * q + g < d) ? zv[q] : T(0);
+        za[q] = ascale * v;
+        s = fma(v, v, s);
+      }
+      s += __shfl_xor(s, 16);
+      s += __shfl_xor(s, 32);
+      s *= c1;
+      T zn[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) zn[r] = __shfl(s, M16::row(lane, r));
+#pragma unroll
+      for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[jt][r] = xn[jt] + zn[r];
+#pragma unroll
+      for (int q = 0; q < KS; ++q)
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) acc[jt] = M16::mma(za[q], xb[jt][q], acc[jt]);
+    };
+    T zv[KS];
+    zfetch(wave < nblk ? wave : 0, zv);
+    distances(zv);
+    for (int kb = wave; kb < nblk; kb += NW) {
+      const int64_t k0 = int64_t(kb) * 16;
+      const bool inside = __builtin_amdgcn_readfirstlane(int(k0 + 16 <= M)) != 0;   // as below
+      // z rows of the wave's next block: in flight under this block's exponentials (the last block fetches its own rows again and
+      // forms its distances a second time: no branch, nothing out of bounds, eight MFMAs per wave and strip)
+      zfetch(kb + NW < nblk ? kb + NW : kb, zv);
+      double out[JT * 4];
+#pragma unroll
+      for (int g0 = 0; g0 < JT; g0 += EG) {
+        double v[EG * 4], o[EG * 4];
+#pragma unroll
+        for (int e = 0; e < EG * 4; ++e) {
+          const double w = acc[g0 + e / 4][e % 4];
+          v[e] = w > c0 ? c0 : w;   // a NaN stays a NaN
+        }
+        kexp_tab_n<EG * 4>(v, o, exptab);
+#pragma unroll
+        for (int e = 0; e < EG * 4; ++e) out[g0 * 4 + e] = o[e];
+        __builtin_amdgcn_sched_barrier(0);   // one group's stages at a time: merged, the groups' live values no longer fit the registers
+      }
+      // The next block's MFMAs go out HERE, in front of this block's stores: their latency runs under the stores and the loop's
+      // scalar work, and no wait for an MFMA result is left.  It is also the one place where waiting for the z rows is free: loads
+      // and stores share one counter and return in any order among themselves, so a wait for a load waits for every store issued
+      // before it as well - here those of the block before (long done), at the top of the loop the ones issued just now.
+      distances(zv);
+      __builtin_amdgcn_sched_barrier(0);
+      if (inside) {
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) work[(k0 + M16::row(lane, r)) * NT + jt * 16 + l15] = out[jt * 4 + r];
+      } else {
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int64_t k = k0 + M16::row(lane, r);
+            work[k * NT + jt * 16 + l15] = (k < M) ? out[jt * 4 + r] : T(0);
+          }
+        asm volatile("" ::: "memory");   // keeps the two store forms apart (merged, the mask is back on every block)
+      }
+    }
+    return;
   }
   for (int kb = wave; kb < int(Mp / 16); kb += NW) {
     const int64_t k0 = int64_t(kb) * 16;
@@ -185,6 +282,9 @@ __device__ __forceinline__ void store_tile_point_major(const typename G::Acc& ac
 #ifndef SVGP_STRIP_PRIO
 #define SVGP_STRIP_PRIO 1
 #endif
+#ifndef SVGP_EPI_LEAN
+#define SVGP_EPI_LEAN 1   // forward calls without optional outputs: the panel epilogues as one straight block each (0: per-value tests; A/B builds)
+#endif
 template <bool ON>
 __device__ __forceinline__ void strip_prio(int strips_done) {
   if constexpr (ON && SVGP_STRIP_PRIO != 0) {
@@ -273,6 +373,13 @@ __global__ void __launch_bounds__(NTHR, MINW) strip_kernel(StripArgs a, int64_t 
   T* __restrict__ workK = (GRAD && !diag::ablate<256>) ? static_cast<T*>(a.work) + (int64_t(gridDim.x) + blockIdx.x) * Mp * NT : work;   // not const: SEG re-points it
   const int tid = threadIdx.x, lane = tid & 63;
   const typename G::QOff qoff = G::q_offsets(NT);           // per-thread byte offsets inside a scratch-strip tile
+  // The lean panel epilogues: the f64 forward one-launch kernels.  The fp32 strips (whose vector work co-executes with the partner
+  // workgroup's MFMAs) would pay for them with registers - the 32-point kernel 162 -> 169 VGPRs, three waves per SIMD -> two - and
+  // the value-and-gradient and segmented kernels keep their code as it is.
+  constexpr bool kLeanEpi = SVGP_EPI_LEAN != 0 && !GRAD && !SEG && sizeof(T) == 8;
+  // this thread's accumulator element (0, 0, 0) inside a panel's rows of the scratch strip and of mp, in bytes (the lean epilogues)
+  [[maybe_unused]] const uint32_t epi_woff = uint32_t((G::acc_row(0, 0) * NT + G::acc_col(0)) * int(sizeof(T)));
+  [[maybe_unused]] const uint32_t epi_moff = uint32_t(G::acc_row(0, 0) * int(sizeof(T)));
 
   // Strips are handed out dynamically (one atomic per strip): workgroups that run alone on their CU near the end
   // of the launch take more strips, which removes most of the ragged last round (C2: 3.05 rounds of strips).
@@ -350,11 +457,11 @@ __global__ void __launch_bounds__(NTHR, MINW) strip_kernel(StripArgs a, int64_t 
           else pregen_mfma<T, NT, NTHR, KM52, 64>(xs, zs, d, Mp, M, a.kp.variance, workK);
         }
       } else if (pre_dl == 8) {
-        if (family == KSE) pregen_mfma<T, NT, NTHR, KSE, 8>(xs, zs, d, Mp, M, a.kp.variance, workK, exptab);
+        if (family == KSE) pregen_mfma<T, NT, NTHR, KSE, 8, !GRAD && !SEG>(xs, zs, d, Mp, M, a.kp.variance, workK, exptab);
         else if (family == KM32) pregen_mfma<T, NT, NTHR, KM32, 8>(xs, zs, d, Mp, M, a.kp.variance, workK);
         else pregen_mfma<T, NT, NTHR, KM52, 8>(xs, zs, d, Mp, M, a.kp.variance, workK);
       } else if (pre_dl == 16) {
-        if (family == KSE) pregen_mfma<T, NT, NTHR, KSE, 16>(xs, zs, d, Mp, M, a.kp.variance, workK, exptab);
+        if (family == KSE) pregen_mfma<T, NT, NTHR, KSE, 16, !GRAD && !SEG>(xs, zs, d, Mp, M, a.kp.variance, workK, exptab);
         else if (family == KM32) pregen_mfma<T, NT, NTHR, KM32, 16>(xs, zs, d, Mp, M, a.kp.variance, workK);
         else pregen_mfma<T, NT, NTHR, KM52, 16>(xs, zs, d, Mp, M, a.kp.variance, workK);
       } else if (family == KSE) pregen(std::integral_constant<int, KSE>{});   // d > 16 in a kernel without the wide bodies (A/B builds)
@@ -395,6 +502,58 @@ __global__ void __launch_bounds__(NTHR, MINW) strip_kernel(StripArgs a, int64_t 
 
       SVGP_SSTAMP(3 + 3 * I);
       // epilogue: A_I -> scratch strip, column sums in fp64
+      if (kLeanEpi && a.A_out == nullptr && a.At_out == nullptr) {
+        // A call without the optional outputs (the ELBO and the marginals): ONE test per panel instead of two per value, which cut the
+        // epilogue into a basic block per value, and every address as a wave-uniform base + the thread's offset (epi_woff / epi_moff,
+        // formed once) + a displacement known at compile time, instead of 64-bit vector address arithmetic per value (~240 vector
+        // instructions per panel, now 20).  Same values into the same places, every sum in the same order.
+        // The m values of the panel's rows are fetched FIRST and all together, and the stores go LAST: loads and stores share one
+        // counter and return in any order among themselves, so with the two interleaved row by row (as below) every wait for an m
+        // value waited for the stores before it as well - sixteen round trips in a row per panel.
+        T* wI = work + int64_t(I) * NB * NT;
+        const T* mpI = mp + I * NB;
+        double mr[MI][4];
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            mr[i][r] = double(*reinterpret_cast<const T*>(reinterpret_cast<const char*>(mpI + G::acc_row_rel(i, r)) + epi_moff));
+        if constexpr (!diag::ablate<16>) {
+#pragma unroll
+          for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+              for (int j = 0; j < NJ; ++j) {
+                const double dv = double(acc.v[i][j][r]);
+                sA[j] = fma(dv, dv, sA[j]);
+              }
+#pragma unroll
+          for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+              for (int j = 0; j < NJ; ++j) sM[j] = fma(double(acc.v[i][j][r]), mr[i][r], sM[j]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+              for (int j = 0; j < NJ; ++j) sA[j] += double(acc.v[i][j][r]) + mr[i][r];
+        }
+        __builtin_amdgcn_sched_barrier(0);   // no store ahead of the last use of an m value
+        if constexpr (!diag::ablate<4>) {
+#pragma unroll
+          for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              T* wr = reinterpret_cast<T*>(reinterpret_cast<char*>(wI + G::acc_row_rel(i, r) * NT) + epi_woff);
+#pragma unroll
+              for (int j = 0; j < NJ; ++j) wr[G::acc_col_rel(j)] = acc.v[i][j][r];
+            }
+        }
+      } else {
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
 #pragma unroll
@@ -419,6 +578,7 @@ __global__ void __launch_bounds__(NTHR, MINW) strip_kernel(StripArgs a, int64_t 
             }
           }
         }
+      }
       }
       if constexpr (GRAD && !diag::ablate<32>) store_tile_point_major<G, T, NT, NTHR>(acc, smem, static_cast<T*>(a.At_out), c0, Mp, I * NB);
       __syncthreads();  // scratch rows of panel I visible to the whole workgroup
@@ -458,6 +618,17 @@ __global__ void __launch_bounds__(NTHR, MINW) strip_kernel(StripArgs a, int64_t 
                                                    smem);
       }
       SVGP_SSTAMP(61 + 2 * J);
+      if (kLeanEpi && a.C_out == nullptr && a.Ct_out == nullptr) {   // as in phase 1: one test per panel, one straight block
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+              const double dv = double(acc.v[i][j][r]);
+              sC[j] = fma(dv, dv, sC[j]);
+            }
+      } else
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
