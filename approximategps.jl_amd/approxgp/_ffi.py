@@ -201,6 +201,11 @@ SYMBOLS = {
     "svgp_nn_get_neighbors": (C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "svgp_nn_clear_neighbors": (C.c_int32, [_P, _P]),
     "svgp_nn_predict_local": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
+    "svgp_nn_set_noise": (C.c_int32, [_P, _P, C.POINTER(PointNoise)]),
+    "svgp_nn_set_mean": (C.c_int32, [_P, _P, C.POINTER(PointMean)]),
+    "svgp_nn_lml_grad_points": (C.c_int32, [_P, _P, C.POINTER(NNDesc), C.POINTER(C.c_double), C.POINTER(NNInfo), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(PointMeanGrad), C.POINTER(PointNoiseGrad)]),
     # the collapsed bound and the optimal q
     "svgp_collapsed_bound": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.POINTER(CollapsedTerms)]),
     "svgp_collapsed_q": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, C.POINTER(C.c_double)]),

@@ -9,14 +9,15 @@ import numpy as np
 
 from . import _ffi
 from . import laplace as _laplace
-from .gp import FiniteGP
+from .gp import Diagonal, FiniteGP
 from .kernels import unpack_kernel
 
 
 class NearestNeighbors:
     """NearestNeighbors(k) (NN:73-75): every point is conditioned on the k points before it in the given order.
     include_noise=False is the reference, which builds U from the kernel alone and ignores fx.Σy (NN:100-101); with
-    include_noise=True the isotropic fx.Σy joins every diagonal entry: the Vecchia approximation of logpdf(fx, y) itself.
+    include_noise=True the isotropic fx.Σy joins every diagonal entry: the Vecchia approximation of logpdf(fx, y) itself; per-point
+    noise variances v are fx = f(x, Diagonal(v)) (every v > 0: diag = min(v) and s = v - min(v) on the device).
     neighbors: None is the reference's window of the previous k points; "nearest" conditions every point on its k nearest
     predecessors, found on the device with the kernel's inverse lengthscales as the metric; an (n, min(k, n - 1)) integer array is
     the caller's own table (row i: distinct indices below i, the valid ones first, -1 after them).  Gradients are taken at the
@@ -37,18 +38,42 @@ class NearestNeighbors:
         self.neighbors = neighbors
 
 
-def _check_inputs(nn: NearestNeighbors, fx: FiniteGP, y):
-    """-> (diag, mean_const).  A CustomMean prior and, with include_noise, a non-isotropic Σy are not supported."""
+def _check_inputs(nn: NearestNeighbors, fx: FiniteGP, y, mean_offsets=None):
+    """-> (diag, mean_const, s or None, mu or None), before the GPU is touched.  A CustomMean prior is not supported: the values of a
+    mean function at x enter as mean_offsets= ((n,), added to the constant).  With include_noise Σy is isotropic or Diagonal(v):
+    diag = min(v) and the per-point variances s = v - min(v) above it (vfe.py's mapping)."""
     if fx.f.mean_fn is not None:
-        raise _ffi.UnsupportedError("NearestNeighbors takes a zero or constant prior mean, not a CustomMean")
-    diag = 0.0
+        raise _ffi.UnsupportedError("NearestNeighbors takes a zero or constant prior mean, not a CustomMean: pass the mean's values "
+                                    "at x as mean_offsets= (an (n,) array, added to the constant)")
+    diag, s = 0.0, None
     if nn.include_noise:
-        if not fx.is_isotropic():
-            raise _ffi.UnsupportedError("include_noise needs an isotropic fx.Σy")
-        diag = float(fx.Sigma_y)
+        if isinstance(fx.Sigma_y, Diagonal):
+            sy = np.asarray(fx.Sigma_y.diag, dtype=np.float64)
+            if sy.ndim != 1 or sy.shape[0] != fx.n:
+                raise ValueError(f"fx.Σy = Diagonal(v) needs a vector with one variance per point ({fx.n}); got shape {sy.shape}")
+            if not np.all((sy > 0.0) & np.isfinite(sy)):   # (NaN included)
+                raise ValueError("fx.Σy must be positive: every per-point noise variance must be > 0 and finite")
+            diag = float(sy.min())
+            s = sy - diag
+        elif not fx.is_isotropic():
+            raise _ffi.UnsupportedError("include_noise needs an isotropic fx.Σy, or per-point noise variances v as "
+                                        "fx = f(x, Diagonal(v))")
+        else:
+            diag = float(fx.Sigma_y)
     if np.shape(y)[0] != fx.n:
         raise ValueError("x and y lengths differ")
-    return diag, float(fx.f.mean_const)
+    mu = None
+    if mean_offsets is not None:
+        mu = np.asarray(mean_offsets, dtype=np.float64)
+        if mu.shape != (fx.n,):
+            raise ValueError(f"mean_offsets: one value per point ({fx.n}); got shape {mu.shape}")
+    return diag, float(fx.f.mean_const), s, mu
+
+
+def _flag(name, v):
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"{name} is True or False")
+    return bool(v)
 
 
 class DeviceNearestNeighbors:
@@ -101,6 +126,50 @@ class DeviceNearestNeighbors:
         self._check(self.ctx.lib.svgp_nn_fit(self.ctx.h, self.h, C.byref(desc), C.byref(lml), C.byref(info)), info)
         self.kb = min(int(desc.k), self.n - 1)
         return lml.value, info
+
+    def set_noise(self, s):
+        """per-point noise variances above the descriptor's diag (sigma_j^2 = diag + s_j): an (n,) numpy array or a contiguous device
+        tensor of the data dtype, copied into the handle; None removes them.  Discards the fit."""
+        self.kb = None
+        if s is None:
+            self.ctx.check(self.ctx.lib.svgp_nn_set_noise(self.ctx.h, self.h, None))
+            return
+        pn, _keep = _ffi.point_noise(s, self.n, self.dtype)
+        self.ctx.check(self.ctx.lib.svgp_nn_set_noise(self.ctx.h, self.h, C.byref(pn)))
+
+    def set_mean(self, mu):
+        """per-point prior-mean offsets (delta_j = y_j - mean_const - mu_j), as set_noise"""
+        self.kb = None
+        if mu is None:
+            self.ctx.check(self.ctx.lib.svgp_nn_set_mean(self.ctx.h, self.h, None))
+            return
+        pm, _keep = _ffi.point_mean(mu, self.n, self.dtype)
+        self.ctx.check(self.ctx.lib.svgp_nn_set_mean(self.ctx.h, self.h, C.byref(pm)))
+
+    def lml_grad_points(self, desc, mean_grad_out=None, noise_grad_out=None):
+        """-> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const", "mean" (n,), "noise" (n,)}, NNInfo): lml_grad's blocks,
+        d / d mean_const, d lml / d mu_j and d lml / d sigma_j^2.  mean_grad_out / noise_grad_out: contiguous device tensors of
+        the data dtype that receive the two vectors in place of host arrays.  Leaves the handle fitted at desc, as fit does."""
+        dt = _ffi.np_dtype(self.dtype)
+        outs, structs = {}, {}
+        for name, dst, cls in (("mean", mean_grad_out, _ffi.PointMeanGrad), ("noise", noise_grad_out, _ffi.PointNoiseGrad)):
+            if dst is None:
+                outs[name] = np.zeros(self.n, dtype=dt)
+                structs[name] = cls(_ffi._ptr(outs[name]), 0, 0)
+            else:
+                if not hasattr(dst, "data_ptr"):
+                    raise ValueError(f"{name}_grad_out: a contiguous device tensor of the data dtype with one entry per point")
+                outs[name] = dst
+                structs[name] = cls(C.c_void_p(_ffi.point_mean_grad_ptr(dst, self.n, self.dtype)), 1, 0)
+        lml, info, dv, dd, dm = C.c_double(), _ffi.NNInfo(), C.c_double(), C.c_double(), C.c_double()
+        dil = np.zeros(self.d)
+        self.kb = None
+        self._check(self.ctx.lib.svgp_nn_lml_grad_points(self.ctx.h, self.h, C.byref(desc), C.byref(lml), C.byref(info), C.byref(dv),
+                                                         dil.ctypes.data_as(C.POINTER(C.c_double)), C.byref(dd), C.byref(dm),
+                                                         C.byref(structs["mean"]), C.byref(structs["noise"])), info)
+        self.kb = min(int(desc.k), self.n - 1)
+        return lml.value, {"variance": dv.value, "inv_lengthscale": dil, "diag": dd.value, "mean_const": dm.value,
+                           "mean": outs["mean"], "noise": outs["noise"]}, info
 
     def set_neighbors(self, table):
         """condition point i on the points table[i, :] ((n, kb) integers: distinct indices below i, the valid ones first, -1 after
@@ -228,15 +297,15 @@ def _dtype_of(fx, dtype):
     return np.dtype(np.float32 if np.asarray(fx.x).dtype == np.float32 else np.float64)
 
 
-def _nn_kwargs(fn, kwargs):
-    extra = set(kwargs) - {"ctx", "dtype"}
+def _nn_kwargs(fn, kwargs, more=()):
+    extra = set(kwargs) - {"ctx", "dtype"} - set(more)
     if extra:
         raise TypeError(f"{fn}() with NearestNeighbors got unexpected keyword arguments {sorted(extra)}")
     return kwargs.get("ctx"), kwargs.get("dtype")
 
 
-def _device(nn: NearestNeighbors, fx: FiniteGP, y, ctx, dtype):
-    diag, mean_const = _check_inputs(nn, fx, y)   # before the GPU is touched
+def _device(nn: NearestNeighbors, fx: FiniteGP, y, ctx, dtype, mean_offsets=None):
+    diag, mean_const, s, mu = _check_inputs(nn, fx, y, mean_offsets)   # before the GPU is touched
     dev = DeviceNearestNeighbors(ctx or _ffi.default_context(), fx.x, y, _dtype_of(fx, dtype))
     desc, keep = dev.desc(fx.f.kernel, nn.k, diag, mean_const)
     try:
@@ -244,6 +313,10 @@ def _device(nn: NearestNeighbors, fx: FiniteGP, y, ctx, dtype):
             dev.build_neighbors(nn.k, keep)
         elif nn.neighbors is not None:
             dev.set_neighbors(nn.neighbors)
+        if s is not None:
+            dev.set_noise(s)
+        if mu is not None:
+            dev.set_mean(mu)
     except Exception:
         dev.free()
         raise
@@ -251,12 +324,12 @@ def _device(nn: NearestNeighbors, fx: FiniteGP, y, ctx, dtype):
 
 
 def approx_lml(approx, fx, y, **kwargs):
-    """approx_lml(nn::NearestNeighbors, fx, y; ctx, dtype) (NN:108-113); any other approximation: the Laplace / SVGP methods with
-    every keyword passed on exactly as given."""
+    """approx_lml(nn::NearestNeighbors, fx, y; ctx, dtype, mean_offsets) (NN:108-113); any other approximation: the Laplace / SVGP
+    methods with every keyword passed on exactly as given.  mean_offsets: the values of a prior mean function at x, (n,)."""
     if not isinstance(approx, NearestNeighbors):
         return _laplace.approx_lml(approx, fx, y, **kwargs)
-    ctx, dtype = _nn_kwargs("approx_lml", kwargs)
-    dev, desc, keep = _device(approx, fx, y, ctx, dtype)
+    ctx, dtype = _nn_kwargs("approx_lml", kwargs, ("mean_offsets",))
+    dev, desc, keep = _device(approx, fx, y, ctx, dtype, kwargs.get("mean_offsets"))
     try:
         return dev.lml(desc)[0]
     finally:
@@ -265,39 +338,69 @@ def approx_lml(approx, fx, y, **kwargs):
 
 def approx_lml_and_gradient(approx, fx, y, **kwargs):
     """NearestNeighbors: -> (lml, {"variance", "inv_lengthscale" (d,), "diag"}), the gradient with respect to the kernel parameters
-    and to the diagonal term (the noise variance under include_noise).  LaplaceApproximation: the Laplace method, unchanged."""
+    and to the diagonal term (the noise variance under include_noise).  wrt_noise=True adds "Sigma_y" (n,), d lml / d of every
+    point's noise variance ("diag" is its sum); wrt_mean=True adds "mean" (n,), d lml / d of the prior mean's value at every point,
+    and "mean_const", their sum.  noise_grad_out / mean_grad_out: contiguous device tensors of the data dtype that receive the two
+    vectors in place of host arrays.  mean_offsets as in approx_lml.  LaplaceApproximation: the Laplace method, unchanged."""
     if not isinstance(approx, NearestNeighbors):
         return _laplace.approx_lml_and_gradient(approx, fx, y, **kwargs)
-    ctx, dtype = _nn_kwargs("approx_lml_and_gradient", kwargs)
-    dev, desc, keep = _device(approx, fx, y, ctx, dtype)
+    ctx, dtype = _nn_kwargs("approx_lml_and_gradient", kwargs, ("mean_offsets", "wrt_noise", "wrt_mean", "noise_grad_out", "mean_grad_out"))
+    wrt_noise, wrt_mean = _flag("wrt_noise", kwargs.get("wrt_noise", False)), _flag("wrt_mean", kwargs.get("wrt_mean", False))
+    ngo, mgo = kwargs.get("noise_grad_out"), kwargs.get("mean_grad_out")
+    if ngo is not None and not wrt_noise:
+        raise ValueError("noise_grad_out needs wrt_noise=True")
+    if mgo is not None and not wrt_mean:
+        raise ValueError("mean_grad_out needs wrt_mean=True")
+    dev, desc, keep = _device(approx, fx, y, ctx, dtype, kwargs.get("mean_offsets"))
     try:
-        lml, dv, dil, dd, _info = dev.lml_grad(desc)
+        if not (wrt_noise or wrt_mean):
+            lml, dv, dil, dd, _info = dev.lml_grad(desc)
+            return lml, {"variance": dv, "inv_lengthscale": dil, "diag": dd}
+        lml, g, _info = dev.lml_grad_points(desc, mean_grad_out=mgo, noise_grad_out=ngo)
     finally:
         dev.free()
-    return lml, {"variance": dv, "inv_lengthscale": dil, "diag": dd}
+    grads = {"variance": g["variance"], "inv_lengthscale": g["inv_lengthscale"], "diag": g["diag"]}
+    if wrt_noise:
+        grads["Sigma_y"] = g["noise"]
+    if wrt_mean:
+        grads["mean"], grads["mean_const"] = g["mean"], g["mean_const"]
+    return lml, grads
 
 
 class NNPosteriorGP:
     """PosteriorGP(fx.f, (α, C = InvRoot(U), x, δ)) (NN:97-106) with B, F and α resident on the device.  Test inputs: a plain
     vector (d = 1) or a (d, n) ColVecs array."""
 
-    def __init__(self, nn: NearestNeighbors, fx: FiniteGP, y, ctx=None, dtype=None):
+    def __init__(self, nn: NearestNeighbors, fx: FiniteGP, y, ctx=None, dtype=None, mean_offsets=None):
         self.approx, self.prior = nn, fx.f
-        if not fx.is_isotropic():
-            raise _ffi.UnsupportedError("fx.Σy must be isotropic noise")
-        self.noise = float(fx.Sigma_y)
-        self.dev, desc, keep = _device(nn, fx, y, ctx, dtype)
+        if nn.include_noise and isinstance(fx.Sigma_y, Diagonal):
+            self.noise = None   # per-point noise: no single value for y*
+        elif not fx.is_isotropic():
+            raise _ffi.UnsupportedError("fx.Σy must be isotropic noise, or with include_noise=True per-point variances Diagonal(v)")
+        else:
+            self.noise = float(fx.Sigma_y)
+        self.dev, desc, keep = _device(nn, fx, y, ctx, dtype, mean_offsets)
         self.lml, self.info = self.dev.fit(desc)
 
-    def mean(self, x):
-        return self.dev.predict(x, mean=True, var=False)[0]
+    @staticmethod
+    def _offset(m, mean_offsets):
+        """a mean function's values at the test points, added on the host"""
+        if mean_offsets is None:
+            return m
+        mo = np.asarray(mean_offsets, dtype=m.dtype)
+        if mo.shape != m.shape:
+            raise ValueError(f"mean_offsets: one value per test point ({m.shape[0]}); got shape {mo.shape}")
+        return m + mo
+
+    def mean(self, x, mean_offsets=None):
+        return self._offset(self.dev.predict(x, mean=True, var=False)[0], mean_offsets)
 
     def var(self, x):
         return self.dev.predict(x, mean=False, var=True)[1]
 
-    def mean_and_var(self, x):
+    def mean_and_var(self, x, mean_offsets=None):
         m, v, _ = self.dev.predict(x, mean=True, var=True)
-        return m, v
+        return self._offset(m, mean_offsets), v
 
     def cov(self, x, y=None):
         if y is None:
@@ -311,30 +414,56 @@ class NNPosteriorGP:
     def factors(self):
         return self.dev.factors()
 
-    def _lik_predictive(self, x, y, want):
-        """the Gaussian observation model y = f + N(0, fx.Σy) on the latent predictions, through the array form the SVGP and Laplace
-        posteriors share (svgp_lik_predictive): one definition of the three"""
-        if not self.noise > 0:
-            raise ValueError("predictions of y need observation noise fx.Σy > 0")
+    def _lik_predictive(self, x, y, want, noise=None):
+        """the Gaussian observation model y = f + N(0, noise) on the latent predictions, through the array form the SVGP and Laplace
+        posteriors share (svgp_lik_predictive): one definition of the three.  noise: the test points' observation noise variance, a
+        scalar or (n,); the posterior's own fx.Σy by default, which a per-point-noise posterior does not have."""
+        if noise is None:
+            if self.noise is None:
+                raise ValueError("the posterior has per-point noise fx.Σy = Diagonal(v): pass noise=, the observation noise variance of "
+                                 "the test points (a scalar or an (n,) array)")
+            if not self.noise > 0:
+                raise ValueError("predictions of y need observation noise fx.Σy > 0")
+            m, v = self.mean_and_var(x)
+            return _ffi.lik_predictive(self.dev.ctx, _ffi.LIK_GAUSSIAN, self.noise, 0, m, v, y, want=want)
+        nv = np.asarray(noise, dtype=np.float64)
+        xa = np.asarray(x)
+        n = xa.shape[0] if xa.ndim == 1 else xa.shape[-1]
+        if nv.ndim > 1 or (nv.ndim == 1 and nv.shape[0] != n):
+            raise ValueError("noise: a scalar or one variance per test point")
+        if not np.all(nv > 0):
+            raise ValueError("predictions of y need observation noise > 0")
         m, v = self.mean_and_var(x)
-        return _ffi.lik_predictive(self.dev.ctx, _ffi.LIK_GAUSSIAN, self.noise, 0, m, v, y, want=want)
+        if nv.ndim == 0:
+            return _ffi.lik_predictive(self.dev.ctx, _ffi.LIK_GAUSSIAN, float(nv), 0, m, v, y, want=want)
+        # one variance per test point: the Gaussian closed forms, O(n) on the host in fp64
+        m64, yv = np.asarray(m, dtype=np.float64), np.asarray(v, dtype=np.float64) + nv
+        out = {"ymean": m64, "yvar": yv}
+        if y is not None:
+            yy = np.asarray(y, dtype=np.float64).reshape(-1)
+            if yy.shape != (n,):
+                raise ValueError("y: one observation per test point")
+            out["lpd"] = -0.5 * (np.log(2.0 * np.pi * yv) + (yy - m64) ** 2 / yv)
+        return {k: out[k] for k in want}
 
-    def predict_y(self, x):
+    def predict_y(self, x, noise=None):
         """(E[y*], Var[y*]) = (mean, var + noise)"""
-        r = self._lik_predictive(x, None, ("ymean", "yvar"))
+        r = self._lik_predictive(x, None, ("ymean", "yvar"), noise)
         return r["ymean"], r["yvar"]
 
-    def log_predictive_density(self, x, y):
-        """log N(y*_i; mean_i, var_i + noise) per point"""
-        return self._lik_predictive(x, y, ("lpd",))["lpd"]
+    def log_predictive_density(self, x, y, noise=None):
+        """log N(y*_i; mean_i, var_i + noise_i) per point"""
+        return self._lik_predictive(x, y, ("lpd",), noise)["lpd"]
 
-    def local_mean_and_var(self, x, k=None):
+    def local_mean_and_var(self, x, k=None, mean_offsets=None):
         """nearest-neighbour kriging (GpGp `predictions`): every test point conditioned on its k nearest observed points, k
-        defaulting to the approximation's; the latent mean and variance, test points independent of each other"""
-        return self.dev.predict_local(x, self.approx.k if k is None else k)
+        defaulting to the approximation's; the latent mean and variance, test points independent of each other.  The blocks carry
+        the posterior's per-point noise variances and mean offsets."""
+        m, v = self.dev.predict_local(x, self.approx.k if k is None else k)
+        return self._offset(m, mean_offsets), v
 
-    def local_mean(self, x, k=None):
-        return self.local_mean_and_var(x, k)[0]
+    def local_mean(self, x, k=None, mean_offsets=None):
+        return self.local_mean_and_var(x, k, mean_offsets)[0]
 
     def local_var(self, x, k=None):
         return self.local_mean_and_var(x, k)[1]
@@ -344,6 +473,6 @@ def posterior(approx, *args, **kwargs):
     """posterior(nn::NearestNeighbors, fx, y) (NN:97-106); any other approximation: the Laplace / SVGP methods."""
     if isinstance(approx, NearestNeighbors):
         fx, y = args
-        ctx, dtype = _nn_kwargs("posterior", kwargs)
-        return NNPosteriorGP(approx, fx, y, ctx=ctx, dtype=dtype)
+        ctx, dtype = _nn_kwargs("posterior", kwargs, ("mean_offsets",))
+        return NNPosteriorGP(approx, fx, y, ctx=ctx, dtype=dtype, mean_offsets=kwargs.get("mean_offsets"))
     return _laplace.posterior(approx, *args, **kwargs)

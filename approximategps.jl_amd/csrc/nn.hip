@@ -25,6 +25,9 @@
 //   local predictions   nearest-neighbour kriging: per test point the min(k, N) nearest training points (nn_query_search_kernel: one
 //                    wavefront per query, 16 per workgroup, double-buffered 64-wide LDS tiles), then the point kernel's sweep over the
 //                    gathered block with the query read from the test array (nn_local_kernel); rounds of 32768 test points
+//   per-point vectors   svgp_nn_set_noise / svgp_nn_set_mean keep N noise variances s and N mean offsets mu on the handle: C carries
+//                    diag(T(diag) + s), delta = y - mean_const - mu.  With either set, and in svgp_nn_lml_grad_points (s_bar, mean_bar =
+//                    alpha), the point and local kernels are the siblings of nn_points.hip; without, the ones below, untouched
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -39,6 +42,8 @@
 #include "ctx.hpp"
 #include "device_common.hpp"
 #include "kernels.hpp"
+#include "nn_common.hpp"
+#include "nn_points.hpp"
 
 namespace svgp {
 namespace {
@@ -55,76 +60,12 @@ namespace {
   } while (0)
 
 constexpr int kNnMaxK = 64;        // one lane per neighbour
-constexpr int kNnNone = 0x7f7f7f7f;   // "no bad point": what hipMemsetAsync(0x7f) leaves in the first-bad-point word
 constexpr int kNnSlots = 3;        // per point: log F, r^2 / F, (F <= 0)
-constexpr int kNnGradSlots = 5;    // ... + d / d variance, d / d diag; the d inverse lengthscales follow
 constexpr int kNnRows = 2048;      // most rows of one V tile
 constexpr int64_t kNnTileElems = int64_t(1) << 23;   // elements of one V tile (rows x padded columns): the workspace rule
 constexpr int64_t kNnMaxCov = 4096;                  // most test points of cov / cross-cov
 constexpr int64_t kNnMaxPred = int64_t(1) << 17;     // most test points of one mean / var call (64-row tiles at the workspace rule)
 constexpr int64_t kNnLocalChunk = int64_t(1) << 15;  // test points of one round of svgp_nn_predict_local: its whole workspace
-
-struct NnParams {
-  int family, d, k;   // k: effective neighbour count min(k, N - 1)
-  int64_t n, ldx;
-  double variance, diag, mean_const;
-  double invl[SVGP_MAX_D];
-};
-
-// lane `l` (uniform) of v, through scalar registers
-__device__ __forceinline__ float nn_rl(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ double nn_rl(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double nn_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// f(integral_constant<I>) for I = I0 .. N - 1: the steps of the factorisation index the register array, so their number is a
-// compile-time constant whatever the unroller's budget
-template <int I, int N, typename Fn>
-__device__ __forceinline__ void nn_static_for(Fn&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    nn_static_for<I + 1, N>(f);
-  }
-}
-
-// d kappa / d r2 of the unit-variance kernel
-template <typename T>
-__device__ __forceinline__ T nn_dkappa(int family, T r2) {
-  if (family == KSE) return T(-0.5) * kexp(T(-0.5) * r2);
-  if (family == KM32) return T(-1.5) * kexp(-T(1.7320508075688772935) * ksqrt(r2));
-  const T s = T(2.2360679774997896964) * ksqrt(r2);
-  return -T(5.0 / 6.0) * (T(1) + s) * kexp(-s);
-}
-
-// A[q] = |s_q - s_j|^2 for the neighbours q, j = lane (s = x .* invl), cr2 = |s_i - s_j|^2; inactive lanes carry s = 0.
-// The lane's neighbour is point base + lane (the window), or with G point `src` (a row of the neighbour table)
-template <typename T, int KB, bool G = false>
-__device__ __forceinline__ void nn_dist2(const NnParams& P, const T* __restrict__ x, int64_t base, int64_t i, int lane, int m, T (&A)[KB],
-                                         T& cr2, int64_t src = 0) {
-#pragma unroll
-  for (int q = 0; q < KB; ++q) A[q] = T(0);
-  cr2 = T(0);
-  for (int f = 0; f < P.d; ++f) {
-    const T il = T(P.invl[f]);
-    const T xj = lane < m ? x[int64_t(f) * P.ldx + (G ? src : base + lane)] * il : T(0);
-    const T dc = xj - x[int64_t(f) * P.ldx + i] * il;
-    cr2 = fma(dc, dc, cr2);
-#pragma unroll
-    for (int g = 0; g < KB / 8; ++g)
-      if (g * 8 < m) {
-#pragma unroll
-        for (int q = g * 8; q < g * 8 + 8; ++q) {
-          const T df = nn_rl(xj, q) - xj;
-          A[q] = fma(df, df, A[q]);
-        }
-      }
-  }
-}
 
 // MODE 0: the lml slots.  MODE 1: + b_i, F_i, r_i / F_i (fit).  MODE 2: + the gradient slots.
 // G (gathered): lane t conditions on point nbr(i, t) of the neighbour table (N x P.k column-major, the valid entries first, -1 after
@@ -270,30 +211,8 @@ __device__ __forceinline__ void nn_point_body(const NnParams& P, const T* __rest
 // ---- the sweep of a local prediction: nn_point_body's distances, block and factorisation with the query read from a second array.
 // A sibling, not a shared body: with the three pieces below factored out of nn_point_body its instantiations did not keep their
 // register counts (f64 KB = 16 value 74 -> 84 VGPRs, 6 -> 5 waves per SIMD; the fp32 ones moved by up to 110), so nn_point_body stays
-// as it was, and the arithmetic and its order are repeated here line for line.
-// nn_dist2 with the lane's neighbour point `src` of x and the query column i of xq (ld ldq)
-template <typename T, int KB>
-__device__ __forceinline__ void nn_dist2_query(const NnParams& P, const T* __restrict__ x, const T* __restrict__ xq, int64_t ldq, int64_t i,
-                                               int lane, int m, T (&A)[KB], T& cr2, int64_t src) {
-#pragma unroll
-  for (int q = 0; q < KB; ++q) A[q] = T(0);
-  cr2 = T(0);
-  for (int f = 0; f < P.d; ++f) {
-    const T il = T(P.invl[f]);
-    const T xj = lane < m ? x[int64_t(f) * P.ldx + src] * il : T(0);
-    const T dc = xj - xq[int64_t(f) * ldq + i] * il;
-    cr2 = fma(dc, dc, cr2);
-#pragma unroll
-    for (int g = 0; g < KB / 8; ++g)
-      if (g * 8 < m) {
-#pragma unroll
-        for (int q = g * 8; q < g * 8 + 8; ++q) {
-          const T df = nn_rl(xj, q) - xj;
-          A[q] = fma(df, df, A[q]);
-        }
-      }
-  }
-}
+// as it was, and the arithmetic and its order are repeated line for line (nn_dist2_query and nn_factor in nn_common.hpp, nn_block here).
+// The same rule made the point kernels with per-point noise variances and mean offsets a second sibling, in nn_points.hip.
 // The block from its squared distances: C = k(ns, ns) + diag I on the m x m corner, identity on the padding; c = k(ns, x_i)
 template <typename T, int KB>
 __device__ __forceinline__ void nn_block(const NnParams& P, int lane, int m, T (&A)[KB], T& c) {
@@ -313,38 +232,6 @@ __device__ __forceinline__ void nn_block(const NnParams& P, int lane, int m, T (
     }
   }
   c = act ? kappa(P.family, c, variance) : T(0);
-}
-
-// The right-looking factorisation of the block with c and dd = delta_ns riding along: F -= l'l, r -= l'z (fp64), lane p keeps
-// 1 / L[p][p], l_p, z_p.  -> a pivot was "not positive": at or below floor_
-template <typename T, int KB>
-__device__ __forceinline__ bool nn_factor(int lane, int m, double floor_, T (&A)[KB], T& c, T& dd, double& F, double& r, T& myrs, T& lme,
-                                          T& zme) {
-  bool isbad = false;
-  nn_static_for<0, KB>([&](auto pc) __attribute__((always_inline)) {
-    constexpr int p = decltype(pc)::value;
-    if (p < m) {
-      const T piv = nn_rl(A[p], p);
-      if (!(double(piv) > floor_)) isbad = true;
-      const T rs = T(1) / ksqrt(piv);
-      const T lj = A[p] * rs;                     // L[j][p] for the lanes j >= p
-      const T ljm = lane > p ? lj : T(0);
-      A[p] = lane >= p ? lj : A[p];               // lanes j < p: column j of the Schur complement stays (scaled in the back-substitution)
-      const T lm = nn_rl(c, p) * rs, zp = nn_rl(dd, p) * rs;
-      F = fma(-double(lm), double(lm), F);
-      r = fma(-double(lm), double(zp), r);
-      if (lane == p) { myrs = rs; lme = lm; zme = zp; }
-      c = fma(-lm, ljm, c);
-      dd = fma(-zp, ljm, dd);
-#pragma unroll
-      for (int g = (p + 1) / 8; g < KB / 8; ++g)
-        if (g * 8 < m) {
-#pragma unroll
-          for (int q = (g * 8 > p + 1 ? g * 8 : p + 1); q < g * 8 + 8; ++q) A[q] = fma(-nn_rl(lj, q), ljm, A[q]);
-        }
-    }
-  });
-  return isbad;
 }
 
 template <typename T, int KB, int MODE>
@@ -795,6 +682,12 @@ struct svgp_nn {
   int tab_kb = -1;
   DevBuf nbr;        // (int) N x tab_kb column-major
   DevBuf roff, rv;   // (int64) the reverse lists: offsets [N + 1], and the places i + t N in B of the pairs with nbr(i, t) = j
+  // per-point noise variances and prior-mean offsets (svgp_nn_set_noise / svgp_nn_set_mean): snapshots in the data dtype, and the
+  // NaN-propagating minimum of s, reduced on the device at set time.  With either set the point kernels are those of nn_points.hip
+  DevBuf sv, mu;
+  bool have_s = false, have_mu = false;
+  double s_min = 0;
+  DevBuf Qd, gF, sbar, gout;   // svgp_nn_lml_grad_points: the per-pair terms (N x kb, data dtype), gF_i and s_bar (fp64), the cast outputs
 };
 
 namespace {
@@ -850,21 +743,42 @@ void nn_launch_point(hipStream_t s, const NnParams& P, const svgp_nn* nn, int S)
   else hipLaunchKernelGGL((nn_point_kernel<T, 64, MODE>), grid, block, 0, s, P, x, y, terms, S, bad, Bd, Fd, rF);
 }
 
-// mode 0: lml; 1: fit; 2: lml and gradient.  out[S] = the reduced slots
+// a noise vector is set: the smallest variance T(diag) + min s of the call's descriptor, before any data pass (svgp_cg_set_noise's rule)
+int nn_noise_check(svgp_ctx* ctx, const svgp_nn* nn, const svgp_nn_desc* ds) {
+  if (!nn->have_s) return SVGP_OK;
+  const double lo = nn->dtype == SVGP_F64 ? ds->diag + nn->s_min : double(float(ds->diag) + float(nn->s_min));
+  if (lo != lo) return fail(ctx, SVGP_NOT_POSDEF, "NearestNeighbors per-point noise: a variance diag + s_i is NaN");
+  if (lo < 0) return fail(ctx, SVGP_NOT_POSDEF, "NearestNeighbors per-point noise: a variance diag + s_i is negative");
+  return SVGP_OK;
+}
+
+// mode 0: lml; 1: fit; 2: lml and gradient; 3: lml, gradient, fit, s_bar and the sum of alpha (svgp_nn_lml_grad_points).
+// out[S] = the reduced slots (mode 3: out[S] = sum_j alpha_j after them)
 int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double* lml_out, svgp_nn_info* info, double* out) {
   int rc = nn_check_desc(ctx, nn, ds);
   if (rc) return rc;
   if (!lml_out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  const bool fits = mode == 1 || mode == 3;
+  if ((rc = nn_noise_check(ctx, nn, ds)) != SVGP_OK) {   // before the data pass
+    if (fits) nn->have_fit = false;
+    *lml_out = NAN;
+    if (info) {
+      std::memset(info, 0, sizeof(*info));
+      info->lml = NAN;
+    }
+    return rc;
+  }
   HIPC(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const NnParams P = nn_params(nn, ds);
   const int64_t N = nn->N;
-  const int S = mode == 2 ? kNnGradSlots + nn->d : kNnSlots;
+  const int S = mode >= 2 ? kNnGradSlots + nn->d : kNnSlots;
   const int nb = int(std::min<int64_t>(1024, (N + 1023) / 1024));
   const int64_t chunk = (N + nb - 1) / nb;
+  const bool vec = nn->have_s || nn->have_mu || mode == 3;   // the kernels of nn_points.hip
   rc = nn->terms.reserve(ctx, size_t(N) * S * 8, "the NearestNeighbors per-point terms");
   if (rc == SVGP_OK) rc = nn->part.reserve(ctx, size_t(nb) * S * 8, "the NearestNeighbors block partials");
-  if (rc == SVGP_OK && mode == 1) {
+  if (rc == SVGP_OK && fits) {
     nn->have_fit = false;
     rc = nn->Bd.reserve(ctx, std::max<size_t>(size_t(N) * P.k * nn->es, 8), "the NearestNeighbors rows b_i");
     if (rc == SVGP_OK) rc = nn->Fd.reserve(ctx, size_t(N) * 8, "F");
@@ -872,18 +786,31 @@ int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double
     if (rc == SVGP_OK) rc = nn->alpha.reserve(ctx, size_t(N) * 8, "alpha");
     if (rc == SVGP_OK && P.k > 0) HIPC(ctx, hipMemsetAsync(nn->Bd.p, 0, size_t(N) * P.k * nn->es, s));   // the ramp-up rows i < k are shorter
   }
+  if (rc == SVGP_OK && mode == 3) {
+    rc = nn->Qd.reserve(ctx, std::max<size_t>(size_t(N) * P.k * nn->es, 8), "the NearestNeighbors per-pair gradient terms");
+    if (rc == SVGP_OK) rc = nn->gF.reserve(ctx, size_t(N) * 8, "gF");
+    if (rc == SVGP_OK) rc = nn->sbar.reserve(ctx, size_t(N) * 8, "s_bar");
+    if (rc == SVGP_OK && P.k > 0) HIPC(ctx, hipMemsetAsync(nn->Qd.p, 0, size_t(N) * P.k * nn->es, s));
+  }
   if (rc) return rc;
   HIPC(ctx, hipMemsetAsync(nn->bad.p, 0x7f, sizeof(int), s));   // kNnNone
-  NN_DISPATCH(nn->dtype, T, {
-    if (mode == 0) nn_launch_point<T, 0>(s, P, nn, S);
-    else if (mode == 1) nn_launch_point<T, 1>(s, P, nn, S);
-    else nn_launch_point<T, 2>(s, P, nn, S);
-  });
+  if (vec) {
+    const NnPointArgs a{nn->data->x.p, nn->data->y.p, nn->have_s ? nn->sv.p : nullptr, nn->have_mu ? nn->mu.p : nullptr,
+                        nn->terms.as<double>(), S, nn->bad.as<int>(), nn->Bd.p, nn->Fd.as<double>(), nn->rF.as<double>(), nn->Qd.p,
+                        nn->gF.as<double>(), nn->tab_kb >= 0 ? nn->nbr.as<int>() : nullptr};
+    launch_nn_point_v(nn->dtype, mode, s, P, a);
+  } else {
+    NN_DISPATCH(nn->dtype, T, {
+      if (mode == 0) nn_launch_point<T, 0>(s, P, nn, S);
+      else if (mode == 1) nn_launch_point<T, 1>(s, P, nn, S);
+      else nn_launch_point<T, 2>(s, P, nn, S);
+    });
+  }
   KCHECK(ctx, "nn_point");
   hipLaunchKernelGGL(nn_reduce1_kernel, dim3((unsigned)nb, (unsigned)S), dim3(k256), 0, s, (const double*)nn->terms.as<double>(), N, S, chunk,
                      nn->part.as<double>());
   hipLaunchKernelGGL(nn_reduce2_kernel, dim3((unsigned)S), dim3(k256), 0, s, (const double*)nn->part.as<double>(), nb, nn->res.as<double>());
-  if (mode == 1)
+  if (fits)
     NN_DISPATCH(nn->dtype, T, {
       if (nn->tab_kb >= 0)
         hipLaunchKernelGGL(nn_alpha_tab_kernel<T>, dim3(nblk(N, 4)), dim3(k256), 0, s, (const T*)nn->Bd.p, (const double*)nn->rF.as<double>(), N,
@@ -892,9 +819,17 @@ int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double
         hipLaunchKernelGGL(nn_alpha_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, (const T*)nn->Bd.p, (const double*)nn->rF.as<double>(), N, P.k,
                            nn->alpha.as<double>());
     });
+  if (mode == 3) {   // s_bar by the same gathers, and the sum of alpha in the fixed order of the slots (the partials are free again)
+    const bool tab = nn->tab_kb >= 0;
+    launch_nn_sbar(nn->dtype, s, nn->Qd.p, nn->gF.as<double>(), N, P.k, tab ? nn->roff.as<int64_t>() : nullptr,
+                   tab ? nn->rv.as<int64_t>() : nullptr, nn->sbar.as<double>());
+    hipLaunchKernelGGL(nn_reduce1_kernel, dim3((unsigned)nb, 1u), dim3(k256), 0, s, (const double*)nn->alpha.as<double>(), N, 1, chunk,
+                       nn->part.as<double>());
+    hipLaunchKernelGGL(nn_reduce2_kernel, dim3(1u), dim3(k256), 0, s, (const double*)nn->part.as<double>(), nb, nn->res.as<double>() + S);
+  }
   KCHECK(ctx, "nn_reduce");
   int badv = 0;
-  HIPC(ctx, hipMemcpyAsync(out, nn->res.p, size_t(S) * 8, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(out, nn->res.p, size_t(S + (mode == 3 ? 1 : 0)) * 8, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipMemcpyAsync(&badv, nn->bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   const bool isbad = badv != kNnNone;
@@ -908,10 +843,38 @@ int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double
   }
   if (isbad)
     return fail(ctx, SVGP_NOT_POSDEF, "NearestNeighbors: the block or F of point " + std::to_string(badv) + " is not positive");
-  if (mode == 1) {
+  if (fits) {
     nn->P = P;
     nn->have_fit = true;
   }
+  return SVGP_OK;
+}
+
+// a snapshot of N values of the data dtype from host or device memory into buf; src null: the vector is removed.  Either way the
+// fit is discarded, as a table call does
+int nn_set_vector(svgp_ctx* ctx, svgp_nn* nn, const void* src, bool given, int32_t on_device, int32_t reserved, DevBuf& buf, bool& have,
+                  const char* what) {
+  if (given && !src) return fail(ctx, SVGP_INVALID_ARG, std::string("null ") + what);
+  if (given && on_device != 0 && on_device != 1) return fail(ctx, SVGP_INVALID_ARG, "on_device must be 0 or 1");
+  if (given && reserved != 0) return fail(ctx, SVGP_INVALID_ARG, "reserved must be 0");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  nn->have_fit = false;
+  have = false;   // (a failure below leaves the handle without the vector)
+  if (!given) return SVGP_OK;
+  const size_t nb = size_t(nn->N) * nn->es;
+  const int rc = buf.reserve(ctx, nb, what);
+  if (rc) return rc;
+  HIPC(ctx, hipMemcpyAsync(buf.p, src, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipStreamSynchronize(s));   // the caller's memory is the caller's again
+  have = true;
+  return SVGP_OK;
+}
+
+int check_point_out(svgp_ctx* ctx, const void* p, int32_t on_device, int32_t reserved, const char* what) {
+  if (!p) return fail(ctx, SVGP_INVALID_ARG, std::string("null ") + what);
+  if ((on_device != 0 && on_device != 1) || reserved != 0)
+    return fail(ctx, SVGP_INVALID_ARG, std::string(what) + ": on_device must be 0 or 1 and reserved 0");
   return SVGP_OK;
 }
 
@@ -1134,7 +1097,7 @@ int32_t svgp_nn_create(svgp_ctx* ctx, const svgp_data* data, svgp_nn** out) {
   nn->d = data->d;
   nn->N = data->n;
   nn->es = data->dtype == SVGP_F64 ? 8 : 4;
-  hipError_t e = nn->res.alloc((kNnGradSlots + SVGP_MAX_D) * 8);
+  hipError_t e = nn->res.alloc((kNnGradSlots + SVGP_MAX_D + 1) * 8);   // the slots' sums, then the sum of alpha
   if (e == hipSuccess) e = nn->bad.alloc(256);
   if (e != hipSuccess) {
     delete nn;
@@ -1173,6 +1136,71 @@ int32_t svgp_nn_lml_grad(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, d
   *d_variance = out[3];
   if (d_diag) *d_diag = out[4];
   for (int f = 0; f < nn->d; ++f) d_inv_lengthscale[f] = out[kNnGradSlots + f];
+  return SVGP_OK;
+}
+
+int32_t svgp_nn_set_noise(svgp_ctx* ctx, svgp_nn* nn, const svgp_point_noise* pn) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  int rc = nn_set_vector(ctx, nn, pn ? pn->s : nullptr, pn != nullptr, pn ? pn->on_device : 0, pn ? pn->reserved : 0, nn->sv, nn->have_s,
+                         "noise vector");
+  if (rc || !pn) return rc;
+  nn->have_s = false;
+  hipStream_t s = ctx->stream;
+  launch_cg_noise_min(nn->dtype, s, nn->sv.p, nn->N, nn->res.as<double>());   // NaN-propagating, one workgroup, a fixed tree
+  KCHECK(ctx, "nn (noise minimum)");
+  double lo = 0;
+  HIPC(ctx, hipMemcpyAsync(&lo, nn->res.p, 8, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  nn->s_min = lo;
+  nn->have_s = true;
+  return SVGP_OK;
+}
+
+int32_t svgp_nn_set_mean(svgp_ctx* ctx, svgp_nn* nn, const svgp_point_mean* pm) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  return nn_set_vector(ctx, nn, pm ? pm->mu : nullptr, pm != nullptr, pm ? pm->on_device : 0, pm ? pm->reserved : 0, nn->mu, nn->have_mu,
+                       "mean offsets");
+}
+
+int32_t svgp_nn_lml_grad_points(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info,
+                                double* d_variance, double* d_inv_lengthscale, double* d_diag, double* d_mean_const,
+                                svgp_point_mean_grad* gpm, svgp_point_noise_grad* gpn) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  int rc = nn_check_desc(ctx, nn, desc);
+  if (rc) return rc;
+  if (!d_variance || !d_inv_lengthscale) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (gpm && (rc = check_point_out(ctx, gpm->mu_bar, gpm->on_device, gpm->reserved, "mean gradient output")) != SVGP_OK) return rc;
+  if (gpn && (rc = check_point_out(ctx, gpn->s_bar, gpn->on_device, gpn->reserved, "noise gradient output")) != SVGP_OK) return rc;
+  double out[kNnGradSlots + SVGP_MAX_D + 1];
+  rc = nn_eval(ctx, nn, desc, 3, lml_out, info, out);
+  if (rc) return rc;
+  *d_variance = out[3];
+  if (d_diag) *d_diag = out[4];
+  for (int f = 0; f < nn->d; ++f) d_inv_lengthscale[f] = out[kNnGradSlots + f];
+  if (d_mean_const) *d_mean_const = out[kNnGradSlots + nn->d];
+  if (!gpm && !gpn) return SVGP_OK;
+  hipStream_t s = ctx->stream;
+  const int64_t N = nn->N;
+  const size_t nb = size_t(N) * nn->es;
+  rc = nn->gout.reserve(ctx, nb, "the per-point gradient in the data dtype");
+  if (rc) return rc;
+  for (int q = 0; q < 2; ++q) {   // fp64 sums, rounded once to the data dtype: into the caller's device memory, or staged for the host's
+    void* dst = q ? (gpn ? gpn->s_bar : nullptr) : (gpm ? gpm->mu_bar : nullptr);
+    if (!dst) continue;
+    const bool dev = q ? gpn->on_device != 0 : gpm->on_device != 0;
+    NN_DISPATCH(nn->dtype, T, {
+      hipLaunchKernelGGL(nn_cast_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, (const double*)(q ? nn->sbar : nn->alpha).as<double>(), N, 0.0, 1.0,
+                         (T*)(dev ? dst : nn->gout.p));
+    });
+    KCHECK(ctx, "nn_cast");
+    if (!dev) {
+      HIPC(ctx, hipMemcpyAsync(dst, nn->gout.p, nb, hipMemcpyDeviceToHost, s));
+      HIPC(ctx, hipStreamSynchronize(s));   // gout is reused by the second vector
+    }
+  }
   return SVGP_OK;
 }
 
@@ -1274,7 +1302,10 @@ int32_t svgp_nn_predict_local(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_
       const dim3 grid(nblk(c, 4)), block(k256);
       const int* nbr = tab.as<int>();
       int* bad = nn->bad.as<int>();
-      if (kq <= 16) hipLaunchKernelGGL((nn_local_kernel<T, 16>), grid, block, 0, s, P, x, y, q, c, c, q0, nbr, bad, (T*)mo.p, (T*)vo.p);
+      if (nn->have_s || nn->have_mu)   // the fit's vectors: setting one discards the fit, so these are the ones it was made with
+        launch_nn_local_v(nn->dtype, s, P, x, y, nn->have_s ? nn->sv.p : nullptr, nn->have_mu ? nn->mu.p : nullptr, q, c, c, q0, nbr, bad,
+                          mo.p, vo.p);
+      else if (kq <= 16) hipLaunchKernelGGL((nn_local_kernel<T, 16>), grid, block, 0, s, P, x, y, q, c, c, q0, nbr, bad, (T*)mo.p, (T*)vo.p);
       else if (kq <= 32) hipLaunchKernelGGL((nn_local_kernel<T, 32>), grid, block, 0, s, P, x, y, q, c, c, q0, nbr, bad, (T*)mo.p, (T*)vo.p);
       else hipLaunchKernelGGL((nn_local_kernel<T, 64>), grid, block, 0, s, P, x, y, q, c, c, q0, nbr, bad, (T*)mo.p, (T*)vo.p);
     });

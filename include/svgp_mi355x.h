@@ -536,7 +536,43 @@ int32_t svgp_laplace_free(svgp_ctx* ctx, svgp_laplace* la);
  *   mean = var = NaN for that test point, every other one is still written, SVGP_NOT_POSDEF, and svgp_last_error names the first such
  *   test point (1-based; one integer atomicMin).
  *   SVGP_INVALID_ARG, before anything is enqueued: NULL ctx / nn / x_host, n < 1, k < 1, no successful fit, a bad layout.
- * Never collective.  Bitwise repeatable: the search uses no atomics, F and the mean's sum are accumulated in fp64 in a fixed order. */
+ * Never collective.  Bitwise repeatable: the search uses no atomics, F and the mean's sum are accumulated in fp64 in a fixed order.
+ *
+ * Per-point noise variances and prior-mean offsets.  A handle may carry N noise variances s and N mean offsets mu (svgp_point_noise,
+ * svgp_point_mean: the collapsed bound's and the CG handle's structs and convention):
+ *   sigma_j^2 = T(desc.diag) + s_j   in the data dtype T with one rounding,      delta_j = y_j - mean_const - mu_j
+ *   C = k(ns, ns) + diag(sigma^2_ns),  kd = variance + sigma_i^2;  b, F, r, lml and alpha as above
+ * in svgp_nn_lml, _lml_grad, _fit (and with it _factors, _predict, _predict_cross_cov, which read the new alpha, B and F) and in
+ * svgp_nn_predict_local (C = k(ns*, ns*) + diag(sigma^2_ns*), mean = mean_const + c' C^-1 delta_ns*), with the window or a table.
+ * A mean function's value at x* is the caller's to add (svgp_predict's rule).  Known measurement errors, a fixed-noise model, a
+ * learned noise or mean function (AbstractGPs' Diagonal Sigma_y, GPyTorch's FixedNoiseGaussianLikelihood).
+ *   svgp_nn_set_noise  N values of the data dtype, host or device memory (pn->on_device), copied into the handle: a snapshot.
+ *           pn = NULL removes the vector: every call is then bitwise what it is on a handle that never had one.  Discards the fit,
+ *           as a table call does: factors / predict return SVGP_INVALID_ARG until the next fit.  One NaN-propagating min-reduction of
+ *           s runs on the device at set time and its result is kept on the host: a later lml / lml_grad / fit / lml_grad_points fails
+ *           BEFORE its data pass with SVGP_NOT_POSDEF when T(desc.diag) + min s is < 0 or NaN; lml = NaN, info->first_bad = 0, and
+ *           the handle stays healthy.  Zero is allowed, as diag = 0 is.
+ *   svgp_nn_set_mean   N offsets mu under the same rules.  A NaN in mu gives lml = NaN with SVGP_OK (the collapsed calls' rule).
+ *   "Not positive" becomes: at or below 4 eps (m + 1) (variance + the largest sigma^2 of the block, point i included); without a
+ *           vector that is the value above.  d / d variance of svgp_nn_lml_grad becomes (gF (F - sigma_i^2) - sum_t sigma_t^2 q_t) /
+ *           variance per point, q_t = gF b_t^2 - (r/F) w_t b_t the diagonal of C_bar; d_diag keeps its meaning, the derivative with
+ *           respect to the common term.
+ *   svgp_nn_lml_grad_points  svgp_nn_lml_grad's arguments, then d_mean_const, gpm and gpn (each of the three may be NULL):
+ *           s_bar_j    = d lml / d sigma_j^2 = gF_j + sum_{(i, t): ns(i)_t = j} (gF_i b_it^2 - (r_i / F_i) w_it b_it)      -> gpn->s_bar
+ *           mean_bar_j = d lml / d mu_j      = alpha_j = r_j / F_j - sum_{(i, t): ns(i)_t = j} b_it r_i / F_i              -> gpm->mu_bar
+ *           d_mean_const = sum_j alpha_j,   d_diag = sum_j s_bar_j (the scalar is the per-point slots' sum, as in svgp_nn_lml_grad)
+ *           N values each in the data dtype, host or device memory (->on_device).  Works with or without vectors set.  The point
+ *           kernel stores b_i, F_i, r_i / F_i, gF_i and the per-pair term laid out like B; two gathers follow in a fixed order: the
+ *           window over the <= kb later rows, a table over its reverse lists, one wavefront per j, the lanes striding the list, a
+ *           fixed tree.  Sums in fp64, rounded once to the data dtype; no floating-point atomics: repeated calls and host / device
+ *           output are bitwise equal, and lml, d_variance, d_inv_lengthscale and d_diag are bitwise those of svgp_nn_lml_grad on the
+ *           same handle state.  The call leaves the handle FITTED at desc (b_i, F_i and alpha are those of svgp_nn_fit: mean_bar is
+ *           the fit's alpha), replacing an earlier fit.  Workspace beyond a fit's: N x kb elements of the data dtype (the per-pair
+ *           terms) and three N-vectors (gF and s_bar in fp64, one staging vector).  SVGP_NOT_POSDEF: the vectors are not written.
+ * SVGP_INVALID_ARG, before anything is enqueued: NULL pn->s / pm->mu / gpm->mu_bar / gpn->s_bar, on_device not 0 / 1, reserved != 0,
+ * and what svgp_nn_lml_grad rejects.  The existing instantiations of the point kernels run whenever no vector is set (lml, lml_grad,
+ * fit, predict_local): the vectors and the per-point gradient live in sibling instantiations.  Out of scope: a full noise
+ * covariance, gradients with respect to x, the selection of a table.  Found by symbol (no ABI version step). */
 typedef struct svgp_nn svgp_nn;
 typedef struct svgp_nn_desc {
   int32_t dtype;            /* SVGP_F64 | SVGP_F32: must be the data's */
@@ -571,6 +607,13 @@ int32_t svgp_nn_get_neighbors(svgp_ctx* ctx, svgp_nn* nn, int32_t* k_out, int32_
 int32_t svgp_nn_clear_neighbors(svgp_ctx* ctx, svgp_nn* nn);
 int32_t svgp_nn_predict_local(svgp_ctx* ctx, svgp_nn* nn, int32_t layout, int64_t n, const void* x_host, int32_t k, void* mean_out,
                               void* var_out, int32_t* nbr_out);
+struct svgp_point_noise;        /* defined with the collapsed bound below; svgp_point_mean: with svgp_elbo_with_mean above */
+struct svgp_point_noise_grad;
+int32_t svgp_nn_set_noise(svgp_ctx* ctx, svgp_nn* nn, const struct svgp_point_noise* pn);
+int32_t svgp_nn_set_mean(svgp_ctx* ctx, svgp_nn* nn, const svgp_point_mean* pm);
+int32_t svgp_nn_lml_grad_points(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info,
+                                double* d_variance, double* d_inv_lengthscale, double* d_diag, double* d_mean_const,
+                                svgp_point_mean_grad* gpm, struct svgp_point_noise_grad* gpn);
 
 /* ---- the collapsed bound of sparse GP regression and the optimal q(u)  (Titsias 2009, eqs. 11 / 12) ---------------------------------
  * For the Gaussian likelihood the q(u) that maximises the ELBO has a closed form; the reference's tests build it on the host
