@@ -206,6 +206,9 @@ SYMBOLS = {
     "svgp_nn_lml_grad_points": (C.c_int32, [_P, _P, C.POINTER(NNDesc), C.POINTER(C.c_double), C.POINTER(NNInfo), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                             C.POINTER(PointMeanGrad), C.POINTER(PointNoiseGrad)]),
+    "svgp_nn_lml_grad_inputs": (C.c_int32, [_P, _P, C.POINTER(NNDesc), C.POINTER(C.c_double), C.POINTER(NNInfo), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(PointMeanGrad), C.POINTER(PointNoiseGrad), C.POINTER(InputGrad)]),
     # the collapsed bound and the optimal q
     "svgp_collapsed_bound": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.POINTER(CollapsedTerms)]),
     "svgp_collapsed_q": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, C.POINTER(C.c_double)]),

@@ -78,14 +78,28 @@ def _flag(name, v):
 
 class DeviceNearestNeighbors:
     """A resident svgp_nn handle over (x, y): x a plain vector (d = 1) or a (d, n) ColVecs array; with layout = ROWVECS an (n, d)
-    RowVecs array.  The neighbours of a point are the points before it in this order."""
+    RowVecs array.  The neighbours of a point are the points before it in this order.  data = an existing _ffi.DeviceData with y
+    (x, y, dtype and layout None) borrows it instead of uploading: e.g. a DeviceData.wrap of torch features, used in place (the
+    handle reads them at every call, so an in-place update of the wrapped tensor is seen by the next one); the caller keeps it
+    alive and frees it."""
 
-    def __init__(self, ctx: _ffi.Context, x, y, dtype, layout=None):
+    def __init__(self, ctx: _ffi.Context, x=None, y=None, dtype=None, layout=None, data=None):
         self.ctx = ctx
-        x = np.asarray(x)
-        if layout is None:
-            layout = _ffi.VEC if x.ndim == 1 else _ffi.COLVECS
-        self.data = _ffi.DeviceData(ctx, x, y, dtype, layout)
+        if data is not None:
+            if not isinstance(data, _ffi.DeviceData):
+                raise TypeError("data: an _ffi.DeviceData")
+            if x is not None or y is not None or dtype is not None or layout is not None:
+                raise ValueError("data replaces x, y, dtype and layout")
+            if getattr(data, "h", None) is None:
+                raise ValueError("data has been freed")
+            self.data, self._owns_data = data, False
+        else:
+            if x is None or y is None or dtype is None:
+                raise ValueError("DeviceNearestNeighbors needs x, y and dtype, or data")
+            x = np.asarray(x)
+            if layout is None:
+                layout = _ffi.VEC if x.ndim == 1 else _ffi.COLVECS
+            self.data, self._owns_data = _ffi.DeviceData(ctx, x, y, dtype, layout), True
         self.dtype, self.d, self.n = self.data.dtype, self.data.d, self.data.n
         h = C.c_void_p()
         ctx.check(ctx.lib.svgp_nn_create(ctx.h, self.data.h, C.byref(h)))
@@ -146,10 +160,29 @@ class DeviceNearestNeighbors:
         pm, _keep = _ffi.point_mean(mu, self.n, self.dtype)
         self.ctx.check(self.ctx.lib.svgp_nn_set_mean(self.ctx.h, self.h, C.byref(pm)))
 
-    def lml_grad_points(self, desc, mean_grad_out=None, noise_grad_out=None):
+    def _x_grad(self, x_grad_out):
+        """-> (InputGrad, what lml_grad_points returns as grads["x"]): a (d, N) array of the data dtype, or the caller's device tensor"""
+        if x_grad_out is None:
+            xg = np.zeros((self.d, self.n), dtype=_ffi.np_dtype(self.dtype))
+            return _ffi.InputGrad(_ffi._ptr(xg), self.n, 0, 0), xg
+        t = x_grad_out
+        if (not _ffi._is_device_tensor(t) or not t.is_contiguous() or not t.is_floating_point() or tuple(t.shape) != (self.d, self.n)
+                or t.element_size() != np.dtype(_ffi.np_dtype(self.dtype)).itemsize):
+            raise ValueError("x_grad_out: a contiguous (d, N) device tensor of the data dtype")
+        return _ffi.InputGrad(C.c_void_p(int(t.data_ptr())), self.n, 1, 0), t
+
+    def lml_grad_points(self, desc, mean_grad_out=None, noise_grad_out=None, wrt_inputs=False, x_grad_out=None):
         """-> (lml, {"variance", "inv_lengthscale" (d,), "diag", "mean_const", "mean" (n,), "noise" (n,)}, NNInfo): lml_grad's blocks,
         d / d mean_const, d lml / d mu_j and d lml / d sigma_j^2.  mean_grad_out / noise_grad_out: contiguous device tensors of
-        the data dtype that receive the two vectors in place of host arrays.  Leaves the handle fitted at desc, as fit does."""
+        the data dtype that receive the two vectors in place of host arrays.  Leaves the handle fitted at desc, as fit does.
+        wrt_inputs: grads["x"] as well, (d, N) in the data dtype: d lml / d x at the fixed conditioning sets
+        (svgp_nn_lml_grad_inputs), every other entry bitwise what it is without; x_grad_out: a contiguous (d, N) torch device tensor
+        to write it into (it is returned as grads["x"]).  A block that is not positive raises PosDefException carrying .x_grad, NaN."""
+        if not isinstance(wrt_inputs, (bool, np.bool_)):
+            raise ValueError("wrt_inputs is True or False")
+        if x_grad_out is not None and not wrt_inputs:
+            raise ValueError("x_grad_out needs wrt_inputs=True")
+        gx, xg = self._x_grad(x_grad_out) if wrt_inputs else (None, None)
         dt = _ffi.np_dtype(self.dtype)
         outs, structs = {}, {}
         for name, dst, cls in (("mean", mean_grad_out, _ffi.PointMeanGrad), ("noise", noise_grad_out, _ffi.PointNoiseGrad)):
@@ -164,12 +197,22 @@ class DeviceNearestNeighbors:
         lml, info, dv, dd, dm = C.c_double(), _ffi.NNInfo(), C.c_double(), C.c_double(), C.c_double()
         dil = np.zeros(self.d)
         self.kb = None
-        self._check(self.ctx.lib.svgp_nn_lml_grad_points(self.ctx.h, self.h, C.byref(desc), C.byref(lml), C.byref(info), C.byref(dv),
-                                                         dil.ctypes.data_as(C.POINTER(C.c_double)), C.byref(dd), C.byref(dm),
-                                                         C.byref(structs["mean"]), C.byref(structs["noise"])), info)
+        args = (self.ctx.h, self.h, C.byref(desc), C.byref(lml), C.byref(info), C.byref(dv), dil.ctypes.data_as(C.POINTER(C.c_double)),
+                C.byref(dd), C.byref(dm), C.byref(structs["mean"]), C.byref(structs["noise"]))
+        if wrt_inputs:
+            try:
+                self._check(self.ctx.lib.svgp_nn_lml_grad_inputs(*args, C.byref(gx)), info)
+            except _ffi.PosDefException as err:
+                err.x_grad = xg
+                raise
+        else:
+            self._check(self.ctx.lib.svgp_nn_lml_grad_points(*args), info)
         self.kb = min(int(desc.k), self.n - 1)
-        return lml.value, {"variance": dv.value, "inv_lengthscale": dil, "diag": dd.value, "mean_const": dm.value,
-                           "mean": outs["mean"], "noise": outs["noise"]}, info
+        grads = {"variance": dv.value, "inv_lengthscale": dil, "diag": dd.value, "mean_const": dm.value,
+                 "mean": outs["mean"], "noise": outs["noise"]}
+        if wrt_inputs:
+            grads["x"] = xg
+        return lml.value, grads, info
 
     def set_neighbors(self, table):
         """condition point i on the points table[i, :] ((n, kb) integers: distinct indices below i, the valid ones first, -1 after
@@ -281,7 +324,8 @@ class DeviceNearestNeighbors:
             self.ctx.lib.svgp_nn_free(self.ctx.h, self.h)
             self.h = None
         if getattr(self, "data", None) is not None:
-            self.data.free()
+            if self._owns_data:
+                self.data.free()
             self.data = None
 
     def __del__(self):
@@ -341,25 +385,37 @@ def approx_lml_and_gradient(approx, fx, y, **kwargs):
     and to the diagonal term (the noise variance under include_noise).  wrt_noise=True adds "Sigma_y" (n,), d lml / d of every
     point's noise variance ("diag" is its sum); wrt_mean=True adds "mean" (n,), d lml / d of the prior mean's value at every point,
     and "mean_const", their sum.  noise_grad_out / mean_grad_out: contiguous device tensors of the data dtype that receive the two
-    vectors in place of host arrays.  mean_offsets as in approx_lml.  LaplaceApproximation: the Laplace method, unchanged."""
+    vectors in place of host arrays.  mean_offsets as in approx_lml.  wrt_inputs=True adds "x" = d lml / d x at the fixed
+    conditioning sets, shaped like fx.x: a vector for a plain vector x, (d, n) ColVecs, or with layout=ROWVECS (fx.x an (n, d)
+    RowVecs array) (n, d); the dependence of Σy and of the mean offsets on x is the caller's to chain through "Sigma_y" and "mean".
+    LaplaceApproximation: the Laplace method, unchanged."""
     if not isinstance(approx, NearestNeighbors):
         return _laplace.approx_lml_and_gradient(approx, fx, y, **kwargs)
-    ctx, dtype = _nn_kwargs("approx_lml_and_gradient", kwargs, ("mean_offsets", "wrt_noise", "wrt_mean", "noise_grad_out", "mean_grad_out"))
+    ctx, dtype = _nn_kwargs("approx_lml_and_gradient", kwargs,
+                            ("mean_offsets", "wrt_noise", "wrt_mean", "noise_grad_out", "mean_grad_out", "wrt_inputs", "layout"))
     wrt_noise, wrt_mean = _flag("wrt_noise", kwargs.get("wrt_noise", False)), _flag("wrt_mean", kwargs.get("wrt_mean", False))
+    wrt_inputs, layout = _flag("wrt_inputs", kwargs.get("wrt_inputs", False)), kwargs.get("layout")
     ngo, mgo = kwargs.get("noise_grad_out"), kwargs.get("mean_grad_out")
     if ngo is not None and not wrt_noise:
         raise ValueError("noise_grad_out needs wrt_noise=True")
     if mgo is not None and not wrt_mean:
         raise ValueError("mean_grad_out needs wrt_mean=True")
+    if layout not in (None, _ffi.COLVECS, _ffi.ROWVECS):
+        raise ValueError("layout is None, COLVECS or ROWVECS")
+    rowvecs = layout == _ffi.ROWVECS and np.ndim(fx.x) == 2
+    if rowvecs:   # the same points as ColVecs; "x" goes back in the caller's layout
+        fx = FiniteGP(fx.f, np.asarray(fx.x).T, fx.Sigma_y)
     dev, desc, keep = _device(approx, fx, y, ctx, dtype, kwargs.get("mean_offsets"))
     try:
-        if not (wrt_noise or wrt_mean):
+        if not (wrt_noise or wrt_mean or wrt_inputs):
             lml, dv, dil, dd, _info = dev.lml_grad(desc)
             return lml, {"variance": dv, "inv_lengthscale": dil, "diag": dd}
-        lml, g, _info = dev.lml_grad_points(desc, mean_grad_out=mgo, noise_grad_out=ngo)
+        lml, g, _info = dev.lml_grad_points(desc, mean_grad_out=mgo, noise_grad_out=ngo, wrt_inputs=wrt_inputs)
     finally:
         dev.free()
     grads = {"variance": g["variance"], "inv_lengthscale": g["inv_lengthscale"], "diag": g["diag"]}
+    if wrt_inputs:
+        grads["x"] = g["x"][0] if np.ndim(fx.x) == 1 else (np.ascontiguousarray(g["x"].T) if rowvecs else g["x"])
     if wrt_noise:
         grads["Sigma_y"] = g["noise"]
     if wrt_mean:

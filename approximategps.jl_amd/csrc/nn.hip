@@ -28,12 +28,14 @@
 //   per-point vectors   svgp_nn_set_noise / svgp_nn_set_mean keep N noise variances s and N mean offsets mu on the handle: C carries
 //                    diag(T(diag) + s), delta = y - mean_const - mu.  With either set, and in svgp_nn_lml_grad_points (s_bar, mean_bar =
 //                    alpha), the point and local kernels are the siblings of nn_points.hip; without, the ones below, untouched
+//   input gradient   svgp_nn_lml_grad_inputs: the point kernel and the gathers of nn_xgrad.hip after the same checks and reservations
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -44,6 +46,7 @@
 #include "kernels.hpp"
 #include "nn_common.hpp"
 #include "nn_points.hpp"
+#include "nn_xgrad.hpp"
 
 namespace svgp {
 namespace {
@@ -688,6 +691,7 @@ struct svgp_nn {
   bool have_s = false, have_mu = false;
   double s_min = 0;
   DevBuf Qd, gF, sbar, gout;   // svgp_nn_lml_grad_points: the per-pair terms (N x kb, data dtype), gF_i and s_bar (fp64), the cast outputs
+  DevBuf Xd, Hd, xout;         // svgp_nn_lml_grad_inputs: the per-pair terms (d x kb x N, data dtype), the own-point terms (d x N, fp64), x_bar staged for the host
 };
 
 namespace {
@@ -753,8 +757,10 @@ int nn_noise_check(svgp_ctx* ctx, const svgp_nn* nn, const svgp_nn_desc* ds) {
 }
 
 // mode 0: lml; 1: fit; 2: lml and gradient; 3: lml, gradient, fit, s_bar and the sum of alpha (svgp_nn_lml_grad_points).
-// out[S] = the reduced slots (mode 3: out[S] = sum_j alpha_j after them)
-int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double* lml_out, svgp_nn_info* info, double* out) {
+// out[S] = the reduced slots (mode 3: out[S] = sum_j alpha_j after them).  gx (mode 3 only): x_bar as well (svgp_nn_lml_grad_inputs),
+// the point kernel of nn_xgrad.hip in place of mode 3's and its gather after s_bar's; on SVGP_NOT_POSDEF gx's memory is the caller's to fill
+int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double* lml_out, svgp_nn_info* info, double* out,
+            const svgp_input_grad* gx = nullptr) {
   int rc = nn_check_desc(ctx, nn, ds);
   if (rc) return rc;
   if (!lml_out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
@@ -778,6 +784,11 @@ int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double
   const bool vec = nn->have_s || nn->have_mu || mode == 3;   // the kernels of nn_points.hip
   rc = nn->terms.reserve(ctx, size_t(N) * S * 8, "the NearestNeighbors per-point terms");
   if (rc == SVGP_OK) rc = nn->part.reserve(ctx, size_t(nb) * S * 8, "the NearestNeighbors block partials");
+  if (rc == SVGP_OK && gx) {   // before the first enqueue: a failure leaves the handle as it was
+    rc = nn->Xd.reserve(ctx, std::max<size_t>(size_t(N) * P.k * nn->d * nn->es, 8), "the NearestNeighbors per-pair input-gradient terms");
+    if (rc == SVGP_OK) rc = nn->Hd.reserve(ctx, size_t(N) * nn->d * 8, "the NearestNeighbors own-point input-gradient terms");
+    if (rc == SVGP_OK && !gx->on_device) rc = nn->xout.reserve(ctx, size_t(N) * nn->d * nn->es, "the input gradient staged for the host");
+  }
   if (rc == SVGP_OK && fits) {
     nn->have_fit = false;
     rc = nn->Bd.reserve(ctx, std::max<size_t>(size_t(N) * P.k * nn->es, 8), "the NearestNeighbors rows b_i");
@@ -798,7 +809,8 @@ int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double
     const NnPointArgs a{nn->data->x.p, nn->data->y.p, nn->have_s ? nn->sv.p : nullptr, nn->have_mu ? nn->mu.p : nullptr,
                         nn->terms.as<double>(), S, nn->bad.as<int>(), nn->Bd.p, nn->Fd.as<double>(), nn->rF.as<double>(), nn->Qd.p,
                         nn->gF.as<double>(), nn->tab_kb >= 0 ? nn->nbr.as<int>() : nullptr};
-    launch_nn_point_v(nn->dtype, mode, s, P, a);
+    if (gx) launch_nn_point_x(nn->dtype, s, P, a, nn->Xd.p, nn->Hd.as<double>());
+    else launch_nn_point_v(nn->dtype, mode, s, P, a);
   } else {
     NN_DISPATCH(nn->dtype, T, {
       if (mode == 0) nn_launch_point<T, 0>(s, P, nn, S);
@@ -826,6 +838,13 @@ int nn_eval(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* ds, int mode, double
     hipLaunchKernelGGL(nn_reduce1_kernel, dim3((unsigned)nb, 1u), dim3(k256), 0, s, (const double*)nn->alpha.as<double>(), N, 1, chunk,
                        nn->part.as<double>());
     hipLaunchKernelGGL(nn_reduce2_kernel, dim3(1u), dim3(k256), 0, s, (const double*)nn->part.as<double>(), nb, nn->res.as<double>() + S);
+    if (gx) {   // x_bar: into the caller's device memory, or staged for the host's
+      launch_nn_xbar(nn->dtype, s, P, nn->Xd.p, nn->Hd.as<double>(), tab ? nn->roff.as<int64_t>() : nullptr,
+                     tab ? nn->rv.as<int64_t>() : nullptr, gx->on_device ? gx->x : nn->xout.p, gx->on_device ? gx->ld : N);
+      if (!gx->on_device)
+        HIPC(ctx, hipMemcpy2DAsync(gx->x, size_t(gx->ld) * nn->es, nn->xout.p, size_t(N) * nn->es, size_t(N) * nn->es, size_t(nn->d),
+                                   hipMemcpyDeviceToHost, s));
+    }
   }
   KCHECK(ctx, "nn_reduce");
   int badv = 0;
@@ -1006,6 +1025,31 @@ int nn_reverse_lists(svgp_ctx* ctx, svgp_nn* nn, int kb) {
   return SVGP_OK;
 }
 
+// mean_bar = alpha and s_bar of the last mode-3 evaluation into gpm / gpn (either may be null)
+int nn_point_outputs(svgp_ctx* ctx, svgp_nn* nn, svgp_point_mean_grad* gpm, svgp_point_noise_grad* gpn) {
+  if (!gpm && !gpn) return SVGP_OK;
+  hipStream_t s = ctx->stream;
+  const int64_t N = nn->N;
+  const size_t nb = size_t(N) * nn->es;
+  const int rc = nn->gout.reserve(ctx, nb, "the per-point gradient in the data dtype");
+  if (rc) return rc;
+  for (int q = 0; q < 2; ++q) {   // fp64 sums, rounded once to the data dtype: into the caller's device memory, or staged for the host's
+    void* dst = q ? (gpn ? gpn->s_bar : nullptr) : (gpm ? gpm->mu_bar : nullptr);
+    if (!dst) continue;
+    const bool dev = q ? gpn->on_device != 0 : gpm->on_device != 0;
+    NN_DISPATCH(nn->dtype, T, {
+      hipLaunchKernelGGL(nn_cast_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, (const double*)(q ? nn->sbar : nn->alpha).as<double>(), N, 0.0, 1.0,
+                         (T*)(dev ? dst : nn->gout.p));
+    });
+    KCHECK(ctx, "nn_cast");
+    if (!dev) {
+      HIPC(ctx, hipMemcpyAsync(dst, nn->gout.p, nb, hipMemcpyDeviceToHost, s));
+      HIPC(ctx, hipStreamSynchronize(s));   // gout is reused by the second vector
+    }
+  }
+  return SVGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1181,27 +1225,59 @@ int32_t svgp_nn_lml_grad_points(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* 
   if (d_diag) *d_diag = out[4];
   for (int f = 0; f < nn->d; ++f) d_inv_lengthscale[f] = out[kNnGradSlots + f];
   if (d_mean_const) *d_mean_const = out[kNnGradSlots + nn->d];
-  if (!gpm && !gpn) return SVGP_OK;
-  hipStream_t s = ctx->stream;
-  const int64_t N = nn->N;
-  const size_t nb = size_t(N) * nn->es;
-  rc = nn->gout.reserve(ctx, nb, "the per-point gradient in the data dtype");
+  return nn_point_outputs(ctx, nn, gpm, gpn);
+}
+
+int32_t svgp_nn_lml_grad_inputs(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info,
+                                double* d_variance, double* d_inv_lengthscale, double* d_diag, double* d_mean_const,
+                                svgp_point_mean_grad* gpm, svgp_point_noise_grad* gpn, const svgp_input_grad* gx) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  if (!nn) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  int rc = nn_check_desc(ctx, nn, desc);
   if (rc) return rc;
-  for (int q = 0; q < 2; ++q) {   // fp64 sums, rounded once to the data dtype: into the caller's device memory, or staged for the host's
-    void* dst = q ? (gpn ? gpn->s_bar : nullptr) : (gpm ? gpm->mu_bar : nullptr);
-    if (!dst) continue;
-    const bool dev = q ? gpn->on_device != 0 : gpm->on_device != 0;
-    NN_DISPATCH(nn->dtype, T, {
-      hipLaunchKernelGGL(nn_cast_kernel<T>, dim3(nblk(N)), dim3(256), 0, s, (const double*)(q ? nn->sbar : nn->alpha).as<double>(), N, 0.0, 1.0,
-                         (T*)(dev ? dst : nn->gout.p));
-    });
-    KCHECK(ctx, "nn_cast");
-    if (!dev) {
-      HIPC(ctx, hipMemcpyAsync(dst, nn->gout.p, nb, hipMemcpyDeviceToHost, s));
-      HIPC(ctx, hipStreamSynchronize(s));   // gout is reused by the second vector
+  if (!d_variance || !d_inv_lengthscale) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (gpm && (rc = check_point_out(ctx, gpm->mu_bar, gpm->on_device, gpm->reserved, "mean gradient output")) != SVGP_OK) return rc;
+  if (gpn && (rc = check_point_out(ctx, gpn->s_bar, gpn->on_device, gpn->reserved, "noise gradient output")) != SVGP_OK) return rc;
+  if (!gx || !gx->x) return fail(ctx, SVGP_INVALID_ARG, "null input-gradient output");
+  if (gx->ld < nn->N) return fail(ctx, SVGP_INVALID_ARG, "input-gradient leading dimension smaller than N");
+  if ((gx->on_device != 0 && gx->on_device != 1) || gx->reserved != 0)
+    return fail(ctx, SVGP_INVALID_ARG, "input-gradient on_device must be 0 or 1 and reserved 0");
+  if (gx->on_device) {   // device ranges: x_bar against the data and against the two per-point outputs
+    const svgp_data* D = nn->data;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(gx->x), a1 = a0 + (size_t(nn->d - 1) * size_t(gx->ld) + size_t(nn->N)) * nn->es;
+    const auto hits = [&](const void* p, size_t bytes) {
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(p);
+      return p && a0 < b0 + bytes && b0 < a1;
+    };
+    if (hits(D->x.p, (size_t(nn->d - 1) * size_t(D->ldx) + size_t(nn->N)) * nn->es))
+      return fail(ctx, SVGP_INVALID_ARG, "input-gradient output overlaps the data's x");
+    if (hits(D->y.p, size_t(nn->N) * nn->es)) return fail(ctx, SVGP_INVALID_ARG, "input-gradient output overlaps the data's y");
+    if (gpm && gpm->on_device && hits(gpm->mu_bar, size_t(nn->N) * nn->es))
+      return fail(ctx, SVGP_INVALID_ARG, "input-gradient output overlaps the mean gradient output");
+    if (gpn && gpn->on_device && hits(gpn->s_bar, size_t(nn->N) * nn->es))
+      return fail(ctx, SVGP_INVALID_ARG, "input-gradient output overlaps the noise gradient output");
+  }
+  double out[kNnGradSlots + SVGP_MAX_D + 1];
+  rc = nn_eval(ctx, nn, desc, 3, lml_out, info, out, gx);
+  if (rc == SVGP_NOT_POSDEF) {   // NaN into every entry of x_bar; the status and the context's message stay
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (gx->on_device) {
+      launch_nn_xfill(nn->dtype, ctx->stream, nn->N, nn->d, nan, gx->x, gx->ld);
+      if (hipGetLastError() == hipSuccess) (void)hipStreamSynchronize(ctx->stream);
+    } else {
+      for (int f = 0; f < nn->d; ++f)
+        for (int64_t j = 0; j < nn->N; ++j) {
+          if (nn->dtype == SVGP_F64) static_cast<double*>(gx->x)[int64_t(f) * gx->ld + j] = nan;
+          else static_cast<float*>(gx->x)[int64_t(f) * gx->ld + j] = std::numeric_limits<float>::quiet_NaN();
+        }
     }
   }
-  return SVGP_OK;
+  if (rc) return rc;
+  *d_variance = out[3];
+  if (d_diag) *d_diag = out[4];
+  for (int f = 0; f < nn->d; ++f) d_inv_lengthscale[f] = out[kNnGradSlots + f];
+  if (d_mean_const) *d_mean_const = out[kNnGradSlots + nn->d];
+  return nn_point_outputs(ctx, nn, gpm, gpn);
 }
 
 int32_t svgp_nn_fit(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info) {

@@ -16,10 +16,13 @@ mkdir -p "$(dirname "$LOG")"
   echo "# $(hipcc --version 2>/dev/null | grep -m1 -i 'clang version' || true)"
 } > "$LOG"
 UNITS=$(cd "$SRC" && for f in *.hip; do echo "${f%.hip}"; done)   # every translation unit: csrc/ holds nothing else that matches
+NO_PK_F32=" nn_xgrad "   # units built without packed fp32 arithmetic (v_pk_*_f32): scalar fp32 VALU only
 pids=()
 for f in $UNITS; do
-  echo "hipcc $FLAGS -c approximategps.jl_amd/csrc/$f.hip -o approximategps.jl_amd/csrc/$f.o" >> "$LOG"
-  hipcc $FLAGS -c "$SRC/$f.hip" -o "$SRC/$f.o" &
+  UF="$FLAGS"
+  [[ "$NO_PK_F32" == *" $f "* ]] && UF="$FLAGS -Xclang -target-feature -Xclang -packed-fp32-ops"
+  echo "hipcc $UF -c approximategps.jl_amd/csrc/$f.hip -o approximategps.jl_amd/csrc/$f.o" >> "$LOG"
+  hipcc $UF -c "$SRC/$f.hip" -o "$SRC/$f.o" &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done

@@ -572,7 +572,33 @@ int32_t svgp_laplace_free(svgp_ctx* ctx, svgp_laplace* la);
  * SVGP_INVALID_ARG, before anything is enqueued: NULL pn->s / pm->mu / gpm->mu_bar / gpn->s_bar, on_device not 0 / 1, reserved != 0,
  * and what svgp_nn_lml_grad rejects.  The existing instantiations of the point kernels run whenever no vector is set (lml, lml_grad,
  * fit, predict_local): the vectors and the per-point gradient live in sibling instantiations.  Out of scope: a full noise
- * covariance, gradients with respect to x, the selection of a table.  Found by symbol (no ABI version step). */
+ * covariance, the selection of a table.  Found by symbol (no ABI version step).
+ *
+ * The gradient with respect to the data inputs: what a feature map in front of the kernel, an input warping or latent inputs chain
+ * through (deep kernel learning at an N only this family reaches).  At the fixed conditioning sets - the selection of neighbours is not
+ * differentiated - with s = invl .* x, L_i = -1/2 (log F_i + r_i^2 / F_i), g = d kappa / d r2 of the unit-variance kernel:
+ *           W_ab = 2 variance g(r2_ab) (C_bar_ab + C_bar_ba),  C_bar_ab = (gF b_a - (r/F) w_a) b_b      a, b in ns(i)
+ *           W_ai = 2 variance g(r2_ai) c_bar_a,                c_bar_a  = -2 gF b_a + (r/F) w_a
+ *           d L_i / d s_{a,f} = sum_b W_ab (s_a - s_b)_f + W_ai (s_a - s_i)_f,    d L_i / d s_{i,f} = -sum_a W_ai (s_a - s_i)_f
+ *           x_bar[f, j] = invl_f (own-block term of j + the sum over the pairs (i, t) with ns(i)_t = j of block i's term)
+ *   svgp_nn_lml_grad_inputs  svgp_nn_lml_grad_points' arguments, then a REQUIRED gx (svgp_input_grad as in svgp_cg_lml_grad_inputs):
+ *           feature-major gx->x[f * gx->ld + j], ld >= N, host or device memory (gx->on_device), the data's dtype.  A per-point noise
+ *           vector and mean offsets enter through sigma_j^2 and delta_j as they do in every call; their dependence on x is the caller's
+ *           to chain through s_bar and mu_bar.  Coincident points give a zero pair term (g is finite, the difference exactly 0).
+ *           Per block sum_j x_bar[f, j] = 0 and sum_j x[f, j] x_bar[f, j] = invl_f d_inv_lengthscale[f], for any table.
+ *           lml, d_variance, d_inv_lengthscale, d_diag, d_mean_const, mu_bar and s_bar are bitwise those of svgp_nn_lml_grad_points on
+ *           the same handle state, and the call leaves the handle fitted exactly as that call does.  Repeated calls are bitwise
+ *           equal, and host and device x_bar are bitwise equal: the point kernel (a sibling of that call's, csrc/nn_xgrad.hip) stores
+ *           the per-pair terms per coordinate laid out like B and the own-point terms in fp64; one gather per (j, f) sums them in
+ *           fp64 in a fixed order (the window's <= kb later rows; a table's reverse list, one wavefront, a fixed tree), no atomics,
+ *           and rounds once to the data dtype.  Every other entry point runs the kernels it ran before.
+ *           Workspace beyond that call's, reserved on the handle and released with it: N x kb x d elements of the data dtype and
+ *           N x d doubles (and N x d elements for a host output): at N = 1e6, k = 30, d = 8, 1.9 GB in fp64 and 0.96 GB in fp32 plus
+ *           64 MB.  A reservation that fails returns SVGP_OOM before anything is enqueued and leaves the handle usable.
+ *           SVGP_NOT_POSDEF (a block or F not positive; a negative variance diag + s_i): x_bar is filled with NaN, info->first_bad is
+ *           as in svgp_nn_lml_grad_points, the context stays healthy.  N = 1: x_bar = 0.
+ *           SVGP_INVALID_ARG, before anything is enqueued: what svgp_nn_lml_grad_points rejects, NULL gx or gx->x, ld < N, on_device not
+ *           0 / 1, reserved != 0, a device x_bar that overlaps the data's x or y or a device mu_bar / s_bar output. */
 typedef struct svgp_nn svgp_nn;
 typedef struct svgp_nn_desc {
   int32_t dtype;            /* SVGP_F64 | SVGP_F32: must be the data's */
@@ -614,6 +640,9 @@ int32_t svgp_nn_set_mean(svgp_ctx* ctx, svgp_nn* nn, const svgp_point_mean* pm);
 int32_t svgp_nn_lml_grad_points(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info,
                                 double* d_variance, double* d_inv_lengthscale, double* d_diag, double* d_mean_const,
                                 svgp_point_mean_grad* gpm, struct svgp_point_noise_grad* gpn);
+int32_t svgp_nn_lml_grad_inputs(svgp_ctx* ctx, svgp_nn* nn, const svgp_nn_desc* desc, double* lml_out, svgp_nn_info* info,
+                                double* d_variance, double* d_inv_lengthscale, double* d_diag, double* d_mean_const,
+                                svgp_point_mean_grad* gpm, struct svgp_point_noise_grad* gpn, const svgp_input_grad* gx);
 
 /* ---- the collapsed bound of sparse GP regression and the optimal q(u)  (Titsias 2009, eqs. 11 / 12) ---------------------------------
  * For the Gaussian likelihood the q(u) that maximises the ELBO has a closed form; the reference's tests build it on the host
