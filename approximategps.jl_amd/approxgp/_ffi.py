@@ -182,6 +182,8 @@ SYMBOLS = {
     "svgp_laplace_fit": (C.c_int32, [_P, _P, C.POINTER(LaplaceDesc), _P, C.POINTER(C.c_double), C.POINTER(LaplaceInfo)]),
     "svgp_laplace_lml_grad": (C.c_int32, [_P, _P, C.POINTER(LaplaceDesc), _P, C.POINTER(C.c_double), C.POINTER(LaplaceInfo),
                                           C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "svgp_laplace_lml_grad_inputs": (C.c_int32, [_P, _P, C.POINTER(LaplaceDesc), _P, C.POINTER(C.c_double), C.POINTER(LaplaceInfo),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(InputGrad)]),
     "svgp_laplace_mode": (C.c_int32, [_P, _P, _P, _P, _P]),
     "svgp_laplace_predict": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P]),
     "svgp_laplace_predict_cross_cov": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P, _P]),

@@ -1,6 +1,6 @@
 """Python host mirror of ApproximateGPs.jl's LaplaceApproximation (/root/reference/src/LaplaceApproximationModule.jl, LA) over the
-C-ABI of libsvgp_mi355x.so: Newton mode finding, approx_lml, its gradient with respect to the kernel parameters and the posterior's
-predictions all run on the device (include/svgp_mi355x.h, svgp_laplace_*).  This file only packs parameters."""
+C-ABI of libsvgp_mi355x.so: Newton mode finding, approx_lml, its gradient with respect to the kernel parameters and to the data
+inputs, and the posterior's predictions all run on the device (include/svgp_mi355x.h, svgp_laplace_*).  This file only packs parameters."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _ffi
 from . import sva as _sva
-from .gp import (BernoulliLikelihood, GammaLikelihood, GaussianLikelihood, LatentFiniteGP, LogisticLink, NormalCDFLink, _as_dn)
+from .gp import (BernoulliLikelihood, FiniteGP, GammaLikelihood, GaussianLikelihood, LatentFiniteGP, LogisticLink, NormalCDFLink, _as_dn)
 from .kernels import unpack_kernel
 
 
@@ -50,14 +50,27 @@ def _check_inputs(lfx: LatentFiniteGP, ys):
 
 class DeviceLaplace:
     """A resident svgp_laplace handle over (x, y): x as lfx.fx.x - a plain vector (d = 1) or a (d, n) ColVecs array; with
-    layout = ROWVECS an (n, d) RowVecs array."""
+    layout = ROWVECS an (n, d) RowVecs array.  data = an existing _ffi.DeviceData with y (x, y, dtype and layout None) borrows it
+    instead of uploading: e.g. a DeviceData.wrap of torch features, read in place at every call (an in-place update of the wrapped
+    tensor is seen by the next one); the caller keeps it alive and frees it."""
 
-    def __init__(self, ctx: _ffi.Context, x, y, dtype, layout=None):
+    def __init__(self, ctx: _ffi.Context, x=None, y=None, dtype=None, layout=None, data=None):
         self.ctx = ctx
-        x = np.asarray(x)
-        if layout is None:
-            layout = _ffi.VEC if x.ndim == 1 else _ffi.COLVECS
-        self.data = _ffi.DeviceData(ctx, x, y, dtype, layout)
+        if data is not None:
+            if not isinstance(data, _ffi.DeviceData):
+                raise TypeError("data: an _ffi.DeviceData")
+            if x is not None or y is not None or dtype is not None or layout is not None:
+                raise ValueError("data replaces x, y, dtype and layout")
+            if getattr(data, "h", None) is None:
+                raise ValueError("data has been freed")
+            self.data, self._owns_data = data, False
+        else:
+            if x is None or y is None or dtype is None:
+                raise ValueError("DeviceLaplace needs x, y and dtype, or data")
+            x = np.asarray(x)
+            if layout is None:
+                layout = _ffi.VEC if x.ndim == 1 else _ffi.COLVECS
+            self.data, self._owns_data = _ffi.DeviceData(ctx, x, y, dtype, layout), True
         self.dtype, self.d, self.n = self.data.dtype, self.data.d, self.data.n
         h = C.c_void_p()
         ctx.check(ctx.lib.svgp_laplace_create(ctx.h, self.data.h, C.byref(h)))
@@ -88,14 +101,41 @@ class DeviceLaplace:
         self.ctx.check(self.ctx.lib.svgp_laplace_fit(self.ctx.h, self.h, C.byref(desc), p, C.byref(lml), C.byref(info)))
         return lml.value, info
 
-    def lml_grad(self, desc, f_init=None):
-        """-> (lml, d lml / d variance, d lml / d inv_lengthscale (d,), LaplaceInfo)"""
+    def _x_grad(self, x_grad_out):
+        """-> (InputGrad, what lml_grad returns as x_bar): a (d, N) array of the data dtype, or the caller's device tensor"""
+        if x_grad_out is None:
+            xg = np.zeros((self.d, self.n), dtype=_ffi.np_dtype(self.dtype))
+            return _ffi.InputGrad(_ffi._ptr(xg), self.n, 0, 0), xg
+        t = x_grad_out
+        if (not _ffi._is_device_tensor(t) or not t.is_contiguous() or not t.is_floating_point() or tuple(t.shape) != (self.d, self.n)
+                or t.element_size() != np.dtype(_ffi.np_dtype(self.dtype)).itemsize):
+            raise ValueError("x_grad_out: a contiguous (d, N) device tensor of the data dtype")
+        return _ffi.InputGrad(C.c_void_p(int(t.data_ptr())), self.n, 1, 0), t
+
+    def lml_grad(self, desc, f_init=None, wrt_inputs=False, x_grad_out=None):
+        """-> (lml, d lml / d variance, d lml / d inv_lengthscale (d,), LaplaceInfo).  wrt_inputs=True: -> (lml, d / d variance,
+        d / d inv_lengthscale, x_bar, LaplaceInfo) with x_bar = d lml / d x (svgp_laplace_lml_grad_inputs: the total derivative at
+        the mode), (d, N) in the data dtype, every other entry bitwise what it is without; x_grad_out: a contiguous (d, N) torch
+        device tensor to write it into (it is returned as x_bar).  When the factorisation fails x_bar is NaN and the error raised
+        carries it as .x_grad."""
+        if not isinstance(wrt_inputs, (bool, np.bool_)):
+            raise ValueError("wrt_inputs is True or False")
+        if x_grad_out is not None and not wrt_inputs:
+            raise ValueError("x_grad_out needs wrt_inputs=True")
         keep, p = self._finit(f_init)
         lml, info, dv = C.c_double(), _ffi.LaplaceInfo(), C.c_double()
         dil = np.zeros(self.d)
-        self.ctx.check(self.ctx.lib.svgp_laplace_lml_grad(self.ctx.h, self.h, C.byref(desc), p, C.byref(lml), C.byref(info),
-                                                          C.byref(dv), dil.ctypes.data_as(C.POINTER(C.c_double))))
-        return lml.value, dv.value, dil, info
+        args = (self.ctx.h, self.h, C.byref(desc), p, C.byref(lml), C.byref(info), C.byref(dv), dil.ctypes.data_as(C.POINTER(C.c_double)))
+        if not wrt_inputs:
+            self.ctx.check(self.ctx.lib.svgp_laplace_lml_grad(*args))
+            return lml.value, dv.value, dil, info
+        gx, xg = self._x_grad(x_grad_out)
+        try:
+            self.ctx.check(self.ctx.lib.svgp_laplace_lml_grad_inputs(*args, C.byref(gx)))
+        except _ffi.SvgpError as err:
+            err.x_grad = xg
+            raise
+        return lml.value, dv.value, dil, xg, info
 
     def mode(self):
         """-> (f_opt, d log p / df, W) at the last fit's mode"""
@@ -140,7 +180,8 @@ class DeviceLaplace:
             self.ctx.lib.svgp_laplace_free(self.ctx.h, self.h)
             self.h = None
         if getattr(self, "data", None) is not None:
-            self.data.free()
+            if self._owns_data:
+                self.data.free()
             self.data = None
 
     def __del__(self):
@@ -156,11 +197,11 @@ def _dtype_of(lfx, dtype):
     return np.dtype(np.float32 if np.asarray(lfx.fx.x).dtype == np.float32 else np.float64)
 
 
-def _fit(la: LaplaceApproximation, lfx: LatentFiniteGP, ys, ctx, dtype, grad):
+def _fit(la: LaplaceApproximation, lfx: LatentFiniteGP, ys, ctx, dtype, grad, wrt_inputs=False):
     _check_inputs(lfx, ys)
     dev = DeviceLaplace(ctx or _ffi.default_context(), lfx.fx.x, ys, _dtype_of(lfx, dtype))
     desc, keep = dev.desc(lfx.fx.f.kernel, lfx.lik, float(lfx.fx.Sigma_y), la.maxiter)
-    out = dev.lml_grad(desc, la.f_init) if grad else dev.fit(desc, la.f_init)
+    out = dev.lml_grad(desc, la.f_init, wrt_inputs=wrt_inputs) if grad else dev.fit(desc, la.f_init)
     return dev, out
 
 
@@ -183,13 +224,26 @@ def approx_lml(approx, lfx, ys, **kwargs):
     return lml
 
 
-def approx_lml_and_gradient(la: LaplaceApproximation, lfx: LatentFiniteGP, ys, *, ctx=None, dtype=None):
+def approx_lml_and_gradient(la: LaplaceApproximation, lfx: LatentFiniteGP, ys, *, ctx=None, dtype=None, wrt_inputs=False, layout=None):
     """approx_lml and its gradient with respect to the kernel parameters, what Zygote gives the reference through the rrule of
     newton_inner_loop (LA:330-369): -> (lml, {"variance": d lml / d variance, "inv_lengthscale": d lml / d inv_lengthscale (d,)}).
-    An isotropic kernel's d lml / d (1 / lengthscale) is the sum of the d entries."""
-    dev, (lml, dv, dil, _info) = _fit(la, lfx, ys, ctx, dtype, grad=True)
+    An isotropic kernel's d lml / d (1 / lengthscale) is the sum of the d entries.  wrt_inputs=True adds "x" = d lml / d x, the
+    total derivative at the mode, shaped like lfx.fx.x: a vector for a plain vector x, (d, n) ColVecs, or with layout=ROWVECS
+    (lfx.fx.x an (n, d) RowVecs array) (n, d)."""
+    if not isinstance(wrt_inputs, (bool, np.bool_)):
+        raise ValueError("wrt_inputs is True or False")
+    if layout not in (None, _ffi.COLVECS, _ffi.ROWVECS):
+        raise ValueError("layout is None, COLVECS or ROWVECS")
+    rowvecs = layout == _ffi.ROWVECS and np.ndim(lfx.fx.x) == 2
+    if rowvecs:   # the same points as ColVecs; "x" goes back in the caller's layout
+        lfx = LatentFiniteGP(FiniteGP(lfx.fx.f, np.asarray(lfx.fx.x).T, lfx.fx.Sigma_y), lfx.lik)
+    dev, out = _fit(la, lfx, ys, ctx, dtype, grad=True, wrt_inputs=bool(wrt_inputs))
     dev.free()
-    return lml, {"variance": dv, "inv_lengthscale": dil}
+    grads = {"variance": out[1], "inv_lengthscale": out[2]}
+    if wrt_inputs:
+        xg = out[3]
+        grads["x"] = xg[0] if np.ndim(lfx.fx.x) == 1 else (np.ascontiguousarray(xg.T) if rowvecs else xg)
+    return out[0], grads
 
 
 class LaplacePosteriorGP:

@@ -441,4 +441,25 @@ struct CgXgradArgs {
 };
 void launch_cg_xgrad(int dtype, hipStream_t s, const CgXgradArgs& a, void* out, int64_t ldo);
 
+// ---- laplace_xgrad.hip (d approx_lml / d x of the Laplace approximation: svgp_laplace_lml_grad_inputs) -----------------------------
+//   out[f * ldo + i] = 4 variance invl_f sum_k P_ik kappa'(r2_ik) (s_if - s_kf),  P = (a a' - R + u g' + g u') / 2,  s = invl o x
+// over the N data points against themselves, after svgp_laplace_lml_grad's reduction (a, g, u and R are the handle's).  Grid (Np / 64
+// row tiles) x (nseg column segments); the segments' partial sums part[seg][f][i] (fp64) are added in ascending order, scaled and
+// rounded once to the data dtype
+struct LpXgradArgs {
+  const void* x;        // [d][ldx] the data, feature-major, unscaled
+  const void* R;        // Np x Np column-major
+  const void *a, *g, *u;   // [Np]
+  const double* invl;   // [d]
+  double* part;         // nseg x d x Np doubles (lp_xgrad_plan)
+  int64_t ldx, n, np;
+  int family, d;
+  double variance;
+  int tps;              // set by the launcher: column tiles per segment
+};
+void lp_xgrad_plan(int64_t np, int* nseg, int* tps);
+void launch_lp_xgrad(int dtype, hipStream_t s, const LpXgradArgs& a, void* out, int64_t ldo);
+// out[f * ldo + i] = v for i < n, f < d
+void launch_lp_xfill(int dtype, hipStream_t s, int64_t n, int d, double v, void* out, int64_t ldo);
+
 }  // namespace svgp

@@ -19,10 +19,13 @@
 //   Sigma_ii = K_ii - (K R K)_ii          lp_diag_krk_kernel;  s2 = Sigma_ii d3ll / 2,  u = s2 - R (K s2)
 //   d lml / d theta = sum_ik P_ik dK_ik / d theta,  P = a a' / 2 - R / 2 + (u g' + g u') / 2, kernel derivatives generated on the
 //   fly from x                            lp_kgrad_kernel (one fused reduction for the variance and every inverse lengthscale)
+//   d lml / d x_if = 4 variance invl_f^2 sum_k P_ik kappa'(r2_ik) (x_if - x_kf), the same contraction kept per row: laplace_xgrad.hip
+//   (svgp_laplace_lml_grad_inputs below runs it after the reduction above, on the same a, g, u and R)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <vector>
 
@@ -422,6 +425,7 @@ struct svgp_laplace {
   DevBuf info;     // (int) chol info + the factorisation's hand-over counters
   DevBuf R, X;     // gradient: R and K R (allocated on first use)
   DevBuf gpart;    // (fp64) the gradient's partial sums, grown on demand
+  DevBuf xpart, xout;   // svgp_laplace_lml_grad_inputs: the column segments' partial sums (fp64); x_bar staged for the host
   Event ev[5];
   // the last fit: its parameters (predictions), whether a mode exists (warm start)
   bool have_mode = false;
@@ -714,6 +718,88 @@ int32_t svgp_laplace_lml_grad(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplac
   HIPC(ctx, hipStreamSynchronize(s));
   *d_variance = out[0];
   for (int f = 0; f < d; ++f) d_inv_lengthscale[f] = out[1 + f];
+  return SVGP_OK;
+}
+
+int32_t svgp_laplace_lml_grad_inputs(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* desc, const void* f_init, double* lml_out,
+                                     svgp_laplace_info* info, double* d_variance, double* d_inv_lengthscale, const svgp_input_grad* gx) {
+  if (!ctx || !la) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  const int64_t N = la->N, Np = la->Np;
+  const int d = la->d;
+  int rc = SVGP_OK;
+  if (!gx || !gx->x) rc = fail(ctx, SVGP_INVALID_ARG, "null input-gradient output");
+  else if (gx->ld < N) rc = fail(ctx, SVGP_INVALID_ARG, "input-gradient leading dimension smaller than N");
+  else if ((gx->on_device != 0 && gx->on_device != 1) || gx->reserved != 0)
+    rc = fail(ctx, SVGP_INVALID_ARG, "input-gradient on_device must be 0 or 1 and reserved 0");
+  else if (gx->on_device) {   // device ranges: x_bar against the data
+    const svgp_data* D = la->data;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(gx->x), a1 = a0 + (size_t(d - 1) * size_t(gx->ld) + size_t(N)) * la->es;
+    const auto hits = [&](const void* p, size_t bytes) {
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(p);
+      return p && a0 < b0 + bytes && b0 < a1;
+    };
+    if (hits(D->x.p, (size_t(d - 1) * size_t(D->ldx) + size_t(N)) * la->es))
+      rc = fail(ctx, SVGP_INVALID_ARG, "input-gradient output overlaps the data's x");
+    else if (hits(D->y.p, size_t(N) * la->es)) rc = fail(ctx, SVGP_INVALID_ARG, "input-gradient output overlaps the data's y");
+  }
+  if (rc) {
+    la->have_mode = false;   // as every rejected argument of the fit
+    return rc;
+  }
+  hipStream_t s = ctx->stream;
+  rc = svgp_laplace_lml_grad(ctx, la, desc, f_init, lml_out, info, d_variance, d_inv_lengthscale);
+  // no mode (the factorisation failed), or a lml that is not finite: NaN into every entry of x_bar; the status and the message stay
+  if (rc == SVGP_NOT_POSDEF || (rc == SVGP_OK && !std::isfinite(*lml_out))) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (gx->on_device) {
+      launch_lp_xfill(la->dtype, s, N, d, nan, gx->x, gx->ld);
+      KCHECK(ctx, "laplace input gradient (NaN outputs)");   // a fill that fails is reported: SVGP_HIP_ERROR, its message
+      HIPC(ctx, hipStreamSynchronize(s));
+    } else {
+      for (int f = 0; f < d; ++f)
+        for (int64_t j = 0; j < N; ++j) {
+          if (la->dtype == SVGP_F64) static_cast<double*>(gx->x)[int64_t(f) * gx->ld + j] = nan;
+          else static_cast<float*>(gx->x)[int64_t(f) * gx->ld + j] = std::numeric_limits<float>::quiet_NaN();
+        }
+    }
+    return rc;
+  }
+  if (rc) return rc;
+  // the gradient above left a, g, u (t3) and R of the mode on the handle: one more N x N pass over them
+  int nseg = 0, tps = 0;
+  lp_xgrad_plan(Np, &nseg, &tps);
+  rc = la->xpart.reserve(ctx, size_t(nseg) * d * Np * 8, "the Laplace input gradient's partial sums");
+  if (rc == SVGP_OK && !gx->on_device) rc = la->xout.reserve(ctx, size_t(d) * N * la->es, "the Laplace input gradient's staging");
+  if (rc) return rc;
+  LpXgradArgs a{};
+  a.x = la->data->x.p;
+  a.R = la->R.p;
+  a.a = la->a.p;
+  a.g = la->g.p;
+  a.u = la->t3.p;
+  a.invl = la->invl_d.as<double>();
+  a.part = la->xpart.as<double>();
+  a.ldx = la->data->ldx;
+  a.n = N;
+  a.np = Np;
+  a.family = la->family;
+  a.d = d;
+  a.variance = la->variance;
+  const bool timed = ctx->timing_on;
+  if (timed) HIPC(ctx, hipEventRecord(la->ev[0], s));
+  launch_lp_xgrad(la->dtype, s, a, gx->on_device ? gx->x : la->xout.p, gx->on_device ? gx->ld : N);
+  if (timed) HIPC(ctx, hipEventRecord(la->ev[1], s));
+  KCHECK(ctx, "laplace input gradient");
+  const size_t col = size_t(N) * la->es;
+  if (!gx->on_device) HIPC(ctx, hipMemcpy2DAsync(gx->x, size_t(gx->ld) * la->es, la->xout.p, col, col, size_t(d), hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  ctx->timing = svgp_timing{};   // svgp_last_timing: the device time of the input gradient's two kernels alone
+  if (timed) {
+    float t = 0;
+    HIPC(ctx, hipEventElapsedTime(&t, la->ev[0], la->ev[1]));
+    ctx->timing.ms_strip = t;
+    ctx->timing.ms_total = t;
+  }
   return SVGP_OK;
 }
 

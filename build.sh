@@ -16,7 +16,11 @@ mkdir -p "$(dirname "$LOG")"
   echo "# $(hipcc --version 2>/dev/null | grep -m1 -i 'clang version' || true)"
 } > "$LOG"
 UNITS=$(cd "$SRC" && for f in *.hip; do echo "${f%.hip}"; done)   # every translation unit: csrc/ holds nothing else that matches
-NO_PK_F32=" nn_xgrad "   # units built without packed fp32 arithmetic (v_pk_*_f32): scalar fp32 VALU only
+# units built without packed fp32 arithmetic (v_pk_*_f32): scalar fp32 VALU only.  nn_xgrad: its fp32 Matern polynomial has to round
+# as nn_points' does.  laplace_xgrad: the rule for units written since - the compiler is not left to pair fp32 operations
+# into packed forms in a new kernel; this one computes in fp64 (fp32 only in conversions), so the flag changes no instruction today and
+# keeps that true when the fp32 instantiation grows fp32 arithmetic
+NO_PK_F32=" nn_xgrad laplace_xgrad "
 pids=()
 for f in $UNITS; do
   UF="$FLAGS"

@@ -415,6 +415,19 @@ double svgp_offload_work(int64_t n_points, int64_t M, int32_t d);
  *   svgp_laplace_lml_grad  the same fit, then d lml / d variance and d lml / d inv_lengthscale (d entries): the closed form of RW
  *                          Alg. 5.1 with d3 log p, the total derivative along the Newton fixed point that the reference's
  *                          implicit-function rrule (:330-369) gives Zygote.  Likelihood parameters, y and x are not differentiated.
+ *   svgp_laplace_lml_grad_inputs  svgp_laplace_lml_grad's arguments, then a REQUIRED gx (svgp_input_grad as in svgp_cg_lml_grad_inputs):
+ *                          the same fit and gradient - lml, d_variance, d_inv_lengthscale and info bitwise those of svgp_laplace_lml_grad
+ *                          on the same handle state, the handle left as that call leaves it - then x_bar[f, i] = d lml / d x_if, the
+ *                          total derivative at the mode (the implicit term d f_opt / d x included):
+ *                            4 variance invl_f^2 sum_k P_ik kappa'(r2_ik) (x_if - x_kf),  P = (a a' - R + u g' + g u') / 2
+ *                          of RW Alg. 5.1's quantities; one more N x N pass, no solve.  Element (f, i) at gx->x[f * gx->ld + i], data
+ *                          dtype, host or device memory (bitwise the same), fixed summation order (repeated calls are bitwise equal);
+ *                          N = 1 gives 0; svgp_last_timing's ms_strip is then the device time of this pass alone.
+ *                          SVGP_INVALID_ARG, before anything is enqueued, for what svgp_laplace_lml_grad rejects, a
+ *                          NULL gx or gx->x, ld < N, on_device not 0 / 1, reserved != 0, or a device gx->x overlapping the data's x
+ *                          or y.  When cholesky(B) fails (SVGP_NOT_POSDEF), or the lml is not finite, every entry of x_bar is NaN and
+ *                          the status is svgp_laplace_lml_grad's.  A non-constant prior mean, y and likelihood parameters are not
+ *                          differentiated; never collective.
  *   svgp_laplace_mode      f_opt, d log p / df and W = -d2 log p / df2 at it (N each, data dtype, host; any may be NULL).
  *   svgp_laplace_predict   mean = k(x, x*)' dll (RW 3.21), var = k(x*, x*) - colsum(v.^2), cov = k(x*, x*) - v'v with
  *                          v = L \ (sW k(x, x*)) (RW 3.29, :425-463); n values (mean, var) / n x n column-major (cov), data dtype,
@@ -455,6 +468,8 @@ int32_t svgp_laplace_fit(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_des
                          svgp_laplace_info* info);
 int32_t svgp_laplace_lml_grad(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* desc, const void* f_init, double* lml_out,
                               svgp_laplace_info* info, double* d_variance, double* d_inv_lengthscale);
+int32_t svgp_laplace_lml_grad_inputs(svgp_ctx* ctx, svgp_laplace* la, const svgp_laplace_desc* desc, const void* f_init, double* lml_out,
+                                     svgp_laplace_info* info, double* d_variance, double* d_inv_lengthscale, const svgp_input_grad* gx);
 int32_t svgp_laplace_mode(svgp_ctx* ctx, svgp_laplace* la, void* f_out, void* dll_out, void* W_out);
 int32_t svgp_laplace_predict(svgp_ctx* ctx, svgp_laplace* la, int32_t layout, int64_t n, const void* x_host, void* mean_out,
                              void* var_out, void* cov_out);

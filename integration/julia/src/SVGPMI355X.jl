@@ -789,6 +789,18 @@ function laplace_lml_and_grad!(L::DeviceLaplace, desc::LaplaceDesc; f_init=nothi
                                        ctx(), L.h, desc, f_init === nothing ? C_NULL : pointer(f_init), out, info, gv, gl))
     return out[], gv[], gl, info
 end
+"laplace_lml_and_grad! and d lml / d x (the total derivative at the mode), an n x d matrix (feature-major: RowVecs storage)."
+function laplace_lml_and_grad_inputs!(L::DeviceLaplace, desc::LaplaceDesc, ::Type{T}; f_init=nothing) where {T<:FT}
+    out, info, gv = Ref{Float64}(), LaplaceInfo(), Ref{Float64}()
+    gl = zeros(Float64, desc.d)
+    gxf = zeros(T, L.data.n, desc.d)
+    gx = InputGrad(pointer(gxf), L.data.n, 0, 0)
+    GC.@preserve f_init gl gxf check(ccall((:svgp_laplace_lml_grad_inputs, lib), Int32,
+                                           (Ptr{Cvoid}, Ptr{Cvoid}, Ref{LaplaceDesc}, Ptr{Cvoid}, Ref{Float64}, Ref{LaplaceInfo}, Ref{Float64},
+                                            Ptr{Float64}, Ref{InputGrad}),
+                                           ctx(), L.h, desc, f_init === nothing ? C_NULL : pointer(f_init), out, info, gv, gl, gx))
+    return out[], gv[], gl, gxf, info
+end
 "(f_opt, d_loglik, W) of the cached intermediates (LaplaceCache :180-199)."
 function laplace_mode(L::DeviceLaplace, ::Type{T}) where {T<:FT}
     f, g, w = zeros(T, L.data.n), zeros(T, L.data.n), zeros(T, L.data.n)
