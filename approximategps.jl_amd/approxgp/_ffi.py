@@ -238,6 +238,10 @@ SYMBOLS = {
     "svgp_sampler_eval_grad": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), _P, C.c_int64, _P, C.c_int64, C.c_int32]),
     "svgp_sampler_state": (C.c_int32, [_P, _P, _P, _P]),
     "svgp_sampler_free": (C.c_int32, [_P, _P]),
+    "svgp_predictor_create": (C.c_int32, [_P, _P, C.POINTER(_P)]),
+    "svgp_predictor_eval": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(PointMean), _P, _P, _P, _P, C.c_int64, C.c_int32]),
+    "svgp_predictor_state": (C.c_int32, [_P, _P, _P, _P]),
+    "svgp_predictor_free": (C.c_int32, [_P, _P]),
     # the exact GP by matrix-free conjugate gradients
     "svgp_cg_create": (C.c_int32, [_P, _P, C.POINTER(_P)]),
     "svgp_cg_free": (C.c_int32, [_P, _P]),
@@ -991,6 +995,10 @@ class DeviceModel:
         random number is the caller's (approxgp.pathwise.draw_basis draws them).  The DeviceSampler is a snapshot of this model."""
         return DeviceSampler(self, *basis)
 
+    def predictor(self):
+        """svgp_predictor_create: the predictive mean and variance with their input gradients, a snapshot of this model."""
+        return DevicePredictor(self)
+
     def kuf(self, data: DeviceData, off=0, length=None, fetch=True):
         length = data.n - off if length is None else length
         out = np.zeros((self.M, length), dtype=np_dtype(self.dtype), order="F") if fetch else None
@@ -1000,6 +1008,54 @@ class DeviceModel:
     def free(self):
         if getattr(self, "h", None):
             self.ctx.lib.svgp_model_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DevicePredictor:
+    """The predictive distribution of a model, resident in HBM (svgp_predictor): mean, variance and their input gradients anywhere."""
+
+    def __init__(self, model: DeviceModel):
+        self.ctx = ctx = model.ctx
+        self.M, self.d, self.dtype = model.M, model.d, model.dtype
+        h = C.c_void_p()
+        ctx.check(ctx.lib.svgp_predictor_create(ctx.h, model.h, C.byref(h)))
+        self.h = h
+
+    def eval(self, data: DeviceData, off=0, length=None, prior_mean=None, want_grad=True, out=None):
+        """svgp_predictor_eval at the points [off, off + length) of `data` -> (mean (length,), var (length,), dmean (d, length), dvar
+        (d, length)) in the model dtype (the gradients None without want_grad): dmean[c, j] = d mu / d x_c at point off + j, the
+        gradient of f - mean (prior_mean enters the mean alone).  var is the raw v + 1e-18.  out: four contiguous device tensors (or
+        device pointers; None skips one) to write there instead, the gradients' rows `length` apart; then nothing is returned."""
+        length = data.n - off if length is None else length
+        pm, _keep = point_mean(prior_mean, length, self.dtype) if prior_mean is not None else (None, None)
+        pmr = C.byref(pm) if pm is not None else None
+        ctx = self.ctx
+        if out is not None:
+            dev = lambda t: None if t is None else C.c_void_p(int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t))
+            ctx.check(ctx.lib.svgp_predictor_eval(ctx.h, self.h, data.h, off, length, pmr, *(dev(t) for t in out), length, 1))
+            return None
+        dt = np_dtype(self.dtype)
+        mean, var = np.zeros(length, dtype=dt), np.zeros(length, dtype=dt)
+        dmean = np.zeros((self.d, length), dtype=dt) if want_grad else None
+        dvar = np.zeros((self.d, length), dtype=dt) if want_grad else None
+        ctx.check(ctx.lib.svgp_predictor_eval(ctx.h, self.h, data.h, off, length, pmr, _ptr(mean), _ptr(var), _ptr(dmean), _ptr(dvar), length, 0))
+        return mean, var, dmean, dvar
+
+    def state(self):
+        """(beta (M,), G (M, M)) in fp64, before their rounding to the model dtype."""
+        beta, G = np.zeros(self.M), np.zeros((self.M, self.M), order="F")
+        self.ctx.check(self.ctx.lib.svgp_predictor_state(self.ctx.h, self.h, _ptr(beta), _ptr(G)))
+        return beta, G
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.svgp_predictor_free(self.ctx.h, self.h)
             self.h = None
 
     def __del__(self):

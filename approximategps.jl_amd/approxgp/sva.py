@@ -316,6 +316,30 @@ class ApproxPosteriorGP:
         from .pathwise import function_samples
         return function_samples(self, n_samples, n_features, rng)
 
+    def mean_and_var_with_grad(self, x, layout=None):
+        """(mean (n,), var (n,), dmean, dvar) at x from one data pass on the device (svgp_predictor_*): the marginal mean and variance
+        (var is the raw v + 1e-18 of f_post(x)) and their gradients with respect to x, shaped like x: a vector, (d, n) ColVecs or,
+        with layout=ROWVECS (x an (n, d) RowVecs array), (n, d).  What gradient ascent of an acquisition function (UCB, EI, maximum variance) needs.  A non-constant prior
+        mean's values enter the mean; its Jacobian is the caller's to add to dmean."""
+        if layout not in (None, _ffi.COLVECS, _ffi.ROWVECS):
+            raise ValueError("layout is None, COLVECS or ROWVECS")
+        layout = _ffi.COLVECS if layout is None else layout
+        xa = np.asarray(x)
+        data = _ffi.DeviceData(self.ctx, xa, None, _ffi.np_dtype(self._model.dtype), layout=layout)
+        try:
+            pred = self._model.predictor()
+            try:
+                m, v, dm, dv = pred.eval(data, prior_mean=self.prior.mean_offsets(x))
+            finally:
+                pred.free()
+        finally:
+            data.free()
+        if xa.ndim == 1:
+            return m, v, dm[0], dv[0]
+        if layout == _ffi.ROWVECS:
+            return m, v, np.ascontiguousarray(dm.T), np.ascontiguousarray(dv.T)
+        return m, v, dm, dv
+
     def _predictive(self, x, y, lik, quadrature, want):
         """svgp_predictive on (x, y): the forward data pass, then the likelihood on the device"""
         lik = lik if lik is not None else self.lik

@@ -913,6 +913,40 @@ int32_t svgp_sampler_free(svgp_ctx* ctx, svgp_sampler* sampler);
 int32_t svgp_sampler_eval_grad(svgp_ctx* ctx, const svgp_sampler* sampler, const svgp_data* data, int64_t batch_off, int64_t batch_len,
                                const svgp_point_mean* pm, void* out, int64_t ldo, void* grad_out, int64_t ldg, int32_t out_on_device);
 
+/* ---- predictive mean and variance with their input gradients ----------------------------------------------------------------------
+ * What a maximiser of an acquisition function of the fitted model needs (UCB, expected improvement, maximum variance, a safe-set
+ * constraint): with xs = invl o x, k_i = variance kappa(r_i^2), r_i^2 = |xs - zs_i|^2, D_ic = 2 g(r_i^2) (xs_c - zs_ic) and g as in
+ * svgp_sampler_eval_grad,
+ *   mu(x) = mean_const (+ pm) + sum_i k_i beta_i          beta = Kuu^-1 (m_u - mean(z)), svgp_posterior's alpha
+ *   v(x)  = k(x, x) + k' G k + 1e-18                      G = Kuu^-1 (S_u - Kuu) Kuu^-1 (symmetric), S_u = cov q(u)
+ *   d mu / d x_c = invl_c sum_i D_ic beta_i               d v / d x_c = 2 invl_c sum_i D_ic (G k)_i
+ * all four from ONE data pass of 2 M^2 flops a point per block of 8 coordinates (4 for fp64 with d > 32); nothing n x M is stored.
+ *   svgp_predictor_create  the model's usual prep (SVGP_NOT_POSDEF as in svgp_elbo), then Kuu, its factor, its explicit inverse factor, G
+ *                          and beta in fp64 for BOTH dtypes (as svgp_sampler_create rebuilds Kuu), rounded once to the model dtype.  It
+ *                          reads the model's device-resident q - what svgp_collapsed_q / svgp_natgrad_step left there counts - and muz.
+ *                          The predictor is a SNAPSHOT (scaled z, kernel parameters, mean_const, G, beta): a later svgp_model_update or
+ *                          svgp_model_free neither changes nor invalidates it.
+ *   svgp_predictor_eval    mean_out[j], var_out[j], mean_grad_out[c * ldg + j], var_grad_out[c * ldg + j] (feature-major, like
+ *                          svgp_input_grad) for the points j < batch_len of the window, in the model dtype; any of the four may be NULL,
+ *                          not all; host memory or device memory of the context's GPU for all of them (out_on_device).  pm: the
+ *                          window's prior mean offsets as in svgp_marginals_with_mean, or NULL; they enter the mean alone, and their
+ *                          Jacobian is the caller's to add (the gradients are of f - mean).  The data may have been uploaded without y.
+ *                          var_out is the RAW v + 1e-18: no negative-variance policy and no clamping is applied, and it is NOT bitwise
+ *                          svgp_marginals' variance (another summation: k' G k loses eps k(x, x) cond-amplified digits where
+ *                          v << k(x, x), the strips' A'A form does not).  ALWAYS LOCAL.  A point's four results do not depend on the
+ *                          window, the call or the kind of output memory, bitwise; repeated calls are bitwise equal.
+ *   svgp_predictor_state   beta [M] and G (M x M, element (i, j) at [j * M + i]) in fp64, before the rounding; either may be NULL.
+ * SVGP_INVALID_ARG, before anything is enqueued: a d or dtype mismatch between predictor and data, a window outside the data,
+ * ldg < batch_len, no output, or what svgp_marginals_with_mean rejects in pm.  Non-finite inputs give non-finite outputs for that point
+ * only, with SVGP_OK.  No other call's result changes by a bit.  Found by symbol (no ABI version step). */
+typedef struct svgp_predictor svgp_predictor;
+int32_t svgp_predictor_create(svgp_ctx* ctx, svgp_model* model, svgp_predictor** out);
+int32_t svgp_predictor_eval(svgp_ctx* ctx, const svgp_predictor* predictor, const svgp_data* data, int64_t batch_off, int64_t batch_len,
+                            const svgp_point_mean* pm, void* mean_out, void* var_out, void* mean_grad_out, void* var_grad_out, int64_t ldg,
+                            int32_t out_on_device);
+int32_t svgp_predictor_state(svgp_ctx* ctx, const svgp_predictor* predictor, double* beta_out, double* G_out);
+int32_t svgp_predictor_free(svgp_ctx* ctx, svgp_predictor* predictor);
+
 /* ---- the exact GP by matrix-free conjugate gradients -------------------------------------------------------------------------------
  * Khat = K(x, x) + diag I over the N points of a data handle, delta = y - mean_const (or the caller's delta):
  *   alpha = Khat^-1 delta,   lml = -1/2 (delta' alpha + log det Khat + N log 2 pi),   the exact GP regression beyond the dense limit.
