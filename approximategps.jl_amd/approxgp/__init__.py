@@ -38,5 +38,8 @@ from .iterative import (CGPosteriorGP, ConjugateGradients, DeviceConjugateGradie
                         posterior)
 # pathwise function samples of the exact GP: CGPosteriorGP.function_samples, DeviceConjugateGradients.sampler
 from .iterative import CGFunctionSamples, DeviceCGSampler, cg_sample_plan, pack_cg_basis
+# StateSpace: the exact 1-D Matern GP in O(N) (Kalman filter / RTS smoother as parallel scans); approx_lml and posterior above dispatch on it
+from ._ffi import SSDesc, SSInfo
+from .statespace import DeviceStateSpace, SSPosteriorGP, StateSpace
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -132,6 +132,17 @@ class CGInfo(C.Structure):
 
 
 # every symbol include/svgp_mi355x.h declares: (restype, argtypes)
+class SSDesc(C.Structure):
+    """svgp_ss_desc: one parameter set of the exact 1-D Matern GP in state-space form (48 bytes)."""
+    _fields_ = [("dtype", C.c_int32), ("kernel", C.c_int32), ("variance", C.c_double), ("inv_lengthscale", C.c_double),
+                ("diag", C.c_double), ("mean_const", C.c_double), ("reserved", C.c_int64)]
+
+
+class SSInfo(C.Structure):
+    """svgp_ss_info: what a state-space fit did (32 bytes)."""
+    _fields_ = [("state_dim", C.c_int32), ("levels", C.c_int32), ("n_tiles", C.c_int64), ("lml", C.c_double), ("ms_total", C.c_double)]
+
+
 _P = C.c_void_p
 SYMBOLS = {
     "svgp_version": (C.c_int32, []),
@@ -279,6 +290,12 @@ SYMBOLS = {
     "svgp_cg_sampler_state": (C.c_int32, [_P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "svgp_cg_sampler_free": (C.c_int32, [_P, _P]),
     "svgp_cg_sampler_plan": (C.c_int32, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    # the exact 1-D Matern GP in O(N) (state-space form)
+    "svgp_ss_create": (C.c_int32, [_P, _P, C.POINTER(_P)]),
+    "svgp_ss_free": (C.c_int32, [_P, _P]),
+    "svgp_ss_set_noise": (C.c_int32, [_P, _P, C.POINTER(PointNoise)]),
+    "svgp_ss_fit": (C.c_int32, [_P, _P, C.POINTER(SSDesc), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(SSInfo)]),
+    "svgp_ss_predict": (C.c_int32, [_P, _P, C.c_int64, _P, _P, _P]),
     "svgp_lanczos_logdet": (C.c_int32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),

@@ -693,8 +693,12 @@ def _device(cg: ConjugateGradients, fx: FiniteGP, y, ctx, dtype):
 
 def approx_lml(approx, fx, y, **kwargs):
     """approx_lml(ConjugateGradients(), fx, y; ctx, dtype): logpdf(fx, y) of the exact GP with log det by stochastic Lanczos
-    quadrature; any other approximation: the existing methods with every keyword passed on exactly as given."""
+    quadrature; StateSpace(): approxgp.statespace's exact O(N) form; any other approximation: the existing methods with every keyword
+    passed on exactly as given."""
     if not isinstance(approx, ConjugateGradients):
+        from . import statespace as _ss   # (imports this module)
+        if isinstance(approx, _ss.StateSpace):
+            return _ss.approx_lml(approx, fx, y, **kwargs)
         return _vfe.approx_lml(approx, fx, y, **kwargs)
     ctx, dtype = _cg_kwargs("approx_lml", kwargs)
     dev, desc, keep, probes, delta = _device(approx, fx, y, ctx, dtype)
@@ -825,7 +829,7 @@ class CGPosteriorGP:
 
 
 def posterior(approx, *args, **kwargs):
-    """posterior(ConjugateGradients(), fx, y; ctx, dtype) -> CGPosteriorGP; any other approximation: the existing methods.  A Diagonal Σy
+    """posterior(ConjugateGradients(), fx, y; ctx, dtype) -> CGPosteriorGP; StateSpace(): SSPosteriorGP; any other approximation: the existing methods.  A Diagonal Σy
     keeps raising UnsupportedError here (existing behaviour): CGPosteriorGP(approx, f(x, Diagonal(v)), y, ctx=, dtype=) is its posterior."""
     if isinstance(approx, ConjugateGradients):
         fx, y = args
@@ -835,4 +839,7 @@ def posterior(approx, *args, **kwargs):
             raise _ffi.UnsupportedError("posterior(ConjugateGradients(), f(x, Diagonal(v)), y) is not dispatched: construct "
                                         "CGPosteriorGP(approx, f(x, Diagonal(v)), y) for the exact posterior with per-point noise")
         return CGPosteriorGP(approx, fx, y, ctx=ctx, dtype=dtype)
+    from . import statespace as _ss   # (imports this module)
+    if isinstance(approx, _ss.StateSpace):
+        return _ss.posterior(approx, *args, **kwargs)
     return _vfe.posterior(approx, *args, **kwargs)

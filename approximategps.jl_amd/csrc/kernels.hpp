@@ -462,4 +462,29 @@ void launch_lp_xgrad(int dtype, hipStream_t s, const LpXgradArgs& a, void* out, 
 // out[f * ldo + i] = v for i < n, f < d
 void launch_lp_xfill(int dtype, hipStream_t s, int64_t n, int d, double v, void* out, int64_t ldo);
 
+// ---- statespace.hip (the exact one-dimensional Matern GP in O(N): svgp_ss_*) -------------------------------------------------------
+// family 1 / 2: Matern-3/2 / -5/2, state dimension 2 / 3.  Every array below is fp64 on the device unless a dtype says otherwise.
+int ss_tile();                             // elements per workgroup at every level of a scan
+int ss_scan_levels(int64_t n);             // levels of a scan over n points (1: a single tile)
+size_t ss_scan_work_doubles(int64_t n);    // room for the aggregates of every level of a scan over n points (either scan, either family)
+// flag |= 1: a time that is not finite; |= 2: a time below its predecessor (x: n values of the data dtype)
+void launch_ss_check_sorted(int dtype, hipStream_t s, const void* x, int64_t n, int* flag);
+// t = x, dl = delta (fp64, or NULL: y - mean_const), r = diag (sv NULL) or T(diag) + sv[i] rounded once in the data dtype; flag |= 4: an r not > 0
+void launch_ss_stage(int dtype, hipStream_t s, const void* x, const void* y, const double* delta, const void* sv, int64_t n, double diag,
+                     double mean_const, double* t, double* dl, double* r, int* flag);
+// the sorted union of the N staged points and n sorted test times ts (data dtype) as unobserved points (r = -1), N + n entries each;
+// slot: the test point's index, -1 for a datum
+void launch_ss_merge(int dtype, hipStream_t s, const double* t, const double* dl, const double* r, int64_t N, const void* ts, int64_t n,
+                     double* tm, double* dm, double* rm, int* slot);
+// the filter's scan: fm [D + D (D + 1) / 2][ld] = the filtered mean and covariance triangle of every point
+void launch_ss_filter(hipStream_t s, int family, double variance, double inv_lengthscale, const double* t, const double* dl, const double* r,
+                      int64_t n, double* work, double* fm, int64_t ld);
+// out[0] = the log marginal likelihood from the filtered moments: partial [1024], a fixed two-stage sum
+void launch_ss_lml(hipStream_t s, int family, double variance, double inv_lengthscale, const double* t, const double* dl, const double* r,
+                   int64_t n, const double* fm, int64_t ld, double* partial, double* out);
+// the smoother's scan in reverse: where slot[k] >= 0, mean_out / var_out [slot[k]] (data dtype, each nullable) = the smoothed latent
+// mean + mean_const and variance of point k
+void launch_ss_smooth(hipStream_t s, int family, double variance, double inv_lengthscale, const double* t, int64_t n, const double* fm, int64_t ld,
+                      double* work, const int* slot, double mean_const, int dtype, void* mean_out, void* var_out);
+
 }  // namespace svgp

@@ -1170,6 +1170,56 @@ int32_t svgp_cg_sampler_plan(int64_t N, int64_t* seg_rows, int32_t* n_segments, 
  * eigenvalue that is not > 0. */
 int32_t svgp_lanczos_logdet(const double* a, const double* b, int32_t iters, double* out);
 
+/* ---- the exact one-dimensional Matern GP in O(N): the state-space (Kalman) form ------------------------------------------------------
+ * A Matern-3/2 or -5/2 GP over a scalar input (a time series) is a linear Gaussian state-space model of state dimension D = 2 or 3
+ * (Hartikainen & Sarkka 2010; TemporalGPs.jl in the reference's ecosystem): the log marginal likelihood and the posterior marginals are
+ * EXACT and cost O(N), by a Kalman filter and a Rauch-Tung-Striebel smoother, run here as two associative scans over small dense
+ * elements (Sarkka & Garcia-Fernandez 2021).  With H = e_1', lam = sqrt(2 nu) inv_lengthscale, N = F + lam I (nilpotent):
+ *   A(dt) = exp(-lam dt) sum_{p < D} N^p dt^p / p!,   Q(dt) = Pinf - A Pinf A'
+ *   Matern-3/2: F = [[0, 1], [-lam^2, -2 lam]], Pinf = diag(v, lam^2 v)
+ *   Matern-5/2: F = [[0, 1, 0], [0, 0, 1], [-lam^3, -3 lam^2, -3 lam]], k = v lam^2 / 3, Pinf = [[v, 0, -k], [0, k, 0], [-k, 0, lam^4 v]]
+ * All arithmetic is fp64 for both data dtypes; an fp32 handle reads x, y, s and the test times and writes the predictions in float32.
+ * A scan is three launches (tile aggregates, their scan - recursive beyond one tile of them -, a downsweep); the tile is 64 elements
+ * and depends on nothing but the position, no workgroup waits for another and every sum has a fixed order: repeated calls are bitwise
+ * equal.  ALWAYS LOCAL.  The handle borrows the data handle, which must outlive it.  Found by symbol (no ABI version step).
+ *   create     data with d = 1 whose times x are finite and NON-DECREASING (one device pass checks it); equal time stamps are legal
+ *              (A = I, Q = 0).  Unsorted data is SVGP_INVALID_ARG: the caller sorts.
+ *   set_noise  svgp_cg_set_noise's convention: per-point noise variances sigma_k^2 = T(desc.diag) + s_k in the data dtype T with one
+ *              rounding; N values, host or device, copied into the handle; NULL removes them.  Clears the cached fit.
+ *   fit        lml = sum_k -1/2 (log 2 pi S_k + e_k^2 / S_k) over the one-step predictions of the filter: log N(delta; 0, K + diag(sigma^2))
+ *              exactly.  delta: N host doubles, or NULL for y - mean_const.  Caches the staged points and the parameter set for predict.
+ *              A variance diag + s_k that is not > 0 is SVGP_NOT_POSDEF with lml = NaN.
+ *   predict    n test times (host, data dtype, finite and NON-DECREASING; before the first datum, after the last, equal to a datum or
+ *              between two data alike) are merged into the sequence on the device as unobserved points behind equal data times; the
+ *              filter and the smoother run over the union.  mean_out / var_out: the latent mean (+ mean_const) and variance at the test
+ *              times, n entries of the data dtype, host, each nullable.
+ * SVGP_UNSUPPORTED: d != 1; SVGP_KERNEL_SE (no finite state); a communicator on the context; more than 2^31 - 1 points.
+ * SVGP_INVALID_ARG, before anything is enqueued: a NULL required pointer; a descriptor dtype different from the data's; an unknown
+ * kernel; variance, inv_lengthscale or diag not > 0 or not finite (NaN counts); a mean_const that is not finite; reserved != 0; data
+ * without y when delta is NULL; predict before a successful fit; n < 1; test times that are not sorted or not finite.
+ * Memory: 12 N doubles for a fit (the staged points, 9 N filtered moments) plus N / 63 elements of 27 doubles; the same over N + n for
+ * predict.  Out of scope: the gradient of the lml (tangents through the same scan), sums and products of kernels, periodic kernels,
+ * non-Gaussian likelihoods, d > 1, multi-GPU, the Julia hooks. */
+typedef struct svgp_ss svgp_ss;
+typedef struct svgp_ss_desc {
+  int32_t dtype, kernel;             /* SVGP_KERNEL_MATERN32 or SVGP_KERNEL_MATERN52 */
+  double variance;                   /* > 0 */
+  double inv_lengthscale;            /* > 0 */
+  double diag;                       /* the noise variance, > 0 */
+  double mean_const;
+  int64_t reserved;                  /* 0 */
+} svgp_ss_desc;                      /* 48 bytes */
+typedef struct svgp_ss_info {
+  int32_t state_dim, levels;         /* D; the levels of the scan (1: one tile) */
+  int64_t n_tiles;                   /* tiles of 64 points at the first level */
+  double lml, ms_total;              /* ms_total: device time of the call */
+} svgp_ss_info;                      /* 32 bytes */
+int32_t svgp_ss_create(svgp_ctx* ctx, const svgp_data* data, svgp_ss** out);
+int32_t svgp_ss_free(svgp_ctx* ctx, svgp_ss* ss);
+int32_t svgp_ss_set_noise(svgp_ctx* ctx, svgp_ss* ss, const svgp_point_noise* pn);
+int32_t svgp_ss_fit(svgp_ctx* ctx, svgp_ss* ss, const svgp_ss_desc* desc, const double* delta, double* lml_out, svgp_ss_info* info);
+int32_t svgp_ss_predict(svgp_ctx* ctx, svgp_ss* ss, int64_t n, const void* t_host, void* mean_out, void* var_out);
+
 #ifdef __cplusplus
 }
 #endif
