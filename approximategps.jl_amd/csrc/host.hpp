@@ -1,6 +1,7 @@
 // host.hpp — the declarations that cross the host-only translation units of the C-ABI (api.hip, api_forward.hip, api_grad.hip,
 // api_qopt.hip, api_predictive.hip, sample_api.hip), each under the unit that defines it.  A function used by one unit only lives in that unit's
-// anonymous namespace; the owning types and the handles are ctx.hpp's.  Not part of the C-ABI.
+// anonymous namespace; the owning types and the handles are ctx.hpp's.  Not part of the C-ABI.  The conjugate-gradient family (cg_solve.hip,
+// cg_precond.hip, cg_fit.hip, cg_sampler_api.hip) keeps its own such header on top of this one: cg_host.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-"""Numpy restatement of the Nystrom preconditioner of the conjugate gradients (csrc/cg.hip, cg_api.hip; svgp_cg_set_preconditioner,
+"""Numpy restatement of the Nystrom preconditioner of the conjugate gradients (csrc/cg.hip, cg_precond.hip; svgp_cg_set_preconditioner,
 svgp_cg_precond_*, svgp_cg_fit_precond), in float64 and with float32 vectors as cg_ref.mbcg does it:
   P = Z Kuu^-1 Z' + s2 I,  Z = K(x, z_p),  Kuu = K(z_p, z_p) + jitter variance I = Lu Lu',
   P^-1 r = (r - Z W Z' r) / s2,  W = Lu^-T B^-1 Lu^-1 / s2,  B = I + Lu^-1 (Z'Z) Lu^-T / s2,  log det P = N log s2 + log det B.

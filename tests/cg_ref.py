@@ -1,4 +1,4 @@
-"""Float64 numpy restatement of the exact GP by conjugate gradients (csrc/cg.hip, cg_api.hip; svgp_cg_*), used by the CPU and the GPU
+"""Float64 numpy restatement of the exact GP by conjugate gradients (csrc/cg.hip, cg_solve.hip, cg_fit.hip; svgp_cg_*), used by the CPU and the GPU
 tests: the dense Khat through svgp_oracle.kernelmatrix, the same batched CG recurrence with per-column stopping, the Lanczos
 quadrature through numpy.linalg.eigh, the dense-solve forms of the estimator and of its gradient, and a float32 chain of the kmv
 product (expansion-form r^2, float32 kappa, float32 accumulation) with which the whole restatement also runs in float32."""

@@ -1,4 +1,4 @@
-"""GPU checks of the exact GP by matrix-free conjugate gradients (csrc/cg.hip, cg_api.hip; svgp_cg_*) against dense numpy and the
+"""GPU checks of the exact GP by matrix-free conjugate gradients (csrc/cg.hip, cg_solve.hip, cg_fit.hip; svgp_cg_*) against dense numpy and the
 float64 restatement tests/cg_ref.py (itself pinned to the oracle's exact GP and to central differences in tests/test_cg_cpu.py).
 Inputs are seeded: x ~ U[-3, 3]^d, lengthscale 0.7, variance 1.3.
 

@@ -1,5 +1,5 @@
 """GPU checks of the exact GP by conjugate gradients with per-point noise variances (svgp_cg_set_noise, svgp_cg_lml_grad_noise; csrc/cg.hip,
-cg_api.hip) against dense numpy and the restatement tests/cg_noise_ref.py (itself pinned to dense closed forms in
+cg_solve.hip, cg_fit.hip) against dense numpy and the restatement tests/cg_noise_ref.py (itself pinned to dense closed forms in
 tests/test_cg_noise_cpu.py).  Inputs: test_gpu_cg.py's _xy, variance 1.3, lengthscale 0.7 and the three families;
 s = exp(U[log 0.02, log 0.5]) from default_rng(11), diag 0.05, so sigma_i^2 = T(0.05) + T(s_i) and cond(Khat) is 2.3e2 to 4.6e2.
 
@@ -560,6 +560,83 @@ def test_statuses_leave_the_context_healthy(ctx):
         healthy()
         assert gradn(C.byref(_ffi.PointNoiseGrad(_ffi._ptr(sb), 0, 0)), T=0) == OK and np.isnan(sb).all()   # T = 0: NaN like the other trace blocks
         # a handle on another device than the context cannot be made here; the check is the first in svgp_cg_set_noise
+    finally:
+        dev.free()
+
+
+SENTINEL = 7.25
+
+
+def _padded_call(ctx, dev, desc, which, B, ld, on_device):
+    """One svgp_cg_matvec / _solve / _precond_apply of the N x S panel B with the leading dimension ld >= N for input and output, in host
+    arrays or in torch device tensors -> (status, the N x S window of the output, its ld - N padding rows, svgp_last_error).  Every
+    entry of the output holds SENTINEL before the call."""
+    lib, h = ctx.lib, ctx.h
+    N, S = B.shape
+    Bh = np.zeros((ld, S), dtype=B.dtype, order="F")
+    Bh[:N] = B
+    Xh = np.full((ld, S), SENTINEL, dtype=B.dtype, order="F")
+    if on_device:
+        Bt, Xt = (torch.from_numpy(np.ascontiguousarray(a.T)).cuda() for a in (Bh, Xh))   # (S, ld) contiguous: column-major, ld
+        torch.cuda.synchronize()
+        bp, xp = C.c_void_p(Bt.data_ptr()), C.c_void_p(Xt.data_ptr())
+    else:
+        bp, xp = _ffi._ptr(Bh), _ffi._ptr(Xh)
+    head = (h, dev.h, C.byref(desc), S, bp, ld, xp, ld, int(on_device))
+    if which == "matvec":
+        rc = lib.svgp_cg_matvec(*head)
+    elif which == "solve":
+        rc = lib.svgp_cg_solve(*head, None, None, None)
+    else:
+        rc = lib.svgp_cg_precond_apply(*head, None)
+    msg = lib.svgp_last_error(h)
+    if on_device:
+        Xh = Xt.cpu().numpy().T
+    return rc, Xh[:N].copy(), Xh[N:].copy(), msg
+
+
+@pytest.mark.parametrize("dtype", [F64, F32])
+def test_padded_outputs_of_failed_and_healthy_calls(ctx, dtype):
+    """The failure paths of matvec, solve and precond_apply with ld = N + 3, host and device outputs: SVGP_NOT_POSDEF, NaN in the N x S
+    window and nowhere else, the noise check's message.  With a good vector the same calls agree bitwise between host and device outputs."""
+    N, d, S = 65, 2, 2
+    ld = N + 3
+    x, y = _xy(N, d)
+    x = x.astype(dtype)
+    s, _ = _noise(N, dtype)
+    B = np.random.default_rng(3).standard_normal((N, S)).astype(dtype)
+    dev = _dev(ctx, x, None, dtype)
+
+    def failed(which, word):
+        for on_device in (0, 1):
+            rc, win, pad, msg = _padded_call(ctx, dev, desc, which, B, ld, on_device)
+            where = (which, on_device)
+            assert rc == _ffi.NOT_POSDEF, where
+            assert win.shape == (N, S) and np.isnan(win).all(), where
+            assert pad.shape == (3, S) and (pad == SENTINEL).all(), where
+            assert msg.startswith(b"per-point noise") and word in msg, (where, msg)
+
+    def healthy(which):
+        (rc0, win0, pad0, _), (rc1, win1, pad1, _) = (_padded_call(ctx, dev, desc, which, B, ld, on_device) for on_device in (0, 1))
+        assert rc0 == rc1 == _ffi.OK, which
+        assert np.isfinite(win0).all() and np.array_equal(win0, win1), which
+        assert (pad0 == SENTINEL).all() and (pad1 == SENTINEL).all(), which
+
+    try:
+        desc, keep = dev.desc(_kernel(M32, d), DIAG, tol=1e-10 if dtype == F64 else 1e-5, maxiter=500)
+        neg = s.copy()
+        neg[7] = -DIAG - 1e-3
+        dev.set_noise(neg)
+        failed("matvec", b"negative")
+        failed("solve", b"negative")
+        zero = s.copy()
+        zero[7] = -DIAG
+        dev.set_noise(zero)
+        dev.set_preconditioner(_points(x, 16), 1e-4)
+        failed("precond_apply", b"zero with a preconditioner")
+        dev.set_noise(s)
+        for which in ("matvec", "solve", "precond_apply"):
+            healthy(which)
     finally:
         dev.free()
 

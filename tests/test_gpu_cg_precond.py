@@ -1,5 +1,5 @@
 """GPU checks of the Nystrom preconditioner of the conjugate gradients (svgp_cg_set_preconditioner, svgp_cg_precond_cross / _apply,
-svgp_cg_fit_precond / _lml_grad_precond; csrc/cg.hip, cg_api.hip).  A wrong preconditioner still lets CG reach the right solution, so the
+svgp_cg_fit_precond / _lml_grad_precond; csrc/cg.hip, cg_precond.hip, cg_fit.hip).  A wrong preconditioner still lets CG reach the right solution, so the
 cross product, P^-1 and log det P are pinned directly against dense float64; the solver, the log det estimate, the gradient and the
 predictions are then checked as tests/test_gpu_cg.py checks the unpreconditioned ones, with the same data, variance and lengthscale.
 

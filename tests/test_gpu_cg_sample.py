@@ -1,4 +1,4 @@
-"""GPU checks of the pathwise function samples of the exact GP (csrc/cg_sample.hip, cg_api.hip; svgp_cg_sampler_*) against the float64
+"""GPU checks of the pathwise function samples of the exact GP (csrc/cg_sample.hip, cg_sampler_api.hip; svgp_cg_sampler_*) against the float64
 restatement tests/cg_sample_ref.py (itself pinned to central differences, to cg_ref's posterior mean and to the exact posterior's
 moments in tests/test_cg_sample_cpu.py).  Inputs are seeded as in test_gpu_cg.py: x ~ U[-3, 3]^d, lengthscale 0.7, variance 1.3.
 
