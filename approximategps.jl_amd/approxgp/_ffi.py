@@ -296,6 +296,7 @@ SYMBOLS = {
     "svgp_ss_set_noise": (C.c_int32, [_P, _P, C.POINTER(PointNoise)]),
     "svgp_ss_fit": (C.c_int32, [_P, _P, C.POINTER(SSDesc), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(SSInfo)]),
     "svgp_ss_predict": (C.c_int32, [_P, _P, C.c_int64, _P, _P, _P]),
+    "svgp_ss_sample": (C.c_int32, [_P, _P, C.c_int64, _P, C.c_int32, _P, _P, _P]),
     "svgp_lanczos_logdet": (C.c_int32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)]),
     # multi-GPU
     "svgp_comm_unique_id": (C.c_int32, [_P]),

@@ -1,8 +1,10 @@
 """The exact one-dimensional Matern GP in O(N) over the C-ABI of libsvgp_mi355x.so (include/svgp_mi355x.h, svgp_ss_*): a Matern-3/2 or
 -5/2 GP over scalar inputs is a linear Gaussian state-space model, and a Kalman filter and a Rauch-Tung-Striebel smoother, run on the
-device as parallel scans, give its log marginal likelihood and its posterior marginals exactly (TemporalGPs.jl's regime).  This file
-sorts the inputs, packs parameters and returns results in the caller's order.  Out of scope: the gradient of the lml, sums and products
-of kernels, periodic kernels, non-Gaussian likelihoods, d > 1, multi-GPU."""
+device as parallel scans, give its log marginal likelihood and its posterior marginals exactly (TemporalGPs.jl's regime); joint posterior
+sample paths over any grid of times (SSPosteriorGP.rand, DeviceStateSpace.sample) come from the same union of points by Matheron's rule
+in state-space form, three scans of affine maps, from the caller's standard-normal draws.  This file sorts the inputs, packs parameters,
+maps draws given in the caller's order to the library's and returns results in the caller's order.  Out of scope: the gradient of the
+lml, sums and products of kernels, periodic kernels, non-Gaussian likelihoods, d > 1, multi-GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -36,6 +38,7 @@ class DeviceStateSpace:
         if not np.all(np.isfinite(x)):
             raise ValueError("the times must be finite")
         self.ctx, self.dtype, self.n = ctx, _ffi.dtype_code(dt), x.shape[0]
+        self.state_dim = None   # D of the last successful fit: the width of sample()'s draws
         self.order = np.argsort(x, kind="stable")
         y = None if y is None else np.asarray(y, dtype=dt).reshape(-1)[self.order]
         self.data = _ffi.DeviceData(ctx, np.ascontiguousarray(x[self.order]), y, dt, _ffi.VEC)
@@ -59,6 +62,7 @@ class DeviceStateSpace:
 
     def set_noise(self, s=None):
         """Per-point noise variances sigma_k^2 = diag + s_k, s in the caller's order; None removes them."""
+        self.state_dim = None   # the library drops the cached fit
         if s is None:
             self.ctx.check(self.ctx.lib.svgp_ss_set_noise(self.ctx.h, self.h, None))
             return
@@ -77,8 +81,10 @@ class DeviceStateSpace:
                 raise ValueError("delta: an (N,) array")
             dl = np.ascontiguousarray(dl[self.order])
         lml, info = C.c_double(), _ffi.SSInfo()
+        self.state_dim = None
         self._check(self.ctx.lib.svgp_ss_fit(self.ctx.h, self.h, C.byref(desc), None if dl is None else dl.ctypes.data_as(C.POINTER(C.c_double)),
                                              C.byref(lml), C.byref(info)))
+        self.state_dim = int(info.state_dim)
         return lml.value, info
 
     def predict(self, t, mean=True, var=True):
@@ -95,6 +101,33 @@ class DeviceStateSpace:
         back = np.empty_like(order)
         back[order] = np.arange(order.shape[0])
         return (None if m is None else m[back]), (None if v is None else v[back])
+
+    def sample(self, t, z, eps):
+        """-> (n, S) joint posterior sample paths at the times t, in t's order: a deterministic, affine function of the caller's
+        standard-normal draws z (S, N + n, D) and eps (S, N).  Draws are addressed in the CALLER's order: z[:, i] belongs to the
+        i-th point of x as given, z[:, N + j] to t[j], eps[:, i] to the noise of y[i].  D: the state dimension of the last fit."""
+        dt = _ffi.np_dtype(self.dtype)
+        t = np.asarray(t, dtype=dt).reshape(-1)
+        n = t.shape[0]
+        if n < 1:
+            raise ValueError("no test points")
+        if self.state_dim is None:
+            raise ValueError("sample needs a successful fit on this handle")
+        z, eps = np.asarray(z, dtype=np.float64), np.asarray(eps, dtype=np.float64)
+        if z.ndim != 3 or z.shape[0] < 1 or z.shape[1:] != (self.n + n, self.state_dim):
+            raise ValueError(f"z: an (S, N + n, D) = (S, {self.n + n}, {self.state_dim}) array of standard-normal draws, S >= 1")
+        S = z.shape[0]
+        if eps.shape != (S, self.n):
+            raise ValueError(f"eps: an (S, N) = ({S}, {self.n}) array of standard-normal draws")
+        order = np.argsort(t, kind="stable")
+        ts = np.ascontiguousarray(t[order])
+        zc = np.ascontiguousarray(z[:, np.concatenate([self.order, self.n + order])])
+        ec = np.ascontiguousarray(eps[:, self.order])
+        out = np.zeros((S, n), dtype=dt)
+        self._check(self.ctx.lib.svgp_ss_sample(self.ctx.h, self.h, n, _ffi._ptr(ts), S, _ffi._ptr(zc), _ffi._ptr(ec), _ffi._ptr(out)))
+        back = np.empty_like(order)
+        back[order] = np.arange(n)
+        return np.ascontiguousarray(out[:, back].T)
 
     def free(self):
         if getattr(self, "h", None):
@@ -171,8 +204,8 @@ def approx_lml(approx, fx, y, **kwargs):
 
 
 class SSPosteriorGP:
-    """posterior(StateSpace(), fx, y): the exact posterior's marginals at any times, each call one filter and one smoother pass over
-    the union of the data and the test times on the device."""
+    """posterior(StateSpace(), fx, y): the exact posterior's marginals and joint sample paths at any times, each call one filter pass
+    and one smoother pass (rand: three scans of sample chunks) over the union of the data and the test times on the device."""
 
     def __init__(self, fx: FiniteGP, y, ctx=None, dtype=None, mean_offsets=None):
         self.prior = fx.f
@@ -192,6 +225,18 @@ class SSPosteriorGP:
 
     def mean_and_var(self, x):
         return self.dev.predict(x)
+
+    def rand(self, x, n_samples, rng=None):
+        """-> (n, n_samples): joint draws of the latent function at the times x (any order), exact in distribution and O((N + n) S);
+        rng: a seed or a numpy Generator (np.random.default_rng(rng) draws z, then eps)"""
+        n = np.asarray(x).reshape(-1).shape[0]
+        if int(n_samples) != n_samples or n_samples < 1:
+            raise ValueError("n_samples: an integer >= 1")
+        if n < 1:
+            raise ValueError("no test points")
+        g = np.random.default_rng(rng)
+        z = g.standard_normal((int(n_samples), self.dev.n + n, self.info.state_dim))
+        return self.dev.sample(x, z, g.standard_normal((int(n_samples), self.dev.n)))
 
     def _lik_predictive(self, x, y, want, noise):
         if noise is None:

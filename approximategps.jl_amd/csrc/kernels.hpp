@@ -486,5 +486,24 @@ void launch_ss_lml(hipStream_t s, int family, double variance, double inv_length
 // mean + mean_const and variance of point k
 void launch_ss_smooth(hipStream_t s, int family, double variance, double inv_lengthscale, const double* t, int64_t n, const double* fm, int64_t ld,
                       double* work, const int* slot, double mean_const, int dtype, void* mean_out, void* var_out);
+// the sampler (svgp_ss_sample): joint posterior paths by three scans of affine maps over chunks of ss_sample_chunk() samples.
+// Memory of a group of ns samples over the union of n = N + nt points, in doubles: z ns n D + eps ns N + ft ns n + mf ns D n, plus
+// ss_sample_work_doubles(n) (~ n / 63 elements of 21 doubles) per chunk and the ns nt outputs in the data dtype
+int ss_sample_chunk();
+size_t ss_sample_work_doubles(int64_t n);   // room for one chunk's aggregates of every level
+// ident[pos] of the union's point at pos: the datum's index in [0, N), or N + the test point's slot (ts: the n sorted test times)
+void launch_ss_ident(int dtype, hipStream_t s, const double* tm, const int* slot, const void* ts, int64_t n, int64_t N, int* ident);
+struct SsSample {
+  const double *t, *dl, *r;   // the union (launch_ss_merge)
+  const double* fm;           // its filtered moments (launch_ss_filter with ld = n; the covariance rows are read)
+  const double *z, *eps;      // the draws: z [ns][n][D] by ident, eps [ns][N]
+  const int *ident, *slot;
+  double *ft, *mf, *work;     // [ns][n], [ns][D][n], chunks * ss_sample_work_doubles(n)
+  void* out;                  // [ns][nt] in the data dtype: the paths at the test points' slots
+  int64_t n, N, nt, stride;   // stride: set by the launcher
+  int ns, f32;
+  double mean_const;
+};
+void launch_ss_sample(hipStream_t s, int family, double variance, double inv_lengthscale, SsSample a);
 
 }  // namespace svgp

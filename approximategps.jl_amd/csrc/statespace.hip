@@ -265,6 +265,172 @@ inline Model model_of(int family, double variance, double inv_lengthscale) {
   return Model{variance, std::sqrt(family == 1 ? 3.0 : 5.0) * inv_lengthscale};
 }
 
+// ---- the sampler (svgp_ss_sample): three scans over AffineElem<D, kSampleChunk> ----------------------------------------------------------
+// Grid: x = the tile, y = the chunk of kSampleChunk samples.  Every chunk rebuilds the shared D x D part of its elements (an exp and ~150
+// flops a point) instead of reading it, so no chunk depends on another; aggregates of chunk y live at y * stride in the work buffer,
+// component-major like the other scans'.  Draws: z [ns][n][D] by point identity (ident[k]: the datum's index, N + the test point's),
+// eps [ns][N].  Intermediates: ft [ns][n] (the prior path's first entry), mf [ns][D][n] (the filtered means of the residual).
+// kSampleChunk = 4 (profiles/statespace/kernel_resources.txt): the D = 3 element is 9 + 12 doubles and its kernels stay at the
+// smoother's register count, without scratch; 8 samples (33 doubles) cost a third of the waves per SIMD for a quarter less shared work,
+// in kernels that wait on memory, not on the VALU.
+constexpr int kSampleChunk = 4;
+
+// the identity of the union's point at pos: a test point's slot j -> N + j; a datum sits at its index + the number of test times below it
+template <typename T>
+__global__ void ss_ident_kernel(const double* __restrict__ tm, const int* __restrict__ slot, const T* __restrict__ ts, int64_t n, int64_t N,
+                                int* __restrict__ ident) {
+  const int64_t pos = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (pos >= N + n) return;
+  const int j = slot[pos];
+  if (j >= 0) { ident[pos] = int(N + j); return; }
+  const double v = tm[pos];
+  int64_t lo = 0, hi = n;   // the number of test times < v, as in ss_merge_kernel
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (double(ts[mid]) < v) lo = mid + 1; else hi = mid;
+  }
+  ident[pos] = int(pos - lo);
+}
+
+// level 1 of the prior path's scan.  DOWN writes ft
+template <int D, int SC, int MODE>
+__global__ void __launch_bounds__(kTile) ss_prior_kernel(Model m, SsSample a, double* __restrict__ agg, int64_t nagg) {
+  using E = AffineElem<D, SC>;
+  const int lane = threadIdx.x, s0 = blockIdx.y * SC;
+  const int64_t tile = blockIdx.x, k = tile * kTile + lane;
+  if (agg) agg += int64_t(blockIdx.y) * a.stride;
+  E e = E::identity();
+  if (k < a.n) {
+    double z[D * SC];
+    const int64_t row = a.ident[k];
+#pragma unroll
+    for (int q = 0; q < SC; ++q)
+#pragma unroll
+      for (int i = 0; i < D; ++i) z[i * SC + q] = s0 + q < a.ns ? a.z[(int64_t(s0 + q) * a.n + row) * D + i] : 0.0;
+    e = E::build_prior(m, k == 0, k == 0 ? 0.0 : a.t[k] - a.t[k - 1], z);
+  }
+  e = tile_finish<E, MODE>(e, lane, tile, agg, nagg);
+  if (MODE == DOWN && k < a.n) {
+#pragma unroll
+    for (int q = 0; q < SC; ++q)
+      if (s0 + q < a.ns) a.ft[int64_t(s0 + q) * a.n + k] = e.v[E::oc + q];
+  }
+}
+
+// level 1 of the scan of the residual's filtered means: the gain from the filtered covariance of point k - 1.  DOWN writes mf
+template <int D, int SC, int MODE>
+__global__ void __launch_bounds__(kTile) ss_fmean_kernel(Model m, SsSample a, double* __restrict__ agg, int64_t nagg) {
+  using E = AffineElem<D, SC>;
+  const int lane = threadIdx.x, s0 = blockIdx.y * SC;
+  const int64_t tile = blockIdx.x, k = tile * kTile + lane;
+  if (agg) agg += int64_t(blockIdx.y) * a.stride;
+  E e = E::identity();
+  if (k < a.n) {
+    double Pp[E::TRI], ft[SC], eps[SC];
+#pragma unroll
+    for (int c = 0; c < E::TRI; ++c) Pp[c] = k > 0 ? a.fm[(D + c) * a.n + k - 1] : 0.0;
+    const double rk = a.r[k];
+    const bool obs = rk >= 0.0;
+    const int64_t row = a.ident[k];   // < N where obs
+#pragma unroll
+    for (int q = 0; q < SC; ++q) {
+      const bool on = s0 + q < a.ns;
+      ft[q] = on ? a.ft[int64_t(s0 + q) * a.n + k] : 0.0;
+      eps[q] = on && obs ? a.eps[int64_t(s0 + q) * a.N + row] : 0.0;
+    }
+    e = E::build_filter(m, k == 0, k == 0 ? 0.0 : a.t[k] - a.t[k - 1], Pp, rk, a.dl[k], ft, eps);
+  }
+  e = tile_finish<E, MODE>(e, lane, tile, agg, nagg);
+  if (MODE == DOWN && k < a.n) {
+#pragma unroll
+    for (int q = 0; q < SC; ++q)
+      if (s0 + q < a.ns) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) a.mf[(int64_t(s0 + q) * D + i) * a.n + k] = e.v[E::oc + i * SC + q];
+      }
+  }
+}
+
+// level 1 of the scan of the smoothed means, position p = point n - 1 - p.  DOWN writes the path ft + smoothed mean + mean_const of
+// every sample at the test points' slots
+template <int D, int SC, int MODE>
+__global__ void __launch_bounds__(kTile) ss_smean_kernel(Model m, SsSample a, double* __restrict__ agg, int64_t nagg) {
+  using E = AffineElem<D, SC>;
+  const int lane = threadIdx.x, s0 = blockIdx.y * SC;
+  const int64_t tile = blockIdx.x, p = tile * kTile + lane, k = a.n - 1 - p;
+  if (agg) agg += int64_t(blockIdx.y) * a.stride;
+  E e = E::identity();
+  if (p < a.n) {
+    double Pk[E::TRI], mk[D * SC];
+#pragma unroll
+    for (int c = 0; c < E::TRI; ++c) Pk[c] = a.fm[(D + c) * a.n + k];
+#pragma unroll
+    for (int q = 0; q < SC; ++q)
+#pragma unroll
+      for (int i = 0; i < D; ++i) mk[i * SC + q] = s0 + q < a.ns ? a.mf[(int64_t(s0 + q) * D + i) * a.n + k] : 0.0;
+    e = E::build_smooth(m, k == a.n - 1, k == a.n - 1 ? 0.0 : a.t[k + 1] - a.t[k], Pk, mk);
+  }
+  e = tile_finish<E, MODE>(e, lane, tile, agg, nagg);
+  if (MODE == DOWN && p < a.n) {
+    const int j = a.slot[k];
+    if (j >= 0) {
+#pragma unroll
+      for (int q = 0; q < SC; ++q)
+        if (s0 + q < a.ns) {
+          const double f = a.ft[int64_t(s0 + q) * a.n + k] + e.v[E::oc + q] + a.mean_const;
+          if (a.f32) static_cast<float*>(a.out)[int64_t(s0 + q) * a.nt + j] = float(f);
+          else static_cast<double*>(a.out)[int64_t(s0 + q) * a.nt + j] = f;
+        }
+    }
+  }
+}
+
+// the levels above, per chunk: ss_elem_kernel over the chunk's stored elements at blockIdx.y * stride
+template <class E, int MODE>
+__global__ void __launch_bounds__(kTile) ss_chunk_elem_kernel(double* __restrict__ buf, int64_t n, double* __restrict__ agg, int64_t nagg,
+                                                              int64_t stride) {
+  const int lane = threadIdx.x;
+  const int64_t tile = blockIdx.x, i = tile * kTile + lane;
+  buf += int64_t(blockIdx.y) * stride;
+  if (agg) agg += int64_t(blockIdx.y) * stride;
+  E e = E::identity();
+  if (i < n) e = load_elem<E>(buf, n, i);
+  e = tile_finish<E, MODE>(e, lane, tile, agg, nagg);
+  if (MODE == DOWN && i < n) store_elem<E>(buf, n, i, e);
+}
+
+template <class E> void scan_stored_chunks(hipStream_t s, double* buf, int64_t n, double* work, int64_t stride, unsigned chunks) {
+  if (n <= kTile) {
+    hipLaunchKernelGGL((ss_chunk_elem_kernel<E, DOWN>), dim3(1, chunks), dim3(kTile), 0, s, buf, n, (double*)nullptr, int64_t(0), stride);
+    return;
+  }
+  const int64_t m = tiles_of(n);
+  hipLaunchKernelGGL((ss_chunk_elem_kernel<E, REDUCE>), dim3((unsigned)m, chunks), dim3(kTile), 0, s, buf, n, work, m, stride);
+  scan_stored_chunks<E>(s, work, m, work + m * E::NV, stride, chunks);
+  hipLaunchKernelGGL((ss_chunk_elem_kernel<E, DOWN>), dim3((unsigned)m, chunks), dim3(kTile), 0, s, buf, n, work, m, stride);
+}
+
+#define SS_SAMPLE_SCAN(KERNEL)                                                                                              \
+  do {                                                                                                                      \
+    if (agg) {                                                                                                              \
+      hipLaunchKernelGGL((KERNEL<D, kSampleChunk, REDUCE>), grid, dim3(kTile), 0, s, m, a, agg, nt);                         \
+      scan_stored_chunks<E>(s, agg, nt, agg + nt * E::NV, a.stride, chunks);                                                \
+    }                                                                                                                       \
+    hipLaunchKernelGGL((KERNEL<D, kSampleChunk, DOWN>), grid, dim3(kTile), 0, s, m, a, agg, nt);                             \
+  } while (0)
+
+template <int D> void sample_scans(hipStream_t s, const Model& m, const SsSample& a) {
+  using E = AffineElem<D, kSampleChunk>;
+  const int64_t nt = tiles_of(a.n);
+  const unsigned chunks = (unsigned)((a.ns + kSampleChunk - 1) / kSampleChunk);
+  const dim3 grid((unsigned)nt, chunks);
+  double* agg = nt > 1 ? a.work : nullptr;
+  SS_SAMPLE_SCAN(ss_prior_kernel);
+  SS_SAMPLE_SCAN(ss_fmean_kernel);
+  SS_SAMPLE_SCAN(ss_smean_kernel);
+}
+#undef SS_SAMPLE_SCAN
+
 }  // namespace
 
 int ss_tile() { return ss::kTile; }
@@ -328,6 +494,30 @@ void launch_ss_smooth(hipStream_t s, int family, double variance, double inv_len
   const Model m = model_of(family, variance, inv_lengthscale);
   if (family == 1) smooth_scan<2>(s, m, t, n, fm, ld, work, slot, mean_const, dtype == 1, mean_out, var_out);
   else smooth_scan<3>(s, m, t, n, fm, ld, work, slot, mean_const, dtype == 1, mean_out, var_out);
+}
+
+int ss_sample_chunk() { return kSampleChunk; }
+
+size_t ss_sample_work_doubles(int64_t n) {
+  size_t total = 0;
+  for (int64_t m = tiles_of(n); m > 1; m = tiles_of(m)) {
+    total += size_t(m) * ss::AffineElem<3, kSampleChunk>::NV;
+    if (m <= ss::kTile) break;
+  }
+  return total + 1;
+}
+
+void launch_ss_ident(int dtype, hipStream_t s, const double* tm, const int* slot, const void* ts, int64_t n, int64_t N, int* ident) {
+  const dim3 g((unsigned)((N + n + 255) / 256));
+  if (dtype == 0) hipLaunchKernelGGL(ss_ident_kernel<double>, g, dim3(256), 0, s, tm, slot, (const double*)ts, n, N, ident);
+  else hipLaunchKernelGGL(ss_ident_kernel<float>, g, dim3(256), 0, s, tm, slot, (const float*)ts, n, N, ident);
+}
+
+void launch_ss_sample(hipStream_t s, int family, double variance, double inv_lengthscale, SsSample a) {
+  const Model m = model_of(family, variance, inv_lengthscale);
+  a.stride = (int64_t)ss_sample_work_doubles(a.n);
+  if (family == 1) sample_scans<2>(s, m, a);
+  else sample_scans<3>(s, m, a);
 }
 
 }  // namespace svgp

@@ -396,5 +396,198 @@ template <int D> SS_HD void predict_obs(const Model& m, bool first, double dt, c
   *var = s;
 }
 
+// ---- the sampler's scans: affine maps x -> A x + c over SC right-hand sides at once ---------------------------------------------------
+// Joint posterior paths by Matheron's rule in state-space form (the Durbin-Koopman simulation smoother) are three recursions of one
+// shape: the prior path x_k = A_k x_{k-1} + Lq_k z_k, the filter's means m_k = Abar_k m_{k-1} + K_k rho_k of the residual rho, and the
+// smoother's means mhat_k = E_k mhat_{k+1} + (I - E_k A_{k+1}) m_k.  Their matrices do not depend on the draws (the gains come from the
+// filtered covariances of one ordinary filter scan), so a chunk of SC samples shares A and carries c as D x SC, sample fastest.
+
+// the lower factor Lq of a symmetric positive SEMI-definite S = Lq Lq', by an unpivoted L D L' in registers.  A pivot that is not > 0
+// (a singular or indefinite-by-rounding S, NaN included) is replaced by 0 together with its column: dt = 0 gives Lq = 0, never a NaN
+template <int D> SS_HD void psd_factor(const double S[D][D], double Lq[D][D]) {
+  double L[D][D], dg[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    double s = S[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k] * dg[k];
+    const bool ok = s > 0.0;
+    dg[j] = ok ? s : 0.0;
+    const double inv = ok ? 1.0 / s : 0.0, rt = ok ? sqrt(s) : 0.0;
+#pragma unroll
+    for (int i = 0; i < j; ++i) Lq[i][j] = 0.0;
+    Lq[j][j] = rt;
+#pragma unroll
+    for (int i = j + 1; i < D; ++i) {
+      double u = S[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) u -= L[i][k] * L[j][k] * dg[k];
+      L[i][j] = u * inv;
+      Lq[i][j] = L[i][j] * rt;
+    }
+  }
+}
+
+template <int D, int SC> struct AffineElem {
+  static constexpr int TRI = Dim<D>::TRI;
+  static constexpr int oA = 0, oc = D * D, NV = oc + D * SC;   // c[i][s] at oc + i * SC + s
+  double v[NV];
+
+  SS_HD static AffineElem identity() {
+    AffineElem e;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) e.v[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) e.v[oA + i * D + i] = 1.0;
+    return e;
+  }
+
+  // x before y (x is applied first): (A_y A_x, A_y c_x + c_y)
+  SS_HD static AffineElem combine(const AffineElem& x, const AffineElem& y) {
+    AffineElem o;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += y.v[oA + i * D + k] * x.v[oA + k * D + j];
+        o.v[oA + i * D + j] = s;
+      }
+#pragma unroll
+      for (int q = 0; q < SC; ++q) {
+        double s = y.v[oc + i * SC + q];
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += y.v[oA + i * D + k] * x.v[oc + k * SC + q];
+        o.v[oc + i * SC + q] = s;
+      }
+    }
+    return o;
+  }
+
+  SS_HD void set(const double A[D][D]) {
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) v[oA + i * D + j] = A[i][j];
+  }
+
+  // the prior path at point k: x_k = A(dt) x_{k-1} + Lq z_k, Lq Lq' = Q(dt); first: x_0 = chol(Pinf) z_0.  z: [D][SC] standard normals
+  SS_HD static AffineElem build_prior(const Model& m, bool first, double dt, const double* z) {
+    AffineElem e;
+    double F[D][D], Q[D][D], Lq[D][D];
+    if (first) {
+      pinf<D>(m, Q);
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) F[i][j] = 0.0;
+    } else {
+      transition<D>(m, dt, F, Q);
+    }
+    psd_factor<D>(Q, Lq);
+    e.set(F);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int q = 0; q < SC; ++q) {
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k <= i; ++k) s += Lq[i][k] * z[k * SC + q];
+        e.v[oc + i * SC + q] = s;
+      }
+    return e;
+  }
+
+  // the filter's mean at point k for the residual rho_k = dl - ft - sqrt(r) eps (ft: the prior path's first entry, [SC]; eps: [SC]),
+  // fused in: m_k = (I - K H) A m_{k-1} + K rho_k, K = P^- H' / (P^-_11 + r), P^- = A P_{k-1} A' + Q from the filtered covariance Pp of
+  // point k - 1 (a stored triangle).  r < 0: no observation, K = 0.  first: the update of (0, Pinf)
+  SS_HD static AffineElem build_filter(const Model& m, bool first, double dt, const double* Pp, double r, double dl, const double* ft,
+                                       const double* eps) {
+    AffineElem e;
+    double F[D][D], Q[D][D];
+    if (first) {
+      pinf<D>(m, Q);
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) F[i][j] = 0.0;
+    } else {
+      double P[D][D], FP[D][D], S[D][D];
+      transition<D>(m, dt, F, Q);
+      unpack<D>(Pp, P);
+      matmul<D>(F, P, FP);
+      matmul_nt<D>(FP, F, S);
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) Q[i][j] = Q[j][i] = Q[i][j] + 0.5 * (S[i][j] + S[j][i]);
+    }
+    const bool obs = r >= 0.0;
+    const double is = obs ? 1.0 / (Q[0][0] + r) : 0.0, sr = obs ? sqrt(r) : 0.0;
+    double K[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) K[i] = Q[i][0] * is;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) e.v[oA + i * D + j] = F[i][j] - K[i] * F[0][j];
+#pragma unroll
+    for (int q = 0; q < SC; ++q) {
+      const double rho = dl - ft[q] - sr * eps[q];
+#pragma unroll
+      for (int i = 0; i < D; ++i) e.v[oc + i * SC + q] = K[i] * rho;
+    }
+    return e;
+  }
+
+  // the smoother's mean at point k, scanned from the last point to the first: mhat_k = E mhat_{k+1} + (m_k - E A m_k) with the gain
+  // E = P_k A' (A P_k A' + Q)^-1 of SmoothElem::build, dt = t_{k+1} - t_k.  mk: the filtered means [D][SC].  last: mhat = m
+  SS_HD static AffineElem build_smooth(const Model& m, bool last, double dt, const double* Pk, const double* mk) {
+    AffineElem e;
+    if (last) {
+#pragma unroll
+      for (int i = 0; i < D * D; ++i) e.v[oA + i] = 0.0;
+#pragma unroll
+      for (int i = 0; i < D * SC; ++i) e.v[oc + i] = mk[i];
+      return e;
+    }
+    double F[D][D], Q[D][D], P[D][D], FP[D][D], S[D][D], E[D][D];
+    transition<D>(m, dt, F, Q);
+    unpack<D>(Pk, P);
+    matmul<D>(F, P, FP);
+    matmul_nt<D>(FP, F, S);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) E[i][j] = FP[j][i];   // P F'
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = i; j < D; ++j) S[i][j] = S[j][i] = S[i][j] + Q[i][j];
+    solve_right_spd<D>(S, E);
+    e.set(E);
+#pragma unroll
+    for (int q = 0; q < SC; ++q) {
+      double fm[D];
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += F[i][k] * mk[k * SC + q];
+        fm[i] = s;
+      }
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        double s = mk[i * SC + q];
+#pragma unroll
+        for (int k = 0; k < D; ++k) s -= E[i][k] * fm[k];
+        e.v[oc + i * SC + q] = s;
+      }
+    }
+    return e;
+  }
+};
+
 }  // namespace ss
 }  // namespace svgp

@@ -1,9 +1,11 @@
-// statespace_api.hip — the exact one-dimensional Matern GP in O(N): svgp_ss_create / _set_noise / _fit / _predict / _free (statespace.hip:
+// statespace_api.hip — the exact one-dimensional Matern GP in O(N): svgp_ss_create / _set_noise / _fit / _predict / _sample / _free (statespace.hip:
 // the kernels).  Host orchestration only.  A Matern-3/2 or -5/2 GP over a scalar input is a linear Gaussian state-space model of state
 // dimension 2 or 3: fit stages the points in fp64, runs the filter's scan and sums the one-step predictive log densities; predict merges
-// the sorted test times into the sequence on the device as unobserved points and runs the filter's and the smoother's scans over the union.
+// the sorted test times into the sequence on the device as unobserved points and runs the filter's and the smoother's scans over the union;
+// sample draws joint posterior paths over the same union by three scans of affine maps, a bounded group of samples at a time.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <memory>
@@ -24,6 +26,7 @@ struct svgp_ss {
   DevBuf flag;                   // one int: what the device-side checks found
   DevBuf delta, noise_s;         // a caller's delta (fp64); the per-point noise snapshot (data dtype)
   DevBuf ts, tm, dm, rm, slot, out;   // predict: the test times, the union, the test points' slots, mean | var in the data dtype
+  DevBuf ident, sz, seps, sft, smf, swork, sout;   // sample: the points' identities; one group's draws, prior paths, filtered means, aggregates, paths
   bool have_noise = false, have_fit = false;
   int family = 0;                // the parameter set of the last fit
   double variance = 0, inv_lengthscale = 0, mean_const = 0;
@@ -32,6 +35,7 @@ struct svgp_ss {
 namespace {
 
 constexpr int64_t kSsMaxPoints = (int64_t(1) << 31) - 1;   // (the slots are int)
+constexpr size_t kSsSampleGroupBytes = size_t(4) << 30;     // svgp_ss_sample: the draws and intermediates of one group of samples
 
 int check_desc(svgp_ctx* ctx, const svgp_ss* h, const svgp_ss_desc* ds) {
   if (!ds) return fail(ctx, SVGP_INVALID_ARG, "null descriptor");
@@ -232,6 +236,79 @@ int32_t svgp_ss_predict(svgp_ctx* ctx, svgp_ss* h, int64_t n, const void* t_host
   (void)elapsed_ms(ctx, &ms, ctx->ev[0], ctx->ev[1]);
   ctx->timing = svgp_timing{};
   ctx->timing.ms_total = ms;
+  return SVGP_OK;
+}
+
+int32_t svgp_ss_sample(svgp_ctx* ctx, svgp_ss* h, int64_t n, const void* t_host, int32_t n_samples, const double* z_host, const double* eps_host,
+                       void* out) {
+  if (!ctx) return SVGP_INVALID_ARG;
+  int rc = handle_checks(ctx, h);
+  if (rc) return rc;
+  if (!t_host || !z_host || !eps_host || !out) return fail(ctx, SVGP_INVALID_ARG, "null argument");
+  if (!h->have_fit) return fail(ctx, SVGP_INVALID_ARG, "no successful svgp_ss_fit on this handle yet");
+  if (n < 1) return fail(ctx, SVGP_INVALID_ARG, "no test points");
+  if (n_samples < 1) return fail(ctx, SVGP_INVALID_ARG, "n_samples must be >= 1");
+  if (n > kSsMaxPoints - h->N) return fail(ctx, SVGP_UNSUPPORTED, "more than 2^31 - 1 points in the union of data and test points");
+  const bool ok = h->dtype == SVGP_F64 ? sorted_and_finite(static_cast<const double*>(t_host), n) : sorted_and_finite(static_cast<const float*>(t_host), n);
+  if (!ok) return fail(ctx, SVGP_INVALID_ARG, "the test times must be finite and non-decreasing (sort them)");
+  HIPC(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int64_t N = h->N, U = N + n, S = n_samples;
+  const int D = h->family == SVGP_KERNEL_MATERN32 ? 2 : 3, SC = ss_sample_chunk();
+  // a group of whole chunks whose draws and intermediates fit kSsSampleGroupBytes (one chunk at least)
+  const size_t stride = ss_sample_work_doubles(U);
+  const size_t per_sample = (size_t(U) * size_t(2 * D + 1) + size_t(N)) * 8 + size_t(n) * h->es;
+  const size_t per_chunk = per_sample * size_t(SC) + stride * 8;
+  const int64_t chunks = (S + SC - 1) / SC;
+  const int64_t gchunks = std::min<int64_t>(chunks, std::max<int64_t>(1, int64_t(kSsSampleGroupBytes / per_chunk)));
+  const int64_t G = std::min<int64_t>(S, gchunks * SC);   // samples per group
+  const size_t nb = size_t(n) * h->es;
+  if ((rc = h->ts.reserve(ctx, nb, "the test times")) != SVGP_OK) return rc;
+  for (DevBuf* b : {&h->tm, &h->dm, &h->rm})
+    if ((rc = b->reserve(ctx, size_t(U) * 8, "the union of data and test points")) != SVGP_OK) return rc;
+  if ((rc = h->slot.reserve(ctx, size_t(U) * sizeof(int), "the test points' slots")) != SVGP_OK) return rc;
+  if ((rc = h->ident.reserve(ctx, size_t(U) * sizeof(int), "the points' identities")) != SVGP_OK) return rc;
+  if ((rc = reserve_scan(ctx, h, U)) != SVGP_OK) return rc;
+  if ((rc = h->sz.reserve(ctx, size_t(G) * size_t(U) * size_t(D) * 8, "the state draws")) != SVGP_OK) return rc;
+  if ((rc = h->seps.reserve(ctx, size_t(G) * size_t(N) * 8, "the noise draws")) != SVGP_OK) return rc;
+  if ((rc = h->sft.reserve(ctx, size_t(G) * size_t(U) * 8, "the prior paths")) != SVGP_OK) return rc;
+  if ((rc = h->smf.reserve(ctx, size_t(G) * size_t(U) * size_t(D) * 8, "the residuals' filtered means")) != SVGP_OK) return rc;
+  if ((rc = h->swork.reserve(ctx, size_t(gchunks) * stride * 8, "the sampler's aggregates")) != SVGP_OK) return rc;
+  if ((rc = h->sout.reserve(ctx, size_t(G) * nb, "the sample paths")) != SVGP_OK) return rc;
+  HIPC(ctx, hipMemcpyAsync(h->ts.p, t_host, nb, hipMemcpyHostToDevice, s));
+  SsSample a{};
+  a.t = h->tm.as<double>(); a.dl = h->dm.as<double>(); a.r = h->rm.as<double>(); a.fm = h->fm.as<double>();
+  a.z = h->sz.as<double>(); a.eps = h->seps.as<double>();
+  a.ident = h->ident.as<int>(); a.slot = h->slot.as<int>();
+  a.ft = h->sft.as<double>(); a.mf = h->smf.as<double>(); a.work = h->swork.as<double>(); a.out = h->sout.p;
+  a.n = U; a.N = N; a.nt = n;
+  a.f32 = h->dtype == SVGP_F32;
+  a.mean_const = h->mean_const;
+  float ms_total = 0;
+  for (int64_t g0 = 0; g0 < S; g0 += G) {
+    const int64_t ns = std::min<int64_t>(G, S - g0);
+    HIPC(ctx, hipMemcpyAsync(h->sz.p, z_host + size_t(g0) * size_t(U) * size_t(D), size_t(ns) * size_t(U) * size_t(D) * 8, hipMemcpyHostToDevice, s));
+    HIPC(ctx, hipMemcpyAsync(h->seps.p, eps_host + size_t(g0) * size_t(N), size_t(ns) * size_t(N) * 8, hipMemcpyHostToDevice, s));
+    TREC(ctx, ctx->ev[0], s);
+    if (g0 == 0) {   // the union, its filtered covariances (they do not depend on the data or the draws) and the points' identities: once
+      launch_ss_merge(h->dtype, s, h->t.as<double>(), h->dl.as<double>(), h->r.as<double>(), N, h->ts.p, n, h->tm.as<double>(), h->dm.as<double>(),
+                      h->rm.as<double>(), h->slot.as<int>());
+      launch_ss_filter(s, h->family, h->variance, h->inv_lengthscale, h->tm.as<double>(), h->dm.as<double>(), h->rm.as<double>(), U,
+                       h->work.as<double>(), h->fm.as<double>(), U);
+      launch_ss_ident(h->dtype, s, h->tm.as<double>(), h->slot.as<int>(), h->ts.p, n, N, h->ident.as<int>());
+    }
+    a.ns = int(ns);
+    launch_ss_sample(s, h->family, h->variance, h->inv_lengthscale, a);
+    TREC(ctx, ctx->ev[1], s);
+    KCHECK(ctx, "ss (sample)");
+    HIPC(ctx, hipMemcpyAsync(static_cast<char*>(out) + size_t(g0) * nb, h->sout.p, size_t(ns) * nb, hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipStreamSynchronize(s));
+    float ms = 0;
+    (void)elapsed_ms(ctx, &ms, ctx->ev[0], ctx->ev[1]);
+    ms_total += ms;
+  }
+  ctx->timing = svgp_timing{};
+  ctx->timing.ms_total = ms_total;   // the kernels of every group; the draws' uploads lie between the groups and are not counted
   return SVGP_OK;
 }
 

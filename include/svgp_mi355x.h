@@ -1193,6 +1193,21 @@ int32_t svgp_lanczos_logdet(const double* a, const double* b, int32_t iters, dou
  *              between two data alike) are merged into the sequence on the device as unobserved points behind equal data times; the
  *              filter and the smoother run over the union.  mean_out / var_out: the latent mean (+ mean_const) and variance at the test
  *              times, n entries of the data dtype, host, each nullable.
+ *   sample     n_samples = S JOINT posterior sample paths at n test times (as predict's), exact in distribution, by Matheron's rule in
+ *              state-space form (the Durbin-Koopman simulation smoother) over the union of the N data and n test points: a prior path
+ *              x_0 = chol(Pinf) z_0, x_k = A(dt_k) x_{k-1} + Lq_k z_k (Lq Lq' = Q(dt_k) by an unpivoted L D L' whose pivots that are not
+ *              > 0 are dropped with their columns: equal time stamps add no innovation), ft = its first entry; the residual
+ *              rho_k = delta_k - ft_k - sqrt(sigma_k^2) eps_k at the data; its smoothed mean at every point of the union.  The path at
+ *              a test point is ft + smoothed mean + mean_const.  The filter's and smoother's gains come from one ordinary filter scan
+ *              (they do not depend on delta), after which all three recursions are scans of affine maps x -> A x + c over chunks of 4
+ *              samples that share A.  Every random number is the caller's: z_host [S][N + n][D] standard normals addressed by point -
+ *              rows 0 .. N - 1 the (sorted) data points, rows N .. N + n - 1 the test times in the given order -, eps_host [S][N];
+ *              out [S][n] in the data dtype, host.  The result is a deterministic function of its inputs, bitwise repeatable, and
+ *              affine in (z, eps); draws that are not finite give paths that are not finite with SVGP_OK.  Uses the parameter set,
+ *              noise and delta of the last successful fit.  SVGP_INVALID_ARG as for predict, and for n_samples < 1 or a NULL z, eps, out.
+ *              Memory: samples are processed in groups of whole chunks of at most 4 GiB (one chunk at least); a group of G samples
+ *              holds G ((2 D + 1) (N + n) + N) doubles (z, the prior paths, the residual's filtered means, eps), G n outputs and
+ *              ~ (N + n) / 63 elements of D D + 4 D doubles per chunk, beside predict's buffers and N + n ints.
  * SVGP_UNSUPPORTED: d != 1; SVGP_KERNEL_SE (no finite state); a communicator on the context; more than 2^31 - 1 points.
  * SVGP_INVALID_ARG, before anything is enqueued: a NULL required pointer; a descriptor dtype different from the data's; an unknown
  * kernel; variance, inv_lengthscale or diag not > 0 or not finite (NaN counts); a mean_const that is not finite; reserved != 0; data
@@ -1219,6 +1234,8 @@ int32_t svgp_ss_free(svgp_ctx* ctx, svgp_ss* ss);
 int32_t svgp_ss_set_noise(svgp_ctx* ctx, svgp_ss* ss, const svgp_point_noise* pn);
 int32_t svgp_ss_fit(svgp_ctx* ctx, svgp_ss* ss, const svgp_ss_desc* desc, const double* delta, double* lml_out, svgp_ss_info* info);
 int32_t svgp_ss_predict(svgp_ctx* ctx, svgp_ss* ss, int64_t n, const void* t_host, void* mean_out, void* var_out);
+int32_t svgp_ss_sample(svgp_ctx* ctx, svgp_ss* ss, int64_t n, const void* t_host, int32_t n_samples, const double* z_host, const double* eps_host,
+                       void* out);
 
 #ifdef __cplusplus
 }
